@@ -6,7 +6,7 @@ that are already resident in HBM: K1 pyramid -> K2 per-cell FAST -> K3 quadtree 
 K4-6 orientation+blur+rBRIEF (2000 keypoints/frame) -> K7 best-2 Hamming match of every frame
 against its predecessor in the ride.  Workload = BASELINE.json configs[1].
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment launches its own N ranks (it
@@ -215,6 +215,54 @@ def verify_against_oracle(ride, kps, desc, n, mout, nfeatures):
                 np.array_equal(mout[2][B - 2, :m].cpu().numpy().view(np.uint16), ob2)):
             raise SystemExit("bench verification FAILED: best-2 match of the last pair differs from the oracle")
     return True
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, kps, desc, n, mout, seed=0):
+    """--dump-outputs: what the last timed step handed its caller, as out_dir/<name>.npy, so that two builds can be
+    compared output for output.  Every buffer keeps the caller's layout (cap = max_keypoints slots per frame); only the
+    first n[f] slots of frame f hold results, the rest is never written by the path and is zeroed here.
+      keypoints.npy          float64 [F, cap, 7]   x, y, size, angle, response, octave, class_id (by value)
+      descriptors.npy        float32 [F, cap, 32]  one descriptor byte per element
+      n_keypoints.npy        float64 [F]
+      match_best_idx.npy     float64 [P, cap]      best-2 match of frame f against f - 1, one row per pair
+      match_best_dist.npy    float32 [P, cap]
+      match_second_dist.npy  float32 [P, cap]
+      frames.npy             float64 [F]           the batch's frame index of each row above
+      match_query_frames.npy float64 [P]           the query frame f of each match row
+    All frames when that fits DUMP_LIMIT_BYTES, else a fixed, seeded sample of them (sorted).  Returns a summary."""
+    import numpy as np
+    from pilotguru_amd.orb import KEYPOINT_DTYPE
+    B, cap = int(kps.shape[0]), int(kps.shape[1])
+    has_match = B > 1
+    per_frame = cap * (7 * 8 + 32 * 4) + 8 * 2 + ((cap * (8 + 4 + 4) + 8) if has_match else 0)
+    nsel = max(1, min(B, DUMP_LIMIT_BYTES // per_frame))
+    frames = np.arange(B) if nsel == B else np.sort(np.random.default_rng(seed).choice(B, nsel, replace=False))
+    nh = n.cpu().numpy().astype(np.int64)
+    live = np.arange(cap)[None, :] < nh[frames][:, None]                      # [F, cap]: slots that hold results
+    rec = kps.cpu().numpy()[frames].view(KEYPOINT_DTYPE)[..., 0]               # [F, cap] records
+    kp = np.stack([rec[f].astype(np.float64) for f in KEYPOINT_DTYPE.names], axis=-1)
+    kp[~live] = 0.0
+    dsc = desc.cpu().numpy()[frames].astype(np.float32)
+    dsc[~live] = 0.0
+    out = {"keypoints": kp, "descriptors": dsc, "n_keypoints": nh[frames].astype(np.float64),
+           "frames": frames.astype(np.float64)}
+    if has_match:
+        q = frames[frames >= 1]                                                # pair p = frame p + 1 against frame p
+        mlive = np.arange(cap)[None, :] < nh[q][:, None]
+        for name, t, dt in (("match_best_idx", mout[0], np.float64), ("match_best_dist", mout[1], np.float32),
+                            ("match_second_dist", mout[2], np.float32)):
+            a = t[:B - 1].cpu().numpy()[q - 1].astype(dt)
+            a[~mlive] = 0.0
+            out[name] = a
+        out["match_query_frames"] = q.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+    return {"dir": os.path.abspath(out_dir), "bytes": int(sum(a.nbytes for a in out.values())), "frames": int(nsel),
+            "of_frames": B, "arrays": sorted(out)}
 
 
 def upload_leg(pg, ext, ride, NF, W, H, B, seconds=2.0, depth=3, frontend=False, link=True, channels=1):
@@ -457,7 +505,13 @@ def main():
                     help="do not re-measure roofline.traffic with rocprofv3 PMC child runs after the timed region (cite the newest committed profile instead)")
     ap.add_argument("--n1-fps", type=float, default=None,
                     help="the N = 1 frames/s of the same configuration; adds scaling_efficiency to the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (rank 0's keypoints, descriptors, "
+                         "counts and best-2 matches) as DIR/<name>.npy in float32 / float64, at most 64 MB (a fixed, seeded "
+                         "sample of the frames when the batch is larger)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if (args.gpus > 1 or os.environ.get("PGORB_BENCH_FORCE_LAUNCH")) and "WORLD_SIZE" not in os.environ:
         self_launch(args.gpus)                                  # does not return
@@ -596,6 +650,10 @@ def main():
     ext.check_async()
 
     # ---- everything below is outside the timed region ------------------------------------------
+    # (first: the legs below reuse kps / desc / n / mout, so the last timed step's results are saved before them)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, kps, desc, n, mout)
     verified = None
     if not args.no_verify and rank == 0:
         verified = verify_against_oracle(ride, kps, desc, n, mout, NF)
@@ -814,6 +872,8 @@ def main():
                 out["speedup_vs_cpu_one_thread"] = fps / out["cpu_baseline"]["one_thread"]["value"]
             except Exception as e:                               # noqa: BLE001 -- the CPU leg must not take the GPU line with it
                 leg_errors["cpu_baseline"] = str(e)[:300]
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
         if leg_errors:
             out["leg_errors"] = leg_errors
         line = json.dumps(out)

@@ -1,12 +1,34 @@
 """DBoW2 vocabulary path: text loader, blob, BowVector/FeatureVector accumulation (pinned
-against the REAL reference BowVector.cpp/FeatureVector.cpp via oracle/_ref), and the GPU
+against the REAL reference BowVector.cpp/FeatureVector.cpp: their outputs stored in
+tests/golden/ref_dbow2.npz, recomputed via oracle/_ref where it is built), and the GPU
 tree descent against the oracle."""
+import hashlib
 import os
 
 import numpy as np
 import pytest
 
 from pilotguru_amd import vocab as V
+
+REF_GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_dbow2.npz")
+
+
+def _reference_bow(oracle, key, word, weight, node, scoring=None, weighting=None):
+    """The reference BowVector / FeatureVector code's output for these inputs: stored under `key` in
+    tests/golden/ref_dbow2.npz (tests/golden/make_ref_vectors.py) and, where oracle/_ref is built,
+    recomputed by the reference code itself, which must reproduce the stored vector."""
+    h = hashlib.sha256()
+    for a in (word, weight, node):
+        a = np.ascontiguousarray(a)
+        h.update(str(a.dtype).encode() + str(a.shape).encode() + a.tobytes())
+    g = np.load(REF_GOLDEN)
+    assert str(g[key + ".inputs"]) == h.hexdigest(), "inputs of %s differ from the ones the golden vector was made of" % key
+    ref = ((g[key + ".bid"], g[key + ".bval"]), (g[key + ".fnode"], g[key + ".fstart"], g[key + ".ffeat"]))
+    if oracle.ref_dbow2() is not None:
+        live = oracle.ref_bow_vectors(word, weight, node, scoring, weighting)
+        for s, r in zip(ref[0] + ref[1], live[0] + live[1]):
+            assert s.dtype == r.dtype and s.tobytes() == r.tobytes()
+    return ref
 
 
 def _vocab_file(tmp_path, k=4, L=3, seed=1, trailing_newline=False):
@@ -65,9 +87,7 @@ def test_vocabulary_cache_beside_the_text_file(tmp_path):
 
 def test_bow_vectors_match_real_reference_code(oracle):
     """pgorb_bow_vectors (product, host) == reference BowVector::addWeight/normalize and
-    FeatureVector::addFeature, bit for bit (oracle/_ref built from /root/reference)."""
-    if oracle.ref_dbow2() is None:
-        pytest.skip("oracle/_ref/libdbow2_ref.so not built and /root/reference absent")
+    FeatureVector::addFeature, bit for bit (tests/golden/ref_dbow2.npz; oracle/_ref where built)."""
     rng = np.random.RandomState(3)
     for n in (0, 1, 7, 500, 2000):
         word = rng.randint(0, 300, n).astype(np.uint32)
@@ -76,7 +96,7 @@ def test_bow_vectors_match_real_reference_code(oracle):
         weight = wtab[word]
         node = (word // 7).astype(np.uint32)
         got = V.bow_vectors(word, weight, node, scoring=0, weighting=0)
-        ref = oracle.ref_bow_vectors(word, weight, node)
+        ref = _reference_bow(oracle, "tfidf_l1_n%d" % n, word, weight, node)
         for g, r in zip(got[0] + got[1], ref[0] + ref[1]):
             assert g.dtype == r.dtype and g.tobytes() == r.tobytes()
         if n:
@@ -89,8 +109,6 @@ def test_bow_vectors_every_scoring_and_weighting_type(oracle, tmp_path, scoring,
     """ScoringObject.h:74-89: L1 norm for L1_NORM / CHI_SQUARE / KL / BHATTACHARYYA, L2 for L2_NORM, none
     for DOT_PRODUCT (then tf / |v| for TF weightings, TemplatedVocabulary.h:1164-1170).  Product ==
     reference BowVector code == oracle, bit for bit."""
-    if oracle.ref_dbow2() is None:
-        pytest.skip("oracle/_ref/libdbow2_ref.so not built and /root/reference absent")
     rng = np.random.RandomState(40 + scoring * 4 + weighting)
     n = 700
     word = rng.randint(0, 120, n).astype(np.uint32)
@@ -98,7 +116,7 @@ def test_bow_vectors_every_scoring_and_weighting_type(oracle, tmp_path, scoring,
     wtab[rng.randint(0, 120, 9)] = 0.0
     weight, node = wtab[word], (word // 5).astype(np.uint32)
     got = V.bow_vectors(word, weight, node, scoring=scoring, weighting=weighting)
-    ref = oracle.ref_bow_vectors(word, weight, node, scoring, weighting)
+    ref = _reference_bow(oracle, "s%d_w%d" % (scoring, weighting), word, weight, node, scoring, weighting)
     for g, r in zip(got[0] + got[1], ref[0] + ref[1]):
         assert g.dtype == r.dtype and g.tobytes() == r.tobytes()
     val = got[0][1]

@@ -302,14 +302,21 @@ def test_gpu_fit_motion_cli_writes_the_oracles_numbers(tmp_path, oracle):
 
 def test_kahan_sum_equals_the_reference_header(oracle):
     """include/math/math.hpp is the one file of the fit_motion path that builds with this image's toolchain:
-    oracle/_ref/libmath_ref.so is the reference's own KahanSum; the oracle's and the product's must agree with it
-    bit for bit (and differ from the naive sum on an ill-conditioned series, or the test tests nothing)."""
+    tests/golden/ref_kahan.npz holds the reference's own KahanSum of this series (oracle/_ref/libmath_ref.so, which
+    recomputes it where it is built); the oracle's and the product's must agree with it bit for bit (and differ from
+    the naive sum on an ill-conditioned series, or the test tests nothing)."""
+    import hashlib
+    import os
     from pilotguru_amd.calibration import KahanSum
     r = np.random.default_rng(6)
     v = r.normal(0, 1, (5000, 3)) * 10.0 ** r.integers(-8, 9, (5000, 1))
-    ref = oracle.ref_kahan_sum(v)
-    if ref is None:
-        pytest.skip("oracle/_ref/libmath_ref.so not built and /root/reference absent")
+    g = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_kahan.npz"))
+    h = hashlib.sha256(str(v.dtype).encode() + str(v.shape).encode() + v.tobytes())
+    assert str(g["kahan.inputs"]) == h.hexdigest(), "the series differs from the one the golden sum was made of"
+    ref = g["kahan.sum"]
+    live = oracle.ref_kahan_sum(v)
+    if live is not None:
+        assert np.array_equal(_bits(live), _bits(ref))
     assert np.array_equal(_bits(oracle.kahan_sum(v)), _bits(ref))
     assert np.array_equal(_bits(KahanSum(v)), _bits(ref))
     naive = np.zeros(3)

@@ -264,9 +264,11 @@ int  pgorb_search_by_projection_frame(pgorb_ctx* ctx,
  *       Tracking::Relocalization (src/Tracking.cc:1434: th 10, ORBdist 100; :1448: th 3, ORBdist 64).  Per map point i of the
  *       key frame the caller passes what its pose arithmetic (:1497-1517, cv::Mat) produced: valid = pMP && !pMP->isBad();
  *       already_found = sAlreadyFound.count(pMP); (u, v) the projection into the current frame; dist3d = |x3Dw - Ow|;
- *       min / max_distance = pMP->GetMin/MaxDistanceInvariance(); kf_angle = pKF->mvKeysUn[i].angle; GetDescriptor().
- *       The device does the rest: the image-bounds and depth-range tests (:1512-1526), MapPoint::PredictScale
- *       (src/MapPoint.cc:516-531) with log_scale_factor = CurrentFrame.mfLogScaleFactor, radius th * mvScaleFactors[level],
+ *       min / max_distance = the point's mfMinDistance / mfMaxDistance (NOT the *Invariance() getters);
+ *       kf_angle = pKF->mvKeysUn[i].angle; GetDescriptor().
+ *       The device does the rest: the image-bounds test (:1512-1515), the depth-range test against
+ *       GetMin/MaxDistanceInvariance() = 0.8f * min_distance / 1.2f * max_distance (:1519-1526, src/MapPoint.cc:390-400),
+ *       MapPoint::PredictScale on the plain max_distance (src/MapPoint.cc:516-531) with log_scale_factor = CurrentFrame.mfLogScaleFactor, radius th * mvScaleFactors[level],
  *       levels level - 1 .. level + 1, best match only with ORBdist, rotation histogram.  Here ANY point in
  *       CurrentFrame.mvpMapPoints[i2] blocks a keypoint (:1542-1543: no Observations() test): kp_has_point[i2] != 0.
  *       PredictScale's `log` is the platform's logf in the reference; here a fixed double-precision sequence rounded once

@@ -309,7 +309,9 @@ int orc_predict_scale(float max_distance, float current_dist, float log_scale_fa
  * &sAlreadyFound, float th, int ORBdist), src/ORBmatcher.cc:1476-1603 (Tracking::Relocalization, Tracking.cc:1434,1448:
  * th 10 / ORBdist 100, then th 3 / ORBdist 64), given per key-frame map point i what the caller's pose arithmetic
  * (:1497-1517, cv::Mat) produced: valid = pMP && !pMP->isBad(); found = sAlreadyFound.count(pMP); (u, v) the projection;
- * dist3d = |x3Dw - Ow|; min / max_distance = GetMin/MaxDistanceInvariance(); kf_angle = pKF->mvKeysUn[i].angle.
+ * dist3d = |x3Dw - Ow|; min / max_distance = the point's mfMinDistance / mfMaxDistance (the depth test forms
+ * GetMin/MaxDistanceInvariance() = 0.8f*min / 1.2f*max from them, PredictScale takes the plain max, MapPoint.cc:390-400,
+ * :521); kf_angle = pKF->mvKeysUn[i].angle.
  * kp_has_point[i2]: CurrentFrame.mvpMapPoints[i2] != NULL before the call (ANY point blocks, :1542-1543 -- no
  * Observations() test here).  assigned[i2] = i, or -1.  Returns nmatches. */
 int orc_search_by_projection_keyframe(const orc_keypoint* kps, const uint8_t* desc, int n,
@@ -333,7 +335,9 @@ int orc_search_by_projection_keyframe(const orc_keypoint* kps, const uint8_t* de
         if (!valid[i] || found[i]) continue;                                          /* :1497-1499 */
         if (u[i] < minX || u[i] > maxX) continue;                                     /* :1512-1515 */
         if (v[i] < minY || v[i] > maxY) continue;
-        if (dist3d[i] < min_distance[i] || dist3d[i] > max_distance[i]) continue;     /* :1525-1526 */
+        const float maxDistance = 1.2f * max_distance[i];                             /* GetMaxDistanceInvariance (:1519) */
+        const float minDistance = 0.8f * min_distance[i];                             /* GetMinDistanceInvariance (:1520) */
+        if (dist3d[i] < minDistance || dist3d[i] > maxDistance) continue;             /* :1525-1526 */
         const int nPredictedLevel = orc_predict_scale(max_distance[i], dist3d[i], log_scale_factor, nlevels);   /* :1528 */
         const float radius = th * scale_factors[nPredictedLevel];                     /* :1531 */
         const int nind = orc_features_in_area(kps, grid_start, grid_idx, minX, maxX, minY, maxY, u[i], v[i], radius,

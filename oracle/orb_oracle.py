@@ -509,7 +509,8 @@ def predict_scale(max_distance, current_dist, log_scale_factor, nlevels):
 def search_by_projection_keyframe(kps, desc, bounds, scale_factors, kp_has_point, valid, found, u, v, dist3d, min_distance,
                                   max_distance, log_scale_factor, kf_angle, pdesc, th, orb_dist, check_orientation=True):
     """ORBmatcher::SearchByProjection(Frame&, KeyFrame*, sAlreadyFound, th, ORBdist) (src/ORBmatcher.cc:1476-1603), the
-    relocalisation search; scale_factors has nlevels + 1 entries like the extractor's table."""
+    relocalisation search; scale_factors has nlevels + 1 entries like the extractor's table; min / max_distance are the
+    points' plain mfMinDistance / mfMaxDistance."""
     kps, desc, gs, gi, has = _prep(kps, desc, bounds, kp_has_point)
     sf = np.ascontiguousarray(scale_factors, np.float32)
     a = [np.ascontiguousarray(valid, np.uint8), np.ascontiguousarray(found, np.uint8), np.ascontiguousarray(u, np.float32),

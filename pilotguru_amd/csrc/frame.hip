@@ -595,8 +595,10 @@ __device__ __forceinline__ bool proj_query(const PgProjBatch& B, int64_t qi, int
         // invariance range, level from MapPoint::PredictScale
         if (B.found[qi]) return false;
         if (x < minX || x > B.maxX || y < minY || y > B.maxY) return false;          // :1512-1515
-        const float d3 = B.dist3d[qi], dmin = B.minDist[qi], dmax = B.maxDist[qi];
-        if (d3 < dmin || d3 > dmax) return false;
+        // minDist / maxDist are mfMinDistance / mfMaxDistance: the depth test takes GetMin/MaxDistanceInvariance() =
+        // 0.8f*mfMinDistance / 1.2f*mfMaxDistance (:1519-1526, MapPoint.cc:390-400), PredictScale the plain mfMaxDistance (MapPoint.cc:521)
+        const float d3 = B.dist3d[qi], dmax = B.maxDist[qi];
+        if (d3 < __fmul_rn(0.8f, B.minDist[qi]) || d3 > __fmul_rn(1.2f, dmax)) return false;
         lvl = pg_predict_scale(dmax, d3, B.logSf, B.nlevels);
     } else {
         lvl = B.level[qi];

@@ -375,7 +375,8 @@ class ORBmatcher:
                                    point_desc, th, ORBdist, kp_has_point=None):
         """The matching loop of SearchByProjection(Frame &CurrentFrame, KeyFrame *pKF, sAlreadyFound, th, ORBdist)
         (src/ORBmatcher.cc:1476-1603; Tracking::Relocalization) for given projections (u, v) and depths: the bounds / depth
-        tests, MapPoint::PredictScale, the window search and the rotation histogram run on the device."""
+        tests, MapPoint::PredictScale, the window search and the rotation histogram run on the device.  min_distance /
+        max_distance are the points' plain mfMinDistance / mfMaxDistance (the depth test forms 0.8f * min / 1.2f * max)."""
         ext = CurrentFrame.ext
         F = CurrentFrame
         has = np.ascontiguousarray(kp_has_point if kp_has_point is not None else np.zeros(max(F.N, 1), np.uint8), np.uint8)

@@ -380,8 +380,56 @@ def fuzz_matchers(cases=100, seed=1, log=True, nf_range=(150, 3000), size_range=
     return state["bad"], "cases %d checks %d matches compared %s mismatches %d seconds %.1f" % (cases, checks, stats, state["bad"], time.time() - t0)
 
 
+def fuzz_matcher_edges(cases=40, seed=1, log=True):
+    """Random mixtures of the constructed edge-case families a-g of tests/matcher_cases.py (ties across cells, thresholds
+    and ratio products, window and grid edges, levels, the rotation histogram, conflicts, list capacities), each drawn with
+    its own random descriptors and positions: the plain reference (tests/matcher_reference.py), the oracle, the single-call
+    ABI and the batched device forms must all agree."""
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import pilotguru_amd as pg
+    import matcher_cases as E
+    from oracle import orb_oracle as oracle
+    oracle.build()
+    rng = np.random.RandomState(seed)
+    ext = pg.ORBextractor(1000, E.SCALE, E.NLEVELS, 20, 7, max_width=E.W, max_height=E.H, max_batch=4)
+    bad = 0; checks = 0; t0 = time.time(); kinds = {}
+    try:
+        for it in range(cases):
+            fams = "".join(rng.choice(list("abcdefg"), int(rng.randint(1, 4)), replace=False))
+            sub = np.random.RandomState(int(rng.randint(0, 2 ** 31 - 1)))
+            mix = [c for f in fams for c in E.FAMILIES[f](sub)]
+            mix = [mix[i] for i in sorted(sub.choice(len(mix), max(1, len(mix) // 2), replace=False))]
+            for case in mix:
+                want = E.run_reference(case)
+                ok = E.same(want, E.run_oracle(case, oracle))
+                if case["kind"] != "area":
+                    ok = ok and E.same(want, E.run_gpu(case, ext))
+                checks += 1; kinds[case["kind"]] = kinds.get(case["kind"], 0) + 1
+                if not ok:
+                    bad += 1
+                    _say(log, "MISMATCH case", it, fams, case["name"])
+            for gi, group in enumerate(E._batch_groups(mix)):
+                _, res = E.run_gpu_batched(group, ext, "nan" if (it + gi) % 2 else "huge")
+                for c, r in zip(group, res):
+                    checks += 1
+                    if not E.same(E.run_reference(c), r):
+                        bad += 1
+                        _say(log, "MISMATCH batched", it, fams, c["name"])
+            for group in E.grid_groups(mix):
+                for c, g in zip(group, E.run_gpu_grid_batched(group, ext, "nan" if it % 2 else "huge")):
+                    checks += 1
+                    if not E.same(E.run_reference(c), g):
+                        bad += 1
+                        _say(log, "MISMATCH batched grid", it, fams, c["name"])
+    finally:
+        ext.close()
+    return bad, "cases %d checks %d kinds %s mismatches %d seconds %.1f" % (cases, checks, kinds, bad, time.time() - t0)
+
+
 FUZZERS = {"parity": fuzz_parity, "levels": fuzz_levels, "batch_parity": fuzz_batch_parity, "best2": fuzz_best2,
-           "ingest": fuzz_ingest, "matchers": fuzz_matchers}
+           "ingest": fuzz_ingest, "matchers": fuzz_matchers,
+           "matcher_edges": fuzz_matcher_edges}
 
 
 def main(name, argv):

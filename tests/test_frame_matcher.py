@@ -242,8 +242,8 @@ def _keyframe_queries(F1keys, F1desc, shift, rng, sf, nlevels, w, h):
     # PredictScale = ceil(log(max / dist) / log(scale)): max = dist * scale^(level + d), d in (-1.5, 0.5) -> level - 1 .. level + 1
     maxd = (dist3d * scale ** (lvl.astype(np.float32) + rng.uniform(-1.5, 0.5, nq).astype(np.float32))).astype(np.float32)
     mind = (maxd / scale ** np.float32(nlevels - 1)).astype(np.float32)
-    mind[3::41] = dist3d[3::41] * np.float32(1.5)                           # dist3D < minDistance (:1525)
-    maxd[7::43] = dist3d[7::43] * np.float32(0.5)                           # dist3D > maxDistance
+    mind[3::41] = dist3d[3::41] * np.float32(1.5)                           # dist3D < 0.8f * mfMinDistance (:1525)
+    maxd[7::43] = dist3d[7::43] * np.float32(0.5)                           # dist3D > 1.2f * mfMaxDistance
     found = (rng.uniform(size=nq) > 0.9).astype(np.uint8)
     ang = F1keys["angle"][sel].copy()
     ang[::7] = (ang[::7] + 100.0) % 360.0                                   # some rotation-inconsistent matches
@@ -319,7 +319,9 @@ def test_oracle_search_by_projection_keyframe_consistency(oracle):
     good = asg >= 0
     q = asg[good]
     assert np.all(valid[q] == 1) and np.all(found[q] == 0) and len(set(q.tolist())) == nm
-    assert np.all((px[q] >= 0) & (px[q] <= 640) & (py[q] >= 0) & (py[q] <= 480) & (dist3d[q] >= mind[q]) & (dist3d[q] <= maxd[q]))
+    # depth inside GetMin/MaxDistanceInvariance() = 0.8f * mfMinDistance .. 1.2f * mfMaxDistance (MapPoint.cc:390-400)
+    assert np.all((px[q] >= 0) & (px[q] <= 640) & (py[q] >= 0) & (py[q] <= 480) & (dist3d[q] >= np.float32(0.8) * mind[q]) &
+                  (dist3d[q] <= np.float32(1.2) * maxd[q]))
     lv = np.array([oracle.predict_scale(maxd[i], dist3d[i], lf, 8) for i in q])
     assert np.all(np.abs(k2["octave"][good] - lv) <= 1)
     assert np.all(np.abs(k2["x"][good] - px[q]) < 10.0 * sf[lv]) and np.all(np.abs(k2["y"][good] - py[q]) < 10.0 * sf[lv])

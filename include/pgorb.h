@@ -116,7 +116,13 @@ int  pgorb_extract_batch(pgorb_ctx* ctx, const uint8_t* const* gray, int nframes
                          pgorb_keypoint* kps, uint8_t* desc, int cap_per_frame, int* n);
 /* Same, everything resident in HBM: d_gray = nframes planes `frame_stride` bytes apart.
  * Asynchronous on `hip_stream`.  d_n[f] receives the true count even when it exceeds
- * cap_per_frame (then only the first cap_per_frame entries were written). */
+ * cap_per_frame (then only the first cap_per_frame entries were written).
+ * Level 0 aliases d_gray when d_gray, stride and frame_stride are multiples of 4.  Only bytes
+ * 0 .. w-1 of each row decide the results: the bytes between w and `stride`, and between
+ * frames, may hold anything, and rows other than a frame's last may be read up to `stride`.
+ * Of a frame's last row no byte past the w-th is read (the pyramid's first resize and the
+ * fused launch copy such chunks byte by byte), so the allocation may end there (a crop, or
+ * buf[..., :w] at the end of a tensor). */
 int  pgorb_extract_batch_device(pgorb_ctx* ctx, const uint8_t* d_gray, int nframes,
                                 int w, int h, int stride, int64_t frame_stride,
                                 pgorb_keypoint* d_kps, uint8_t* d_desc, int cap_per_frame,
@@ -604,6 +610,7 @@ int      pgorb_stream_frontend_results(pgorb_stream* s, int slot, const int32_t*
  * key "fused_levels": 1 = the launch that resizes level l -> l + 1 also detects level l (csrc/fused.hip: every level read from HBM
  *     once, one wave per cell slot; bit-exact; measured SLOWER than the two launches in every form tried, profiles/r06_fused_forms.txt),
  *     0 = K1 + K2 (default).  Levels whose geometry the fused launch does not take (cells wider than 32 px, generic scale factors) run K1 + K2 either way.
+ * key "fused_launches" (read only): how many levels the last batch sent through the fused launch.
  * key "pipeline_pyramid": 1 = the resize chain on a side stream beside K2, level by level (slower).
  * key "pipeline_levels": bit l set = a group of levels starts at level l; K3 / K4-6 of one group run on side streams beside K2
  * of the next (slower for every grouping measured).  0 = one launch per kernel (default).

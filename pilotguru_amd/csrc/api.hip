@@ -81,6 +81,7 @@ struct pgorb_ctx {
     int vocabK = 0, vocabL = 0, vocabNodes = 0;
     int lastFrames = 0;
     bool lastAliased = false;
+    int lastFusedLaunches = 0;                // fused resize + detect launches the last batch issued (pgorb_get_option "fused_launches")
     // stage profiling (HIP events on the launch stream)
     std::vector<hipEvent_t> evExtract;        // 5 per armed extract call
     std::vector<hipEvent_t> evMatch;          // 2 per armed match call
@@ -601,6 +602,7 @@ int run_batch(pgorb_ctx* c, const uint8_t* d_gray, bool resident_in_level0, int 
 {
     PgPlan P = c->plan;                                   // by-value copy handed to the kernels
     c->lastAliased = false;
+    c->lastFusedLaunches = 0;
     if (!resident_in_level0) {
         const bool aligned = ((uintptr_t)d_gray % 4 == 0) && (stride % 4 == 0) && (frame_stride % 4 == 0);
         if (aligned) {                                    // zero-copy: level 0 is the caller's buffer
@@ -694,6 +696,7 @@ int run_batch(pgorb_ctx* c, const uint8_t* d_gray, bool resident_in_level0, int 
         int pending = -1;                                     // first level of a run of levels still waiting for K2
         for (int l = 0; l + 1 < P.nlevels; l++) {
             if (pg_launch_pyr_fast(P, c->fuse, l, nframes, s)) {
+                c->lastFusedLaunches++;
                 if (pending >= 0) { pg_launch_fast_levels(P, nframes, pending, l, s); pending = -1; }
             } else {
                 pg_launch_pyramid_level(P, l + 1, nframes, s);
@@ -1357,6 +1360,7 @@ int pgorb_get_option(const pgorb_ctx* c, const char* key)
     if (!strcmp(key, "matcher")) return c->mx.popcount;
     if (!strcmp(key, "match_mode")) return c->mx.mode;
     if (!strcmp(key, "fused_levels")) return c->fused;
+    if (!strcmp(key, "fused_launches")) return c->lastFusedLaunches;
     if (!strcmp(key, "pipeline_pyramid")) return c->pipePyr;
     if (!strcmp(key, "pipeline_levels")) return c->pipeLev;
     if (!strcmp(key, "pipeline_levels_priority")) return c->pipeLevPrio;

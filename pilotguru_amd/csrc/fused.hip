@@ -26,8 +26,9 @@
 // front of the DMA (k_fast_cells: kernarg -> record -> window, three dependent round trips; here two).  The last level is
 // detected by k_fast_cells (fast.hip) as before.  Per level: algorithmic bytes w_l*h_l read + w_{l+1}*h_{l+1} written.
 // A slot row is read 48 bytes wide, past the window into the neighbouring cell or the next row of the level: always inside the
-// plane (the arena keeps 64 bytes of slack behind every plane) -- except when level 0 IS the caller's buffer, whose last row may
-// end its allocation: there (safeLastRow) the chunks of the last row that would pass the row pitch are copied byte by byte.
+// plane (the arena keeps 64 bytes of slack behind every plane) -- except when level 0 IS the caller's buffer: the caller guarantees
+// only the w bytes of each frame's last row (its allocation may end there, e.g. buf[..., :w] at the end of a tensor).  There
+// (safeLastRow) a chunk of a frame's last row that would pass w is copied byte by byte up to w and zero-filled behind it.
 //
 // blockIdx -> slot is XCD-aware like K2's: XCD k takes the k-th eighth of the frame's slots in (band, column) order, so
 // neighbours -- which share 128-B lines and 6 halo rows -- read them through the same L2.
@@ -112,8 +113,8 @@ __global__ __launch_bounds__(64, 8) void k_fast_resize(const PgFuseArgs A)
                 const int grow = min(Y + row, A.sh - 1);
                 if (lane < 63 && row < A.rows) {
                     const uint8_t* g = fb + (int64_t)grow * A.spitch + gx;
-                    if (A.safeLastRow && grow == A.sh - 1 && gx + 16 > A.spitch) {
-                        for (int i = 0; i < 16 && gx + i < A.spitch; i++) tile[row * 48 + ch * 16 + i] = g[i];
+                    if (A.safeLastRow && grow == A.sh - 1 && gx + 16 > A.sw) {
+                        for (int i = 0; i < 16; i++) tile[row * 48 + ch * 16 + i] = gx + i < A.sw ? g[i] : (uint8_t)0;
                     } else {
                         __builtin_amdgcn_global_load_lds((pg_gptr_t)g, (pg_lptr_t)(tile + k * 21 * 48), 16, 0, 0);
                     }
@@ -181,7 +182,7 @@ __global__ __launch_bounds__(64, 8) void k_fast_resize(const PgFuseArgs A)
 }
 
 // Resize level `level` -> level + 1 and detect level `level` in one launch.  Returns false (nothing launched) when the level has no
-// fused tables or the source pitch does not tile into 16-byte chunks (an aliased caller buffer): the caller then takes K1 + K2.
+// fused tables: the caller then takes K1 + K2.  An aliased level 0 takes this launch whatever its pitch, with safeLastRow set.
 bool pg_launch_pyr_fast(const PgPlan& P, const PgFusePlan& FP, int level, int nframes, hipStream_t s)
 {
     const PgLevel& S = P.lvl[level];

@@ -335,11 +335,12 @@ __global__ __launch_bounds__(256) void k_pyr_resize_rows4_lds(
     const uint8_t* __restrict__ src, int spitch, int64_t sfstride, int sh,
     uint8_t* __restrict__ dst, int dpitch, int64_t dfstride, int dw, int dh,
     const PgQuadTab2* __restrict__ qtab, const PgRowGrp* __restrict__ rowgrp, int nx, uint32_t nxMagic,
-    const int32_t* __restrict__ tilex, int cpr, int cprInv, int rowsTile, int32_t* __restrict__ clearWord)
+    const int32_t* __restrict__ tilex, int cpr, int cprInv, int rowsTile, int32_t* __restrict__ clearWord, int lastRowW)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t pyr_lds[];      // [rowsTile][cpr * 16]
     asm volatile("" :: "s"(src), "s"(spitch), "s"(sfstride), "s"(sh), "s"(dst), "s"(dpitch), "s"(dfstride),
-                 "s"(dw), "s"(dh), "s"(qtab), "s"(rowgrp), "s"(nx), "s"(nxMagic), "s"(tilex), "s"(cpr), "s"(cprInv), "s"(rowsTile), "s"(clearWord));
+                 "s"(dw), "s"(dh), "s"(qtab), "s"(rowgrp), "s"(nx), "s"(nxMagic), "s"(tilex), "s"(cpr), "s"(cprInv), "s"(rowsTile), "s"(clearWord),
+                 "s"(lastRowW));
     // the first launch of a batch also clears the context's device status word (K2 / K3 report through it and come later in the
     // stream): a memset of its own was a 4-us launch in front of every step
     if (clearWord && blockIdx.x == 0 && blockIdx.z == 0 && threadIdx.x == 0 && threadIdx.y == 0) *clearWord = 0;
@@ -363,7 +364,9 @@ __global__ __launch_bounds__(256) void k_pyr_resize_rows4_lds(
         sTile = rowgrp[ty * (4 * GPW)].sFirst;
         x0a = tilex[tx];
     }
-    // stage the tile's source rectangle: cpr lanes per row, 64 / cpr rows per instruction
+    // stage the tile's source rectangle: cpr lanes per row, 64 / cpr rows per instruction.  lastRowW > 0 (the source is the caller's
+    // buffer, which guarantees only w bytes of a frame's last row): a chunk of the last row that would pass w is copied byte by byte
+    // up to w and zero-filled behind it
     {
         const int pitch = cpr * 16, rowsPer = 64 / cpr;
         const int r0 = (lane * cprInv) >> 16, ch = lane - r0 * cpr;
@@ -371,9 +374,16 @@ __global__ __launch_bounds__(256) void k_pyr_resize_rows4_lds(
         const bool laneOn = r0 < rowsPer && x0a + ch * 16 + 16 <= spitch;      // never past the row pitch
         for (int k = wv; k * rowsPer < rowsTile; k += 4) {
             const int r = k * rowsPer + r0;
-            if (laneOn && r < rowsTile)
-                __builtin_amdgcn_global_load_lds((pg_gptr_t)(sb + (int64_t)min(sTile + r, sh - 1) * spitch),
-                                                 (pg_lptr_t)(pyr_lds + k * rowsPer * pitch), 16, 0, 0);
+            if (laneOn && r < rowsTile) {
+                const int srow = min(sTile + r, sh - 1);
+                const uint8_t* g = sb + (int64_t)srow * spitch;
+                if (lastRowW > 0 && srow == sh - 1 && x0a + ch * 16 + 16 > lastRowW) {
+                    uint8_t* l = pyr_lds + k * rowsPer * pitch + lane * 16;        // where the lane's DMA chunk would land
+                    for (int i = 0; i < 16; i++) l[i] = x0a + ch * 16 + i < lastRowW ? g[i] : (uint8_t)0;
+                } else {
+                    __builtin_amdgcn_global_load_lds((pg_gptr_t)g, (pg_lptr_t)(pyr_lds + k * rowsPer * pitch), 16, 0, 0);
+                }
+            }
         }
         __builtin_amdgcn_s_waitcnt(0);
     }
@@ -420,6 +430,9 @@ bool pg_launch_pyramid_level(const PgPlan& P, int level, int nframes, hipStream_
     const PgLevel& S = P.lvl[level - 1];
     const PgLevel& D = P.lvl[level];
     static const bool noLds = getenv("PGORB_PYR_NO_LDS") != nullptr;
+    // level 0 as the caller's buffer: only the w bytes of a frame's last row are guaranteed to exist (include/pgorb.h).  With
+    // pitch == w no read passes the pitch anyway.
+    const int lastRowW = (level == 1 && S.img != P.pyrBase && S.pitch > S.w) ? S.w : 0;
     if (D.qtab2 && D.yrel && D.pyrCpr > 0 && S.pitch % 16 == 0 && !noLds) {
         const int tileRows = 16 * D.pyrGpw;
         const int nx = (D.w + 255) / 256, ny = (D.h + tileRows - 1) / tileRows;
@@ -429,7 +442,7 @@ bool pg_launch_pyramid_level(const PgPlan& P, int level, int nframes, hipStream_
         const size_t lds = (size_t)D.pyrRows * D.pyrCpr * 16;
         dim3 block(64, 4), grid(tiles, 1, nframes);
 #define PG_PYR_LDS(G) hipLaunchKernelGGL(k_pyr_resize_rows4_lds<G>, grid, block, lds, s, S.img, S.pitch, S.fstride, S.h, D.img, D.pitch, D.fstride, \
-                                         D.w, D.h, D.qtab2, D.rowgrp, nx, nxMagic, D.tilex, D.pyrCpr, cprInv, D.pyrRows, clearWord)
+                                         D.w, D.h, D.qtab2, D.rowgrp, nx, nxMagic, D.tilex, D.pyrCpr, cprInv, D.pyrRows, clearWord, lastRowW)
         if (D.pyrGpw == 1) PG_PYR_LDS(1); else if (D.pyrGpw == 4) PG_PYR_LDS(4); else PG_PYR_LDS(2);
 #undef PG_PYR_LDS
         return true;
@@ -443,7 +456,7 @@ bool pg_launch_pyramid_level(const PgPlan& P, int level, int nframes, hipStream_
                            D.img, D.pitch, D.fstride, D.w, D.h, D.qtab2, D.rowgrp, nx, nxMagic);
         return false;
     }
-    if (D.qtab) {
+    if (D.qtab && !(lastRowW > 0 && (S.w & 3))) {         // (its aligned dword loads reach past w when w % 4 != 0: byte loads below)
         dim3 block(64, 4), grid((D.w + 255) / 256, (D.h + 4 * PYR_ROWS - 1) / (4 * PYR_ROWS), nframes);
         hipLaunchKernelGGL(k_pyr_resize_quads, grid, block, 0, s, S.img, S.pitch, S.fstride, S.w,
                            D.img, D.pitch, D.fstride, D.w, D.h, D.qtab, D.yofs, D.ybeta);

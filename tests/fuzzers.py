@@ -427,9 +427,63 @@ def fuzz_matcher_edges(cases=40, seed=1, log=True):
     return bad, "cases %d checks %d kinds %s mismatches %d seconds %.1f" % (cases, checks, kinds, bad, time.time() - t0)
 
 
+def fuzz_extractor_edges(cases=40, seed=1, log=True):
+    """Random mixtures of the constructed edge-case families a-h of tests/extractor_cases.py (thresholds and the retry, NMS,
+    cell geometry, candidate order and the quadtree, orientation, the blur and rBRIEF at the borders, levels, 0/255 content):
+    features of several families are pasted at random offsets into one frame, with random thresholds, feature counts, scale
+    factor, level count, blur tie mode, K2 tile shape, K3 form and fused launch.  The plain reference
+    (tests/extractor_reference.py), the oracle and pgorb_extract must agree byte for byte."""
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import pilotguru_amd as pg
+    import extractor_cases as E
+    from oracle import orb_oracle as oracle
+    oracle.build()
+    rng = np.random.RandomState(seed)
+    bad = 0; checks = 0; t0 = time.time()
+    for it in range(cases):
+        fams = "".join(rng.choice(list("abdefgh"), int(rng.randint(1, 4)), replace=False))
+        sub = np.random.RandomState(int(rng.randint(0, 2 ** 31 - 1)))
+        parts = [c["img"] for f in fams for c in E.FAMILIES[f](sub)]
+        w, h = int(rng.randint(160, 330)), int(rng.randint(130, 250))
+        img = np.full((h, w), E.BG, np.uint8)
+        for p in [parts[i] for i in sub.choice(len(parts), min(len(parts), 3), replace=False)]:
+            ph, pw = min(p.shape[0], h), min(p.shape[1], w)
+            y0, x0 = int(rng.randint(0, h - ph + 1)), int(rng.randint(0, w - pw + 1))
+            sy, sx = int(rng.randint(0, p.shape[0] - ph + 1)), int(rng.randint(0, p.shape[1] - pw + 1))
+            img[y0:y0 + ph, x0:x0 + pw] = p[sy:sy + ph, sx:sx + pw]
+        scale = float(rng.choice([1.2, 2.0]))
+        nl = int(rng.randint(1, 4 if scale < 1.5 else 3))
+        while nl > 1 and min(w, h) / scale ** (nl - 1) < 64:
+            nl -= 1
+        ini = int(rng.choice([20, 12, 30]))
+        case = E.case("mix", "mix_%d_%s" % (it, fams), img, nfeatures=int(rng.randint(5, 400)), scale=scale, nlevels=nl,
+                      ini=ini, mn=int(rng.choice([7, 8, ini - 1])), tie=int(rng.randint(0, 2)))
+        kps, desc, levels = E.run_oracle(case, oracle)
+        want = E.run_reference(case, levels)
+        ok = E.same(want, (kps, desc))
+        ext = pg.ORBextractor(case["nfeatures"], scale, nl, case["ini"], case["min"], max_width=w, max_height=h,
+                              blur_tie_mode=case["tie"])
+        try:
+            ext.set_option("fused_levels", int(rng.randint(0, 2)))
+            ext.set_option("quadtree_split", int(rng.randint(0, 3)))
+            if rng.randint(0, 2):
+                ext.set_option("fast_tile_pitch", int(rng.choice([48, 64, 128])))
+                ext.set_option("fast_waves_per_block", int(rng.choice([1, 2, 4])))
+            for _ in range(2):
+                ok = ok and E.same(want, ext(img))
+        finally:
+            ext.close()
+        checks += 1
+        if not ok:
+            bad += 1
+            _say(log, "MISMATCH case", it, case["name"], w, h, scale, nl)
+    return bad, "cases %d checks %d mismatches %d seconds %.1f" % (cases, checks, bad, time.time() - t0)
+
+
 FUZZERS = {"parity": fuzz_parity, "levels": fuzz_levels, "batch_parity": fuzz_batch_parity, "best2": fuzz_best2,
            "ingest": fuzz_ingest, "matchers": fuzz_matchers,
-           "matcher_edges": fuzz_matcher_edges}
+           "matcher_edges": fuzz_matcher_edges, "extractor_edges": fuzz_extractor_edges}
 
 
 def main(name, argv):

@@ -14,7 +14,7 @@ pytestmark = pytest.mark.gpu
 
 @pytest.mark.parametrize("name,cases,seed", [("parity", 300, 41), ("levels", 20, 42), ("batch_parity", 100, 43), ("matchers", 100, 44),
                                               ("ingest", 50, 45), ("best2", 500, 46),
-                                              ("matcher_edges", 30, 47)])
+                                              ("matcher_edges", 30, 47), ("extractor_edges", 80, 48)])
 def test_fuzz_slice(oracle, name, cases, seed):
     bad, summary = fuzzers.FUZZERS[name](cases=cases, seed=seed)
     print(summary)

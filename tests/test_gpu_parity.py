@@ -945,26 +945,81 @@ def test_fused_resize_and_detect_every_level_bit_exact(oracle, w, h, nf, scale, 
 
 
 def test_fused_levels_on_an_aliased_batch_with_odd_pitch(oracle):
-    """Level 0 aliases the caller's device buffer: a row pitch that is a multiple of 16 takes the fused launch on the caller's rows
-    (band chunks never pass the pitch: the last row of the last frame is the end of the caller's allocation), any other 4-aligned
-    pitch sends level 0 through K1 + K2 and the rest through the fused launches -- the same keypoints either way."""
+    """fused_levels = 1 with level 0 aliasing the caller's device buffer: the fused launch stages 16-byte chunks of the caller's
+    rows whatever the pitch (a multiple of 16 or not).  The caller guarantees only the w bytes of a frame's last row, so there
+    (safeLastRow) the chunks that would pass w are copied byte by byte up to w and zero-filled.  Covered: padded batches of
+    pitch = 0, 12 and 4 (mod 16); a batch whose last frame's last row ends its allocation exactly ((B-1) frame strides + (h-1)
+    pitches + w bytes, viewed with as_strided); and the device-resident stream with 2 lanes -- the same keypoints each time, and
+    every batch through the fused launch."""
     import torch
     import pilotguru_amd as pg
     w, h, nf, B = 636, 476, 800, 3
     ride = synth_ride(5, w, h, B)
     want = [oracle.OrbOracle(nf, 1.2, 8, 20, 7).extract(f) for f in ride]
     ext = pg.ORBextractor(nf, 1.2, 8, 20, 7, max_width=w, max_height=h, max_batch=B)
-    for pitch in (640, 636, 644):
-        buf = torch.zeros((B, h, pitch), dtype=torch.uint8, device="cuda")
-        buf[:, :, :w] = torch.from_numpy(np.stack(ride)).cuda()
-        kps, desc, n = ext.extract_batch_device(buf[:, :, :w])
+    ext.set_option("fused_levels", 1)
+    assert ext.get_option("fused_levels") == 1
+
+    def check(kps, desc, n, label, fused=True):
         ext.check_async()
         torch.cuda.synchronize()
+        if fused:
+            assert ext.get_option("fused_launches") >= 1, label
         n = n.cpu().numpy()
         for k in range(B):
-            assert n[k] == len(want[k][0]), (pitch, k)
-            assert kps[k, :n[k]].cpu().numpy().tobytes() == want[k][0].tobytes(), (pitch, k)
-            assert np.array_equal(desc[k, :n[k]].cpu().numpy(), want[k][1]), (pitch, k)
+            assert n[k] == len(want[k][0]), (label, k)
+            assert kps[k, :n[k]].cpu().numpy().tobytes() == want[k][0].tobytes(), (label, k)
+            assert np.array_equal(desc[k, :n[k]].cpu().numpy(), want[k][1]), (label, k)
+    frames = torch.from_numpy(np.stack(ride)).cuda()
+    for pitch in (640, 636, 644):
+        buf = torch.full((B, h, pitch), 255, dtype=torch.uint8, device="cuda")
+        buf[:, :, :w] = frames
+        check(*ext.extract_batch_device(buf[:, :, :w]), "pitch %d" % pitch)
+    for pitch in (640, 644):
+        fstride = h * pitch + 48
+        flat = torch.full(((B - 1) * fstride + (h - 1) * pitch + w,), 255, dtype=torch.uint8, device="cuda")
+        view = torch.as_strided(flat, (B, h, w), (fstride, pitch, 1))
+        view.copy_(frames)
+        check(*ext.extract_batch_device(view), "exact end, pitch %d" % pitch)
+    st = pg.DeviceFrameStream(ext, w, h, B, 2, 2)
+    assert st.lanes() == 2
+    try:
+        padded = torch.zeros((B, h, 644), dtype=torch.uint8, device="cuda")
+        padded[:, :, :w] = frames
+        for slot in (0, 1):
+            st.submit(slot, padded[:, :, :w])
+        for slot in (0, 1):
+            n, kps, desc = st.wait(slot)[:3]
+            check(kps, desc, n, "stream slot %d" % slot, fused=False)        # (the lanes are contexts of their own)
+    finally:
+        st.close()
+
+
+@pytest.mark.parametrize("w,h,scale,pitch", [(636, 476, 1.2, 640), (637, 475, 2.0, 640), (640, 480, 1.2, 640)])
+def test_k1_on_an_aliased_batch_ending_at_w(oracle, w, h, scale, pitch):
+    """fused_levels = 0 (the default): K1 reads level 0 from the caller's buffer.  The batch ends with the w bytes of the last
+    frame's last row, at a row pitch that is a multiple of 16 (the LDS-staged resize, whose last-row chunks stop at w) and, at
+    scale 2.0 with w % 4 != 0, the dword-tap resize (not taken there: the byte-tap one is) -- the oracle's keypoints each time."""
+    import torch
+    import pilotguru_amd as pg
+    nf, B = 800, 2
+    ride = synth_ride(7, w, h, B)
+    ora = oracle.OrbOracle(nf, scale, 3, 20, 7)
+    want = [ora.extract(f) for f in ride]
+    ext = pg.ORBextractor(nf, scale, 3, 20, 7, max_width=w, max_height=h, max_batch=B)
+    assert ext.get_option("fused_levels") == 0
+    fstride = h * pitch + 32
+    flat = torch.full(((B - 1) * fstride + (h - 1) * pitch + w,), 255, dtype=torch.uint8, device="cuda")
+    view = torch.as_strided(flat, (B, h, w), (fstride, pitch, 1))
+    view.copy_(torch.from_numpy(np.stack(ride)).cuda())
+    kps, desc, n = ext.extract_batch_device(view)
+    ext.check_async()
+    torch.cuda.synchronize()
+    n = n.cpu().numpy()
+    for k in range(B):
+        assert n[k] == len(want[k][0]), k
+        assert kps[k, :n[k]].cpu().numpy().tobytes() == want[k][0].tobytes(), k
+        assert np.array_equal(desc[k, :n[k]].cpu().numpy(), want[k][1]), k
 
 
 def test_registered_caller_buffer_uploads_directly(oracle):

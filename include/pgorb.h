@@ -350,6 +350,43 @@ int  pgorb_search_by_bow_batch_device(pgorb_ctx* ctx,
         const int32_t* d_pair_kf, const int32_t* d_pair_f, int npairs, const uint8_t* d_kf_point_valid,
         float nnratio, int check_orientation, int32_t* d_matches, int32_t* d_nmatches, void* hip_stream);
 
+/* ---- Matcher of the local-mapping thread ------------------------------------------------------------------------------
+ *   pgorb_search_for_triangulation   ORBmatcher::SearchForTriangulation(pKF1, pKF2, F12, vMatchedPairs, bOnlyStereo = false)
+ *       src/ORBmatcher.cc:659-825 with CheckDistEpipolarLine :142-159, monocular (mvuRight < 0) -- called by
+ *       LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:266) for every covisible neighbour of a new key frame.  Keypoints
+ *       are the undistorted mvKeysUn of each key frame, FeatureVectors the CSR arrays pgorb_bow_vectors /
+ *       pgorb_feature_vectors_batch_device produce.  F12 = F12.at<float>(r, c) row-major and the epipole (ex, ey) in KF2 are what
+ *       the caller's pose arithmetic produced (:665-672, LocalMapping::ComputeF12 :538-555, cv::Mat float).  has_point1[i] /
+ *       has_point2[j] = GetMapPoint(i) != NULL, bad or not (:701-705, :724-728); NULL = no keypoint has one.  The thresholds
+ *       come from the context: 100*mvScaleFactors[octave] (float) and 3.84*mvLevelSigma2[octave] (double); octaves are taken
+ *       to lie in [0, levels).  matches12[i] = the KF2 keypoint matched to KF1 keypoint i, or -1; the reference's vMatchedPairs
+ *       are the (i, matches12[i] >= 0) in ascending i.  Returns nmatches.
+ *       Exact: every float operation in the reference's order, the epipolar comparison in double, fp32 denormals kept.  Like the
+ *       reference, a KF2 keypoint may be matched to several KF1 keypoints (vbMatched2 is never set, :679, :727), and among the
+ *       candidates that pass the last one of the smallest distance wins (bestDist only moves on a passing candidate, :753-757).
+ *       Each pair equals the reference called with those masks: CreateNewMapPoints adds map points to KF1 between neighbours
+ *       (LocalMapping.cc:441), so reproducing that loop exactly means one call per neighbour with the updated has_point1. */
+int  pgorb_search_for_triangulation(pgorb_ctx* ctx,
+        const pgorb_keypoint* kps1, const uint8_t* desc1, const uint8_t* has_point1, int n1,
+        const uint32_t* fv1_node, const int32_t* fv1_start, const uint32_t* fv1_feat, int nfv1,
+        const pgorb_keypoint* kps2, const uint8_t* desc2, const uint8_t* has_point2, int n2,
+        const uint32_t* fv2_node, const int32_t* fv2_start, const uint32_t* fv2_feat, int nfv2,
+        const float F12[9], float ex, float ey, int check_orientation, int32_t* matches12 /*[n1]*/);
+/* Batched, resident: pair p matches key frame d_pair_kf1[p] against d_pair_kf2[p] of one batch in the layout of
+ * pgorb_extract_batch_device, FeatureVectors as pgorb_feature_vectors_batch_device writes them.  d_F12 [npairs][9],
+ * d_epipole [npairs][2]; d_has_point1 / d_has_point2 [npairs][cap_per_frame] (NULL = none); d_matches12
+ * [npairs][cap_per_frame], d_nmatches [npairs].  One wave per (pair, common vocabulary node), then one finishing wave per pair
+ * (KF1's mask, the count, the rotation histogram).  Like pgorb_search_by_bow_batch_device, this form does not check the
+ * FeatureVectors: keypoints, descriptors and masks are reached only through them, so d_nfv / d_fv_* must be what
+ * pgorb_feature_vectors_batch_device writes (every feature index below the frame's d_n, at most cap_per_frame); the single call
+ * checks its host FeatureVectors instead (PGORB_E_ARG). */
+int  pgorb_search_for_triangulation_batch_device(pgorb_ctx* ctx,
+        const pgorb_keypoint* d_kps, const uint8_t* d_desc, const int32_t* d_n, int cap_per_frame,
+        const uint32_t* d_fv_node, const int32_t* d_fv_start, const uint32_t* d_fv_feat, const int32_t* d_nfv,
+        const int32_t* d_pair_kf1, const int32_t* d_pair_kf2, int npairs, const float* d_F12, const float* d_epipole,
+        const uint8_t* d_has_point1, const uint8_t* d_has_point2, int check_orientation,
+        int32_t* d_matches12, int32_t* d_nmatches, void* hip_stream);
+
 /* ---- ORB vocabulary (DBoW2 TemplatedVocabulary<FORB::TDescriptor, FORB>) -----------------
  *   pgorb_vocab_load_text     ORBVocabulary(text_file) -> TemplatedVocabulary::loadFromTextFile
  *                             thirdparty/orb-slam2/src/ORBVocabulary.cc:7-9,

@@ -31,6 +31,7 @@ SYMBOLS = (
     "pgorb_search_by_projection_points", "pgorb_search_by_projection_frame", "pgorb_search_by_bow",
     "pgorb_search_by_projection_points_batch_device", "pgorb_search_by_projection_frame_batch_device",
     "pgorb_feature_vectors_batch_device", "pgorb_search_by_bow_batch_device",
+    "pgorb_search_for_triangulation", "pgorb_search_for_triangulation_batch_device",
     "pgorb_search_by_projection_keyframe", "pgorb_search_by_projection_keyframe_batch_device",
     "pgorb_log_f", "pgorb_log_scale_factor", "pgorb_predict_scale",
     "pgorb_undistort_keypoints", "pgorb_undistort_keypoints_batch_device", "pgorb_image_bounds",
@@ -149,6 +150,10 @@ def lib():
     L.pgorb_predict_scale.argtypes = [vp, C.c_float, C.c_float]
     L.pgorb_feature_vectors_batch_device.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp]
     L.pgorb_search_by_bow_batch_device.argtypes = [vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp, C.c_int, vp, C.c_float, C.c_int, vp, vp, vp]
+    # (ctx, kps1, desc1, has_point1, n1, fv1 x 3, nfv1, kps2, desc2, has_point2, n2, fv2 x 3, nfv2, F12, ex, ey, check, matches12)
+    L.pgorb_search_for_triangulation.argtypes = [vp] + ([vp] * 3 + [C.c_int] + [vp] * 3 + [C.c_int]) * 2 + [vp, C.c_float, C.c_float, C.c_int, vp]
+    L.pgorb_search_for_triangulation_batch_device.argtypes = [vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp, C.c_int] + [vp] * 4 + \
+        [C.c_int, vp, vp, vp]
     L.pgorb_undistort_keypoints.argtypes = [vp, vp, C.c_int, vp, vp, vp]
     L.pgorb_undistort_keypoints_batch_device.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp]
     L.pgorb_image_bounds.argtypes = [C.c_int, C.c_int, vp, vp, vp]

@@ -5,6 +5,7 @@
 //   Frame::GetFeaturesInArea                  src/Frame.cc:331-384
 //   ORBmatcher::SearchForInitialization       src/ORBmatcher.cc:407-522
 //   ORBmatcher::ComputeThreeMaxima            src/ORBmatcher.cc:1605-1646
+//   ORBmatcher::SearchForTriangulation        src/ORBmatcher.cc:659-825, 142-159 (further down, with SearchByBoW)
 //
 // The matcher is sequential over F1's keypoints by construction: whether candidate i2 is
 // considered depends on vMatchedDistance[i2], which earlier keypoints wrote (:445-446, :469).
@@ -1067,14 +1068,22 @@ __global__ __launch_bounds__(64) void k_search_by_bow(PgBowBatch B, float nnrati
     }
 }
 
-// after the nodes: count the matches of a pair and apply the rotation histogram
-__global__ __launch_bounds__(64) void k_bow_finish(PgBowBatch B, int checkOrientation, int32_t* __restrict__ matchesOut,
-                                                    const int8_t* __restrict__ binIn, int32_t* __restrict__ nmatchesOut)
+// after the nodes: count the matches of a pair and apply the rotation histogram.  The output side of pair p is frame
+// pairSide[p] (SearchByBoW: the frame; SearchForTriangulation: key frame 1).  drop ([npairs][cap] or null) clears the entries
+// it marks before anything is counted: SearchForTriangulation's "KF1 keypoint already has a map point" (ORBmatcher.cc:701-705).
+__global__ __launch_bounds__(64) void k_match_finish(const int32_t* __restrict__ pairSide, const int32_t* __restrict__ nper, int cap,
+                                                     const uint8_t* __restrict__ drop, int checkOrientation, int32_t* __restrict__ matchesOut,
+                                                     const int8_t* __restrict__ binIn, int32_t* __restrict__ nmatchesOut)
 {
-    const int p = blockIdx.x, fb = B.pairF[p], cap = B.cap, nf = min(B.n[fb], cap), lane = threadIdx.x;
+    const int p = blockIdx.x, nf = min(nper[pairSide[p]], cap), lane = threadIdx.x;
     matchesOut += (int64_t)p * cap; binIn += (int64_t)p * cap; nmatchesOut += p;
+    if (drop) drop += (int64_t)p * cap;
     int nmatches = 0;
-    for (int i = lane; i < nf; i += 64) nmatches += matchesOut[i] >= 0;
+    for (int i = lane; i < nf; i += 64) {
+        int m = matchesOut[i];
+        if (m >= 0 && drop && drop[i]) { matchesOut[i] = -1; m = -1; }
+        nmatches += m >= 0;
+    }
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) nmatches += __shfl_xor(nmatches, d);
     const int8_t* rotBin = binIn;
@@ -1085,7 +1094,7 @@ __global__ __launch_bounds__(64) void k_bow_finish(PgBowBatch B, int checkOrient
         __shared__ int hist[64];
         hist[lane] = 0;
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        for (int i = lane; i < nf; i += 64) { const int bb = rotBin[i]; if (bb >= 0) atomicAdd(&hist[bb & 63], 1); }
+        for (int i = lane; i < nf; i += 64) { const int bb = rotBin[i]; if (bb >= 0 && !(drop && drop[i])) atomicAdd(&hist[bb & 63], 1); }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         const int h = hist[lane];
         int ind1 = -1, ind2 = -1, ind3 = -1, max1 = 0, max2 = 0, max3 = 0;
@@ -1107,6 +1116,155 @@ __global__ __launch_bounds__(64) void k_bow_finish(PgBowBatch B, int checkOrient
         nmatches -= removed;
     }
     if (lane == 0) *nmatchesOut = nmatches;
+}
+
+// ---- SearchForTriangulation(KF1, KF2, F12, vMatchedPairs, bOnlyStereo = false), src/ORBmatcher.cc:659-825, 142-159 ----
+// The same node walk as SearchByBoW, from KF1's side, with no order dependence at all: vbMatched2 (:679) is read (:727) but never
+// set, so every KF1 keypoint is decided on its own and two of them may take the same KF2 keypoint.  One wave per (pair, KF1
+// node): KF2's keypoints of the node one per lane and held in registers together with what does not depend on KF1 -- the
+// has_point2 mask and the epipole test (:745-751) fold into "no candidate" -- and KF1's keypoints walked with their descriptors
+// prefetched.  Per KF1 keypoint a candidate passes on dist <= TH_LOW and the epipolar test; bestDist only moves on a passing
+// candidate (:753-757), so the reference keeps the LAST passing candidate of the smallest distance: a wave minimum on
+// (dist << 16 | 0xFFFF - list position).  KF1's own mask (:701-705) is applied by k_match_finish, so this pass depends only on
+// (KF1, KF2, F12, epipole, has_point2).
+struct PgTriBatch {
+    const pgorb_keypoint* K; const uint8_t* D; const int32_t* n; int cap;
+    const uint32_t* fvNode; const int32_t* fvStart; const uint32_t* fvFeat; const int32_t* nfv;
+    const int32_t* pairKF1; const int32_t* pairKF2; const float* F12; const float* epipole;
+    const uint8_t* hasPoint2;              // [npairs][cap] (a zeroed scratch array when the caller passes none)
+    float epiTh[PG_MAXL + 1];              // 100*mvScaleFactors[octave] (float, :749)
+    double lineTh[PG_MAXL + 1];            // 3.84*mvLevelSigma2[octave] (double, :158)
+};
+#define TRI_R 4                  // KF2 keypoints per lane held in registers: nodes of up to 256 KF2 keypoints
+#define TRI_WAVES 64             // waves per pair, each takes the KF1 nodes a = wave, wave + 64, ...
+
+// the KF1-independent part of a candidate: has_point2 (:724-728) and the epipole test (:745-751, float; a NaN / infinite
+// epipole never rejects)
+__device__ __forceinline__ bool tri_candidate(const pgorb_keypoint& kp2, bool hasPoint, float ex, float ey, const float* epiTh)
+{
+    if (hasPoint) return false;
+    const float dx = __fsub_rn(ex, kp2.x), dy = __fsub_rn(ey, kp2.y);
+    return !(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)) < epiTh[min((unsigned)kp2.octave, (unsigned)PG_MAXL)]);
+}
+// CheckDistEpipolarLine (:142-159) past the den == 0 test: num = a*x2 + b*y2 + c, dsqr = num*num/den in float, compared in double
+__device__ __forceinline__ bool tri_on_line(float la, float lb, float lc, float den, float x2, float y2, double th)
+{
+    const float num = __fadd_rn(__fadd_rn(__fmul_rn(la, x2), __fmul_rn(lb, y2)), lc);
+    return (double)__fdiv_rn(__fmul_rn(num, num), den) < th;
+}
+
+__global__ __launch_bounds__(64) void k_search_for_triangulation(PgTriBatch T, int checkOrientation, int32_t* __restrict__ matchesOut,
+                                                                 int8_t* __restrict__ binOut)
+{
+    const int p = blockIdx.y, f1 = T.pairKF1[p], f2 = T.pairKF2[p], cap = T.cap, lane = threadIdx.x;
+    __shared__ float sEpi[PG_MAXL + 1];
+    __shared__ double sLine[PG_MAXL + 1];
+    __shared__ float sGeo[11];                                            // F12 (row-major), ex, ey
+    if (lane <= PG_MAXL) { sEpi[lane] = T.epiTh[lane]; sLine[lane] = T.lineTh[lane]; }
+    if (lane < 9) sGeo[lane] = T.F12[(int64_t)p * 9 + lane];
+    else if (lane < 11) sGeo[lane] = T.epipole[2 * p + lane - 9];
+    __syncthreads();
+    const uint8_t* __restrict__ desc1 = T.D + (int64_t)f1 * cap * 32;
+    const uint8_t* __restrict__ desc2 = T.D + (int64_t)f2 * cap * 32;
+    const pgorb_keypoint* __restrict__ K1 = T.K + (int64_t)f1 * cap;
+    const pgorb_keypoint* __restrict__ K2 = T.K + (int64_t)f2 * cap;
+    const uint8_t* __restrict__ has2 = T.hasPoint2 + (int64_t)p * cap;
+    const uint32_t* __restrict__ aNode = T.fvNode + (int64_t)f1 * cap; const int32_t* __restrict__ aStart = T.fvStart + (int64_t)f1 * (cap + 1);
+    const uint32_t* __restrict__ aFeat = T.fvFeat + (int64_t)f1 * cap;
+    const uint32_t* __restrict__ bNode = T.fvNode + (int64_t)f2 * cap; const int32_t* __restrict__ bStart = T.fvStart + (int64_t)f2 * (cap + 1);
+    const uint32_t* __restrict__ bFeat = T.fvFeat + (int64_t)f2 * cap;
+    const int nA = T.nfv[f1], nB = T.nfv[f2];
+    const float ex = sGeo[9], ey = sGeo[10];
+    matchesOut += (int64_t)p * cap; binOut += (int64_t)p * cap;
+    for (int a = blockIdx.x; a < nA; a += TRI_WAVES) {
+        const uint32_t node = aNode[a];
+        int lo = 0, hi = nB;                                              // KF2's entry of the same node (both lists ascend)
+        while (lo < hi) { const int mid = (lo + hi) >> 1; if (bNode[mid] < node) lo = mid + 1; else hi = mid; }
+        if (lo >= nB || bNode[lo] != node) continue;
+        const int a0 = aStart[a], a1 = aStart[a + 1], b0 = bStart[lo], b1 = bStart[lo + 1], nb = b1 - b0;
+        const bool inRegs = nb <= 64 * TRI_R;
+        // KF2's keypoints of the node: lane holds list positions k = lane, lane + 64, ...; idx2 = -1: no candidate for any KF1 keypoint
+        uint4 d0[TRI_R], d1[TRI_R]; float x2[TRI_R], y2[TRI_R], ang2[TRI_R]; double th2[TRI_R]; int idx2[TRI_R];
+#pragma unroll
+        for (int r = 0; r < TRI_R; r++) {
+            const int k = 64 * r + lane;
+            idx2[r] = -1; x2[r] = y2[r] = ang2[r] = 0.f; th2[r] = 0.0; d0[r] = make_uint4(0, 0, 0, 0); d1[r] = d0[r];
+            if (inRegs && k < nb) {
+                const int j = (int)bFeat[b0 + k];
+                const pgorb_keypoint kp2 = K2[j];
+                if (tri_candidate(kp2, has2[j] != 0, ex, ey, sEpi)) {
+                    idx2[r] = j;
+                    d0[r] = reinterpret_cast<const uint4*>(desc2 + (int64_t)j * 32)[0];
+                    d1[r] = reinterpret_cast<const uint4*>(desc2 + (int64_t)j * 32)[1];
+                    x2[r] = kp2.x; y2[r] = kp2.y; ang2[r] = kp2.angle;
+                    th2[r] = sLine[min((unsigned)kp2.octave, (unsigned)PG_MAXL)];
+                }
+            }
+        }
+        // KF1's keypoints of the node: the index two iterations ahead, descriptor and keypoint one ahead (all lanes load the same
+        // addresses); nothing inside the loop depends on an earlier KF1 keypoint
+        int idxN = a0 < a1 ? (int)aFeat[a0] : 0, idxN2 = a0 + 1 < a1 ? (int)aFeat[a0 + 1] : 0;
+        uint4 nq0 = make_uint4(0, 0, 0, 0), nq1 = nq0;
+        float nx = 0.f, ny = 0.f, nang = 0.f;
+        if (a0 < a1) {
+            nq0 = reinterpret_cast<const uint4*>(desc1 + (int64_t)idxN * 32)[0]; nq1 = reinterpret_cast<const uint4*>(desc1 + (int64_t)idxN * 32)[1];
+            nx = K1[idxN].x; ny = K1[idxN].y; nang = K1[idxN].angle;
+        }
+        for (int ia = a0; ia < a1; ia++) {
+            const int idx1 = __builtin_amdgcn_readfirstlane(idxN);
+            const uint4 q0 = nq0, q1 = nq1;
+            const float x1 = nx, y1 = ny, ang1 = nang;
+            idxN = idxN2;
+            idxN2 = ia + 2 < a1 ? (int)aFeat[ia + 2] : 0;
+            if (ia + 1 < a1) {
+                nq0 = reinterpret_cast<const uint4*>(desc1 + (int64_t)idxN * 32)[0]; nq1 = reinterpret_cast<const uint4*>(desc1 + (int64_t)idxN * 32)[1];
+                nx = K1[idxN].x; ny = K1[idxN].y; nang = K1[idxN].angle;
+            }
+            // the epipolar line of kp1 in KF2, l = x1'F12 = [a b c] (:145-147), and den = a*a + b*b (:151); F12.at<float>(r, c) =
+            // sGeo[3 * r + c], read from the LDS per keypoint (held in SGPRs across the loop they overflowed the SGPR file)
+            const float F00 = sGeo[0], F01 = sGeo[1], F02 = sGeo[2], F10 = sGeo[3], F11 = sGeo[4], F12 = sGeo[5], F20 = sGeo[6], F21 = sGeo[7], F22 = sGeo[8];
+            const float la = __fadd_rn(__fadd_rn(__fmul_rn(x1, F00), __fmul_rn(y1, F10)), F20);
+            const float lb = __fadd_rn(__fadd_rn(__fmul_rn(x1, F01), __fmul_rn(y1, F11)), F21);
+            const float lc = __fadd_rn(__fadd_rn(__fmul_rn(x1, F02), __fmul_rn(y1, F12)), F22);
+            const float den = __fadd_rn(__fmul_rn(la, la), __fmul_rn(lb, lb));
+            if (den == 0.0f) continue;                                    // every candidate fails CheckDistEpipolarLine (:153-154)
+            unsigned best = 0xFFFFFFFFu;
+            if (inRegs) {
+#pragma unroll
+                for (int r = 0; r < TRI_R; r++) {                       // (no branches: every slot is evaluated, empty ones drop out)
+                    const int dist = __popc(q0.x ^ d0[r].x) + __popc(q0.y ^ d0[r].y) + __popc(q0.z ^ d0[r].z) + __popc(q0.w ^ d0[r].w) +
+                                     __popc(q1.x ^ d1[r].x) + __popc(q1.y ^ d1[r].y) + __popc(q1.z ^ d1[r].z) + __popc(q1.w ^ d1[r].w);
+                    const bool pass = idx2[r] >= 0 && dist <= TH_LOW && tri_on_line(la, lb, lc, den, x2[r], y2[r], th2[r]);
+                    best = min(best, pass ? ((unsigned)dist << 16) | (unsigned)(0xFFFF - (64 * r + lane)) : 0xFFFFFFFFu);
+                }
+            } else {                                                      // a node with more KF2 keypoints than the registers hold
+                for (int k = lane; k < nb; k += 64) {
+                    const int j = (int)bFeat[b0 + k];
+                    const pgorb_keypoint kp2 = K2[j];
+                    if (!tri_candidate(kp2, has2[j] != 0, ex, ey, sEpi)) continue;
+                    const int dist = sfi_distance(q0, q1, desc2 + (int64_t)j * 32);
+                    if (dist > TH_LOW || !tri_on_line(la, lb, lc, den, kp2.x, kp2.y, sLine[min((unsigned)kp2.octave, (unsigned)PG_MAXL)])) continue;
+                    best = min(best, ((unsigned)dist << 16) | (unsigned)(0xFFFF - k));
+                }
+            }
+            const unsigned w = wave_min_u32(best);
+            if (w == 0xFFFFFFFFu) continue;
+            const int kbest = 0xFFFF - (int)(w & 0xFFFFu);
+            if ((kbest & 63) == lane) {                                   // the lane that holds the winner files it (:758-777)
+                int j; float a2;
+                if (inRegs) {
+                    const int r = kbest >> 6;
+                    j = idx2[0]; a2 = ang2[0];
+#pragma unroll
+                    for (int rr = 1; rr < TRI_R; rr++) if (r == rr) { j = idx2[rr]; a2 = ang2[rr]; }
+                } else {
+                    j = (int)bFeat[b0 + kbest]; a2 = K2[j].angle;
+                }
+                matchesOut[idx1] = j;
+                binOut[idx1] = (int8_t)(checkOrientation ? proj_bin(ang1, a2) : -1);
+            }
+        }
+    }
 }
 
 // FeatureVector of every frame of a batch (DBoW2 FeatureVector::addFeature, FeatureVector.cpp:31-45, as
@@ -1411,7 +1569,8 @@ int pgorb_search_by_bow_batch_device(pgorb_ctx* c, const pgorb_keypoint* d_kps, 
         hipMemsetAsync(bins, 0xFF, (size_t)npairs * cap, (hipStream_t)stream) != hipSuccess) return pg_ctx_fail(c, PGORB_E_HIP, "hipMemsetAsync failed");
     PgBowBatch B = {d_kps, d_desc, d_n, cap, d_fv_node, d_fv_start, d_fv_feat, d_nfv, d_pair_kf, d_pair_f, d_kf_point_valid};
     hipLaunchKernelGGL(k_search_by_bow, dim3(BOW_WAVES, npairs), dim3(64), 0, (hipStream_t)stream, B, nnratio, check_orientation, d_matches, bins);
-    hipLaunchKernelGGL(k_bow_finish, dim3(npairs), dim3(64), 0, (hipStream_t)stream, B, check_orientation, d_matches, bins, d_nmatches);
+    hipLaunchKernelGGL(k_match_finish, dim3(npairs), dim3(64), 0, (hipStream_t)stream, d_pair_f, d_n, cap, (const uint8_t*)nullptr,
+                       check_orientation, d_matches, bins, d_nmatches);
     if (hipGetLastError() != hipSuccess) return pg_ctx_fail(c, PGORB_E_HIP, "k_search_by_bow launch failed");
     return pg_ctx_scratch_done(c, (hipStream_t)stream);
 }
@@ -1467,6 +1626,110 @@ int pgorb_search_by_bow(pgorb_ctx* c, const uint8_t* kf_desc, const float* kf_an
     if (hipMemcpyAsync(h, d + oM, downBytes, hipMemcpyDeviceToHost, 0) != hipSuccess || hipStreamSynchronize(0) != hipSuccess)
         return pg_ctx_fail(c, PGORB_E_HIP, "hipMemcpy D2H failed");
     memcpy(matches, h, (size_t)nf * 4);
+    int32_t nm;
+    memcpy(&nm, h + (oNM - oM), 4);
+    return nm;
+}
+
+int pgorb_search_for_triangulation_batch_device(pgorb_ctx* c, const pgorb_keypoint* d_kps, const uint8_t* d_desc, const int32_t* d_n, int cap,
+                                                const uint32_t* d_fv_node, const int32_t* d_fv_start, const uint32_t* d_fv_feat, const int32_t* d_nfv,
+                                                const int32_t* d_pair_kf1, const int32_t* d_pair_kf2, int npairs, const float* d_F12,
+                                                const float* d_epipole, const uint8_t* d_has_point1, const uint8_t* d_has_point2,
+                                                int check_orientation, int32_t* d_matches12, int32_t* d_nmatches, void* stream)
+{
+    if (!c) return PGORB_E_ARG;
+    if (!d_kps || !d_desc || !d_n || cap < 1 || !d_fv_node || !d_fv_start || !d_fv_feat || !d_nfv || npairs < 0 ||
+        (npairs && (!d_pair_kf1 || !d_pair_kf2 || !d_F12 || !d_epipole || !d_matches12 || !d_nmatches)))
+        return pg_ctx_fail(c, PGORB_E_ARG, "bad argument to pgorb_search_for_triangulation_batch_device");
+    if (cap > 16000) return pg_ctx_fail(c, PGORB_E_LIMIT, "more than 16000 keypoints per frame");
+    if (!npairs) return 0;
+    if (hipSetDevice(pg_ctx_device(c)) != hipSuccess) return pg_ctx_fail(c, PGORB_E_HIP, "hipSetDevice failed");
+    PgTriBatch T = {d_kps, d_desc, d_n, cap, d_fv_node, d_fv_start, d_fv_feat, d_nfv, d_pair_kf1, d_pair_kf2, d_F12, d_epipole, d_has_point2, {0}, {0}};
+    // the thresholds per octave exactly as the reference forms them: 100*float (int promoted to float) and 3.84*double(float)
+    float sf[PG_MAXL + 1] = {0}, s2[PG_MAXL + 1] = {0};
+    pgorb_scale_tables(c, sf, nullptr, s2, nullptr);
+    for (int l = 0; l <= PG_MAXL; l++) { T.epiTh[l] = 100.0f * sf[l]; T.lineTh[l] = 3.84 * (double)s2[l]; }
+    // scratch: the rotation bin of every matched KF1 keypoint [npairs][cap] i8, then (no d_has_point2) an all-zero mask
+    void* scratch;
+    const size_t binBytes = ((size_t)npairs * cap + 255) & ~(size_t)255;
+    int rcs = pg_ctx_scratch(c, binBytes + (d_has_point2 ? 0 : (size_t)npairs * cap) + 256, (hipStream_t)stream, &scratch);
+    if (rcs) return rcs;
+    int8_t* bins = (int8_t*)scratch;
+    if (!d_has_point2) {
+        T.hasPoint2 = (const uint8_t*)scratch + binBytes;
+        if (hipMemsetAsync((uint8_t*)scratch + binBytes, 0, (size_t)npairs * cap, (hipStream_t)stream) != hipSuccess)
+            return pg_ctx_fail(c, PGORB_E_HIP, "hipMemsetAsync failed");
+    }
+    if (hipMemsetAsync(d_matches12, 0xFF, (size_t)npairs * cap * 4, (hipStream_t)stream) != hipSuccess ||
+        hipMemsetAsync(bins, 0xFF, (size_t)npairs * cap, (hipStream_t)stream) != hipSuccess) return pg_ctx_fail(c, PGORB_E_HIP, "hipMemsetAsync failed");
+    hipLaunchKernelGGL(k_search_for_triangulation, dim3(TRI_WAVES, npairs), dim3(64), 0, (hipStream_t)stream, T, check_orientation, d_matches12, bins);
+    hipLaunchKernelGGL(k_match_finish, dim3(npairs), dim3(64), 0, (hipStream_t)stream, d_pair_kf1, d_n, cap, d_has_point1,
+                       check_orientation, d_matches12, bins, d_nmatches);
+    if (hipGetLastError() != hipSuccess) return pg_ctx_fail(c, PGORB_E_HIP, "k_search_for_triangulation launch failed");
+    return pg_ctx_scratch_done(c, (hipStream_t)stream);
+}
+
+// a FeatureVector as CSR: starts from 0, ascending, inside n, every feature index below n
+static bool pg_fv_ok(const int32_t* start, const uint32_t* feat, int nfv, int n)
+{
+    if (nfv > n || start[0] != 0 || start[nfv] > n) return false;
+    for (int a = 0; a < nfv; a++) if (start[a + 1] < start[a]) return false;
+    for (int i = 0; i < start[nfv]; i++) if (feat[i] >= (uint32_t)n) return false;
+    return true;
+}
+
+// single pair through host buffers: the pair becomes a two-frame batch (KF1 = frame 0, KF2 = frame 1)
+int pgorb_search_for_triangulation(pgorb_ctx* c, const pgorb_keypoint* kps1, const uint8_t* desc1, const uint8_t* has_point1, int n1,
+                                   const uint32_t* fv1_node, const int32_t* fv1_start, const uint32_t* fv1_feat, int nfv1,
+                                   const pgorb_keypoint* kps2, const uint8_t* desc2, const uint8_t* has_point2, int n2,
+                                   const uint32_t* fv2_node, const int32_t* fv2_start, const uint32_t* fv2_feat, int nfv2,
+                                   const float F12[9], float ex, float ey, int check_orientation, int32_t* matches12)
+{
+    if (!c) return PGORB_E_ARG;
+    if (n1 < 0 || n2 < 0 || nfv1 < 0 || nfv2 < 0 || !F12 || (n1 && !matches12) || (n1 && (!kps1 || !desc1)) || (n2 && (!kps2 || !desc2)) ||
+        !fv1_start || !fv2_start || (nfv1 && (!fv1_node || !fv1_feat)) || (nfv2 && (!fv2_node || !fv2_feat)))
+        return pg_ctx_fail(c, PGORB_E_ARG, "bad argument to pgorb_search_for_triangulation");
+    if (n1 > 16000 || n2 > 16000) return pg_ctx_fail(c, PGORB_E_LIMIT, "more than 16000 keypoints");
+    if (!pg_fv_ok(fv1_start, fv1_feat, nfv1, n1) || !pg_fv_ok(fv2_start, fv2_feat, nfv2, n2))
+        return pg_ctx_fail(c, PGORB_E_ARG, "pgorb_search_for_triangulation: FeatureVector names more features than the key frame has");
+    for (int i = 0; i < n1; i++) matches12[i] = -1;
+    if (!n1 || !n2 || !nfv1 || !nfv2) return 0;
+    const int cap = std::max(n1, n2);
+    auto al = [](size_t v) { return (v + 63) & ~(size_t)63; };
+    size_t off = 0;
+    auto place = [&](size_t bytes) { const size_t o = off; off += al(bytes); return o; };
+    const size_t oK = place((size_t)2 * cap * sizeof(pgorb_keypoint)), oD = place((size_t)2 * cap * 32), oN = place(8),
+                 oH1 = place(cap), oH2 = place(cap), oFN = place((size_t)2 * cap * 4), oFS = place((size_t)2 * (cap + 1) * 4),
+                 oFF = place((size_t)2 * cap * 4), oNF = place(8), oP = place(8), oF = place(9 * 4), oE = place(8),
+                 oM = place((size_t)cap * 4), oNM = place(64);
+    void *dv, *hv;
+    int rc = pg_ctx_stage(c, 0, off, &dv);
+    if (rc) return rc;
+    // everything the host supplies sits before oM: one upload from the page-locked buffer; oM.. is one download
+    const size_t upBytes = oM, downBytes = off - oM;
+    if ((rc = pg_ctx_pinned(c, std::max(upBytes, downBytes), &hv))) return rc;
+    uint8_t* d = (uint8_t*)dv; uint8_t* h = (uint8_t*)hv;
+    memset(h, 0, upBytes);
+    const int32_t nn[2] = {n1, n2}, nfvs[2] = {nfv1, nfv2}, pr[2] = {0, 1};
+    const float ep[2] = {ex, ey};
+    auto up = [&](size_t o, const void* p, size_t n) { if (n && p) memcpy(h + o, p, n); };
+    up(oK, kps1, (size_t)n1 * sizeof(pgorb_keypoint)); up(oK + (size_t)cap * sizeof(pgorb_keypoint), kps2, (size_t)n2 * sizeof(pgorb_keypoint));
+    up(oD, desc1, (size_t)n1 * 32); up(oD + (size_t)cap * 32, desc2, (size_t)n2 * 32);
+    up(oN, nn, 8); up(oH1, has_point1, n1); up(oH2, has_point2, n2);
+    up(oFN, fv1_node, (size_t)nfv1 * 4); up(oFN + (size_t)cap * 4, fv2_node, (size_t)nfv2 * 4);
+    up(oFS, fv1_start, (size_t)(nfv1 + 1) * 4); up(oFS + (size_t)(cap + 1) * 4, fv2_start, (size_t)(nfv2 + 1) * 4);
+    up(oFF, fv1_feat, (size_t)fv1_start[nfv1] * 4); up(oFF + (size_t)cap * 4, fv2_feat, (size_t)fv2_start[nfv2] * 4);
+    up(oNF, nfvs, 8); up(oP, pr, 8); up(oF, F12, 9 * 4); up(oE, ep, 8);
+    if (hipMemcpyAsync(d, h, upBytes, hipMemcpyHostToDevice, 0) != hipSuccess) return pg_ctx_fail(c, PGORB_E_HIP, "hipMemcpy H2D failed");
+    rc = pgorb_search_for_triangulation_batch_device(c, (const pgorb_keypoint*)(d + oK), d + oD, (const int32_t*)(d + oN), cap,
+                                                     (const uint32_t*)(d + oFN), (const int32_t*)(d + oFS), (const uint32_t*)(d + oFF),
+                                                     (const int32_t*)(d + oNF), (const int32_t*)(d + oP), (const int32_t*)(d + oP) + 1, 1,
+                                                     (const float*)(d + oF), (const float*)(d + oE), d + oH1, d + oH2, check_orientation,
+                                                     (int32_t*)(d + oM), (int32_t*)(d + oNM), nullptr);
+    if (rc) return rc;
+    if (hipMemcpyAsync(h, d + oM, downBytes, hipMemcpyDeviceToHost, 0) != hipSuccess || hipStreamSynchronize(0) != hipSuccess)
+        return pg_ctx_fail(c, PGORB_E_HIP, "hipMemcpy D2H failed");
+    memcpy(matches12, h, (size_t)n1 * 4);
     int32_t nm;
     memcpy(&nm, h + (oNM - oM), 4);
     return nm;

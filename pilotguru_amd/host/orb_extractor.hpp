@@ -1,13 +1,15 @@
 // orb_extractor.hpp -- C++ host-side mirror of ORB_SLAM2::ORBextractor / ORBmatcher over the
 // C ABI (include/pgorb.h).  Same names, argument meaning and error behaviour as
 //   thirdparty/orb-slam2/include/ORBextractor.h:44-110   (operator(), Get* accessors)
-//   thirdparty/orb-slam2/include/ORBmatcher.h:40-53      (DescriptorDistance, SearchForInitialization)
+//   thirdparty/orb-slam2/include/ORBmatcher.h:40-53      (DescriptorDistance, SearchForInitialization,
+//                                                          SearchForTriangulation)
 // but OpenCV-free: images are raw 8-bit planes, keypoints are pgorb_keypoint (the cv::KeyPoint
 // layout), descriptors are N x 32 bytes.  INTEGRATION.md shows the cv::Mat-typed variant a
 // pilotguru maintainer drops into Frame::ExtractORB.
 #pragma once
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/pgorb.h"
@@ -76,6 +78,15 @@ struct Frame {
     int N() const { return (int)mvKeysUndistorted.size(); }
 };
 
+// DBoW2::FeatureVector as CSR (what pgorb_bow_vectors returns): node ids ascending, the features of node k at
+// mFeat[mStart[k] .. mStart[k + 1]).
+struct FeatureVector {
+    std::vector<uint32_t> mNode;
+    std::vector<int32_t> mStart{0};
+    std::vector<uint32_t> mFeat;
+    int size() const { return (int)mNode.size(); }
+};
+
 class ORBmatcher {
  public:
     static const int TH_LOW = 50, TH_HIGH = 100, HISTO_LENGTH = 30;     // ORBmatcher.cc:38-40
@@ -94,6 +105,40 @@ class ORBmatcher {
                                                        vbPrevMatched.data(), vnMatches12.data(), windowSize, mfNNratio,
                                                        mbCheckOrientation ? 1 : 0);
         if (rc < 0) throw std::runtime_error(pgorb_last_error(ctx_));
+        return rc;
+    }
+    // SearchForTriangulation(pKF1, pKF2, F12, vMatchedPairs, bOnlyStereo = false) (ORBmatcher.cc:659-825): F12 row-major
+    // (F12.at<float>(r, c)), (ex, ey) the epipole in KF2 (:665-672), hasPoint[i] = GetMapPoint(i) != NULL (empty = none).
+    int SearchForTriangulation(const Frame& KF1, const Frame& KF2, const FeatureVector& fv1, const FeatureVector& fv2,
+                               const float F12[9], float ex, float ey, const std::vector<uint8_t>& hasPoint1,
+                               const std::vector<uint8_t>& hasPoint2, std::vector<std::pair<size_t, size_t> >& vMatchedPairs)
+    {
+        // the library reads N mask entries, N descriptors and mStart[n] feature indices through these pointers
+        const Frame* kf[2] = {&KF1, &KF2};
+        const std::vector<uint8_t>* has[2] = {&hasPoint1, &hasPoint2};
+        const FeatureVector* fv[2] = {&fv1, &fv2};
+        for (int k = 0; k < 2; k++) {
+            if (kf[k]->mDescriptors.size() != (size_t)kf[k]->N() * 32)
+                throw std::invalid_argument("SearchForTriangulation: descriptors are not N x 32 bytes");
+            if (!has[k]->empty() && has[k]->size() != (size_t)kf[k]->N())
+                throw std::invalid_argument("SearchForTriangulation: a hasPoint mask is neither empty nor N entries long");
+            if (fv[k]->mStart.size() != fv[k]->mNode.size() + 1 || fv[k]->mStart.back() < 0 ||
+                fv[k]->mFeat.size() < (size_t)fv[k]->mStart.back())
+                throw std::invalid_argument("SearchForTriangulation: FeatureVector arrays of inconsistent lengths");
+        }
+        vMatchedPairs.clear();
+        std::vector<int32_t> m12(KF1.N() > 0 ? KF1.N() : 1, -1);
+        const int rc = pgorb_search_for_triangulation(ctx_, KF1.mvKeysUndistorted.data(), KF1.mDescriptors.data(),
+                                                      hasPoint1.empty() ? nullptr : hasPoint1.data(), KF1.N(),
+                                                      fv1.mNode.data(), fv1.mStart.data(), fv1.mFeat.data(), fv1.size(),
+                                                      KF2.mvKeysUndistorted.data(), KF2.mDescriptors.data(),
+                                                      hasPoint2.empty() ? nullptr : hasPoint2.data(), KF2.N(),
+                                                      fv2.mNode.data(), fv2.mStart.data(), fv2.mFeat.data(), fv2.size(),
+                                                      F12, ex, ey, mbCheckOrientation ? 1 : 0, m12.data());
+        if (rc < 0) throw std::runtime_error(pgorb_last_error(ctx_));
+        vMatchedPairs.reserve(rc);
+        for (int i = 0; i < KF1.N(); i++)                              // :814-822
+            if (m12[i] >= 0) vMatchedPairs.push_back(std::make_pair((size_t)i, (size_t)m12[i]));
         return rc;
     }
 

@@ -408,6 +408,34 @@ class ORBmatcher:
             self.mfNNratio, int(self.mbCheckOrientation), _p(out)))
         return nm, out[:F.N].copy()
 
+    def SearchForTriangulation(self, KF1, KF2, F12, epipole, fv1, fv2, has_point1=None, has_point2=None):
+        """SearchForTriangulation(pKF1, pKF2, F12, vMatchedPairs, bOnlyStereo=false) (src/ORBmatcher.cc:659-825, 142-159) on
+        the undistorted keypoints of two Frames.  F12: 3x3 (or 9) float32, F12.at<float>(r, c) row-major; epipole = (ex, ey) in
+        KF2; fv1 / fv2 the (nodes, starts, features) triples of ORBVocabulary.transform(); has_point*[i] = GetMapPoint(i) != NULL.
+        Returns (nmatches, matches12) with matches12[i] = the KF2 keypoint matched to KF1 keypoint i, or -1 (vMatchedPairs =
+        the (i, matches12[i]) with matches12[i] >= 0)."""
+        F = np.ascontiguousarray(F12, np.float32).reshape(9)
+        masks = [np.ascontiguousarray(m if m is not None else np.zeros(max(K.N, 1), np.uint8), np.uint8).reshape(-1)
+                 for m, K in ((has_point1, KF1), (has_point2, KF2))]
+        fvs = [[np.ascontiguousarray(fv[0], np.uint32).reshape(-1), np.ascontiguousarray(fv[1], np.int32).reshape(-1),
+                np.ascontiguousarray(fv[2], np.uint32).reshape(-1)] for fv in (fv1, fv2)]
+        # the library reads N mask entries, N descriptors and start[nfv] feature indices through these pointers
+        for name, K, given, fv in (("KF1", KF1, has_point1, fvs[0]), ("KF2", KF2, has_point2, fvs[1])):
+            if K.mDescriptors.shape != (K.N, 32) or len(K.mvKeysUndistorted) != K.N:
+                raise ValueError("%s: %d keypoints need %d x 32 descriptors" % (name, K.N, K.N))
+            if given is not None and np.size(given) != K.N:
+                raise ValueError("%s: has_point holds %d entries for %d keypoints" % (name, np.size(given), K.N))
+            if len(fv[1]) != len(fv[0]) + 1 or len(fv[2]) < int(fv[1][-1]):
+                raise ValueError("%s: FeatureVector arrays of inconsistent lengths" % name)
+        ext = KF1.ext
+        m12 = np.full(max(KF1.N, 1), -1, np.int32)
+        args = []
+        for K, m, fv in ((KF1, masks[0], fvs[0]), (KF2, masks[1], fvs[1])):
+            args += [_p(K.mvKeysUndistorted), _p(K.mDescriptors), _p(m), K.N, _p(fv[0]), _p(fv[1]), _p(fv[2]), len(fv[0])]
+        nm = ext._check(ext._L.pgorb_search_for_triangulation(ext._h, *args, _p(F), float(np.float32(epipole[0])),
+                                                              float(np.float32(epipole[1])), int(self.mbCheckOrientation), _p(m12)))
+        return nm, m12[:KF1.N].copy()
+
     def SearchForInitialization(self, F1, F2, vbPrevMatched, windowSize=10):
         """(nmatches, vnMatches12); vbPrevMatched ([N1,2] float32) is updated in place, as in
         src/ORBmatcher.cc:407-522."""

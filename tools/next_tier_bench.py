@@ -7,6 +7,8 @@ next to each, the oracle's CPU time for the same work (1 thread, a few frames, s
   grid         Frame::AssignFeaturesToGrid (Frame.cc:234-249), 64 x 48 cells, CSR
   init-match   ORBmatcher::SearchForInitialization (ORBmatcher.cc:407-522), window 100, every frame vs its predecessor
   bow          ORBVocabulary::transform (TemplatedVocabulary.h:1126-1259) on an ORBvoc-sized tree (k = 10, L = 6)
+  triangulate  ORBmatcher::SearchForTriangulation (ORBmatcher.cc:659-825): one host pair, and key frames of the batch against
+               20 neighbours each, as LocalMapping::CreateNewMapPoints calls it (LocalMapping.cc:212-270); no CPU column
 
 usage: python tools/next_tier_bench.py [--batch 128] [--out profiles/r02_next_tier.txt]"""
 import argparse, ctypes as C, os, sys, time
@@ -137,6 +139,23 @@ prevm = np.stack([F1.mvKeys["x"], F1.mvKeys["y"]], 1).astype(np.float32)
 g_ms = wall(lambda: sm.SearchForInitialization(F1, F2, prevm.copy(), 100))
 host_rows.append(("SearchForInitialization(F1, F2, 100), one pair through the host API", g_ms, c_sfi / (B - 1)))
 
+
+def sideways_geometry(frames_apart, focal=500.0):
+    """F12 and the epipole of a sideways motion along the ride's (2, 1) px shift (LocalMapping::ComputeF12, float32)."""
+    K = np.array([[focal, 0, w / 2.0], [0, focal, h / 2.0], [0, 0, 1]], np.float32)
+    Ki = np.linalg.inv(K.astype(np.float64)).astype(np.float32)
+    t = np.array([0.02 * frames_apart, 0.01 * frames_apart, 1e-4], np.float32)
+    tx = np.array([[0, -t[2], t[1]], [t[2], 0, -t[0]], [-t[1], t[0], 0]], np.float32)
+    return (Ki.T @ tx @ Ki).astype(np.float32), (np.float32(focal * t[0] / t[2] + w / 2.0), np.float32(focal * t[1] / t[2] + h / 2.0))
+
+
+F12h, eph = sideways_geometry(1)
+has1 = (rng.uniform(size=F1.N) < 0.3).astype(np.uint8); has2 = (rng.uniform(size=F2.N) < 0.3).astype(np.uint8)
+m = pg.ORBmatcher(0.6, True)
+tnm, _ = m.SearchForTriangulation(F1, F2, F12h, eph, fvK, fvF, has1, has2)
+g_ms = wall(lambda: m.SearchForTriangulation(F1, F2, F12h, eph, fvK, fvF, has1, has2))
+host_rows.append(("SearchForTriangulation(KF1, KF2, F12), %d nodes -> %d" % (len(fvK[0]), tnm), g_ms, float("nan")))
+
 # ---- round 3: the same three matchers as BATCHED, RESIDENT calls: every frame against its predecessor, all pairs in one launch ----
 npairs = B - 1
 qn = min(int(nk * 0.8), 2000)
@@ -177,6 +196,22 @@ kfvd = torch.from_numpy((rng.uniform(size=(npairs, cap)) > 0.3).astype(np.uint8)
 t_bw = timed(lambda: ext._check(ext._L.pgorb_search_by_bow_batch_device(ext._h, p(kps), p(desc), p(n), cap, p(fvn), p(fvs), p(fvf), p(nfvd), p(pairK), p(pairF), npairs,
              p(kfvd), 0.7, 1, p(asg), p(nmb), s)))
 batch_rows.append(("SearchByBoW(KeyFrame, Frame): %d pairs -> %d" % (npairs, int(nmb.float().mean())), t_bw, host_rows[2][2]))
+# SearchForTriangulation: every 5th frame from the 21st on is a new key frame matched against its 20 predecessors (CreateNewMapPoints'
+# covisible neighbours), all pairs in one launch; the per-pair figures divide by these pairs, not by npairs
+tri = [(k, k - d) for k in range(20, B, 5) for d in range(1, 21)]
+ntri = len(tri)
+if ntri:
+    geo = [sideways_geometry(a - b) for a, b in tri]
+    tF = torch.from_numpy(np.stack([g[0].reshape(9) for g in geo])).cuda()
+    tE = torch.from_numpy(np.array([g[1] for g in geo], np.float32)).cuda()
+    tA = torch.tensor([a for a, _ in tri], dtype=torch.int32, device="cuda"); tB = torch.tensor([b for _, b in tri], dtype=torch.int32, device="cuda")
+    tH1 = torch.from_numpy((rng.uniform(size=(ntri, cap)) < 0.3).astype(np.uint8)).cuda()
+    tH2 = torch.from_numpy((rng.uniform(size=(ntri, cap)) < 0.3).astype(np.uint8)).cuda()
+    tM = torch.empty((ntri, cap), dtype=torch.int32, device="cuda"); tN = torch.empty(ntri, dtype=torch.int32, device="cuda")
+    t_tr = timed(lambda: ext._check(ext._L.pgorb_search_for_triangulation_batch_device(ext._h, p(kps), p(desc), p(n), cap, p(fvn), p(fvs), p(fvf), p(nfvd),
+                 p(tA), p(tB), ntri, p(tF), p(tE), p(tH1), p(tH2), 1, p(tM), p(tN), s)))
+    batch_rows.append(("SearchForTriangulation: %d key frames x 20 neighbours = %d pairs -> %d" % (ntri // 20, ntri, int(tN.float().mean())),
+                       t_tr, float("nan"), ntri))
 
 lines = ["# python tools/next_tier_bench.py --batch %d --features %d   (MI355X; ms per %d-frame 1080p batch; CPU = oracle, 1 thread, one frame or pair scaled to the batch)" % (B, nf, B),
          "# extraction alone (K1-K6): %.3f ms" % t_plain,
@@ -189,8 +224,8 @@ for name, g, cc in host_rows:
     lines.append("%-72s %10.3f %10.2f" % (name, g, cc))
 lines.append("# round 3: batched, resident forms (every frame vs its predecessor, one launch for all pairs; GPU ms per batch and per pair) next to the oracle's one-core ms per pair")
 lines.append("%-86s %10s %12s %12s" % ("call", "GPU ms", "GPU ms/pair", "CPU ms/pair"))
-for name, g, cc in batch_rows:
-    lines.append("%-86s %10.3f %12.4f %12.2f" % (name, g, g / npairs, cc))
+for name, g, cc, *np_ in batch_rows:
+    lines.append("%-86s %10.3f %12.4f %12.2f" % (name, g, g / (np_[0] if np_ else npairs), cc))
 print("\n".join(lines))
 if a.out:
     open(a.out, "w").write("\n".join(lines) + "\n")

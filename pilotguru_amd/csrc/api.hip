@@ -733,13 +733,13 @@ int run_batch(pgorb_ctx* c, const uint8_t* d_gray, bool resident_in_level0, int 
 
 }  // namespace
 
-// ---- helpers used by bow.hip ---------------------------------------------------------------
+// ---- the context services of pgorb_internal.h -----------------------------------------------
 extern "C" void pg_forward_option_to_lanes(pgorb_ctx* c, const char* key, int value);      // (defined behind pgorb_stream)
 int pg_ctx_fail(pgorb_ctx* c, int code, const char* msg) { return fail(c, code, "%s", msg); }
 int pg_ctx_device(pgorb_ctx* c) { return c->prm.device; }
-int pg_ctx_stage(pgorb_ctx* c, int which, size_t bytes, void** p)
+int pg_ctx_stage(pgorb_ctx* c, PgStage which, size_t bytes, void** p)
 {
-    Arena* a = which == 0 ? &c->stageA : which == 1 ? &c->stageB : which == 3 ? &c->stageSfi : &c->stageOut;
+    Arena* a = which == PG_STAGE_A ? &c->stageA : which == PG_STAGE_SFI ? &c->stageSfi : &c->stageOut;
     PG_HIP(c, hipSetDevice(c->prm.device));
     int rc = ensure(c, *a, bytes);
     if (rc) return rc;
@@ -752,7 +752,7 @@ int pg_ctx_stage(pgorb_ctx* c, int which, size_t bytes, void** p)
 // pg_ctx_scratch_done records the event after the last launch that touches the arena.
 int pg_ctx_scratch(pgorb_ctx* c, size_t bytes, hipStream_t s, void** p)
 {
-    int rc = pg_ctx_stage(c, 3, bytes, p);
+    int rc = pg_ctx_stage(c, PG_STAGE_SFI, bytes, p);
     if (rc) return rc;
     if (c->sfiUsed && c->sfiStream != s) PG_HIP(c, hipStreamWaitEvent(s, c->evSfi, 0));
     return 0;
@@ -777,7 +777,6 @@ int pg_ctx_pinned(pgorb_ctx* c, size_t bytes, void** p)
     *p = c->pinned;
     return 0;
 }
-void pg_ctx_vocab_drop(pgorb_ctx* c);
 // header checks of a vocabulary blob of `nbytes` bytes (bow.hip, blob layout): magic, version, and that the sections the
 // header implies fit; the structure itself is checked by pgorb_vocab_from_blob / the loader on the host path and by
 // k_vocab_validate on the device path

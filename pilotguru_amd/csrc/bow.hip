@@ -115,14 +115,6 @@ std::vector<uint8_t> pack_blob(int k, int L, int scoring, int weighting, const s
 
 }  // namespace
 
-// lives in api.hip
-int pg_ctx_vocab_store(pgorb_ctx* c, const void* src, size_t nbytes, bool src_on_device, hipStream_t s);
-int pg_ctx_vocab_get(pgorb_ctx* c, const uint8_t** d_blob, int* k, int* L, int* nnodes);
-void pg_ctx_vocab_drop(pgorb_ctx* c);
-int pg_ctx_fail(pgorb_ctx* c, int code, const char* msg);
-int pg_ctx_stage(pgorb_ctx* c, int which, size_t bytes, void** p);
-int pg_ctx_device(pgorb_ctx* c);
-
 // structural checks of a blob that is already on the device (the host path runs view_blob): child ranges inside
 // children[], child ids and parents inside [0, n), and every child list agrees with the parent array
 // (parent[children[c0 + j]] == i).  With child ids >= 1 that rules out cycles on any path from the root: a node is
@@ -357,7 +349,7 @@ int pg_vocab_validate_resident(pgorb_ctx* c, hipStream_t stream)
     if (rc) return rc;
     if (hipSetDevice(pg_ctx_device(c)) != hipSuccess) return pg_ctx_fail(c, PGORB_E_HIP, "hipSetDevice failed");
     void* flag;
-    if ((rc = pg_ctx_stage(c, 2, 64, &flag))) return rc;
+    if ((rc = pg_ctx_stage(c, PG_STAGE_OUT, 64, &flag))) return rc;
     if (hipMemsetAsync(flag, 0, 4, stream) != hipSuccess) return pg_ctx_fail(c, PGORB_E_HIP, "hipMemsetAsync failed");
     hipLaunchKernelGGL(k_vocab_validate, dim3((nn + 255) / 256), dim3(256), 0, stream, blob, nn, (int*)flag);
     int bad = 0;
@@ -402,19 +394,17 @@ int pgorb_bow_transform(pgorb_ctx* c, const uint8_t* desc, int n, int levelsup, 
     if (n < 0 || (n && (!desc || !word || !weight || !node)))
         return pg_ctx_fail(c, PGORB_E_ARG, "bad argument to pgorb_bow_transform");
     if (!n) return 0;
-    void *dd, *dw, *dwt, *dn;
-    int rc;
-    if ((rc = pg_ctx_stage(c, 0, (size_t)n * 32, &dd))) return rc;
-    if ((rc = pg_ctx_stage(c, 1, (size_t)n * 16 + 64, &dw))) return rc;
-    if ((rc = pg_ctx_stage(c, 2, (size_t)n * 8 + 64, &dwt))) return rc;
-    dn = (uint8_t*)dw + (size_t)n * 4 + (8 - ((size_t)n * 4) % 8) % 8;
-    if (hipMemcpy(dd, desc, (size_t)n * 32, hipMemcpyHostToDevice) != hipSuccess)
-        return pg_ctx_fail(c, PGORB_E_HIP, "hipMemcpy H2D failed");
-    if ((rc = pgorb_bow_transform_device(c, (uint8_t*)dd, n, levelsup, (uint32_t*)dw, (double*)dwt, (uint32_t*)dn, 0))) return rc;
-    if (hipMemcpy(word, dw, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess ||
-        hipMemcpy(weight, dwt, (size_t)n * 8, hipMemcpyDeviceToHost) != hipSuccess ||
-        hipMemcpy(node, dn, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess)
-        return pg_ctx_fail(c, PGORB_E_HIP, "hipMemcpy D2H failed");
+    PgHostCall s(c);
+    const size_t oD = s.region(PG_UP, (size_t)n * 32), oW = s.region(PG_DOWN, (size_t)n * 4), oWt = s.region(PG_DOWN, (size_t)n * 8),
+                 oN = s.region(PG_DOWN, (size_t)n * 4);
+    int rc = s.begin();
+    if (rc) return rc;
+    s.put(oD, desc, (size_t)n * 32);
+    if ((rc = s.run([&] { return pgorb_bow_transform_device(c, s.dev(oD), n, levelsup, s.dev<uint32_t>(oW), s.dev<double>(oWt),
+                                                            s.dev<uint32_t>(oN), nullptr); }))) return rc;
+    memcpy(word, s.host(oW), (size_t)n * 4);
+    memcpy(weight, s.host(oWt), (size_t)n * 8);
+    memcpy(node, s.host(oN), (size_t)n * 4);
     return 0;
 }
 

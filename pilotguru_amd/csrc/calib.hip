@@ -37,9 +37,6 @@
 #include <thread>
 #include <vector>
 
-int pg_ctx_fail(pgorb_ctx* c, int code, const char* msg);
-int pg_ctx_device(pgorb_ctx* c);
-
 namespace {
 
 #define CB_FWD 8

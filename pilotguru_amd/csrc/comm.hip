@@ -32,12 +32,6 @@
 #include <string>
 #include <vector>
 
-int pg_ctx_vocab_reserve(pgorb_ctx* c, size_t nbytes, void** p);           // api.hip
-int pg_ctx_vocab_commit(pgorb_ctx* c, size_t nbytes, hipStream_t s);
-int pg_ctx_vocab_get(pgorb_ctx* c, const uint8_t** d_blob, int* k, int* L, int* nnodes);
-int pg_ctx_vocab_store(pgorb_ctx* c, const void* src, size_t nbytes, bool src_on_device, hipStream_t s);
-int pg_ctx_fail(pgorb_ctx* c, int code, const char* msg);
-int pg_ctx_device(pgorb_ctx* c);
 extern "C" int pg_vocab_validate_resident(pgorb_ctx* c, hipStream_t stream);   // bow.hip
 
 namespace {

@@ -37,13 +37,6 @@
 #define HISTO_LENGTH 30
 #define TH_LOW 50
 
-int pg_ctx_fail(pgorb_ctx* c, int code, const char* msg);
-int pg_ctx_stage(pgorb_ctx* c, int which, size_t bytes, void** p);
-int pg_ctx_device(pgorb_ctx* c);
-int pg_ctx_scratch(pgorb_ctx* c, size_t bytes, hipStream_t s, void** p);      // the matchers' shared arena, ordered across caller streams
-int pg_ctx_scratch_done(pgorb_ctx* c, hipStream_t s);
-int pg_ctx_pinned(pgorb_ctx* c, size_t bytes, void** p);                       // the context's page-locked bounce buffer (synchronous host calls only)
-
 __device__ __forceinline__ int grid_cell_of(const pgorb_keypoint& kp, float minX, float minY, float invW, float invH)
 {
     const int posX = (int)roundf(__fmul_rn(__fsub_rn(kp.x, minX), invW));       // PosInGrid (:388-389)
@@ -1460,6 +1453,19 @@ __global__ __launch_bounds__(256) void k_undistort_keypoints(const pgorb_keypoin
     out[(int64_t)f * cap + i] = k;
 }
 
+// raises kernel K's dynamic LDS limit to `lds` on the context's device, once per device and size (one record per kernel)
+template <auto K> static bool pg_raise_lds(pgorb_ctx* c, size_t lds)
+{
+    static size_t configured[64] = {0};
+    const int dv = pg_ctx_device(c) & 63;
+    if (lds > 160 * 1024) return false;
+    if (lds > configured[dv]) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(K), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return false;
+        configured[dv] = lds;
+    }
+    return true;
+}
+
 extern "C" {
 
 int pgorb_undistort_keypoints_batch_device(pgorb_ctx* c, const pgorb_keypoint* d_kps, const int32_t* d_n, int nframes,
@@ -1482,17 +1488,15 @@ int pgorb_undistort_keypoints(pgorb_ctx* c, const pgorb_keypoint* kps, int n, co
     if (!c) return PGORB_E_ARG;
     if (n < 0 || (n && (!kps || !out)) || !camera || !dist) return pg_ctx_fail(c, PGORB_E_ARG, "bad argument to pgorb_undistort_keypoints");
     if (!n) return 0;
-    void* dv;
-    int rc = pg_ctx_stage(c, 0, (size_t)2 * n * sizeof(pgorb_keypoint) + 128, &dv);
+    const size_t kb = (size_t)n * sizeof(pgorb_keypoint);
+    PgHostCall s(c);
+    const size_t oN = s.region(PG_UP, 4), oK = s.region(PG_UP, kb), oOut = s.region(PG_DOWN, kb);
+    int rc = s.begin();
     if (rc) return rc;
-    pgorb_keypoint* din = (pgorb_keypoint*)dv;
-    pgorb_keypoint* dout = din + n;
-    int32_t* dn = (int32_t*)(((uintptr_t)(dout + n) + 63) & ~(uintptr_t)63);
-    if (hipMemcpy(din, kps, (size_t)n * sizeof(pgorb_keypoint), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(dn, &n, 4, hipMemcpyHostToDevice) != hipSuccess) return pg_ctx_fail(c, PGORB_E_HIP, "hipMemcpy H2D failed");
-    if ((rc = pgorb_undistort_keypoints_batch_device(c, din, dn, 1, n, camera, dist, dout, 0))) return rc;
-    if (hipMemcpy(out, dout, (size_t)n * sizeof(pgorb_keypoint), hipMemcpyDeviceToHost) != hipSuccess)
-        return pg_ctx_fail(c, PGORB_E_HIP, "hipMemcpy D2H failed");
+    s.put(oN, &n, 4); s.put(oK, kps, kb);
+    if ((rc = s.run([&] { return pgorb_undistort_keypoints_batch_device(c, s.dev<pgorb_keypoint>(oK), s.dev<int32_t>(oN), 1, n, camera, dist,
+                                                                        s.dev<pgorb_keypoint>(oOut), nullptr); }))) return rc;
+    memcpy(out, s.host(oOut), kb);
     return 0;
 }
 
@@ -1512,19 +1516,6 @@ int pgorb_image_bounds(int cols, int rows, const float camera[4], const float di
     return 0;
 }
 
-// per-device "dynamic LDS limit already raised to" bookkeeping of the three latency kernels below
-static bool pg_raise_lds(pgorb_ctx* c, const void* fn, int which, size_t lds)
-{
-    static size_t configured[7][64] = {{0}};
-    const int dv = pg_ctx_device(c) & 63;
-    if (lds > 160 * 1024) return false;
-    if (lds > configured[which][dv]) {
-        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return false;
-        configured[which][dv] = lds;
-    }
-    return true;
-}
-
 int pgorb_feature_vectors_batch_device(pgorb_ctx* c, const uint32_t* d_node, const int32_t* d_n, int nframes, int cap,
                                        uint32_t* d_fv_node, int32_t* d_fv_start, uint32_t* d_fv_feat, int32_t* d_nfv, void* stream)
 {
@@ -1536,13 +1527,13 @@ int pgorb_feature_vectors_batch_device(pgorb_ctx* c, const uint32_t* d_node, con
     static const bool counting = getenv("PGORB_FV_COUNTING") != nullptr;      // (A / B switch: the O(n^2) counting form for every size)
     if (cap <= FV_T * FV_IPT && !counting) {
         const size_t ldsS = (size_t)2 * FV_T * FV_IPT * 8 + (2 * FV_T / 64 + 2) * 4;       // two key buffers + the wave totals
-        if (!pg_raise_lds(c, reinterpret_cast<const void*>(k_feature_vectors_sorted), 6, ldsS)) return pg_ctx_fail(c, PGORB_E_LIMIT, "feature vector scratch exceeds the LDS");
+        if (!pg_raise_lds<k_feature_vectors_sorted>(c, ldsS)) return pg_ctx_fail(c, PGORB_E_LIMIT, "feature vector scratch exceeds the LDS");
         hipLaunchKernelGGL(k_feature_vectors_sorted, dim3(nframes), dim3(FV_T), ldsS, (hipStream_t)stream, d_node, d_n, cap, d_fv_node, d_fv_start, d_fv_feat, d_nfv);
         if (hipGetLastError() != hipSuccess) return pg_ctx_fail(c, PGORB_E_HIP, "k_feature_vectors_sorted launch failed");
         return 0;
     }
     const size_t lds = (size_t)cap * 8 + 1025 * 4;
-    if (!pg_raise_lds(c, reinterpret_cast<const void*>(k_feature_vectors), 2, lds)) return pg_ctx_fail(c, PGORB_E_LIMIT, "feature vector scratch exceeds the LDS");
+    if (!pg_raise_lds<k_feature_vectors>(c, lds)) return pg_ctx_fail(c, PGORB_E_LIMIT, "feature vector scratch exceeds the LDS");
     hipLaunchKernelGGL(k_feature_vectors, dim3(nframes), dim3(1024), lds, (hipStream_t)stream, d_node, d_n, cap, d_fv_node, d_fv_start, d_fv_feat, d_nfv);
     if (hipGetLastError() != hipSuccess) return pg_ctx_fail(c, PGORB_E_HIP, "k_feature_vectors launch failed");
     return 0;
@@ -1575,6 +1566,56 @@ int pgorb_search_by_bow_batch_device(pgorb_ctx* c, const pgorb_keypoint* d_kps, 
     return pg_ctx_scratch_done(c, (hipStream_t)stream);
 }
 
+// a FeatureVector as CSR: starts from 0, ascending, inside n, every feature index below n
+static bool pg_fv_ok(const int32_t* start, const uint32_t* feat, int nfv, int n)
+{
+    if (nfv > n || start[0] != 0 || start[nfv] > n) return false;
+    for (int a = 0; a < nfv; a++) if (start[a + 1] < start[a]) return false;
+    for (int i = 0; i < start[nfv]; i++) if (feat[i] >= (uint32_t)n) return false;
+    return true;
+}
+
+// One frame of a single-pair BoW-node call (SearchByBoW, SearchForTriangulation)
+struct PgFvFrame {
+    const pgorb_keypoint* kps;   // null: zero keypoints that carry `angle` only
+    const float* angle;
+    const uint8_t* desc;
+    const uint8_t* mask;         // null: all zero
+    int n;
+    const uint32_t* node; const int32_t* start; const uint32_t* feat; int nfv;
+};
+// ... and the pair as the uploads of a two-frame batch (frame 0, frame 1): keypoints, descriptors, masks and FeatureVectors in
+// slots of cap = max(n) entries (cap + 1 starts), the tail of every slot zero; n[2], nfv[2] and the pair {0, 1}.  The
+// FeatureVector arrays are read up to start[nfv] only.
+struct PgFvPair {
+    int cap;
+    size_t K, D, H, N, FN, FS, FF, NF, P;
+    PgFvPair(PgHostCall& s, const PgFvFrame* f) : cap(std::max(f[0].n, f[1].n))
+    {
+        const size_t slots = (size_t)2 * cap;
+        K = s.region(PG_UP, slots * sizeof(pgorb_keypoint)); D = s.region(PG_UP, slots * 32); H = s.region(PG_UP, slots);
+        N = s.region(PG_UP, 8); FN = s.region(PG_UP, slots * 4); FS = s.region(PG_UP, (slots + 2) * 4); FF = s.region(PG_UP, slots * 4);
+        NF = s.region(PG_UP, 8); P = s.region(PG_UP, 8);
+    }
+    void pack(PgHostCall& s, const PgFvFrame* f) const
+    {
+        const int32_t nn[2] = {f[0].n, f[1].n}, nfv[2] = {f[0].nfv, f[1].nfv}, pr[2] = {0, 1};
+        s.put(N, nn, 8); s.put(NF, nfv, 8); s.put(P, pr, 8);
+        const size_t kb = sizeof(pgorb_keypoint);
+        for (int k = 0; k < 2; k++) {
+            const PgFvFrame& F = f[k];
+            const size_t n = F.n, m = F.nfv, slot = (size_t)k * cap;
+            s.put(K, F.kps, n * kb, slot * kb, cap * kb);
+            if (!F.kps) for (size_t i = 0; i < n; i++) s.host<pgorb_keypoint>(K)[slot + i].angle = F.angle[i];
+            s.put(D, F.desc, n * 32, slot * 32, cap * 32);
+            s.put(H, F.mask, n, slot, cap);
+            s.put(FN, F.node, m * 4, slot * 4, cap * 4);
+            s.put(FS, F.start, (m + 1) * 4, (slot + k) * 4, (cap + 1) * 4);
+            s.put(FF, F.feat, (size_t)F.start[m] * 4, slot * 4, cap * 4);
+        }
+    }
+};
+
 // single pair through host buffers: the pair becomes a two-frame batch (key frame = frame 0, frame = frame 1)
 int pgorb_search_by_bow(pgorb_ctx* c, const uint8_t* kf_desc, const float* kf_angle, const uint8_t* kf_point_valid, int nkf,
                         const uint32_t* kf_fv_node, const int32_t* kf_fv_start, const uint32_t* kf_fv_feat, int kf_nfv,
@@ -1590,45 +1631,23 @@ int pgorb_search_by_bow(pgorb_ctx* c, const uint8_t* kf_desc, const float* kf_an
     for (int i = 0; i < nf; i++) matches[i] = -1;
     if (!nkf || !nf || !kf_nfv || !f_nfv) return 0;
     if (nf > 16000 || nkf > 16000) return pg_ctx_fail(c, PGORB_E_LIMIT, "more than 16000 keypoints");
-    const int cap = std::max(nkf, nf);
-    if (kf_nfv > cap || f_nfv > cap || kf_fv_start[kf_nfv] > nkf || f_fv_start[f_nfv] > nf)
+    if (!pg_fv_ok(kf_fv_start, kf_fv_feat, kf_nfv, nkf) || !pg_fv_ok(f_fv_start, f_fv_feat, f_nfv, nf))
         return pg_ctx_fail(c, PGORB_E_ARG, "pgorb_search_by_bow: FeatureVector names more features than the frame has");
-    auto al = [](size_t v) { return (v + 63) & ~(size_t)63; };
-    size_t off = 0;
-    auto place = [&](size_t bytes) { const size_t o = off; off += al(bytes); return o; };
-    const size_t oK = place((size_t)2 * cap * sizeof(pgorb_keypoint)), oD = place((size_t)2 * cap * 32), oN = place(8), oV = place(cap),
-                 oFN = place((size_t)2 * cap * 4), oFS = place((size_t)2 * (cap + 1) * 4), oFF = place((size_t)2 * cap * 4), oNF = place(8),
-                 oP = place(8), oM = place((size_t)cap * 4), oNM = place(64);
-    void *dv, *hv;
-    int rc = pg_ctx_stage(c, 0, off, &dv);
+    const PgFvFrame f[2] = {{nullptr, kf_angle, kf_desc, kf_point_valid, nkf, kf_fv_node, kf_fv_start, kf_fv_feat, kf_nfv},
+                            {nullptr, f_angle, f_desc, nullptr, nf, f_fv_node, f_fv_start, f_fv_feat, f_nfv}};
+    PgHostCall s(c);
+    const PgFvPair p(s, f);
+    const size_t oM = s.region(PG_DOWN, (size_t)p.cap * 4), oNM = s.region(PG_DOWN, 4);
+    int rc = s.begin();
     if (rc) return rc;
-    // everything the host supplies sits before oM: one upload from the page-locked buffer; oM.. is one download
-    const size_t upBytes = oM, downBytes = off - oM;
-    if ((rc = pg_ctx_pinned(c, std::max(upBytes, downBytes), &hv))) return rc;
-    uint8_t* d = (uint8_t*)dv; uint8_t* h = (uint8_t*)hv;
-    pgorb_keypoint* kk = (pgorb_keypoint*)(h + oK);
-    memset(kk, 0, (size_t)2 * cap * sizeof(pgorb_keypoint));
-    for (int i = 0; i < nkf; i++) kk[i].angle = kf_angle[i];
-    for (int i = 0; i < nf; i++) kk[(size_t)cap + i].angle = f_angle[i];
-    const int32_t nn[2] = {nkf, nf}, nfvs[2] = {kf_nfv, f_nfv}, pr[2] = {0, 1};
-    auto up = [&](size_t o, const void* p, size_t n) { if (n) memcpy(h + o, p, n); };
-    up(oD, kf_desc, (size_t)nkf * 32); up(oD + (size_t)cap * 32, f_desc, (size_t)nf * 32);
-    up(oN, nn, 8); up(oV, kf_point_valid, nkf);
-    up(oFN, kf_fv_node, (size_t)kf_nfv * 4); up(oFN + (size_t)cap * 4, f_fv_node, (size_t)f_nfv * 4);
-    up(oFS, kf_fv_start, (size_t)(kf_nfv + 1) * 4); up(oFS + (size_t)(cap + 1) * 4, f_fv_start, (size_t)(f_nfv + 1) * 4);
-    up(oFF, kf_fv_feat, (size_t)kf_fv_start[kf_nfv] * 4); up(oFF + (size_t)cap * 4, f_fv_feat, (size_t)f_fv_start[f_nfv] * 4);
-    up(oNF, nfvs, 8); up(oP, pr, 8);
-    if (hipMemcpyAsync(d, h, upBytes, hipMemcpyHostToDevice, 0) != hipSuccess) return pg_ctx_fail(c, PGORB_E_HIP, "hipMemcpy H2D failed");
-    rc = pgorb_search_by_bow_batch_device(c, (const pgorb_keypoint*)(d + oK), d + oD, (const int32_t*)(d + oN), cap, (const uint32_t*)(d + oFN),
-                                          (const int32_t*)(d + oFS), (const uint32_t*)(d + oFF), (const int32_t*)(d + oNF), (const int32_t*)(d + oP),
-                                          (const int32_t*)(d + oP) + 1, 1, d + oV, nnratio, check_orientation, (int32_t*)(d + oM), (int32_t*)(d + oNM), nullptr);
-    if (rc) return rc;
-    if (hipMemcpyAsync(h, d + oM, downBytes, hipMemcpyDeviceToHost, 0) != hipSuccess || hipStreamSynchronize(0) != hipSuccess)
-        return pg_ctx_fail(c, PGORB_E_HIP, "hipMemcpy D2H failed");
-    memcpy(matches, h, (size_t)nf * 4);
-    int32_t nm;
-    memcpy(&nm, h + (oNM - oM), 4);
-    return nm;
+    p.pack(s, f);
+    if ((rc = s.run([&] {
+            return pgorb_search_by_bow_batch_device(c, s.dev<pgorb_keypoint>(p.K), s.dev(p.D), s.dev<int32_t>(p.N), p.cap, s.dev<uint32_t>(p.FN),
+                                                    s.dev<int32_t>(p.FS), s.dev<uint32_t>(p.FF), s.dev<int32_t>(p.NF), s.dev<int32_t>(p.P),
+                                                    s.dev<int32_t>(p.P) + 1, 1, s.dev(p.H), nnratio, check_orientation, s.dev<int32_t>(oM),
+                                                    s.dev<int32_t>(oNM), nullptr); }))) return rc;
+    memcpy(matches, s.host(oM), (size_t)nf * 4);
+    return *s.host<int32_t>(oNM);
 }
 
 int pgorb_search_for_triangulation_batch_device(pgorb_ctx* c, const pgorb_keypoint* d_kps, const uint8_t* d_desc, const int32_t* d_n, int cap,
@@ -1669,15 +1688,6 @@ int pgorb_search_for_triangulation_batch_device(pgorb_ctx* c, const pgorb_keypoi
     return pg_ctx_scratch_done(c, (hipStream_t)stream);
 }
 
-// a FeatureVector as CSR: starts from 0, ascending, inside n, every feature index below n
-static bool pg_fv_ok(const int32_t* start, const uint32_t* feat, int nfv, int n)
-{
-    if (nfv > n || start[0] != 0 || start[nfv] > n) return false;
-    for (int a = 0; a < nfv; a++) if (start[a + 1] < start[a]) return false;
-    for (int i = 0; i < start[nfv]; i++) if (feat[i] >= (uint32_t)n) return false;
-    return true;
-}
-
 // single pair through host buffers: the pair becomes a two-frame batch (KF1 = frame 0, KF2 = frame 1)
 int pgorb_search_for_triangulation(pgorb_ctx* c, const pgorb_keypoint* kps1, const uint8_t* desc1, const uint8_t* has_point1, int n1,
                                    const uint32_t* fv1_node, const int32_t* fv1_start, const uint32_t* fv1_feat, int nfv1,
@@ -1694,45 +1704,24 @@ int pgorb_search_for_triangulation(pgorb_ctx* c, const pgorb_keypoint* kps1, con
         return pg_ctx_fail(c, PGORB_E_ARG, "pgorb_search_for_triangulation: FeatureVector names more features than the key frame has");
     for (int i = 0; i < n1; i++) matches12[i] = -1;
     if (!n1 || !n2 || !nfv1 || !nfv2) return 0;
-    const int cap = std::max(n1, n2);
-    auto al = [](size_t v) { return (v + 63) & ~(size_t)63; };
-    size_t off = 0;
-    auto place = [&](size_t bytes) { const size_t o = off; off += al(bytes); return o; };
-    const size_t oK = place((size_t)2 * cap * sizeof(pgorb_keypoint)), oD = place((size_t)2 * cap * 32), oN = place(8),
-                 oH1 = place(cap), oH2 = place(cap), oFN = place((size_t)2 * cap * 4), oFS = place((size_t)2 * (cap + 1) * 4),
-                 oFF = place((size_t)2 * cap * 4), oNF = place(8), oP = place(8), oF = place(9 * 4), oE = place(8),
-                 oM = place((size_t)cap * 4), oNM = place(64);
-    void *dv, *hv;
-    int rc = pg_ctx_stage(c, 0, off, &dv);
+    const PgFvFrame f[2] = {{kps1, nullptr, desc1, has_point1, n1, fv1_node, fv1_start, fv1_feat, nfv1},
+                            {kps2, nullptr, desc2, has_point2, n2, fv2_node, fv2_start, fv2_feat, nfv2}};
+    PgHostCall s(c);
+    const PgFvPair p(s, f);
+    const size_t oF = s.region(PG_UP, 9 * 4), oE = s.region(PG_UP, 8), oM = s.region(PG_DOWN, (size_t)p.cap * 4), oNM = s.region(PG_DOWN, 4);
+    int rc = s.begin();
     if (rc) return rc;
-    // everything the host supplies sits before oM: one upload from the page-locked buffer; oM.. is one download
-    const size_t upBytes = oM, downBytes = off - oM;
-    if ((rc = pg_ctx_pinned(c, std::max(upBytes, downBytes), &hv))) return rc;
-    uint8_t* d = (uint8_t*)dv; uint8_t* h = (uint8_t*)hv;
-    memset(h, 0, upBytes);
-    const int32_t nn[2] = {n1, n2}, nfvs[2] = {nfv1, nfv2}, pr[2] = {0, 1};
+    p.pack(s, f);
     const float ep[2] = {ex, ey};
-    auto up = [&](size_t o, const void* p, size_t n) { if (n && p) memcpy(h + o, p, n); };
-    up(oK, kps1, (size_t)n1 * sizeof(pgorb_keypoint)); up(oK + (size_t)cap * sizeof(pgorb_keypoint), kps2, (size_t)n2 * sizeof(pgorb_keypoint));
-    up(oD, desc1, (size_t)n1 * 32); up(oD + (size_t)cap * 32, desc2, (size_t)n2 * 32);
-    up(oN, nn, 8); up(oH1, has_point1, n1); up(oH2, has_point2, n2);
-    up(oFN, fv1_node, (size_t)nfv1 * 4); up(oFN + (size_t)cap * 4, fv2_node, (size_t)nfv2 * 4);
-    up(oFS, fv1_start, (size_t)(nfv1 + 1) * 4); up(oFS + (size_t)(cap + 1) * 4, fv2_start, (size_t)(nfv2 + 1) * 4);
-    up(oFF, fv1_feat, (size_t)fv1_start[nfv1] * 4); up(oFF + (size_t)cap * 4, fv2_feat, (size_t)fv2_start[nfv2] * 4);
-    up(oNF, nfvs, 8); up(oP, pr, 8); up(oF, F12, 9 * 4); up(oE, ep, 8);
-    if (hipMemcpyAsync(d, h, upBytes, hipMemcpyHostToDevice, 0) != hipSuccess) return pg_ctx_fail(c, PGORB_E_HIP, "hipMemcpy H2D failed");
-    rc = pgorb_search_for_triangulation_batch_device(c, (const pgorb_keypoint*)(d + oK), d + oD, (const int32_t*)(d + oN), cap,
-                                                     (const uint32_t*)(d + oFN), (const int32_t*)(d + oFS), (const uint32_t*)(d + oFF),
-                                                     (const int32_t*)(d + oNF), (const int32_t*)(d + oP), (const int32_t*)(d + oP) + 1, 1,
-                                                     (const float*)(d + oF), (const float*)(d + oE), d + oH1, d + oH2, check_orientation,
-                                                     (int32_t*)(d + oM), (int32_t*)(d + oNM), nullptr);
-    if (rc) return rc;
-    if (hipMemcpyAsync(h, d + oM, downBytes, hipMemcpyDeviceToHost, 0) != hipSuccess || hipStreamSynchronize(0) != hipSuccess)
-        return pg_ctx_fail(c, PGORB_E_HIP, "hipMemcpy D2H failed");
-    memcpy(matches12, h, (size_t)n1 * 4);
-    int32_t nm;
-    memcpy(&nm, h + (oNM - oM), 4);
-    return nm;
+    s.put(oF, F12, 9 * 4); s.put(oE, ep, 8);
+    if ((rc = s.run([&] {
+            return pgorb_search_for_triangulation_batch_device(c, s.dev<pgorb_keypoint>(p.K), s.dev(p.D), s.dev<int32_t>(p.N), p.cap,
+                                                               s.dev<uint32_t>(p.FN), s.dev<int32_t>(p.FS), s.dev<uint32_t>(p.FF),
+                                                               s.dev<int32_t>(p.NF), s.dev<int32_t>(p.P), s.dev<int32_t>(p.P) + 1, 1,
+                                                               s.dev<float>(oF), s.dev<float>(oE), s.dev(p.H), s.dev(p.H) + p.cap,
+                                                               check_orientation, s.dev<int32_t>(oM), s.dev<int32_t>(oNM), nullptr); }))) return rc;
+    memcpy(matches12, s.host(oM), (size_t)n1 * 4);
+    return *s.host<int32_t>(oNM);
 }
 
 int pgorb_frame_grid_batch_device(pgorb_ctx* c, const pgorb_keypoint* d_kps, const int32_t* d_n, int nframes,
@@ -1774,8 +1763,7 @@ int pgorb_search_for_initialization_batch_device(pgorb_ctx* c, const pgorb_keypo
     if (rc) return rc;
     pg_lists_layout(scratch, npairs, cap, &Ls);
     const size_t ldsA = (size_t)4 * cap * 2, ldsB = (size_t)cap * 10 + 192;      // (+ the 32-bin histogram)
-    if (!pg_raise_lds(c, reinterpret_cast<const void*>(k_sfi_candidates), 4, ldsA) ||
-        !pg_raise_lds(c, reinterpret_cast<const void*>(k_search_for_initialization), 5, ldsB))
+    if (!pg_raise_lds<k_sfi_candidates>(c, ldsA) || !pg_raise_lds<k_search_for_initialization>(c, ldsB))
         return pg_ctx_fail(c, PGORB_E_LIMIT, "SearchForInitialization state exceeds the LDS");
     if (hipMemsetAsync(Ls.poolTop, 0, (size_t)npairs * 4, (hipStream_t)stream) != hipSuccess) return pg_ctx_fail(c, PGORB_E_HIP, "hipMemsetAsync failed");
     hipLaunchKernelGGL(k_sfi_candidates, dim3((cap + 3) / 4, npairs), dim3(256), ldsA, (hipStream_t)stream, d_kps, d_desc, d_n, cap,
@@ -1825,8 +1813,8 @@ static int pg_search_by_projection_batch(pgorb_ctx* c, int mode, const pgorb_key
     pg_lists_layout(scratch, npairs, std::max(qcap, 1), &Ls);
     const size_t ldsA = (size_t)4 * cap * 2;
     const size_t lds = (size_t)cap * 13 + (size_t)qcap * 10 + 256;
-    if (!pg_raise_lds(c, reinterpret_cast<const void*>(k_search_by_projection), 0, lds) ||
-        !pg_raise_lds(c, reinterpret_cast<const void*>(k_proj_candidates), 3, ldsA)) return pg_ctx_fail(c, PGORB_E_LIMIT, "SearchByProjection state exceeds the LDS (keypoints * 13 + queries * 10 bytes, 160 KB)");
+    if (!pg_raise_lds<k_search_by_projection>(c, lds) ||
+        !pg_raise_lds<k_proj_candidates>(c, ldsA)) return pg_ctx_fail(c, PGORB_E_LIMIT, "SearchByProjection state exceeds the LDS (keypoints * 13 + queries * 10 bytes, 160 KB)");
     if (hipMemsetAsync(Ls.poolTop, 0, (size_t)npairs * 4, stream) != hipSuccess) return pg_ctx_fail(c, PGORB_E_HIP, "hipMemsetAsync failed");
     if (qcap) hipLaunchKernelGGL(k_proj_candidates, dim3((qcap + 3) / 4, npairs), dim3(256), ldsA, stream, B, min_x, min_y, invW, invH, mode, Ls);
     hipLaunchKernelGGL(k_search_by_projection, dim3(npairs), dim3(RR_T), lds, stream, B, min_x, min_y, invW, invH, mode, nnratio,
@@ -1890,15 +1878,12 @@ int pgorb_predict_scale(const pgorb_ctx* c, float max_distance, float current_di
     return pg_predict_scale(max_distance, current_dist, pgorb_log_scale_factor(c), pgorb_levels(c));
 }
 
-// single frame through host buffers: a one-pair batch.  Round 4: the eleven input arrays are packed into the context's
-// page-locked bounce buffer and travel as ONE asynchronous upload, the results (assignment array + count) as one
-// download -- eleven synchronous pageable hipMemcpy calls were 0.3 ms of a 1.6-ms call.
-struct PgProjHostKF { const uint8_t* found; const float* dist3d; const float* minDist; const float* maxDist; float logSf; int orbDist; };
+// single frame through host buffers: a one-pair batch
 static int pg_search_by_projection_host(pgorb_ctx* c, int mode, const pgorb_keypoint* kps, const uint8_t* desc, int n,
                                         float min_x, float max_x, float min_y, float max_y, const uint8_t* kp_has_point,
                                         int nq, const uint8_t* valid, const float* qx, const float* qy, const int32_t* level,
                                         const float* aux, const uint8_t* qdesc, const uint8_t* qobs, float th, float nnratio,
-                                        int check_orientation, int32_t* assigned, const PgProjHostKF* kf = nullptr)
+                                        int check_orientation, int32_t* assigned, const PgProjKeyFrame* kf = nullptr)
 {
     const bool m2 = mode == 2;
     if (n < 0 || nq < 0 || (n && (!kps || !desc || !assigned)) ||
@@ -1909,47 +1894,31 @@ static int pg_search_by_projection_host(pgorb_ctx* c, int mode, const pgorb_keyp
     for (int i = 0; i < n; i++) assigned[i] = -1;
     if (!n || !nq) return 0;
     if (n > 16000 || nq > 16000) return pg_ctx_fail(c, PGORB_E_LIMIT, "more than 16000 keypoints / queries");
-    auto al = [](size_t v) { return (v + 63) & ~(size_t)63; };
-    // uploaded part first (one copy), device-only scratch and the results behind it
-    size_t off = 0;
-    auto place = [&](size_t bytes) { const size_t o = off; off += al(bytes); return o; };
-    const size_t oN = place(64), oK = place((size_t)n * sizeof(pgorb_keypoint)), oD = place((size_t)n * 32), oH = place(n), oV = place(nq),
-                 oX = place((size_t)nq * 4), oY = place((size_t)nq * 4), oL = place((size_t)nq * 4), oA = place((size_t)nq * 4),
-                 oQD = place((size_t)nq * 32), oO = place(nq), oF = place(m2 ? nq : 0), oD3 = place(m2 ? (size_t)nq * 4 : 0),
-                 oDmin = place(m2 ? (size_t)nq * 4 : 0), oDmax = place(m2 ? (size_t)nq * 4 : 0);
-    const size_t upBytes = off;
-    const size_t oGS = place((size_t)(GRID_CELLS + 1) * 4), oGI = place((size_t)n * 4);
-    const size_t oAs = place((size_t)n * 4), oR = place(64);
-    const size_t total = off, downBytes = total - oAs;
-    void *dv, *hv;
-    int rc = pg_ctx_stage(c, 0, total, &dv);
+    const size_t q4 = (size_t)nq * 4, k4 = m2 ? q4 : 0;
+    PgHostCall s(c);
+    const size_t oN = s.region(PG_UP, 8), oK = s.region(PG_UP, (size_t)n * sizeof(pgorb_keypoint)), oD = s.region(PG_UP, (size_t)n * 32),
+                 oH = s.region(PG_UP, n), oV = s.region(PG_UP, nq), oX = s.region(PG_UP, q4), oY = s.region(PG_UP, q4), oL = s.region(PG_UP, q4),
+                 oA = s.region(PG_UP, q4), oQD = s.region(PG_UP, (size_t)nq * 32), oO = s.region(PG_UP, nq), oF = s.region(PG_UP, m2 ? nq : 0),
+                 oD3 = s.region(PG_UP, k4), oDmin = s.region(PG_UP, k4), oDmax = s.region(PG_UP, k4), oAs = s.region(PG_DOWN, (size_t)n * 4),
+                 oR = s.region(PG_DOWN, 4), oGS = s.region(PG_DEV, (size_t)(GRID_CELLS + 1) * 4), oGI = s.region(PG_DEV, (size_t)n * 4);
+    int rc = s.begin();
     if (rc) return rc;
-    if ((rc = pg_ctx_pinned(c, std::max(upBytes, downBytes), &hv))) return rc;
-    uint8_t* d = (uint8_t*)dv; uint8_t* h = (uint8_t*)hv;
     const int32_t cnt[2] = {n, nq};
-    memcpy(h + oN, cnt, 8);
-    memcpy(h + oK, kps, (size_t)n * sizeof(pgorb_keypoint)); memcpy(h + oD, desc, (size_t)n * 32);
-    if (kp_has_point) memcpy(h + oH, kp_has_point, n);
-    memcpy(h + oV, valid, nq); memcpy(h + oX, qx, (size_t)nq * 4); memcpy(h + oY, qy, (size_t)nq * 4);
-    if (level) memcpy(h + oL, level, (size_t)nq * 4);
-    memcpy(h + oA, aux, (size_t)nq * 4); memcpy(h + oQD, qdesc, (size_t)nq * 32);
-    if (qobs) memcpy(h + oO, qobs, nq);
-    if (m2) { memcpy(h + oF, kf->found, nq); memcpy(h + oD3, kf->dist3d, (size_t)nq * 4); memcpy(h + oDmin, kf->minDist, (size_t)nq * 4); memcpy(h + oDmax, kf->maxDist, (size_t)nq * 4); }
-    if (hipMemcpyAsync(d, h, upBytes, hipMemcpyHostToDevice, 0) != hipSuccess) return pg_ctx_fail(c, PGORB_E_HIP, "hipMemcpy H2D failed");
-    if ((rc = pgorb_frame_grid_batch_device(c, (pgorb_keypoint*)(d + oK), (int32_t*)(d + oN), 1, n, min_x, max_x, min_y,
-                                            max_y, (int32_t*)(d + oGS), (int32_t*)(d + oGI), 0))) return rc;
-    const PgProjKeyFrame dkf = {d + oF, (float*)(d + oD3), (float*)(d + oDmin), (float*)(d + oDmax), m2 ? kf->logSf : 1.0f, m2 ? kf->orbDist : 0};
-    rc = pg_search_by_projection_batch(c, mode, (pgorb_keypoint*)(d + oK), d + oD, (int32_t*)(d + oN), n, (int32_t*)(d + oGS), (int32_t*)(d + oGI),
-                                       nullptr, 1, min_x, max_x, min_y, max_y, kp_has_point ? d + oH : nullptr, nq, (int32_t*)(d + oN) + 1, d + oV,
-                                       (float*)(d + oX), (float*)(d + oY), (int32_t*)(d + oL), (float*)(d + oA), d + oQD, d + oO, th, nnratio,
-                                       check_orientation, (int32_t*)(d + oAs), (int32_t*)(d + oR), 0, m2 ? &dkf : nullptr);
-    if (rc) return rc;
-    if (hipMemcpyAsync(h, d + oAs, downBytes, hipMemcpyDeviceToHost, 0) != hipSuccess || hipStreamSynchronize(0) != hipSuccess)
-        return pg_ctx_fail(c, PGORB_E_HIP, "hipMemcpy D2H failed");
-    memcpy(assigned, h, (size_t)n * 4);
-    int32_t nm;
-    memcpy(&nm, h + (oR - oAs), 4);
-    return nm;
+    s.put(oN, cnt, 8); s.put(oK, kps, (size_t)n * sizeof(pgorb_keypoint)); s.put(oD, desc, (size_t)n * 32); s.put(oH, kp_has_point, n);
+    s.put(oV, valid, nq); s.put(oX, qx, q4); s.put(oY, qy, q4); s.put(oL, level, q4); s.put(oA, aux, q4);
+    s.put(oQD, qdesc, (size_t)nq * 32); s.put(oO, qobs, nq);
+    if (m2) { s.put(oF, kf->found, nq); s.put(oD3, kf->dist3d, q4); s.put(oDmin, kf->minDist, q4); s.put(oDmax, kf->maxDist, q4); }
+    const PgProjKeyFrame dkf = {s.dev(oF), s.dev<float>(oD3), s.dev<float>(oDmin), s.dev<float>(oDmax), m2 ? kf->logSf : 1.0f, m2 ? kf->orbDist : 0};
+    if ((rc = s.run([&] {
+            int r = pgorb_frame_grid_batch_device(c, s.dev<pgorb_keypoint>(oK), s.dev<int32_t>(oN), 1, n, min_x, max_x, min_y, max_y,
+                                                  s.dev<int32_t>(oGS), s.dev<int32_t>(oGI), nullptr);
+            return r ? r : pg_search_by_projection_batch(c, mode, s.dev<pgorb_keypoint>(oK), s.dev(oD), s.dev<int32_t>(oN), n, s.dev<int32_t>(oGS),
+                                                         s.dev<int32_t>(oGI), nullptr, 1, min_x, max_x, min_y, max_y, kp_has_point ? s.dev(oH) : nullptr,
+                                                         nq, s.dev<int32_t>(oN) + 1, s.dev(oV), s.dev<float>(oX), s.dev<float>(oY), s.dev<int32_t>(oL),
+                                                         s.dev<float>(oA), s.dev(oQD), s.dev(oO), th, nnratio, check_orientation, s.dev<int32_t>(oAs),
+                                                         s.dev<int32_t>(oR), nullptr, m2 ? &dkf : nullptr); }))) return rc;
+    memcpy(assigned, s.host(oAs), (size_t)n * 4);
+    return *s.host<int32_t>(oR);
 }
 
 int pgorb_search_by_projection_keyframe(pgorb_ctx* c, const pgorb_keypoint* kps, const uint8_t* desc, int n, float min_x,
@@ -1961,7 +1930,7 @@ int pgorb_search_by_projection_keyframe(pgorb_ctx* c, const pgorb_keypoint* kps,
 {
     if (!c) return PGORB_E_ARG;
     if (!(log_scale_factor > 0.0f)) return pg_ctx_fail(c, PGORB_E_ARG, "pgorb_search_by_projection_keyframe: log_scale_factor must be positive");
-    const PgProjHostKF kf = {already_found, dist3d, min_distance, max_distance, log_scale_factor, orb_dist};
+    const PgProjKeyFrame kf = {already_found, dist3d, min_distance, max_distance, log_scale_factor, orb_dist};
     return pg_search_by_projection_host(c, 2, kps, desc, n, min_x, max_x, min_y, max_y, kp_has_point, npoints, valid, u, v, nullptr,
                                         kf_angle, point_desc, nullptr, th, 0.f, check_orientation, assigned, &kf);
 }
@@ -1994,23 +1963,16 @@ int pgorb_frame_grid(pgorb_ctx* c, const pgorb_keypoint* kps, int n, float min_x
     if (!c) return PGORB_E_ARG;
     if (n < 0 || (n && (!kps || !grid_idx)) || !grid_start) return pg_ctx_fail(c, PGORB_E_ARG, "bad argument to pgorb_frame_grid");
     const int cap = n > 0 ? n : 1;
-    // [n | keypoints] go up in one copy, [grid_start | grid_idx] come back in one
-    const size_t oK = 64, oS = oK + (((size_t)cap * sizeof(pgorb_keypoint) + 63) & ~(size_t)63);
-    const size_t oI = oS + (size_t)(GRID_CELLS + 1) * 4, total = oI + (size_t)cap * 4;
-    void *dv, *hv;
-    int rc = pg_ctx_stage(c, 0, total, &dv);
+    PgHostCall s(c);
+    const size_t oN = s.region(PG_UP, 4), oK = s.region(PG_UP, (size_t)cap * sizeof(pgorb_keypoint)),
+                 oS = s.region(PG_DOWN, (size_t)(GRID_CELLS + 1) * 4), oI = s.region(PG_DOWN, (size_t)cap * 4);
+    int rc = s.begin();
     if (rc) return rc;
-    if ((rc = pg_ctx_pinned(c, std::max(oS, total - oS), &hv))) return rc;
-    uint8_t* d = (uint8_t*)dv; uint8_t* h = (uint8_t*)hv;
-    memcpy(h, &n, 4);
-    if (n) memcpy(h + oK, kps, (size_t)n * sizeof(pgorb_keypoint));
-    if (hipMemcpyAsync(d, h, oS, hipMemcpyHostToDevice, 0) != hipSuccess) return pg_ctx_fail(c, PGORB_E_HIP, "hipMemcpy failed");
-    if ((rc = pgorb_frame_grid_batch_device(c, (pgorb_keypoint*)(d + oK), (int32_t*)d, 1, cap, min_x, max_x, min_y, max_y,
-                                            (int32_t*)(d + oS), (int32_t*)(d + oI), 0))) return rc;
-    if (hipMemcpyAsync(h, d + oS, total - oS, hipMemcpyDeviceToHost, 0) != hipSuccess || hipStreamSynchronize(0) != hipSuccess)
-        return pg_ctx_fail(c, PGORB_E_HIP, "hipMemcpy failed");
-    memcpy(grid_start, h, (size_t)(GRID_CELLS + 1) * 4);
-    if (n) memcpy(grid_idx, h + (oI - oS), (size_t)n * 4);
+    s.put(oN, &n, 4); s.put(oK, kps, (size_t)n * sizeof(pgorb_keypoint));
+    if ((rc = s.run([&] { return pgorb_frame_grid_batch_device(c, s.dev<pgorb_keypoint>(oK), s.dev<int32_t>(oN), 1, cap, min_x, max_x, min_y,
+                                                               max_y, s.dev<int32_t>(oS), s.dev<int32_t>(oI), nullptr); }))) return rc;
+    memcpy(grid_start, s.host(oS), (size_t)(GRID_CELLS + 1) * 4);
+    if (n) memcpy(grid_idx, s.host(oI), (size_t)n * 4);
     return 0;
 }
 
@@ -2023,48 +1985,29 @@ int pgorb_search_for_initialization(pgorb_ctx* c, const pgorb_keypoint* kps1, co
     if (n1 < 0 || n2 < 0 || (n1 && (!kps1 || !desc1 || !prev_matched || !matches12)) || (n2 && (!kps2 || !desc2)))
         return pg_ctx_fail(c, PGORB_E_ARG, "bad argument to pgorb_search_for_initialization");
     if (n1 == 0) return 0;
-    const int cap = (n1 > n2 ? n1 : n2) > 0 ? (n1 > n2 ? n1 : n2) : 1;
-    // One slab, laid out so that everything the host supplies is one upload and everything it reads back one
-    // download: [misc | kps x2 | desc x2 | prev | matches | nmatches] then the device-only grids.
-    auto up64 = [](size_t v) { return (v + 63) & ~(size_t)63; };
-    const size_t oMisc = 0;
-    const size_t oK = 64;
-    const size_t oD = oK + up64((size_t)2 * cap * sizeof(pgorb_keypoint));
-    const size_t oP = oD + up64((size_t)2 * cap * 32);
-    const size_t oM = oP + up64((size_t)cap * 8);
-    const size_t oNm = oM + up64((size_t)cap * 4);
-    const size_t oGS = oNm + 64;
-    const size_t oGI = oGS + up64((size_t)2 * (GRID_CELLS + 1) * 4);
-    const size_t total = oGI + up64((size_t)2 * cap * 4);
-    const size_t upBytes = oM, downBytes = oGS - oP;
-    void *dv, *hv;
-    int rc = pg_ctx_stage(c, 0, total, &dv);
+    const int cap = std::max(n1, n2);
+    const size_t kb = sizeof(pgorb_keypoint);
+    PgHostCall s(c);
+    const size_t oMisc = s.region(PG_UP, 16), oK = s.region(PG_UP, (size_t)2 * cap * kb), oD = s.region(PG_UP, (size_t)2 * cap * 32),
+                 oP = s.region(PG_INOUT, (size_t)cap * 8), oM = s.region(PG_DOWN, (size_t)cap * 4), oNm = s.region(PG_DOWN, 4),
+                 oGS = s.region(PG_DEV, (size_t)2 * (GRID_CELLS + 1) * 4), oGI = s.region(PG_DEV, (size_t)2 * cap * 4);
+    int rc = s.begin();
     if (rc) return rc;
-    if ((rc = pg_ctx_pinned(c, std::max(upBytes, downBytes), &hv))) return rc;
-    uint8_t* d = (uint8_t*)dv; uint8_t* h = (uint8_t*)hv;
-    const int32_t misc[5] = {n1, n2, 0, 1, 0};   // n[2], f1, f2
-    memcpy(h + oMisc, misc, sizeof(misc));
-    memcpy(h + oK, kps1, (size_t)n1 * sizeof(pgorb_keypoint));
-    memcpy(h + oD, desc1, (size_t)n1 * 32);
-    if (n2) {
-        memcpy(h + oK + (size_t)cap * sizeof(pgorb_keypoint), kps2, (size_t)n2 * sizeof(pgorb_keypoint));
-        memcpy(h + oD + (size_t)cap * 32, desc2, (size_t)n2 * 32);
-    }
-    memcpy(h + oP, prev_matched, (size_t)n1 * 8);
-    if (hipMemcpyAsync(d, h, upBytes, hipMemcpyHostToDevice, 0) != hipSuccess) return pg_ctx_fail(c, PGORB_E_HIP, "hipMemcpy H2D failed");
-    pgorb_keypoint* dk = (pgorb_keypoint*)(d + oK);
-    int32_t* dmisc = (int32_t*)(d + oMisc);
-    if ((rc = pgorb_frame_grid_batch_device(c, dk, dmisc, 2, cap, min_x, max_x, min_y, max_y, (int32_t*)(d + oGS), (int32_t*)(d + oGI), 0))) return rc;
-    if ((rc = pgorb_search_for_initialization_batch_device(c, dk, d + oD, dmisc, cap, (int32_t*)(d + oGS), (int32_t*)(d + oGI), dmisc + 2,
-                                                           dmisc + 3, 1, min_x, max_x, min_y, max_y, (float*)(d + oP), (int32_t*)(d + oM),
-                                                           (int32_t*)(d + oNm), window_size, nnratio, check_orientation, 0))) return rc;
-    if (hipMemcpyAsync(h, d + oP, downBytes, hipMemcpyDeviceToHost, 0) != hipSuccess || hipStreamSynchronize(0) != hipSuccess)
-        return pg_ctx_fail(c, PGORB_E_HIP, "hipMemcpy D2H failed");
-    memcpy(prev_matched, h, (size_t)n1 * 8);
-    memcpy(matches12, h + (oM - oP), (size_t)n1 * 4);
-    int32_t nm;
-    memcpy(&nm, h + (oNm - oP), 4);
-    return nm;
+    const int32_t misc[4] = {n1, n2, 0, 1};   // n[2], f1, f2
+    s.put(oMisc, misc, sizeof(misc));
+    s.put(oK, kps1, n1 * kb); s.put(oK, kps2, n2 * kb, cap * kb);
+    s.put(oD, desc1, (size_t)n1 * 32); s.put(oD, desc2, (size_t)n2 * 32, (size_t)cap * 32);
+    s.put(oP, prev_matched, (size_t)n1 * 8);
+    pgorb_keypoint* dk = s.dev<pgorb_keypoint>(oK);
+    int32_t* dmisc = s.dev<int32_t>(oMisc);
+    if ((rc = s.run([&] {
+            int r = pgorb_frame_grid_batch_device(c, dk, dmisc, 2, cap, min_x, max_x, min_y, max_y, s.dev<int32_t>(oGS), s.dev<int32_t>(oGI), nullptr);
+            return r ? r : pgorb_search_for_initialization_batch_device(c, dk, s.dev(oD), dmisc, cap, s.dev<int32_t>(oGS), s.dev<int32_t>(oGI), dmisc + 2,
+                                                                        dmisc + 3, 1, min_x, max_x, min_y, max_y, s.dev<float>(oP), s.dev<int32_t>(oM),
+                                                                        s.dev<int32_t>(oNm), window_size, nnratio, check_orientation, nullptr); }))) return rc;
+    memcpy(prev_matched, s.host(oP), (size_t)n1 * 8);
+    memcpy(matches12, s.host(oM), (size_t)n1 * 4);
+    return *s.host<int32_t>(oNm);
 }
 
 }  // extern "C"

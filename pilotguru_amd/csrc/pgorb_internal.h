@@ -14,6 +14,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <string.h>
 #include "../../include/pgorb.h"
 
 #define PG_EDGE 16            // minBorderX = EDGE_THRESHOLD-3 (ORBextractor.cc:773)
@@ -289,5 +290,71 @@ void pg_launch_match_batch(const PgMatchOpts& o, const uint8_t* d_desc, const in
 void pg_launch_best2(const PgMatchOpts& o, const uint8_t* d_a, int na, const uint8_t* d_b, int nb, uint8_t* d_scratch,
                      int32_t* d_best_idx, uint16_t* d_best, uint16_t* d_second, hipStream_t s);
 bool pg_match_uses_popcount(const PgMatchOpts& o, int cap_per_frame);
+
+// the context's host-side services (api.hip)
+enum PgStage { PG_STAGE_A, PG_STAGE_OUT, PG_STAGE_SFI };      // device arenas: the single host calls', a small result arena, the matchers' scratch
+int pg_ctx_fail(pgorb_ctx* c, int code, const char* msg);
+int pg_ctx_device(pgorb_ctx* c);
+int pg_ctx_stage(pgorb_ctx* c, PgStage which, size_t bytes, void** p);
+int pg_ctx_scratch(pgorb_ctx* c, size_t bytes, hipStream_t s, void** p);      // the matchers' shared arena, ordered across caller streams
+int pg_ctx_scratch_done(pgorb_ctx* c, hipStream_t s);
+int pg_ctx_pinned(pgorb_ctx* c, size_t bytes, void** p);                       // the page-locked bounce buffer (synchronous host calls only)
+int pg_ctx_vocab_store(pgorb_ctx* c, const void* src, size_t nbytes, bool src_on_device, hipStream_t s);
+int pg_ctx_vocab_reserve(pgorb_ctx* c, size_t nbytes, void** p);
+int pg_ctx_vocab_commit(pgorb_ctx* c, size_t nbytes, hipStream_t s);
+int pg_ctx_vocab_get(pgorb_ctx* c, const uint8_t** d_blob, int* k, int* L, int* nnodes);
+void pg_ctx_vocab_drop(pgorb_ctx* c);
+
+// One synchronous host call of a batched device form.  Its arrays are 64-byte aligned regions at the same offsets in the
+// context's stage arena (device) and page-locked buffer (host), declared in the order: uploads, in-out, downloads, device-only.
+// begin() sizes both buffers, put() fills the uploads, and run() is one H2D copy of the uploads and in-out regions, the
+// launches, one D2H copy of the in-out and download regions and one synchronisation, all on the null stream.
+enum PgDir { PG_UP, PG_INOUT, PG_DOWN, PG_DEV };
+class PgHostCall {
+public:
+    explicit PgHostCall(pgorb_ctx* c) : c_(c) {}
+    size_t region(PgDir dir, size_t bytes)                      // its offset
+    {
+        const size_t o = end_;
+        end_ += (bytes + 63) & ~(size_t)63;
+        if (dir <= PG_INOUT) upEnd_ = end_;
+        if (dir == PG_INOUT || dir == PG_DOWN) { if (o < downBeg_) downBeg_ = o; downEnd_ = end_; }
+        return o;
+    }
+    int begin()
+    {
+        void* p;
+        int rc = pg_ctx_stage(c_, PG_STAGE_A, end_, &p);
+        if (rc) return rc;
+        d_ = (uint8_t*)p;
+        if ((rc = pg_ctx_pinned(c_, downEnd_ > upEnd_ ? downEnd_ : upEnd_, &p))) return rc;
+        h_ = (uint8_t*)p;
+        return 0;
+    }
+    template <class T = uint8_t> T* dev(size_t r) const { return (T*)(d_ + r); }
+    template <class T = uint8_t> T* host(size_t r) const { return (T*)(h_ + r); }
+    // `bytes` from src (nothing when src is null) at byte `at` of region r, then zeros up to `span` bytes from `at`
+    void put(size_t r, const void* src, size_t bytes, size_t at = 0, size_t span = 0)
+    {
+        uint8_t* p = h_ + r + at;
+        if (!src) bytes = 0;
+        if (bytes) memcpy(p, src, bytes);
+        if (span > bytes) memset(p + bytes, 0, span - bytes);
+    }
+    template <class F> int run(F&& launch)
+    {
+        if (hipMemcpyAsync(d_, h_, upEnd_, hipMemcpyHostToDevice, 0) != hipSuccess) return pg_ctx_fail(c_, PGORB_E_HIP, "hipMemcpy H2D failed");
+        const int rc = launch();
+        if (rc) return rc;
+        if (hipMemcpyAsync(h_ + downBeg_, d_ + downBeg_, downEnd_ - downBeg_, hipMemcpyDeviceToHost, 0) != hipSuccess ||
+            hipStreamSynchronize(0) != hipSuccess) return pg_ctx_fail(c_, PGORB_E_HIP, "hipMemcpy D2H failed");
+        return 0;
+    }
+private:
+    pgorb_ctx* c_;
+    size_t end_ = 0, upEnd_ = 0, downBeg_ = SIZE_MAX, downEnd_ = 0;
+    uint8_t* d_ = nullptr;
+    uint8_t* h_ = nullptr;
+};
 
 static_assert(sizeof(PgPlan) <= 4000, "PgPlan is passed by value as a kernel argument (4 KiB limit)");

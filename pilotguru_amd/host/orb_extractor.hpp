@@ -97,6 +97,11 @@ class ORBmatcher {
     int SearchForInitialization(Frame& F1, Frame& F2, std::vector<float>& vbPrevMatched,
                                 std::vector<int32_t>& vnMatches12, int windowSize = 10)
     {
+        // the library reads N descriptors of each frame and 2 * N1 floats of vbPrevMatched through these pointers
+        checkDescriptors(F1, "SearchForInitialization");
+        checkDescriptors(F2, "SearchForInitialization");
+        if (vbPrevMatched.size() != (size_t)F1.N() * 2)
+            throw std::invalid_argument("SearchForInitialization: vbPrevMatched does not hold 2 floats per F1 keypoint");
         vnMatches12.assign(F1.N(), -1);
         if (F1.N() == 0) return 0;
         const int rc = pgorb_search_for_initialization(ctx_, F1.mvKeysUndistorted.data(), F1.mDescriptors.data(), F1.N(),
@@ -118,8 +123,7 @@ class ORBmatcher {
         const std::vector<uint8_t>* has[2] = {&hasPoint1, &hasPoint2};
         const FeatureVector* fv[2] = {&fv1, &fv2};
         for (int k = 0; k < 2; k++) {
-            if (kf[k]->mDescriptors.size() != (size_t)kf[k]->N() * 32)
-                throw std::invalid_argument("SearchForTriangulation: descriptors are not N x 32 bytes");
+            checkDescriptors(*kf[k], "SearchForTriangulation");
             if (!has[k]->empty() && has[k]->size() != (size_t)kf[k]->N())
                 throw std::invalid_argument("SearchForTriangulation: a hasPoint mask is neither empty nor N entries long");
             if (fv[k]->mStart.size() != fv[k]->mNode.size() + 1 || fv[k]->mStart.back() < 0 ||
@@ -143,6 +147,10 @@ class ORBmatcher {
     }
 
  private:
+    static void checkDescriptors(const Frame& F, const char* fn)
+    {
+        if (F.mDescriptors.size() != (size_t)F.N() * 32) throw std::invalid_argument(std::string(fn) + ": descriptors are not N x 32 bytes");
+    }
     pgorb_ctx* ctx_;
     float mfNNratio;
     bool mbCheckOrientation;

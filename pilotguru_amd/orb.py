@@ -22,6 +22,36 @@ def _p(a):
     return C.c_void_p(a.ctypes.data)
 
 
+def _arr(x, dtype, n, name, width=None):
+    """x as a C-contiguous `dtype` array of exactly n entries, or n rows of `width` (descriptors: 32 bytes, vbPrevMatched: 2
+    floats); anything else is a ValueError.  The library reads exactly that much through the pointer."""
+    a = np.ascontiguousarray(x, dtype)
+    if a.shape != ((n,) if width is None else (n, width)):
+        raise ValueError("%s: shape %s, expected %s" % (name, a.shape, (n,) if width is None else (n, width)))
+    return a
+
+
+def _frame(F, name):
+    """A frame's keypoints and descriptors, checked against F.N."""
+    return (_arr(F.mvKeysUndistorted, KEYPOINT_DTYPE, F.N, name + " keypoints"),
+            _arr(F.mDescriptors, np.uint8, F.N, name + " descriptors", 32))
+
+
+def _mask(m, n, name):
+    """A per-keypoint flag array of n entries; None = all zero."""
+    return np.zeros(max(n, 1), np.uint8) if m is None else _arr(m, np.uint8, n, name)
+
+
+def _featvec(fv, name):
+    """(nodes, starts, features) of a FeatureVector: nfv + 1 starts and at least starts[-1] features (the library reads
+    that many)."""
+    fv = [np.ascontiguousarray(fv[0], np.uint32).reshape(-1), np.ascontiguousarray(fv[1], np.int32).reshape(-1),
+          np.ascontiguousarray(fv[2], np.uint32).reshape(-1)]
+    if len(fv[1]) != len(fv[0]) + 1 or len(fv[2]) < int(fv[1][-1]):
+        raise ValueError("%s: FeatureVector arrays of inconsistent lengths" % name)
+    return fv
+
+
 class ORBextractor:
     """ORBextractor(nfeatures, scaleFactor, nlevels, iniThFAST, minThFAST) (ORBextractor.h:51-52).
 
@@ -347,12 +377,16 @@ class ORBmatcher:
         Returns (nmatches, assigned) with assigned[i] = index into `points` written to
         F.mvpMapPoints[i], or -1."""
         ext = F.ext
-        has = np.ascontiguousarray(kp_has_point if kp_has_point is not None else np.zeros(max(F.N, 1), np.uint8), np.uint8)
+        kp, desc = _frame(F, "F")
+        has = _mask(kp_has_point, F.N, "kp_has_point")
+        n = len(points.valid)
+        q = [_arr(points.valid, np.uint8, n, "valid"), _arr(points.proj_x, np.float32, n, "proj_x"),
+             _arr(points.proj_y, np.float32, n, "proj_y"), _arr(points.level, np.int32, n, "level"),
+             _arr(points.view_cos, np.float32, n, "view_cos"), _arr(points.descriptors, np.uint8, n, "descriptors", 32),
+             _arr(points.has_obs, np.uint8, n, "has_obs")]
         out = np.full(max(F.N, 1), -1, np.int32)
         nm = ext._check(ext._L.pgorb_search_by_projection_points(
-            ext._h, _p(F.mvKeysUndistorted), _p(F.mDescriptors), F.N, *F.bounds, _p(has), len(points.valid),
-            _p(points.valid), _p(points.proj_x), _p(points.proj_y), _p(points.level), _p(points.view_cos),
-            _p(points.descriptors), _p(points.has_obs), float(th), self.mfNNratio, _p(out)))
+            ext._h, _p(kp), _p(desc), F.N, *F.bounds, _p(has), n, *[_p(x) for x in q], float(th), self.mfNNratio, _p(out)))
         return nm, out[:F.N].copy()
 
     def SearchByProjectionLastFrame(self, CurrentFrame, valid, u, v, last_octave, last_angle, point_desc, point_has_obs,
@@ -361,13 +395,15 @@ class ORBmatcher:
         bMono=true) (src/ORBmatcher.cc:1355-1474) for given projections (u, v)."""
         ext = CurrentFrame.ext
         F = CurrentFrame
-        has = np.ascontiguousarray(kp_has_point if kp_has_point is not None else np.zeros(max(F.N, 1), np.uint8), np.uint8)
-        a = [np.ascontiguousarray(valid, np.uint8), np.ascontiguousarray(u, np.float32), np.ascontiguousarray(v, np.float32),
-             np.ascontiguousarray(last_octave, np.int32), np.ascontiguousarray(last_angle, np.float32),
-             np.ascontiguousarray(point_desc, np.uint8), np.ascontiguousarray(point_has_obs, np.uint8)]
+        kp, desc = _frame(F, "CurrentFrame")
+        has = _mask(kp_has_point, F.N, "kp_has_point")
+        n = len(valid)
+        a = [_arr(valid, np.uint8, n, "valid"), _arr(u, np.float32, n, "u"), _arr(v, np.float32, n, "v"),
+             _arr(last_octave, np.int32, n, "last_octave"), _arr(last_angle, np.float32, n, "last_angle"),
+             _arr(point_desc, np.uint8, n, "point_desc", 32), _arr(point_has_obs, np.uint8, n, "point_has_obs")]
         out = np.full(max(F.N, 1), -1, np.int32)
         nm = ext._check(ext._L.pgorb_search_by_projection_frame(
-            ext._h, _p(F.mvKeysUndistorted), _p(F.mDescriptors), F.N, *F.bounds, _p(has), len(a[0]),
+            ext._h, _p(kp), _p(desc), F.N, *F.bounds, _p(has), n,
             *[_p(x) for x in a], float(th), int(self.mbCheckOrientation), _p(out)))
         return nm, out[:F.N].copy()
 
@@ -379,13 +415,16 @@ class ORBmatcher:
         max_distance are the points' plain mfMinDistance / mfMaxDistance (the depth test forms 0.8f * min / 1.2f * max)."""
         ext = CurrentFrame.ext
         F = CurrentFrame
-        has = np.ascontiguousarray(kp_has_point if kp_has_point is not None else np.zeros(max(F.N, 1), np.uint8), np.uint8)
-        a = [np.ascontiguousarray(valid, np.uint8), np.ascontiguousarray(already_found, np.uint8), np.ascontiguousarray(u, np.float32),
-             np.ascontiguousarray(v, np.float32), np.ascontiguousarray(dist3d, np.float32), np.ascontiguousarray(min_distance, np.float32),
-             np.ascontiguousarray(max_distance, np.float32), np.ascontiguousarray(kf_angle, np.float32), np.ascontiguousarray(point_desc, np.uint8)]
+        kp, desc = _frame(F, "CurrentFrame")
+        has = _mask(kp_has_point, F.N, "kp_has_point")
+        n = len(valid)
+        a = [_arr(valid, np.uint8, n, "valid"), _arr(already_found, np.uint8, n, "already_found"), _arr(u, np.float32, n, "u"),
+             _arr(v, np.float32, n, "v"), _arr(dist3d, np.float32, n, "dist3d"), _arr(min_distance, np.float32, n, "min_distance"),
+             _arr(max_distance, np.float32, n, "max_distance"), _arr(kf_angle, np.float32, n, "kf_angle"),
+             _arr(point_desc, np.uint8, n, "point_desc", 32)]
         out = np.full(max(F.N, 1), -1, np.int32)
         nm = ext._check(ext._L.pgorb_search_by_projection_keyframe(
-            ext._h, _p(F.mvKeysUndistorted), _p(F.mDescriptors), F.N, *F.bounds, _p(has), len(a[0]), *[_p(x) for x in a],
+            ext._h, _p(kp), _p(desc), F.N, *F.bounds, _p(has), n, *[_p(x) for x in a],
             ext.log_scale_factor(), float(th), int(ORBdist), int(self.mbCheckOrientation), _p(out)))
         return nm, out[:F.N].copy()
 
@@ -393,18 +432,17 @@ class ORBmatcher:
         """SearchByBoW(KeyFrame* pKF, Frame &F, vpMapPointMatches) (src/ORBmatcher.cc:161-290).
         Feature vectors are the (nodes, starts, features) triples of ORBVocabulary.transform().
         Returns (nmatches, matches) with matches[j] = key-frame keypoint index or -1."""
-        kd = np.ascontiguousarray(kf_desc, np.uint8).reshape(-1, 32)
-        ka = np.ascontiguousarray(kf_angle, np.float32)
-        kv = np.ascontiguousarray(kf_point_valid, np.uint8)
-        A = [np.ascontiguousarray(kf_featvec[0], np.uint32), np.ascontiguousarray(kf_featvec[1], np.int32),
-             np.ascontiguousarray(kf_featvec[2], np.uint32)]
-        B = [np.ascontiguousarray(f_featvec[0], np.uint32), np.ascontiguousarray(f_featvec[1], np.int32),
-             np.ascontiguousarray(f_featvec[2], np.uint32)]
-        fa = np.ascontiguousarray(F.mvKeys["angle"], np.float32)
+        nkf = len(kf_angle)
+        kd = _arr(kf_desc, np.uint8, nkf, "kf_desc", 32)
+        ka = _arr(kf_angle, np.float32, nkf, "kf_angle")
+        kv = _arr(kf_point_valid, np.uint8, nkf, "kf_point_valid")
+        A, B = _featvec(kf_featvec, "kf_featvec"), _featvec(f_featvec, "f_featvec")
+        fd = _arr(F.mDescriptors, np.uint8, F.N, "F descriptors", 32)
+        fa = _arr(F.mvKeys["angle"], np.float32, F.N, "F angles")
         out = np.full(max(F.N, 1), -1, np.int32)
         nm = ext._check(ext._L.pgorb_search_by_bow(
-            ext._h, _p(kd), _p(ka), _p(kv), len(kd), _p(A[0]), _p(A[1]), _p(A[2]), len(A[0]),
-            _p(F.mDescriptors), _p(fa), F.N, _p(B[0]), _p(B[1]), _p(B[2]), len(B[0]),
+            ext._h, _p(kd), _p(ka), _p(kv), nkf, _p(A[0]), _p(A[1]), _p(A[2]), len(A[0]),
+            _p(fd), _p(fa), F.N, _p(B[0]), _p(B[1]), _p(B[2]), len(B[0]),
             self.mfNNratio, int(self.mbCheckOrientation), _p(out)))
         return nm, out[:F.N].copy()
 
@@ -415,23 +453,13 @@ class ORBmatcher:
         Returns (nmatches, matches12) with matches12[i] = the KF2 keypoint matched to KF1 keypoint i, or -1 (vMatchedPairs =
         the (i, matches12[i]) with matches12[i] >= 0)."""
         F = np.ascontiguousarray(F12, np.float32).reshape(9)
-        masks = [np.ascontiguousarray(m if m is not None else np.zeros(max(K.N, 1), np.uint8), np.uint8).reshape(-1)
-                 for m, K in ((has_point1, KF1), (has_point2, KF2))]
-        fvs = [[np.ascontiguousarray(fv[0], np.uint32).reshape(-1), np.ascontiguousarray(fv[1], np.int32).reshape(-1),
-                np.ascontiguousarray(fv[2], np.uint32).reshape(-1)] for fv in (fv1, fv2)]
-        # the library reads N mask entries, N descriptors and start[nfv] feature indices through these pointers
-        for name, K, given, fv in (("KF1", KF1, has_point1, fvs[0]), ("KF2", KF2, has_point2, fvs[1])):
-            if K.mDescriptors.shape != (K.N, 32) or len(K.mvKeysUndistorted) != K.N:
-                raise ValueError("%s: %d keypoints need %d x 32 descriptors" % (name, K.N, K.N))
-            if given is not None and np.size(given) != K.N:
-                raise ValueError("%s: has_point holds %d entries for %d keypoints" % (name, np.size(given), K.N))
-            if len(fv[1]) != len(fv[0]) + 1 or len(fv[2]) < int(fv[1][-1]):
-                raise ValueError("%s: FeatureVector arrays of inconsistent lengths" % name)
+        args = []
+        for name, K, m, fv in (("KF1", KF1, has_point1, fv1), ("KF2", KF2, has_point2, fv2)):
+            kp, desc = _frame(K, name)
+            node, start, feat = _featvec(fv, name)
+            args += [_p(kp), _p(desc), _p(_mask(m, K.N, name + " has_point")), K.N, _p(node), _p(start), _p(feat), len(node)]
         ext = KF1.ext
         m12 = np.full(max(KF1.N, 1), -1, np.int32)
-        args = []
-        for K, m, fv in ((KF1, masks[0], fvs[0]), (KF2, masks[1], fvs[1])):
-            args += [_p(K.mvKeysUndistorted), _p(K.mDescriptors), _p(m), K.N, _p(fv[0]), _p(fv[1]), _p(fv[2]), len(fv[0])]
         nm = ext._check(ext._L.pgorb_search_for_triangulation(ext._h, *args, _p(F), float(np.float32(epipole[0])),
                                                               float(np.float32(epipole[1])), int(self.mbCheckOrientation), _p(m12)))
         return nm, m12[:KF1.N].copy()
@@ -440,11 +468,12 @@ class ORBmatcher:
         """(nmatches, vnMatches12); vbPrevMatched ([N1,2] float32) is updated in place, as in
         src/ORBmatcher.cc:407-522."""
         ext = F1.ext
-        prev = np.ascontiguousarray(vbPrevMatched, np.float32)
+        k1, d1 = _frame(F1, "F1")
+        k2, d2 = _frame(F2, "F2")
+        prev = _arr(vbPrevMatched, np.float32, F1.N, "vbPrevMatched", 2)
         m12 = np.full(max(F1.N, 1), -1, np.int32)
         nm = ext._check(ext._L.pgorb_search_for_initialization(
-            ext._h, _p(F1.mvKeysUndistorted), _p(F1.mDescriptors), F1.N,
-            _p(F2.mvKeysUndistorted), _p(F2.mDescriptors), F2.N, *F2.bounds, _p(prev), _p(m12),
+            ext._h, _p(k1), _p(d1), F1.N, _p(k2), _p(d2), F2.N, *F2.bounds, _p(prev), _p(m12),
             int(windowSize), self.mfNNratio, int(self.mbCheckOrientation)))
         vbPrevMatched[...] = prev
         return nm, m12[:F1.N].copy()

@@ -48,6 +48,52 @@ def test_oracle_search_for_initialization_finds_the_shift(oracle):
     assert np.array_equal(prev2[m12 >= 0], np.stack([k2["x"], k2["y"]], 1)[m12[m12 >= 0]])
 
 
+SFI_CPP_DRIVER = r"""
+// pgorb::ORBmatcher::SearchForInitialization (pilotguru_amd/host/orb_extractor.hpp) with a NULL context on well-formed and
+// mis-sized input: prints what came back, or the exception it threw
+#include <cstdio>
+#include "pilotguru_amd/host/orb_extractor.hpp"
+using namespace pgorb;
+int main()
+{
+    for (int v = 0; v < 6; v++) {
+        Frame F1, F2;
+        F1.mvKeysUndistorted.resize(4); F1.mDescriptors.resize(4 * 32);
+        F2.mvKeysUndistorted.resize(5); F2.mDescriptors.resize(5 * 32);
+        F2.mnMaxX = 640; F2.mnMaxY = 480;
+        std::vector<float> prev(8);
+        std::vector<int32_t> m12;
+        if (v == 1) F1.mDescriptors.resize(3 * 32);
+        if (v == 2) F2.mDescriptors.resize(6 * 32);
+        if (v == 3) prev.resize(6);
+        if (v == 4) prev.resize(10);
+        if (v == 5) prev.clear();
+        try {
+            std::printf("%d\n", ORBmatcher(nullptr).SearchForInitialization(F1, F2, prev, m12));
+        } catch (const std::invalid_argument&) { std::printf("invalid_argument\n");
+        } catch (const std::runtime_error&) { std::printf("runtime_error\n"); }
+    }
+    return 0;
+}
+"""
+
+
+def test_cpp_mirror_search_for_initialization_checks_sizes(tmp_path):
+    """pgorb::ORBmatcher::SearchForInitialization refuses descriptor buffers that are not N x 32 bytes and a vbPrevMatched
+    that is not 2 * N1 floats (std::invalid_argument) before any pointer reaches the library; well-formed input reaches it
+    (here a NULL context, so the library's PGORB_E_ARG comes back as std::runtime_error)."""
+    import os
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    src, exe = os.path.join(str(tmp_path), "sfi_driver.cc"), os.path.join(str(tmp_path), "sfi_driver")
+    open(src, "w").write(SFI_CPP_DRIVER)
+    lib = os.path.join(root, "pilotguru_amd")
+    subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-I", root, src, "-o", exe, "-L", lib, "-lpgorb", "-Wl,-rpath," + lib,
+                    "-Wl,-rpath,/opt/rocm/lib"], check=True)
+    out = subprocess.run([exe], stdout=subprocess.PIPE, universal_newlines=True, check=True).stdout.splitlines()
+    assert out == ["runtime_error"] + ["invalid_argument"] * 5, out
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("ratio,ori,win", [(0.9, True, 100), (0.7, False, 40), (0.9, True, 8)])
 def test_gpu_grid_and_search_for_initialization(oracle, ratio, ori, win):

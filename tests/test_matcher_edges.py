@@ -107,6 +107,72 @@ def test_c_round_and_three_maxima_by_hand():
     assert R.rotation_bin(10.0, 10.0) == 0 and R.rotation_bin(10.0, 10.0001) == 12 and R.rotation_bin(15.0, 0.0) == 1
 
 
+class _HostFrame:
+    """A frame without a device (ext is None): the wrappers' own checks come before any library call."""
+
+    def __init__(self, n, ndesc=None):
+        self.ext, self.N, self.bounds = None, n, BOUNDS
+        self.mvKeys = self.mvKeysUndistorted = np.zeros(n, KEYPOINT_DTYPE)
+        self.mDescriptors = np.zeros((n if ndesc is None else ndesc, 32), np.uint8)
+
+
+def _wrapper_calls():
+    """(call, well-formed arguments, [(name, arguments that must be refused)]) for every matcher wrapper; N = 4, 3 queries."""
+    import pilotguru_amd as pg
+    m, n, q = pg.ORBmatcher(), 4, 3
+    F, Fshort = _HostFrame(n), _HostFrame(n, n - 1)
+    u8, f4, i4 = (lambda k: np.ones(k, np.uint8)), (lambda k: np.zeros(k, np.float32)), (lambda k: np.zeros(k, np.int32))
+    d32 = lambda k: np.zeros((k, 32), np.uint8)
+    fv = (np.array([1, 2], np.uint32), np.array([0, 2, 4], np.int32), np.arange(4, dtype=np.uint32))
+    bad_fv = [("FeatureVector starts of the wrong length", (fv[0], fv[1][:2], fv[2])),
+              ("FeatureVector features shorter than start[nfv]", (fv[0], fv[1], fv[2][:3]))]
+    masks = [("short kp_has_point", dict(kp_has_point=u8(n - 1))), ("long kp_has_point", dict(kp_has_point=u8(n + 1))),
+             ("frame descriptors short", dict(F=Fshort))]
+    pts = dict(F=F, kp_has_point=u8(n), valid=u8(q), proj_x=f4(q), proj_y=f4(q), level=i4(q), view_cos=f4(q), descriptors=d32(q),
+               has_obs=u8(q))
+    last = dict(F=F, kp_has_point=None, valid=u8(q), u=f4(q), v=f4(q), last_octave=i4(q), last_angle=f4(q), point_desc=d32(q),
+                point_has_obs=u8(q))
+    kf = dict(F=F, kp_has_point=None, valid=u8(q), already_found=u8(q), u=f4(q), v=f4(q), dist3d=f4(q), min_distance=f4(q),
+              max_distance=f4(q), kf_angle=f4(q), point_desc=d32(q))
+    bow = dict(F=F, kf_desc=d32(n), kf_angle=f4(n), kf_point_valid=u8(n), kf_featvec=fv, f_featvec=fv)
+    sfi = dict(F1=F, F2=_HostFrame(n + 1), vbPrevMatched=np.zeros((n, 2), np.float32))
+    return {
+        "points": (lambda F, kp_has_point, **a: m.SearchByProjection(F, pg.MapPoints(**a), 3.0, kp_has_point), pts,
+                   masks + [("short proj_x", dict(proj_x=f4(q - 1))), ("long level", dict(level=i4(q + 1))),
+                            ("short query descriptors", dict(descriptors=d32(q - 1))), ("short has_obs", dict(has_obs=u8(q - 1)))]),
+        "last_frame": (lambda F, kp_has_point, **a: m.SearchByProjectionLastFrame(F, th=7.0, kp_has_point=kp_has_point, **a), last,
+                       masks + [("short u", dict(u=f4(q - 1))), ("long last_angle", dict(last_angle=f4(q + 1))),
+                                ("short point_desc", dict(point_desc=d32(q - 1))), ("short point_has_obs", dict(point_has_obs=u8(q - 1)))]),
+        "keyframe": (lambda F, kp_has_point, **a: m.SearchByProjectionKeyFrame(F, th=7.0, ORBdist=100, kp_has_point=kp_has_point, **a), kf,
+                     masks + [("short already_found", dict(already_found=u8(q - 1))), ("long dist3d", dict(dist3d=f4(q + 1))),
+                              ("short max_distance", dict(max_distance=f4(q - 1))), ("short kf_angle", dict(kf_angle=f4(q - 1))),
+                              ("long point_desc", dict(point_desc=d32(q + 1)))]),
+        "bow": (lambda **a: m.SearchByBoW(None, **a), bow,
+                [("short kf_point_valid", dict(kf_point_valid=u8(n - 1))), ("short kf_desc", dict(kf_desc=d32(n - 1))),
+                 ("long kf_desc", dict(kf_desc=d32(n + 1))), ("frame descriptors short", dict(F=Fshort))] +
+                [(k, dict(kf_featvec=v)) for k, v in bad_fv] + [(k, dict(f_featvec=v)) for k, v in bad_fv]),
+        "sfi": (lambda **a: m.SearchForInitialization(**a), sfi,
+                [("short vbPrevMatched", dict(vbPrevMatched=np.zeros((n - 1, 2), np.float32))),
+                 ("flat vbPrevMatched", dict(vbPrevMatched=np.zeros(2 * n, np.float32))),
+                 ("vbPrevMatched of 3 columns", dict(vbPrevMatched=np.zeros((n, 3), np.float32))),
+                 ("F1 descriptors short", dict(F1=Fshort)), ("F2 descriptors short", dict(F2=_HostFrame(n + 1, n)))]),
+    }
+
+
+@pytest.mark.parametrize("form", ["points", "last_frame", "keyframe", "bow", "sfi"])
+def test_python_wrapper_rejects_short_masks_and_inconsistent_feature_vectors(form):
+    """The wrappers hand the library one count per frame and per query set and every array by pointer: a per-query array,
+    mask or descriptor block of another length, a vbPrevMatched that is not (N1, 2) and a FeatureVector whose arrays disagree
+    are refused with ValueError before any library call.  Well-formed input gets past the checks (to the missing device)."""
+    call, good, bad = _wrapper_calls()[form]
+    with pytest.raises(AttributeError):
+        call(**good)
+    for name, kw in bad:
+        with pytest.raises(ValueError):
+            call(**dict(good, **kw))
+            pytest.fail(name)
+
+
 @pytest.fixture(scope="module")
 def ext():
     import pilotguru_amd as pg
@@ -138,6 +204,44 @@ def test_gpu_single_calls_and_batched_forms_equal_the_reference(oracle, ext, fam
     for gi_, group in enumerate(grid_groups(cases)):                      # the grid cases through the batched grid as well
         for c, g in zip(group, run_gpu_grid_batched(group, ext, "huge" if gi_ % 2 == 0 else "nan")):
             assert same(run_reference(c), g), "%s: batched grid %r" % (c["name"], g)
+
+
+@pytest.mark.gpu
+def test_gpu_search_by_bow_refuses_feature_vectors_outside_the_frame(ext):
+    """pgorb_search_by_bow checks both FeatureVectors as pgorb_search_for_triangulation does: a feature index >= n, a first
+    start other than 0 or a descending start is PGORB_E_ARG (the kernel would read outside the frame's slot).  An empty side
+    still gives all -1 and 0, with NULL FeatureVector pointers allowed when nfv == 0."""
+    import pilotguru_amd as pg
+    from matcher_cases import ArrayFrame, keys, rand_desc
+    from pilotguru_amd import _lib
+    rng = np.random.RandomState(11)
+    n = 4
+    k = keys([100.0, 200.0, 300.0, 400.0], [100.0, 150.0, 200.0, 250.0])
+    kd, F = rand_desc(rng, n), ArrayFrame(ext, k, rand_desc(rng, n), BOUNDS)
+    ka, kv = k["angle"].copy(), np.ones(n, np.uint8)
+    m = pg.ORBmatcher(0.9, True)
+    fv = (np.array([1, 2], np.uint32), np.array([0, 2, 4], np.int32), np.arange(4, dtype=np.uint32))
+    nm, mt = m.SearchByBoW(ext, kd, ka, kv, fv, F, fv)
+    assert nm >= 0 and len(mt) == n
+    bad = [(fv[0], fv[1], np.array([0, 1, 2, 4], np.uint32)), (fv[0], np.array([1, 2, 4], np.int32), fv[2]),
+           (fv[0], np.array([0, 3, 2], np.int32), fv[2])]
+    for b in bad:
+        for kfv, ffv in ((b, fv), (fv, b)):
+            with pytest.raises(_lib.PgorbError) as e:
+                m.SearchByBoW(ext, kd, ka, kv, kfv, F, ffv)
+            assert e.value.code == _lib.PGORB_E_ARG
+    empty = (np.zeros(0, np.uint32), np.zeros(1, np.int32), np.zeros(0, np.uint32))
+    for kfv, ffv in ((empty, fv), (fv, empty)):
+        nm, got = m.SearchByBoW(ext, kd, ka, kv, kfv, F, ffv)
+        assert nm == 0 and (got == -1).all()
+    nm, got = m.SearchByBoW(ext, np.zeros((0, 32), np.uint8), np.zeros(0, np.float32), np.zeros(0, np.uint8), empty, F, fv)
+    assert nm == 0 and (got == -1).all()
+    p = lambda a: C.c_void_p(a.ctypes.data)
+    out = np.full(n, 7, np.int32)
+    fa = F.mvKeys["angle"].copy()
+    assert ext._L.pgorb_search_by_bow(ext._h, p(kd), p(ka), p(kv), n, None, None, None, 0, p(F.mDescriptors), p(fa), n,
+                                      p(fv[0]), p(fv[1]), p(fv[2]), 2, C.c_float(0.9), 1, p(out)) == 0
+    assert (out == -1).all()
 
 
 @pytest.mark.gpu

@@ -6,15 +6,21 @@ that are already resident in HBM: K1 pyramid -> K2 per-cell FAST -> K3 quadtree 
 K4-6 orientation+blur+rBRIEF (2000 keypoints/frame) -> K7 best-2 Hamming match of every frame
 against its predecessor in the ride.  Workload = BASELINE.json configs[1].
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run does what its headline figure needs: set-up, the sustained leg (it brings the clocks up before the
+warm-up), the W warm-up and K timed steps, --dump-outputs when given, and the JSON line.  --full adds everything
+else the bench measures or checks, all of it after the timed region: the oracle verification, the vocabulary
+broadcast and BoW check (N > 1), the two-batches-in-flight, popcount-matcher, uploaded-frames and single-frame
+legs, the rocprofv3 traffic runs and the CPU baseline.  The --no-* switches turn single legs of --full off.
 
 `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment launches its own N ranks (it
 re-executes itself under torch.distributed.run on 127.0.0.1 with a free port), so both command shapes work.
 
 Multi-GPU: frames are independent, so every rank runs its own ride on its own GPU (weak
-scaling, no data-path collective); the only collective is one RCCL broadcast of the ORB
-vocabulary at start-up (outside the timed region), plus the barrier / max-over-ranks timing.
+scaling, no data-path collective); the only collectives are the barrier / max-over-ranks timing
+and, with --full, one RCCL broadcast of the ORB vocabulary at start-up (outside the timed region).
 Rank 0 prints ONE JSON line.
 """
 import argparse
@@ -352,8 +358,7 @@ def live_pmc(args, kname):
     base = tempfile.mkdtemp(prefix="pgorb_pmc_")
     child = [sys.executable, os.path.abspath(__file__), "--steps", "3", "--warmup", "1", "--batch", str(args.batch),
              "--width", str(args.width), "--height", str(args.height), "--features", str(args.features), "--scene", args.scene,
-             "--no-cpu-baseline", "--no-verify", "--sustain-seconds", "0", "--no-upload-leg", "--no-overlap-leg",
-             "--no-single-frame-leg", "--no-traffic-leg"] + (["--fused-levels", str(args.fused_levels)] if args.fused_levels is not None else [])
+             "--sustain-seconds", "0"] + (["--fused-levels", str(args.fused_levels)] if args.fused_levels is not None else [])
     env = dict(os.environ, TMPDIR="/tmp", PGORB_BENCH_CHILD="1")
     out = {}
     try:
@@ -509,9 +514,16 @@ def main():
                     help="after the timed steps, write what the last timed step computed (rank 0's keypoints, descriptors, "
                          "counts and best-2 matches) as DIR/<name>.npy in float32 / float64, at most 64 MB (a fixed, seeded "
                          "sample of the frames when the batch is larger)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every leg beyond the headline figure: oracle verification, vocabulary "
+                         "broadcast + BoW check (N > 1), two batches in flight, popcount matcher, uploaded frames, single frame, "
+                         "rocprofv3 traffic runs, CPU baseline (each --no-* switch turns one of them off)")
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if not args.full:                                           # a plain run: nothing the headline figure does not need
+        args.no_cpu_baseline = args.no_verify = args.no_upload_leg = args.no_overlap_leg = True
+        args.no_single_frame_leg = args.no_traffic_leg = True
 
     if (args.gpus > 1 or os.environ.get("PGORB_BENCH_FORCE_LAUNCH")) and "WORLD_SIZE" not in os.environ:
         self_launch(args.gpus)                                  # does not return
@@ -566,7 +578,8 @@ def main():
     # vocabulary arena; torch.distributed only hands the 128-byte RCCL id round).  Reference: one ORBVocabulary shared by
     # pointer, src/optical_trajectories.cc:87-94.
     vocab_bytes, vocab_bcast_s, voc, voc_path, voc_comm = 0, None, None, None, None
-    if dist is not None:
+    vocab_path_used, rccl_info = None, None
+    if dist is not None and args.full:
         from pilotguru_amd import dist as pgd
         from pilotguru_amd import vocab as V
         if rank == 0:
@@ -661,7 +674,7 @@ def main():
     # config 4's criterion: every rank's BoW words -- of ITS OWN ride's first frame, through the
     # vocabulary that reached it by the broadcast -- equal the CPU oracle's on rank 0 (words, weights and nodes themselves)
     bow_verified = None
-    if dist is not None:
+    if dist is not None and args.full:
         import ctypes as C
         n0 = int(n[0].item())
         pw = torch.empty(n0, dtype=torch.int32, device=dev)
@@ -736,7 +749,7 @@ def main():
     # the matcher the north star describes (ballot / popcount), timed on the same descriptors
     matcher = ext.matcher_name(cap)
     popcount_ms = None
-    if dist is None and B > 1:
+    if args.full and dist is None and B > 1:
         try:
             ext.set_option("matcher", 1)
             for _ in range(2):
@@ -823,8 +836,8 @@ def main():
                        "fused_levels": fused,
                        "batch": B, "keypoints_per_frame": nkp, "parallelism": "frames-sharded x%d" % world,
                        "vocab_broadcast_bytes": vocab_bytes, "vocab_broadcast_s": vocab_bcast_s,
-                       "vocab_broadcast": None if dist is None else vocab_path_used,
-                       "vocab_broadcast_librccl": None if dist is None else rccl_info,
+                       "vocab_broadcast": vocab_path_used,
+                       "vocab_broadcast_librccl": rccl_info,
                        "bow_words_equal_oracle_on_every_rank": bow_verified,
                        "matcher": matcher, "matcher_popcount_ms_per_step": popcount_ms},
             "roofline": {"bound": "hbm", "kernel": kname,

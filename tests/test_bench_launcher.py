@@ -48,7 +48,7 @@ def test_launched_rank_rejects_a_mismatched_world():
 
 @pytest.mark.gpu
 def test_bench_at_n1_directly_and_through_the_self_launch_path():
-    quick = ["--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "8", "--no-cpu-baseline", "--no-upload-leg",
+    quick = ["--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "8", "--full", "--no-cpu-baseline", "--no-upload-leg",
              "--no-overlap-leg", "--sustain-seconds", "0"]
     a = _last_json(_run(quick, {}, 900))
     b = _last_json(_run(quick, {"PGORB_BENCH_FORCE_LAUNCH": "1", "PGORB_BENCH_FORCE_DIST": "1"}, 900))
@@ -56,3 +56,18 @@ def test_bench_at_n1_directly_and_through_the_self_launch_path():
         assert out["n_gpus"] == 1 and out["verified"] is True and out["value"] > 0
         assert len(out["per_rank_fps"]) == 1 and out["roofline"]["frac"] > 0
     assert b["config"]["vocab_broadcast_bytes"] > 0          # the RCCL branch ran in the launched rank
+
+
+@pytest.mark.gpu
+def test_plain_bench_run_has_the_headline_and_none_of_the_full_legs():
+    """Without --full the run is set-up, warm-up, the timed steps and the line: nothing checked against the oracle, no leg
+    after the timed region, no rocprofv3 child runs (roofline.traffic is cited from a committed profile, if any)."""
+    out = _last_json(_run(["--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "8", "--sustain-seconds", "0"], {}, 600))
+    assert out["n_gpus"] == 1 and out["steps"] == 3 and out["warmup"] == 1 and out["value"] > 0
+    assert out["unit"] == "frames/s" and out["higher_is_better"] is True and out["dtype"] == "u8"
+    assert abs(out["value"] - 8 * 3 / out["max_rank_seconds"]) < 1e-6 * out["value"]
+    assert abs(out["ms_per_step"] - out["max_rank_seconds"] / 3 * 1e3) < 1e-6 * out["ms_per_step"]
+    assert out["verified"] is None and out["roofline"]["traffic_measured_by_this_run"] is False
+    assert out["config"]["matcher_popcount_ms_per_step"] is None and out["config"]["vocab_broadcast"] is None
+    for leg in ("cpu_baseline", "single_frame", "frames_uploaded", "two_batches_in_flight", "leg_errors"):
+        assert leg not in out, leg

@@ -135,7 +135,7 @@ def test_multi_gpu_code_path_on_one_gpu():
     env = dict(os.environ, PGORB_BENCH_FORCE_DIST="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
            "--master-addr", "127.0.0.1", "--master-port", "29631", os.path.join(ROOT, "bench.py"),
-           "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "8", "--no-cpu-baseline"]
+           "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "8", "--full", "--no-cpu-baseline"]
     r = subprocess.run(cmd, env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, universal_newlines=True,
                        timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]

@@ -1,13 +1,13 @@
 #!/bin/bash
-# BASELINE.md's results table: the three single-GPU configurations through bench.py (CPU legs included),
+# BASELINE.md's results table: the three single-GPU configurations through bench.py --full (CPU legs included),
 # the driving-like scene, one line each under gpurun_out/<tag>/ (copy the ones to keep into profiles/).
 TAG=${1:-r02_table}
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
-python bench.py --width 640 --height 480 --features 1000 --batch 512 > $OUT/${TAG}_640x480_1000.json 2> $OUT/err_640.log
-python bench.py > $OUT/${TAG}_1920x1080_2000.json 2> $OUT/err_1080.log
-python bench.py --width 3840 --height 2160 --features 4000 --batch 32 > $OUT/${TAG}_3840x2160_4000.json 2> $OUT/err_4k.log
-python bench.py --scene road > $OUT/${TAG}_1920x1080_2000_road.json 2> $OUT/err_road.log
+python bench.py --full --width 640 --height 480 --features 1000 --batch 512 > $OUT/${TAG}_640x480_1000.json 2> $OUT/err_640.log
+python bench.py --full > $OUT/${TAG}_1920x1080_2000.json 2> $OUT/err_1080.log
+python bench.py --full --width 3840 --height 2160 --features 4000 --batch 32 > $OUT/${TAG}_3840x2160_4000.json 2> $OUT/err_4k.log
+python bench.py --full --scene road > $OUT/${TAG}_1920x1080_2000_road.json 2> $OUT/err_road.log
 for f in $OUT/*.json; do echo "== $f"; tail -1 $f | python -c "
 import sys, json
 d = json.loads(sys.stdin.read())

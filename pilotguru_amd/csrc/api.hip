@@ -57,20 +57,13 @@ struct pgorb_ctx {
     // K3 / K4-6 of a group of levels beside K2 of the next group (pgorb_set_option "pipeline_levels", bit l = a group
     // starts at level l): K3 is one workgroup's critical path per (frame, level) and leaves the chip mostly idle
     int pipeLev = 0, pipeLevPrio = 0;
-    // a device-resident stream's lanes (pgorb_stream_create_device): recorded behind the batch's last pyramid launch / behind K2,
-    // so that the NEXT batch (on another lane) can be held back until this one has reached that point (stagger)
-    hipEvent_t evPyrEnd = nullptr, evFastEnd = nullptr;
     hipStream_t sQt = nullptr, sDesc = nullptr;
     hipEvent_t evGrpFast[PG_MAXL] = {}, evGrpQt[PG_MAXL] = {}, evDescDone = nullptr;
-    Arena stageA, stageB, stageOut, stageSfi, vocab;
+    Arena stageA, stageOut, stageSfi, vocab;
     Arena xdesc;                              // matcher scratch: train descriptors as +-1 bytes (match.hip, match_mode 0 only)
     PgMatchOpts mx;                           // this context's matcher settings (pgorb_set_option "matcher" / "match_mode")
     void* pinned = nullptr;                   // page-locked bounce buffer for bulk result download
     size_t pinnedBytes = 0;
-    uint8_t* pinIn = nullptr;                 // page-locked input staging of the host-frame calls (pgorb_extract*)
-    size_t pinInBytes = 0;
-    int chunkBytes = 512 << 10, noStage = 1;  // PGORB_EXTRACT_STAGE=1: frames through the context's page-locked staging buffer in chunks of this size (measured SLOWER
-                                              // than the runtime's own pageable-copy path, DESIGN.md section 6 round 4: kept as the A/B switch)
     Arena outBlk;                             // status word | counts | keypoints | descriptors of a host-frame call: one download
     double hostUs[4] = {0, 0, 0, 0}; int hostCalls = 0;
     // the host-frame calls run on a stream of the context's own, and replay their kernel chain (K1..K6 + the result download)
@@ -189,6 +182,332 @@ void build_resize_tables(int sw, int sh, int dw, int dh, std::vector<int32_t>& x
 
 size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// The plan's host tables.  The builders below make no HIP call: make_plan uploads what they return and resolves the pointers.
+
+// the resize tables of level l from level l - 1 (S the source level, D the level itself)
+struct ResizeTabs {
+    std::vector<int32_t> xofs, xofs1, yofs, tilex;
+    std::vector<int16_t> xalpha, ybeta;
+    std::vector<PgQuadTab> qt;
+    std::vector<PgQuadTab2> q2;
+    std::vector<uint8_t> yrel;
+    std::vector<PgRowGrp> rg;
+    bool hasQ = false, hasQ2 = false, hasY = false;
+    int cpr = 0, prows = 0;                                           // LDS-staged form: 16-byte chunks per row, staged rows (0: does not fit)
+};
+
+ResizeTabs build_resize_level(const LevelGeom& S, const LevelGeom& D, int pyrGpw)
+{
+    ResizeTabs R;
+    build_resize_tables(S.w, S.h, D.w, D.h, R.xofs, R.xofs1, R.xalpha, R.yofs, R.ybeta);
+    const std::vector<int32_t>& xo = R.xofs; const std::vector<int32_t>& xo1 = R.xofs1; const std::vector<int32_t>& yo = R.yofs;
+    const std::vector<int16_t>& xa = R.xalpha; const std::vector<int16_t>& yb = R.ybeta;
+    // quad table for the fast path
+    const int nq = (D.w + 3) / 4;
+    std::vector<PgQuadTab>& qt = R.qt;
+    qt.resize(nq);
+    bool ok = true;
+    for (int q = 0; q < nq; q++) {
+        PgQuadTab& T = qt[q];
+        memset(&T, 0, sizeof(T));
+        T.base_dw = xo[4 * q] >> 2;
+        for (int k = 0; k < 4; k++) {
+            const int dx = 4 * q + k;
+            if (dx >= D.w) break;
+            const int o = xo[dx] - 4 * T.base_dw;
+            if (o < 0 || o > 8) ok = false;
+            // tap 1 is read at o+1; where cv::resize clamps it (xofs1 == xofs) its weight is 0
+            if (xo1[dx] != xo[dx] + 1 && xa[2 * dx + 1] != 0) ok = false;
+            T.offs |= (uint32_t)(o & 15) << (4 * k);
+            T.a0[k] = xa[2 * dx]; T.a1[k] = xa[2 * dx + 1];
+        }
+    }
+    R.hasQ = ok;
+    // 8-byte-window table: xb = first tap of the quad (clamped so the window stays inside the row)
+    std::vector<PgQuadTab2>& q2 = R.q2;
+    q2.resize(nq);
+    bool ok2 = S.w >= 8;
+    for (int q = 0; q < nq && ok2; q++) {
+        PgQuadTab2& T = q2[q];
+        memset(&T, 0, sizeof(T));
+        T.xb = std::min(xo[4 * q], S.w - 8);
+        for (int k = 0; k < 4; k++) {
+            const int dx = 4 * q + k;
+            if (dx >= D.w) { T.sel[k] = 0x0c0c0c0cu; continue; }
+            const int o0 = xo[dx] - T.xb, o1 = xo1[dx] - T.xb;
+            if (o0 < 0 || o0 > 7 || o1 < 0 || o1 > 7) { ok2 = false; break; }
+            T.sel[k] = (uint32_t)o0 | (0x0cu << 8) | ((uint32_t)o1 << 16) | (0x0cu << 24);
+            T.coef[k] = (uint32_t)(uint16_t)xa[2 * dx] | ((uint32_t)(uint16_t)xa[2 * dx + 1] << 16);
+            if (xa[2 * dx] < 0 || xa[2 * dx + 1] < 0) ok2 = false;
+        }
+    }
+    R.hasQ2 = ok2;
+    // row pattern for the 4-rows-per-lane kernel: r0(dy) - r0(group base) - d in {0,1}, r1 - r0 in {0,1}
+    std::vector<uint8_t>& yr = R.yrel;
+    yr.assign(D.h, 0);
+    bool oky = true;
+    for (int dy = 0; dy < D.h; dy++) {
+        const int base = yo[2 * (dy & ~3)], d = dy & 3;
+        const int e0 = yo[2 * dy] - base - d, e1 = yo[2 * dy + 1] - yo[2 * dy];
+        if (e0 < 0 || e0 > 1 || e1 < 0 || e1 > 1) oky = false;
+        yr[dy] = (uint8_t)((e0 & 1) | ((e1 & 1) << 1));
+    }
+    R.hasY = oky;
+    std::vector<PgRowGrp>& rg = R.rg;
+    rg.resize((D.h + 3) / 4 + 4);                                     // + records of slack (a wave loads its 1, 2 or 4 records at once)
+    for (size_t gi = 0; gi < rg.size(); gi++) {
+        PgRowGrp& G = rg[gi];
+        memset(&G, 0, sizeof(G));
+        G.sFirst = yo[2 * std::min((int)(4 * gi), D.h - 1)];
+        for (int d = 0; d < 4; d++) {
+            const int dy = std::min((int)(4 * gi) + d, D.h - 1);
+            G.yrel4 |= (uint32_t)yr[dy] << (8 * d);
+            G.ybeta[2 * d] = yb[2 * dy]; G.ybeta[2 * d + 1] = yb[2 * dy + 1];
+        }
+    }
+    // LDS-staged variant of the 4x4 kernel: a 256 x 32 destination tile stages its source
+    // rectangle (16-byte chunks from a 16-aligned first column) through LDS
+    const int tileRows = 16 * pyrGpw, gpt = 4 * pyrGpw;               // rows / 4-row groups per tile
+    const int ntx = (D.w + 255) / 256, nty = (D.h + tileRows - 1) / tileRows, ngrp = (D.h + 3) / 4;
+    std::vector<int32_t>& tx0 = R.tilex;
+    tx0.assign(ntx, 0);
+    int span = 0, rows = 0;
+    if (ok2 && oky) {
+        for (int tx = 0; tx < ntx; tx++) {
+            const int qf = 64 * tx, ql = std::min(64 * tx + 63, nq - 1);
+            tx0[tx] = q2[qf].xb & ~15;
+            span = std::max(span, q2[ql].xb + 8 - tx0[tx]);
+        }
+        for (int ty = 0; ty < nty; ty++) {
+            const int gf = gpt * ty, gl = std::min(gpt * ty + gpt - 1, ngrp - 1);
+            rows = std::max(rows, rg[gl].sFirst + 6 - rg[gf].sFirst);
+        }
+        const int cpr = (span + 4 + 15) / 16;
+        if (cpr <= 32 && (size_t)rows * cpr * 16 <= (size_t)10 * 1024 * pyrGpw) { R.cpr = cpr; R.prows = rows; }
+    }
+    return R;
+}
+
+// the fused launch's tables with S as the source level (D the next level, R its resize tables); nb == 0: the level takes K1 + K2
+struct FusedTabs {
+    std::vector<int32_t> bands, cols;
+    int nb = 0, spb = 0, rows = 0;
+};
+
+FusedTabs build_fused_level(const LevelGeom& S, const LevelGeom& D, const ResizeTabs& R)
+{
+    // fused resize + detect (fused.hip) with level l - 1 as the source: bands = the source level's cell rows (hCell + 6 staged
+    // rows from row 16 + i hCell) between an edge band above (rows 0 ...) and below; a band owns the 4-row groups of level l whose
+    // first source row lies in [its first row, the next band's first row), so that the six source rows of every group are staged;
+    // tile columns = NS cells, a column owns the quads whose window starts in [15 + first cell * wCell, ... of the next column).
+    FusedTabs F;
+    const std::vector<PgQuadTab2>& q2 = R.q2;
+    const std::vector<PgRowGrp>& rg = R.rg;
+    const int nq = (int)q2.size();
+    const int ngrp = (D.h + 3) / 4, rowsB = S.hCell + 6;
+    bool fok = R.hasQ2 && R.hasY && S.wCell <= 32 && S.hCell <= 40 && S.hCell >= 16 && S.wCell >= 16;       // (the detector's narrow form; 3 x 21 staged rows)
+    std::vector<int32_t> bands, cols;
+    int nb = 0;
+    if (fok) {
+        const int maxS = rg[ngrp - 1].sFirst;
+        std::vector<int> Y{0};
+        for (int i = 0; i < S.nRows || PG_EDGE + i * S.hCell <= maxS; i++) Y.push_back(PG_EDGE + i * S.hCell);
+        int gi = 0;
+        for (size_t b = 0; b < Y.size(); b++) {
+            const int yNext = b + 1 < Y.size() ? Y[b + 1] : INT32_MAX;
+            const int g0 = gi;
+            while (gi < ngrp && rg[gi].sFirst < yNext) {
+                if (rg[gi].sFirst < Y[b] || rg[gi].sFirst + 5 - Y[b] > rowsB - 1) fok = false;
+                gi++;
+            }
+            bands.insert(bands.end(), {g0, gi - g0});          // (the kernel derives the band's first row and cell row from b)
+            nb++;
+        }
+        if (gi != ngrp) fok = false;
+    }
+    int spbF = 0;
+    if (fok) {
+        // slot columns: s = -1 the left edge's pseudo-cell (source columns from 0), s >= 0 from column 15 + s wCell (the cell's
+        // iniX - 1; past the last cell column: pseudo-cells that only serve the resize); a quad belongs to the column its
+        // 8-byte window starts in -- and then lies inside that column's 48 bytes
+        auto slotOf = [&](int xb) { return xb < PG_EDGE - 1 ? -1 : (xb - (PG_EDGE - 1)) / S.wCell; };
+        auto slotX = [&](int sl) { return sl < 0 ? 0 : PG_EDGE - 1 + sl * S.wCell; };
+        int nSlotsTotal = S.nCols;
+        for (int q = 0; q < nq; q++) {
+            const int sl = slotOf(q2[q].xb), off = q2[q].xb - slotX(sl);
+            if (q > 0 && q2[q].xb < q2[q - 1].xb) fok = false;
+            if (off < 0 || (off & ~3) + 12 > 48) fok = false;
+            nSlotsTotal = std::max(nSlotsTotal, sl + 1);
+        }
+        spbF = nSlotsTotal + 1;
+        int qi = 0, maxNq = 0, maxNg = 0;
+        for (int sl = -1; sl < nSlotsTotal; sl++) {
+            const int q0 = qi;
+            while (qi < nq && slotOf(q2[qi].xb) <= sl) qi++;
+            const int n = qi - q0, magic = n > 0 ? 65536 / n + 1 : 65536;
+            for (int lane = 0; lane < 64 && n > 0; lane++) if (((lane * magic) >> 16) != lane / n) fok = false;
+            maxNq = std::max(maxNq, n);
+            cols.insert(cols.end(), {q0, n, magic, 0});
+        }
+        if (qi != nq) fok = false;
+        for (int b = 0; b < nb; b++) maxNg = std::max(maxNg, bands[2 * b + 1]);
+        if (maxNq * maxNg > 64) fok = false;                   // lane = (quad, group)
+    }
+    if (fok) {
+        F.bands = std::move(bands); F.cols = std::move(cols);
+        F.nb = nb; F.spb = spbF; F.rows = rowsB;
+    }
+    return F;
+}
+
+// the per-frame sizes of the arenas and where every level starts in them
+struct PlanLayout {
+    size_t pyrOff[PG_MAXL];
+    size_t pyrFrame = 0, candFrame = 0, selFrame = 0, nodeFrame = 0, cellCandFrame = 0;
+    int cells = 0, selTotal = 0;
+};
+
+// Caps, slab offsets and node placement of every level into P.lvl, and the limits of the kernels (PGORB_E_LIMIT).
+int build_layout(pgorb_ctx* c, const LevelGeom* g, PgPlan& P, PlanLayout& A)
+{
+    for (int l = 0; l < P.nlevels; l++) {
+        PgLevel& V = P.lvl[l];
+        V.w = g[l].w; V.h = g[l].h;
+        V.pitch = (int)align_up(V.w, 64);
+        V.fstride = (int64_t)align_up((size_t)V.pitch * V.h + 64, 256);
+        A.pyrOff[l] = A.pyrFrame;
+        A.pyrFrame += (size_t)V.fstride;
+        V.nCols = g[l].nCols; V.nRows = g[l].nRows; V.wCell = g[l].wCell; V.hCell = g[l].hCell;
+        V.cellBase = A.cells; A.cells += V.nCols * V.nRows;
+        V.quota = c->mnFeaturesPerLevel[l];
+        V.nIni = g[l].nIni; V.hX = g[l].hX;
+        V.selCap = std::max(V.quota + 2, 4 * V.nIni);
+        V.nodeCap = (int)align_up(V.selCap + 8, 4);
+        // NMS survivors are never 8-adjacent: at most ceil(IW/2)*ceil(IH/2) per cell
+        V.candCap = ((V.w - 2 * PG_EDGE) / 2 + V.nCols + 1) * ((V.h - 2 * PG_EDGE) / 2 + V.nRows + 1);
+        V.candOff = (int64_t)A.candFrame; A.candFrame += align_up(V.candCap, 64);
+        V.cellCap = ((V.wCell + 1) / 2) * ((V.hCell + 1) / 2);
+        V.cellCandOff = (int64_t)A.cellCandFrame;
+        A.cellCandFrame += align_up((size_t)V.cellCap * V.nCols * V.nRows, 64);
+        V.selOff = (int64_t)A.selFrame; A.selFrame += V.selCap;      // slab offset == capacity prefix: K4-6's slot s of a frame IS entry s
+        // node arrays of the quadtree: LDS when 30 ints per node fit its 140 KB, else a global slab
+        // (quotas above ~1180 keypoints on one level: slower, but no configuration is refused)
+        V.nodeOff = -1;
+        // K3 keeps a level's node arrays (28 ints per node) in LDS beside its count pyramid (17 KB static) and its aux area
+        // (max(pyramid leaves <= 3072, cells of the largest level + 1) ints); what does not fit 160 KB goes to a global slab
+        const size_t qtAux = std::max((size_t)3072, (size_t)g[0].nCols * g[0].nRows + 1);
+        const size_t qtTab = (size_t)2 * ((g[0].w - 2 * PG_EDGE) + (g[0].h - 2 * PG_EDGE));      // the prologue's coordinate tables share the node area
+        if (std::max((size_t)V.nodeCap * 28, qtTab) * sizeof(int) + qtAux * sizeof(int) + 17 * 1024 > 160 * 1024) {
+            V.nodeOff = (int64_t)A.nodeFrame;
+            A.nodeFrame += align_up((size_t)V.nodeCap * 30, 64);
+        }
+        V.scale = c->mvScaleFactor[l];
+        V.patchSize = (float)(int)(31 * c->mvScaleFactor[l]);                     // :836
+        A.selTotal += V.selCap;
+        if ((size_t)(V.nCols * V.nRows + 1) * sizeof(int) > 140 * 1024)
+            return fail(c, PGORB_E_LIMIT, "too many cells on one level for the quadtree kernel's LDS budget");
+        if (V.w > 4095 + 2 * PG_EDGE || V.h > 4095 + 2 * PG_EDGE)
+            return fail(c, PGORB_E_LIMIT, "level larger than 4095 px is not supported");
+        if (V.selCap > 65535)      // K3's dispatch-order sort packs a keypoint's arrival index into 16 bits
+            return fail(c, PGORB_E_LIMIT, "more than 65533 keypoints on one pyramid level are not supported");
+    }
+    A.selFrame = align_up(A.selFrame, 16);
+    P.totalCells = A.cells; P.selTotal = A.selTotal;
+    P.cellCandFrame = (int64_t)A.cellCandFrame;
+    P.candFrame = (int64_t)A.candFrame; P.selFrame = (int64_t)A.selFrame; P.nodeFrame = (int64_t)A.nodeFrame;
+    return 0;
+}
+
+// K2's 64-byte cell records (PgPlan::cellTab) of a batch of B frames, and the same records in K2's balanced order
+// (PgPlan::cellTabBal, `per` records per XCD)
+void build_cell_tables(const PgPlan& P, const PlanLayout& A, size_t B, std::vector<uint32_t>& ct, std::vector<uint32_t>& cb, size_t& per)
+{
+    ct.assign((size_t)A.cells * 16, 0u);
+    for (int l = 0; l < P.nlevels; l++) {
+        const PgLevel& V = P.lvl[l];
+        const int maxBorderX = V.w - PG_EDGE, maxBorderY = V.h - PG_EDGE;
+        for (int i = 0; i < V.nRows; i++)
+            for (int j = 0; j < V.nCols; j++) {
+                const int cidx = i * V.nCols + j;
+                uint32_t* r = &ct[((size_t)V.cellBase + cidx) * 16];
+                const int iniY = PG_EDGE + i * V.hCell, iniX = PG_EDGE + j * V.wCell;      // :791-801
+                const int W = std::min(iniX + V.wCell + 6, maxBorderX) - iniX;
+                const int H = std::min(iniY + V.hCell + 6, maxBorderY) - iniY;
+                // skipped cells (:794, :803) and windows cv::FAST finds nothing in (< 7 px)
+                const bool skip = iniY >= maxBorderY - 3 || iniX >= maxBorderX - 6 || W < 7 || H < 7;
+                const uint64_t off = (uint64_t)(A.pyrOff[l] * B) + (uint64_t)iniY * V.pitch + (uint64_t)(iniX - 1);
+                r[0] = (uint32_t)l | ((uint32_t)(V.cellBase + cidx) << 4);
+                r[1] = (uint32_t)iniX | ((uint32_t)iniY << 16);
+                r[2] = (uint32_t)(skip ? 0 : W) | ((uint32_t)(skip ? 0 : H) << 8) | ((uint32_t)skip << 16) | ((uint32_t)V.cellCap << 17);
+                r[3] = (uint32_t)V.pitch;
+                r[4] = (uint32_t)off; r[5] = (uint32_t)(off >> 32);
+                r[6] = (uint32_t)V.fstride;
+                r[7] = (uint32_t)(V.cellCandOff + (int64_t)cidx * V.cellCap);
+                // w8-w15: which lanes / result bits of the necessary test lie inside the interior, as LANE MASKS and bit
+                // patterns (fast.hip, quick_pass_b: lane = quad (lane & 7) x row lr = 2 ((lane >> 3) & 3) + (lane >> 5), steps of 8
+                // rows) -- a per-cell constant that used to cost every wave 17 vector instructions
+                const int IW = W - 6, IH = H - 6;
+                if (!skip && IW <= 32 && IH <= 40) {
+                    const int qFull = IW >> 2, rem = IW & 3, base = IH >> 3, rr = IH & 7;
+                    r[8] = ((1u << qFull) - 1u) * 0x01010101u;                     // lanes of whole quads (both 32-lane halves)
+                    r[9] = qFull < 8 ? (1u << qFull) * 0x01010101u : 0u;           // lanes of the partial quad
+                    r[10] = (1u << (8 * rem)) - 1u;                                // its pixels, one byte each
+                    const int kLo = (rr + 1) >> 1, kHi = rr >> 1;                  // lanes whose row takes one step more than IH / 8
+                    r[11] = kLo >= 4 ? 0xFFFFFFFFu : (1u << (8 * kLo)) - 1u;       //   lanes 0-31: lr = 2 (lane >> 3)
+                    r[12] = (1u << (8 * kHi)) - 1u;                                //   lanes 32-63: lr = 2 ((lane >> 3) & 3) + 1
+                    r[13] = ((1u << std::min(base, 4)) - 1u) * 0x11111111u;        // step bits every row has
+                    r[14] = base < 4 ? 0x11111111u << base : 0u;                   // the step more
+                    r[15] = base >= 5 ? 2u : (base == 4 ? 1u : 0u);                // fifth step: all rows / the rows of w11-w12 / none
+                }
+            }
+    }
+    // balanced dispatch order (fast.hip, k_fast_cells): XCD x takes cells [n_l x / 8, n_l (x + 1) / 8) of every level l
+    std::vector<std::vector<int>> lists(8);
+    for (int x = 0; x < 8; x++)
+        for (int l = 0; l < P.nlevels; l++) {
+            const PgLevel& V = P.lvl[l];
+            const int n = V.nCols * V.nRows;
+            for (int k = (int)((int64_t)n * x / 8); k < (int)((int64_t)n * (x + 1) / 8); k++) lists[x].push_back(V.cellBase + k);
+        }
+    per = 0;
+    for (auto& v : lists) per = std::max(per, v.size());
+    cb.assign(8 * per * 16, 0u);
+    for (int x = 0; x < 8; x++)
+        for (size_t k = 0; k < per; k++) {
+            uint32_t* r = &cb[((size_t)x * per + k) * 16];
+            if (k < lists[x].size()) memcpy(r, &ct[(size_t)lists[x][k] * 16], 64);
+            else { r[0] = 0xFFFFFFF0u; r[2] = 1u << 16; }                                // padding: the wave returns at once
+        }
+}
+
+// K3's coordinate tables for its pass kernel (quadtree.hip, k_qt_leaves: leaf column / row and candidate-order rank are separable
+// in x and y), per level: [regionW] x entries, [regionH] y entries, [2^D + 1] first y of every leaf row; sets each level's qtTabOff
+std::vector<uint2> build_qt_tables(PgPlan& P)
+{
+    std::vector<uint2> qt;
+    for (int l = 0; l < P.nlevels; l++) {
+        PgLevel& V = P.lvl[l];
+        const int regionW = V.w - 2 * PG_EDGE, regionH = V.h - 2 * PG_EDGE, D = qt_pyr_depth(V.nIni);
+        V.qtTabOff = (int32_t)qt.size();
+        for (int x = 0; x < regionW; x++) {
+            const uint2 e = qt_tab_entry(false, x, V.hX, V.nIni, regionH, D, V.wCell, V.hCell, V.nCols);
+            qt.push_back(make_uint2(((e.x >> (2 * D)) << D) | qt_compact_bits(e.x & ((1u << (2 * D)) - 1)), e.y));
+        }
+        std::vector<int> rowY((size_t)(1 << D) + 1, regionH);
+        for (int y = regionH - 1; y >= 0; y--) {
+            const uint2 e = qt_tab_entry(true, y, V.hX, V.nIni, regionH, D, V.wCell, V.hCell, V.nCols);
+            const uint32_t row = qt_compact_bits(e.x >> 1);
+            for (uint32_t r = 0; r <= row; r++) rowY[r] = std::min(rowY[r], y);       // first y whose row is >= r
+        }
+        for (int y = 0; y < regionH; y++) {
+            const uint2 e = qt_tab_entry(true, y, V.hX, V.nIni, regionH, D, V.wCell, V.hCell, V.nCols);
+            qt.push_back(make_uint2(qt_compact_bits(e.x >> 1), e.y));
+        }
+        for (int r = 0; r <= (1 << D); r++) qt.push_back(make_uint2((uint32_t)rowY[r], 0u));
+    }
+    return qt;
+}
+
 // Build (or reuse) the plan for w x h frames and a batch of `nframes`.
 int make_plan(pgorb_ctx* c, int w, int h, int nframes)
 {
@@ -216,376 +535,112 @@ int make_plan(pgorb_ctx* c, int w, int h, int nframes)
     P.nlevels = L; P.iniTh = c->prm.ini_th_fast; P.minTh = c->prm.min_th_fast;
     P.tieMode = c->prm.blur_tie_mode;
 
-    // --- resize tables ---
+    // --- host tables ---
+    PlanLayout A;
+    if ((rc = build_layout(c, g, P, A))) return rc;
+    // resize tables, and the fused tables of the source level, of every level l >= 1: 16-aligned in one blob
     std::vector<uint8_t> tab;
-    struct TabOff { size_t xofs, xofs1, xalpha, yofs, ybeta, qtab, yrel, qtab2, rowgrp, tilex, fbands, fcols; int cpr, prows, fnb, fspb, frows; bool hasQ, hasY, hasQ2; } toff[PG_MAXL];
-    for (int l = 0; l < PG_MAXL; l++) toff[l].fnb = 0;
+    auto put = [&](const void* p, size_t n) {
+        size_t off = align_up(tab.size(), 16);
+        tab.resize(off + n);
+        memcpy(tab.data() + off, p, n);
+        return off;
+    };
+    struct TabOff { size_t xofs, xofs1, xalpha, yofs, ybeta, qtab, yrel, qtab2, rowgrp, tilex, fbands, fcols; } toff[PG_MAXL];
+    ResizeTabs rt[PG_MAXL];
+    FusedTabs ft[PG_MAXL];
     int pyrGpw = 2;                                                   // 4-row groups per wave of the LDS-staged resize
     if (const char* e = getenv("PGORB_PYR_TILE_ROWS")) { const int r = atoi(e); if (r == 16 || r == 32 || r == 64) pyrGpw = r / 16; }
     for (int l = 1; l < L; l++) {
-        std::vector<int32_t> xo, xo1, yo; std::vector<int16_t> xa, yb;
-        build_resize_tables(g[l - 1].w, g[l - 1].h, g[l].w, g[l].h, xo, xo1, xa, yo, yb);
-        auto put = [&](const void* p, size_t n) {
-            size_t off = align_up(tab.size(), 16);
-            tab.resize(off + n);
-            memcpy(tab.data() + off, p, n);
-            return off;
-        };
-        toff[l].xofs = put(xo.data(), xo.size() * 4);
-        toff[l].xofs1 = put(xo1.data(), xo1.size() * 4);
-        toff[l].xalpha = put(xa.data(), xa.size() * 2);
-        toff[l].yofs = put(yo.data(), yo.size() * 4);
-        toff[l].ybeta = put(yb.data(), yb.size() * 2);
-        // quad table for the fast path
-        const int nq = (g[l].w + 3) / 4;
-        std::vector<PgQuadTab> qt(nq);
-        bool ok = true;
-        for (int q = 0; q < nq; q++) {
-            PgQuadTab& T = qt[q];
-            memset(&T, 0, sizeof(T));
-            T.base_dw = xo[4 * q] >> 2;
-            for (int k = 0; k < 4; k++) {
-                const int dx = 4 * q + k;
-                if (dx >= g[l].w) break;
-                const int o = xo[dx] - 4 * T.base_dw;
-                if (o < 0 || o > 8) ok = false;
-                // tap 1 is read at o+1; where cv::resize clamps it (xofs1 == xofs) its weight is 0
-                if (xo1[dx] != xo[dx] + 1 && xa[2 * dx + 1] != 0) ok = false;
-                T.offs |= (uint32_t)(o & 15) << (4 * k);
-                T.a0[k] = xa[2 * dx]; T.a1[k] = xa[2 * dx + 1];
-            }
-        }
-        toff[l].hasQ = ok;
-        toff[l].qtab = put(qt.data(), qt.size() * sizeof(PgQuadTab));
-        // 8-byte-window table: xb = first tap of the quad (clamped so the window stays inside the row)
-        std::vector<PgQuadTab2> q2(nq);
-        bool ok2 = g[l - 1].w >= 8;
-        for (int q = 0; q < nq && ok2; q++) {
-            PgQuadTab2& T = q2[q];
-            memset(&T, 0, sizeof(T));
-            T.xb = std::min(xo[4 * q], g[l - 1].w - 8);
-            for (int k = 0; k < 4; k++) {
-                const int dx = 4 * q + k;
-                if (dx >= g[l].w) { T.sel[k] = 0x0c0c0c0cu; continue; }
-                const int o0 = xo[dx] - T.xb, o1 = xo1[dx] - T.xb;
-                if (o0 < 0 || o0 > 7 || o1 < 0 || o1 > 7) { ok2 = false; break; }
-                T.sel[k] = (uint32_t)o0 | (0x0cu << 8) | ((uint32_t)o1 << 16) | (0x0cu << 24);
-                T.coef[k] = (uint32_t)(uint16_t)xa[2 * dx] | ((uint32_t)(uint16_t)xa[2 * dx + 1] << 16);
-                if (xa[2 * dx] < 0 || xa[2 * dx + 1] < 0) ok2 = false;
-            }
-        }
-        toff[l].hasQ2 = ok2;
-        toff[l].qtab2 = put(q2.data(), q2.size() * sizeof(PgQuadTab2));
-        // row pattern for the 4-rows-per-lane kernel: r0(dy) - r0(group base) - d in {0,1}, r1 - r0 in {0,1}
-        std::vector<uint8_t> yr(g[l].h, 0);
-        bool oky = true;
-        for (int dy = 0; dy < g[l].h; dy++) {
-            const int base = yo[2 * (dy & ~3)], d = dy & 3;
-            const int e0 = yo[2 * dy] - base - d, e1 = yo[2 * dy + 1] - yo[2 * dy];
-            if (e0 < 0 || e0 > 1 || e1 < 0 || e1 > 1) oky = false;
-            yr[dy] = (uint8_t)((e0 & 1) | ((e1 & 1) << 1));
-        }
-        toff[l].hasY = oky;
-        toff[l].yrel = put(yr.data(), yr.size());
-        std::vector<PgRowGrp> rg((g[l].h + 3) / 4 + 4);               // + records of slack (a wave loads its 1, 2 or 4 records at once)
-        for (size_t gi = 0; gi < rg.size(); gi++) {
-            PgRowGrp& R = rg[gi];
-            memset(&R, 0, sizeof(R));
-            R.sFirst = yo[2 * std::min((int)(4 * gi), g[l].h - 1)];
-            for (int d = 0; d < 4; d++) {
-                const int dy = std::min((int)(4 * gi) + d, g[l].h - 1);
-                R.yrel4 |= (uint32_t)yr[dy] << (8 * d);
-                R.ybeta[2 * d] = yb[2 * dy]; R.ybeta[2 * d + 1] = yb[2 * dy + 1];
-            }
-        }
-        toff[l].rowgrp = put(rg.data(), rg.size() * sizeof(PgRowGrp));
-        // LDS-staged variant of the 4x4 kernel: a 256 x 32 destination tile stages its source
-        // rectangle (16-byte chunks from a 16-aligned first column) through LDS
-        toff[l].cpr = 0; toff[l].prows = 0;
-        {
-            const int tileRows = 16 * pyrGpw, gpt = 4 * pyrGpw;         // rows / 4-row groups per tile
-            const int ntx = (g[l].w + 255) / 256, nty = (g[l].h + tileRows - 1) / tileRows, ngrp = (g[l].h + 3) / 4;
-            std::vector<int32_t> tx0(ntx, 0);
-            int span = 0, rows = 0;
-            if (ok2 && oky) {
-                for (int tx = 0; tx < ntx; tx++) {
-                    const int qf = 64 * tx, ql = std::min(64 * tx + 63, nq - 1);
-                    tx0[tx] = q2[qf].xb & ~15;
-                    span = std::max(span, q2[ql].xb + 8 - tx0[tx]);
-                }
-                for (int ty = 0; ty < nty; ty++) {
-                    const int gf = gpt * ty, gl = std::min(gpt * ty + gpt - 1, ngrp - 1);
-                    rows = std::max(rows, rg[gl].sFirst + 6 - rg[gf].sFirst);
-                }
-                const int cpr = (span + 4 + 15) / 16;
-                if (cpr <= 32 && (size_t)rows * cpr * 16 <= (size_t)10 * 1024 * pyrGpw) { toff[l].cpr = cpr; toff[l].prows = rows; }
-            }
-            toff[l].tilex = put(tx0.data(), tx0.size() * 4);
-        }
-        // fused resize + detect (fused.hip) with level l - 1 as the source: bands = the source level's cell rows (hCell + 6 staged
-        // rows from row 16 + i hCell) between an edge band above (rows 0 ...) and below; a band owns the 4-row groups of level l whose
-        // first source row lies in [its first row, the next band's first row), so that the six source rows of every group are staged;
-        // tile columns = NS cells, a column owns the quads whose window starts in [15 + first cell * wCell, ... of the next column).
-        toff[l].fnb = 0;
-        {
-            const LevelGeom& S = g[l - 1];
-            const int ngrp = (g[l].h + 3) / 4, rowsB = S.hCell + 6;
-            bool fok = ok2 && oky && S.wCell <= 32 && S.hCell <= 40 && S.hCell >= 16 && S.wCell >= 16;       // (the detector's narrow form; 3 x 21 staged rows)
-            std::vector<int32_t> bands, cols;
-            int nb = 0;
-            if (fok) {
-                const int maxS = rg[ngrp - 1].sFirst;
-                std::vector<int> Y{0};
-                for (int i = 0; i < S.nRows || PG_EDGE + i * S.hCell <= maxS; i++) Y.push_back(PG_EDGE + i * S.hCell);
-                int gi = 0;
-                for (size_t b = 0; b < Y.size(); b++) {
-                    const int yNext = b + 1 < Y.size() ? Y[b + 1] : INT32_MAX;
-                    const int g0 = gi;
-                    while (gi < ngrp && rg[gi].sFirst < yNext) {
-                        if (rg[gi].sFirst < Y[b] || rg[gi].sFirst + 5 - Y[b] > rowsB - 1) fok = false;
-                        gi++;
-                    }
-                    bands.insert(bands.end(), {g0, gi - g0});          // (the kernel derives the band's first row and cell row from b)
-                    nb++;
-                }
-                if (gi != ngrp) fok = false;
-            }
-            int spbF = 0;
-            if (fok) {
-                // slot columns: s = -1 the left edge's pseudo-cell (source columns from 0), s >= 0 from column 15 + s wCell (the cell's
-                // iniX - 1; past the last cell column: pseudo-cells that only serve the resize); a quad belongs to the column its
-                // 8-byte window starts in -- and then lies inside that column's 48 bytes
-                auto slotOf = [&](int xb) { return xb < PG_EDGE - 1 ? -1 : (xb - (PG_EDGE - 1)) / S.wCell; };
-                auto slotX = [&](int sl) { return sl < 0 ? 0 : PG_EDGE - 1 + sl * S.wCell; };
-                int nSlotsTotal = S.nCols;
-                for (int q = 0; q < nq; q++) {
-                    const int sl = slotOf(q2[q].xb), off = q2[q].xb - slotX(sl);
-                    if (q > 0 && q2[q].xb < q2[q - 1].xb) fok = false;
-                    if (off < 0 || (off & ~3) + 12 > 48) fok = false;
-                    nSlotsTotal = std::max(nSlotsTotal, sl + 1);
-                }
-                spbF = nSlotsTotal + 1;
-                int qi = 0, maxNq = 0, maxNg = 0;
-                for (int sl = -1; sl < nSlotsTotal; sl++) {
-                    const int q0 = qi;
-                    while (qi < nq && slotOf(q2[qi].xb) <= sl) qi++;
-                    const int n = qi - q0, magic = n > 0 ? 65536 / n + 1 : 65536;
-                    for (int lane = 0; lane < 64 && n > 0; lane++) if (((lane * magic) >> 16) != lane / n) fok = false;
-                    maxNq = std::max(maxNq, n);
-                    cols.insert(cols.end(), {q0, n, magic, 0});
-                }
-                if (qi != nq) fok = false;
-                for (int b = 0; b < nb; b++) maxNg = std::max(maxNg, bands[2 * b + 1]);
-                if (maxNq * maxNg > 64) fok = false;                   // lane = (quad, group)
-            }
-            if (fok) {
-                toff[l].fbands = put(bands.data(), bands.size() * 4);
-                toff[l].fcols = put(cols.data(), cols.size() * 4);
-                toff[l].fnb = nb; toff[l].fspb = spbF; toff[l].frows = rowsB;
-            }
+        const ResizeTabs& R = rt[l] = build_resize_level(g[l - 1], g[l], pyrGpw);
+        toff[l].xofs = put(R.xofs.data(), R.xofs.size() * 4);
+        toff[l].xofs1 = put(R.xofs1.data(), R.xofs1.size() * 4);
+        toff[l].xalpha = put(R.xalpha.data(), R.xalpha.size() * 2);
+        toff[l].yofs = put(R.yofs.data(), R.yofs.size() * 4);
+        toff[l].ybeta = put(R.ybeta.data(), R.ybeta.size() * 2);
+        toff[l].qtab = put(R.qt.data(), R.qt.size() * sizeof(PgQuadTab));
+        toff[l].qtab2 = put(R.q2.data(), R.q2.size() * sizeof(PgQuadTab2));
+        toff[l].yrel = put(R.yrel.data(), R.yrel.size());
+        toff[l].rowgrp = put(R.rg.data(), R.rg.size() * sizeof(PgRowGrp));
+        toff[l].tilex = put(R.tilex.data(), R.tilex.size() * 4);
+        const FusedTabs& F = ft[l] = build_fused_level(g[l - 1], g[l], R);
+        if (F.nb > 0) {
+            toff[l].fbands = put(F.bands.data(), F.bands.size() * 4);
+            toff[l].fcols = put(F.cols.data(), F.cols.size() * 4);
         }
     }
+    std::vector<uint32_t> ct, cb;
+    size_t per = 0;
+    build_cell_tables(P, A, B, ct, cb, per);
+    const std::vector<uint2> qt = build_qt_tables(P);
+
+    // --- arenas and uploads ---
     if ((rc = ensure(c, c->tables, tab.size() + 16))) return rc;
     if (!tab.empty()) PG_HIP(c, hipMemcpy(c->tables.p, tab.data(), tab.size(), hipMemcpyHostToDevice));
-
-    // --- arenas ---
-    size_t pyrFrame = 0, candFrame = 0, selFrame = 0, nodeFrame = 0, cellCandFrame = 0;
-    int cells = 0, selTotal = 0;
-    size_t pyrOff[PG_MAXL];
-    for (int l = 0; l < L; l++) {
-        PgLevel& V = P.lvl[l];
-        V.w = g[l].w; V.h = g[l].h;
-        V.pitch = (int)align_up(V.w, 64);
-        pyrOff[l] = pyrFrame;
-        pyrFrame += align_up((size_t)V.pitch * V.h + 64, 256);
-        V.nCols = g[l].nCols; V.nRows = g[l].nRows; V.wCell = g[l].wCell; V.hCell = g[l].hCell;
-        V.cellBase = cells; cells += V.nCols * V.nRows;
-        V.quota = c->mnFeaturesPerLevel[l];
-        V.nIni = g[l].nIni; V.hX = g[l].hX;
-        V.selCap = std::max(V.quota + 2, 4 * V.nIni);
-        V.nodeCap = (int)align_up(V.selCap + 8, 4);
-        // NMS survivors are never 8-adjacent: at most ceil(IW/2)*ceil(IH/2) per cell
-        V.candCap = ((V.w - 2 * PG_EDGE) / 2 + V.nCols + 1) * ((V.h - 2 * PG_EDGE) / 2 + V.nRows + 1);
-        V.candOff = (int64_t)candFrame; candFrame += align_up(V.candCap, 64);
-        V.cellCap = ((V.wCell + 1) / 2) * ((V.hCell + 1) / 2);
-        V.cellCandOff = (int64_t)cellCandFrame;
-        cellCandFrame += align_up((size_t)V.cellCap * V.nCols * V.nRows, 64);
-        V.selOff = (int64_t)selFrame; selFrame += V.selCap;          // slab offset == capacity prefix: K4-6's slot s of a frame IS entry s
-        // node arrays of the quadtree: LDS when 30 ints per node fit its 140 KB, else a global slab
-        // (quotas above ~1180 keypoints on one level: slower, but no configuration is refused)
-        V.nodeOff = -1;
-        // K3 keeps a level's node arrays (28 ints per node) in LDS beside its count pyramid (17 KB static) and its aux area
-        // (max(pyramid leaves <= 3072, cells of the largest level + 1) ints); what does not fit 160 KB goes to a global slab
-        const size_t qtAux = std::max((size_t)3072, (size_t)g[0].nCols * g[0].nRows + 1);
-        const size_t qtTab = (size_t)2 * ((g[0].w - 2 * PG_EDGE) + (g[0].h - 2 * PG_EDGE));      // the prologue's coordinate tables share the node area
-        if (std::max((size_t)V.nodeCap * 28, qtTab) * sizeof(int) + qtAux * sizeof(int) + 17 * 1024 > 160 * 1024) {
-            V.nodeOff = (int64_t)nodeFrame;
-            nodeFrame += align_up((size_t)V.nodeCap * 30, 64);
-        }
-        V.scale = c->mvScaleFactor[l];
-        V.patchSize = (float)(int)(31 * c->mvScaleFactor[l]);                     // :836
-        selTotal += V.selCap;
-        if ((size_t)(V.nCols * V.nRows + 1) * sizeof(int) > 140 * 1024)
-            return fail(c, PGORB_E_LIMIT, "too many cells on one level for the quadtree kernel's LDS budget");
-        if (V.w > 4095 + 2 * PG_EDGE || V.h > 4095 + 2 * PG_EDGE)
-            return fail(c, PGORB_E_LIMIT, "level larger than 4095 px is not supported");
-        if (V.selCap > 65535)      // K3's dispatch-order sort packs a keypoint's arrival index into 16 bits
-            return fail(c, PGORB_E_LIMIT, "more than 65533 keypoints on one pyramid level are not supported");
-    }
-    P.totalCells = cells; P.selTotal = selTotal;
-    P.cellCandFrame = (int64_t)cellCandFrame;
-    P.candFrame = (int64_t)candFrame; P.selFrame = (int64_t)selFrame; P.nodeFrame = (int64_t)nodeFrame;
-    if ((rc = ensure(c, c->pyr, pyrFrame * B))) return rc;
-    if ((rc = ensure(c, c->cand, candFrame * 8 * B))) return rc;          // uint2 key records
-    if ((rc = ensure(c, c->cellCand, cellCandFrame * 4 * B + 64))) return rc;      // (+64: K3's pass reads a cell's slots 16 bytes at a time)
-    if ((rc = ensure(c, c->cellCount, (size_t)cells * 4 * B + 64))) return rc;
-    selFrame = align_up(selFrame, 16);
-    P.selFrame = (int64_t)selFrame;
-    if ((rc = ensure(c, c->sel, selFrame * 32 * B))) return rc;           // one 32-byte selection record per keypoint (quadtree.hip, PgSelRec)
-    if ((rc = ensure(c, c->nodes, nodeFrame * 4 * B + 64))) return rc;
+    if ((rc = ensure(c, c->pyr, A.pyrFrame * B))) return rc;
+    if ((rc = ensure(c, c->cand, A.candFrame * 8 * B))) return rc;          // uint2 key records
+    if ((rc = ensure(c, c->cellCand, A.cellCandFrame * 4 * B + 64))) return rc;      // (+64: K3's pass reads a cell's slots 16 bytes at a time)
+    if ((rc = ensure(c, c->cellCount, (size_t)A.cells * 4 * B + 64))) return rc;
+    if ((rc = ensure(c, c->sel, A.selFrame * 32 * B))) return rc;           // one 32-byte selection record per keypoint (quadtree.hip, PgSelRec)
+    if ((rc = ensure(c, c->nodes, A.nodeFrame * 4 * B + 64))) return rc;
     if ((rc = ensure(c, c->counters, (size_t)B * PG_MAXL * 4 * 2 + 64))) return rc;
     // per-level counts: K3 writes the entries of the plan's levels in every batch, the others stay zero from here on (K4-6 sums all 16)
     PG_HIP(c, hipMemset(c->counters.p, 0, (size_t)B * PG_MAXL * 4 * 2 + 64));
+    // + slack: a K2 wave loads its record BEFORE it knows whether the position exists (fast.hip), and the last workgroup's positions
+    // run up to waves per workgroup x records per wave (4 x 64) past the table (round 6: 8 records of slack faulted under
+    // "fast_cells_per_wave" = 64 when the table happened to end a mapping)
+    const size_t cellTabSlack = (size_t)(4 * 64 + 8) * 64;
+    if ((rc = ensure(c, c->cellTab, ct.size() * 4 + cellTabSlack))) return rc;
+    PG_HIP(c, hipMemcpy(c->cellTab.p, ct.data(), ct.size() * 4, hipMemcpyHostToDevice));
+    if ((rc = ensure(c, c->cellTabBal, cb.size() * 4 + cellTabSlack))) return rc;
+    PG_HIP(c, hipMemcpy(c->cellTabBal.p, cb.data(), cb.size() * 4, hipMemcpyHostToDevice));
+    if ((rc = ensure(c, c->qtTab, qt.size() * sizeof(uint2) + 64))) return rc;
+    PG_HIP(c, hipMemcpy(c->qtTab.p, qt.data(), qt.size() * sizeof(uint2), hipMemcpyHostToDevice));
+    if ((rc = ensure(c, c->qtLeaf, (size_t)B * L * PG_QT_LEAF_CAP * sizeof(uint2)))) return rc;
+    // the status word heads the result block of the host-frame calls (pgorb_extract*: one download brings status, counts,
+    // keypoints and descriptors); K1's first launch of a batch clears it
+    const size_t ob = 64 + (((size_t)B * 4 + 63) & ~(size_t)63) + (((size_t)B * A.selTotal * sizeof(pgorb_keypoint) + 63) & ~(size_t)63) + (size_t)B * A.selTotal * 32 + 64;
+    if ((rc = ensure(c, c->outBlk, ob))) return rc;
+    PG_HIP(c, hipMemset(c->outBlk.p, 0, 64));
+    // the memset runs on the null stream and may return before it has executed; the host-frame calls launch on a private
+    // NON-BLOCKING stream (no implicit order with stream 0), so make it land before anything can write a status
+    PG_HIP(c, hipStreamSynchronize(nullptr));
+
+    // --- device pointers ---
+    const uint8_t* t = (const uint8_t*)c->tables.p;
     for (int l = 0; l < L; l++) {
         PgLevel& V = P.lvl[l];
-        V.img = (uint8_t*)c->pyr.p + pyrOff[l] * B;        // level-major: frames of a level adjacent
-        V.fstride = (int64_t)align_up((size_t)V.pitch * V.h + 64, 256);
-        if (l >= 1) {
-            const uint8_t* t = (const uint8_t*)c->tables.p;
-            V.xofs = (const int32_t*)(t + toff[l].xofs);
-            V.xofs1 = (const int32_t*)(t + toff[l].xofs1);
-            V.xalpha = (const int16_t*)(t + toff[l].xalpha);
-            V.yofs = (const int32_t*)(t + toff[l].yofs);
-            V.ybeta = (const int16_t*)(t + toff[l].ybeta);
-            V.qtab = toff[l].hasQ ? (const PgQuadTab*)(t + toff[l].qtab) : nullptr;
-            V.yrel = toff[l].hasY ? (t + toff[l].yrel) : nullptr;
-            V.rowgrp = (const PgRowGrp*)(t + toff[l].rowgrp);
-            V.tilex = (const int32_t*)(t + toff[l].tilex);
-            V.pyrCpr = toff[l].cpr; V.pyrRows = toff[l].prows; V.pyrGpw = pyrGpw;
-            V.qtab2 = toff[l].hasQ2 ? (const PgQuadTab2*)(t + toff[l].qtab2) : nullptr;
-            if (toff[l].fnb > 0) {                          // the fused tables belong to the SOURCE level l - 1
-                PgFuseLevel& SV = c->fuse.lvl[l - 1];
-                SV.bands = (const int32_t*)(t + toff[l].fbands); SV.cols = (const int32_t*)(t + toff[l].fcols);
-                SV.nBands = toff[l].fnb; SV.spb = toff[l].fspb; SV.rows = toff[l].frows;
-            }
+        V.img = (uint8_t*)c->pyr.p + A.pyrOff[l] * B;        // level-major: frames of a level adjacent
+        if (l == 0) continue;
+        const ResizeTabs& R = rt[l];
+        V.xofs = (const int32_t*)(t + toff[l].xofs);
+        V.xofs1 = (const int32_t*)(t + toff[l].xofs1);
+        V.xalpha = (const int16_t*)(t + toff[l].xalpha);
+        V.yofs = (const int32_t*)(t + toff[l].yofs);
+        V.ybeta = (const int16_t*)(t + toff[l].ybeta);
+        V.qtab = R.hasQ ? (const PgQuadTab*)(t + toff[l].qtab) : nullptr;
+        V.yrel = R.hasY ? (t + toff[l].yrel) : nullptr;
+        V.rowgrp = (const PgRowGrp*)(t + toff[l].rowgrp);
+        V.tilex = (const int32_t*)(t + toff[l].tilex);
+        V.pyrCpr = R.cpr; V.pyrRows = R.prows; V.pyrGpw = pyrGpw;
+        V.qtab2 = R.hasQ2 ? (const PgQuadTab2*)(t + toff[l].qtab2) : nullptr;
+        if (ft[l].nb > 0) {                                 // the fused tables belong to the SOURCE level l - 1
+            PgFuseLevel& SV = c->fuse.lvl[l - 1];
+            SV.bands = (const int32_t*)(t + toff[l].fbands); SV.cols = (const int32_t*)(t + toff[l].fcols);
+            SV.nBands = ft[l].nb; SV.spb = ft[l].spb; SV.rows = ft[l].rows;
         }
     }
     P.cellCand = (uint32_t*)c->cellCand.p; P.cellCount = (int32_t*)c->cellCount.p;
-    {
-        std::vector<uint32_t> ct((size_t)cells * 16, 0u);
-        for (int l = 0; l < L; l++) {
-            const PgLevel& V = P.lvl[l];
-            const int maxBorderX = V.w - PG_EDGE, maxBorderY = V.h - PG_EDGE;
-            for (int i = 0; i < V.nRows; i++)
-                for (int j = 0; j < V.nCols; j++) {
-                    const int cidx = i * V.nCols + j;
-                    uint32_t* r = &ct[((size_t)V.cellBase + cidx) * 16];
-                    const int iniY = PG_EDGE + i * V.hCell, iniX = PG_EDGE + j * V.wCell;      // :791-801
-                    const int W = std::min(iniX + V.wCell + 6, maxBorderX) - iniX;
-                    const int H = std::min(iniY + V.hCell + 6, maxBorderY) - iniY;
-                    // skipped cells (:794, :803) and windows cv::FAST finds nothing in (< 7 px)
-                    const bool skip = iniY >= maxBorderY - 3 || iniX >= maxBorderX - 6 || W < 7 || H < 7;
-                    const uint64_t off = (uint64_t)(pyrOff[l] * B) + (uint64_t)iniY * V.pitch + (uint64_t)(iniX - 1);
-                    r[0] = (uint32_t)l | ((uint32_t)(V.cellBase + cidx) << 4);
-                    r[1] = (uint32_t)iniX | ((uint32_t)iniY << 16);
-                    r[2] = (uint32_t)(skip ? 0 : W) | ((uint32_t)(skip ? 0 : H) << 8) | ((uint32_t)skip << 16) | ((uint32_t)V.cellCap << 17);
-                    r[3] = (uint32_t)V.pitch;
-                    r[4] = (uint32_t)off; r[5] = (uint32_t)(off >> 32);
-                    r[6] = (uint32_t)V.fstride;
-                    r[7] = (uint32_t)(V.cellCandOff + (int64_t)cidx * V.cellCap);
-                    // w8-w15: which lanes / result bits of the necessary test lie inside the interior, as LANE MASKS and bit
-                    // patterns (fast.hip, quick_pass_b: lane = quad (lane & 7) x row lr = 2 ((lane >> 3) & 3) + (lane >> 5), steps of 8
-                    // rows) -- a per-cell constant that used to cost every wave 17 vector instructions
-                    const int IW = W - 6, IH = H - 6;
-                    if (!skip && IW <= 32 && IH <= 40) {
-                        const int qFull = IW >> 2, rem = IW & 3, base = IH >> 3, rr = IH & 7;
-                        r[8] = ((1u << qFull) - 1u) * 0x01010101u;                     // lanes of whole quads (both 32-lane halves)
-                        r[9] = qFull < 8 ? (1u << qFull) * 0x01010101u : 0u;           // lanes of the partial quad
-                        r[10] = (1u << (8 * rem)) - 1u;                                // its pixels, one byte each
-                        const int kLo = (rr + 1) >> 1, kHi = rr >> 1;                  // lanes whose row takes one step more than IH / 8
-                        r[11] = kLo >= 4 ? 0xFFFFFFFFu : (1u << (8 * kLo)) - 1u;       //   lanes 0-31: lr = 2 (lane >> 3)
-                        r[12] = (1u << (8 * kHi)) - 1u;                                //   lanes 32-63: lr = 2 ((lane >> 3) & 3) + 1
-                        r[13] = ((1u << std::min(base, 4)) - 1u) * 0x11111111u;        // step bits every row has
-                        r[14] = base < 4 ? 0x11111111u << base : 0u;                   // the step more
-                        r[15] = base >= 5 ? 2u : (base == 4 ? 1u : 0u);                // fifth step: all rows / the rows of w11-w12 / none
-                    }
-                }
-        }
-        // + slack: a K2 wave loads its record BEFORE it knows whether the position exists (fast.hip), and the last workgroup's positions
-        // run up to waves per workgroup x records per wave (4 x 64) past the table (round 6: 8 records of slack faulted under
-        // "fast_cells_per_wave" = 64 when the table happened to end a mapping)
-        const size_t cellTabSlack = (size_t)(4 * 64 + 8) * 64;
-        if ((rc = ensure(c, c->cellTab, ct.size() * 4 + cellTabSlack))) return rc;
-        PG_HIP(c, hipMemcpy(c->cellTab.p, ct.data(), ct.size() * 4, hipMemcpyHostToDevice));
-        P.cellTab = (const uint32_t*)c->cellTab.p;
-        P.pyrBase = (const uint8_t*)c->pyr.p;
-        // balanced dispatch order (fast.hip, k_fast_cells): XCD x takes cells [n_l x / 8, n_l (x + 1) / 8) of every level l
-        std::vector<std::vector<int>> lists(8);
-        for (int x = 0; x < 8; x++)
-            for (int l = 0; l < L; l++) {
-                const PgLevel& V = P.lvl[l];
-                const int n = V.nCols * V.nRows;
-                for (int k = (int)((int64_t)n * x / 8); k < (int)((int64_t)n * (x + 1) / 8); k++) lists[x].push_back(V.cellBase + k);
-            }
-        size_t per = 0;
-        for (auto& v : lists) per = std::max(per, v.size());
-        std::vector<uint32_t> cb(8 * per * 16, 0u);
-        for (int x = 0; x < 8; x++)
-            for (size_t k = 0; k < per; k++) {
-                uint32_t* r = &cb[((size_t)x * per + k) * 16];
-                if (k < lists[x].size()) memcpy(r, &ct[(size_t)lists[x][k] * 16], 64);
-                else { r[0] = 0xFFFFFFF0u; r[2] = 1u << 16; }                                // padding: the wave returns at once
-            }
-        if ((rc = ensure(c, c->cellTabBal, cb.size() * 4 + cellTabSlack))) return rc;
-        PG_HIP(c, hipMemcpy(c->cellTabBal.p, cb.data(), cb.size() * 4, hipMemcpyHostToDevice));
-        P.cellTabBal = (const uint32_t*)c->cellTabBal.p;
-        P.cellsPerXcdBal = (int)per;
-    }
-    {
-        // K3's coordinate tables for its pass kernel (quadtree.hip, k_qt_leaves: leaf column / row and candidate-order rank are separable
-        // in x and y), per level: [regionW] x entries, [regionH] y entries, [2^D + 1] first y of every leaf row
-        std::vector<uint2> qt;
-        for (int l = 0; l < L; l++) {
-            PgLevel& V = P.lvl[l];
-            const int regionW = V.w - 2 * PG_EDGE, regionH = V.h - 2 * PG_EDGE, D = qt_pyr_depth(V.nIni);
-            V.qtTabOff = (int32_t)qt.size();
-            for (int x = 0; x < regionW; x++) {
-                const uint2 e = qt_tab_entry(false, x, V.hX, V.nIni, regionH, D, V.wCell, V.hCell, V.nCols);
-                qt.push_back(make_uint2(((e.x >> (2 * D)) << D) | qt_compact_bits(e.x & ((1u << (2 * D)) - 1)), e.y));
-            }
-            std::vector<int> rowY((size_t)(1 << D) + 1, regionH);
-            for (int y = regionH - 1; y >= 0; y--) {
-                const uint2 e = qt_tab_entry(true, y, V.hX, V.nIni, regionH, D, V.wCell, V.hCell, V.nCols);
-                const uint32_t row = qt_compact_bits(e.x >> 1);
-                for (uint32_t r = 0; r <= row; r++) rowY[r] = std::min(rowY[r], y);       // first y whose row is >= r
-            }
-            for (int y = 0; y < regionH; y++) {
-                const uint2 e = qt_tab_entry(true, y, V.hX, V.nIni, regionH, D, V.wCell, V.hCell, V.nCols);
-                qt.push_back(make_uint2(qt_compact_bits(e.x >> 1), e.y));
-            }
-            for (int r = 0; r <= (1 << D); r++) qt.push_back(make_uint2((uint32_t)rowY[r], 0u));
-        }
-        if ((rc = ensure(c, c->qtTab, qt.size() * sizeof(uint2) + 64))) return rc;
-        PG_HIP(c, hipMemcpy(c->qtTab.p, qt.data(), qt.size() * sizeof(uint2), hipMemcpyHostToDevice));
-        const size_t leafBytes = (size_t)B * L * PG_QT_LEAF_CAP * sizeof(uint2);
-        if ((rc = ensure(c, c->qtLeaf, leafBytes))) return rc;
-        P.qtTab = (const uint2*)c->qtTab.p; P.qtLeaf = (uint2*)c->qtLeaf.p; P.qtSplit = c->qtSplit; P.qtThreads = c->qtThreads; P.qtWide = getenv("PGORB_QT_WIDE") ? atoi(getenv("PGORB_QT_WIDE")) != 0 : 1;
-    }
-    P.fastTilePitch = c->fastTilePitch; P.fastWpb = c->fastWpb; P.fastCpw = c->fastCpw; c->fuse.enabled = c->fused;
+    P.cellTab = (const uint32_t*)c->cellTab.p;
+    P.cellTabBal = (const uint32_t*)c->cellTabBal.p;
+    P.cellsPerXcdBal = (int)per;
+    P.pyrBase = (const uint8_t*)c->pyr.p;
+    P.qtTab = (const uint2*)c->qtTab.p; P.qtLeaf = (uint2*)c->qtLeaf.p;
+    P.qtWide = getenv("PGORB_QT_WIDE") ? atoi(getenv("PGORB_QT_WIDE")) != 0 : 1;
     P.cand = (uint32_t*)c->cand.p; P.sel = (uint32_t*)c->sel.p;
     P.nodeScratch = (int32_t*)c->nodes.p;
     P.candCount = (int32_t*)c->counters.p;
     P.kpCount = P.candCount + (size_t)B * PG_MAXL;
-    // the status word heads the result block of the host-frame calls (pgorb_extract*: one download brings status, counts,
-    // keypoints and descriptors); K1's first launch of a batch clears it
-    {
-        const size_t ob = 64 + (((size_t)B * 4 + 63) & ~(size_t)63) + (((size_t)B * selTotal * sizeof(pgorb_keypoint) + 63) & ~(size_t)63) + (size_t)B * selTotal * 32 + 64;
-        if ((rc = ensure(c, c->outBlk, ob))) return rc;
-        PG_HIP(c, hipMemset(c->outBlk.p, 0, 64));
-        // the memset runs on the null stream and may return before it has executed; the host-frame calls launch on a private
-        // NON-BLOCKING stream (no implicit order with stream 0), so make it land before anything can write a status
-        PG_HIP(c, hipStreamSynchronize(nullptr));
-    }
     P.status = (int32_t*)c->outBlk.p;
     c->planW = w; c->planH = h; c->planBatch = B; c->planValid = true;
     c->planEpoch++;                                            // (captured graphs hold the old plan by value)
@@ -600,7 +655,8 @@ int run_batch(pgorb_ctx* c, const uint8_t* d_gray, bool resident_in_level0, int 
               int stride, int64_t frame_stride, pgorb_keypoint* d_kps, uint8_t* d_desc,
               int cap_per_frame, int32_t* d_n, hipStream_t s)
 {
-    PgPlan P = c->plan;                                   // by-value copy handed to the kernels
+    PgPlan P = c->plan;                                   // by-value copy handed to the kernels, with the context's tunables
+    P.fastTilePitch = c->fastTilePitch; P.fastWpb = c->fastWpb; P.fastCpw = c->fastCpw; P.qtSplit = c->qtSplit; P.qtThreads = c->qtThreads;
     c->lastAliased = false;
     c->lastFusedLaunches = 0;
     if (!resident_in_level0) {
@@ -616,7 +672,7 @@ int run_batch(pgorb_ctx* c, const uint8_t* d_gray, bool resident_in_level0, int 
     }
     // the device status word is per batch: cleared by the first pyramid launch (pyramid.hip) where the order of the kernels allows it,
     // by a memset otherwise
-    const bool fusedPath = c->fuse.enabled && !c->pipePyr && !c->pipeLev && P.nlevels > 1;
+    const bool fusedPath = c->fused && !c->pipePyr && !c->pipeLev && P.nlevels > 1;
     const bool foldClear = !c->pipePyr && P.nlevels > 1 && !fusedPath;
     if (!foldClear) PG_HIP(c, hipMemsetAsync(P.status, 0, 16, s));
     hipEvent_t* ev = (c->profExtract < c->profMax) ? &c->evExtract[5 * (size_t)c->profExtract] : nullptr;
@@ -688,7 +744,7 @@ int run_batch(pgorb_ctx* c, const uint8_t* d_gray, bool resident_in_level0, int 
         PG_HIP(c, hipGetLastError());
         c->lastFrames = nframes;
         return 0;
-    } else if (c->fuse.enabled && P.nlevels > 1) {
+    } else if (c->fused && P.nlevels > 1) {
         // Every level read ONCE (fused.hip): the launch that resizes level l -> l + 1 detects level l; a level without fused tables
         // takes K1 + its own K2; the last level is detected by K2.  (Stage events: "pyramid" = the chain of fused launches, i.e. the
         // whole pyramid AND the detection of levels 0 .. L-2; "fast" = what is left for K2.)
@@ -704,21 +760,17 @@ int run_batch(pgorb_ctx* c, const uint8_t* d_gray, bool resident_in_level0, int 
             }
         }
         if (ev) PG_HIP(c, hipEventRecord(ev[1], s));
-        if (c->evPyrEnd) PG_HIP(c, hipEventRecord(c->evPyrEnd, s));
         pg_launch_fast_levels(P, nframes, pending >= 0 ? pending : P.nlevels - 1, P.nlevels, s);
         if (ev) PG_HIP(c, hipEventRecord(ev[2], s));
-        if (c->evFastEnd) PG_HIP(c, hipEventRecord(c->evFastEnd, s));
     } else {
         for (int l = 1; l < P.nlevels; l++) {
             if (!pg_launch_pyramid_level(P, l, nframes, s, l == 1 ? P.status : nullptr) && l == 1) PG_HIP(c, hipMemsetAsync(P.status, 0, 16, s));
             PG_DBG_SYNC("K1 pyramid level");
         }
         if (ev) PG_HIP(c, hipEventRecord(ev[1], s));
-        if (c->evPyrEnd) PG_HIP(c, hipEventRecord(c->evPyrEnd, s));
         pg_launch_fast(P, nframes, s);
         PG_DBG_SYNC("K2 fast");
         if (ev) PG_HIP(c, hipEventRecord(ev[2], s));
-        if (c->evFastEnd) PG_HIP(c, hipEventRecord(c->evFastEnd, s));
     }
     pg_launch_quadtree(P, nframes, s);
     PG_DBG_SYNC("K3 quadtree");
@@ -729,6 +781,43 @@ int run_batch(pgorb_ctx* c, const uint8_t* d_gray, bool resident_in_level0, int 
     PG_HIP(c, hipGetLastError());
     c->lastFrames = nframes;
     return 0;
+}
+
+// Every option of pgorb_set_option / pgorb_get_option: where the context keeps it, which values it takes (no rule: all) with the
+// message for the others, and what it keeps of a value (no rule: the value).  copy_tunables hands all of them to a stream's lanes.
+struct PgOption {
+    const char* key;
+    int& (*at)(pgorb_ctx* c);
+    bool (*valid)(int v);
+    const char* error;
+    int (*store)(int v);
+};
+#define PG_OPT_AT(field) [](pgorb_ctx* c) -> int& { return c->field; }
+const PgOption kOptions[] = {
+    {"matcher", PG_OPT_AT(mx.popcount), nullptr, nullptr,
+     [](int v) { return v ? 1 : pg_match_default_opts().popcount; }},                                  // 0 = what the environment says
+    {"match_mode", PG_OPT_AT(mx.mode), [](int v) { return v >= -1 && v <= 2; }, "match_mode must be -1, 0, 1 or 2", nullptr},
+    {"fast_tile_pitch", PG_OPT_AT(fastTilePitch), [](int v) { return v == 0 || (v >= 48 && v <= 128 && v % 16 == 0); },
+     "fast_tile_pitch must be 0 (automatic) or 48, 64, ... 128", nullptr},
+    {"fast_waves_per_block", PG_OPT_AT(fastWpb), [](int v) { return v == 1 || v == 2 || v == 4; },
+     "fast_waves_per_block must be 1, 2 or 4", nullptr},
+    {"fast_cells_per_wave", PG_OPT_AT(fastCpw), [](int v) { return v >= 1 && v <= 64; }, "fast_cells_per_wave must be 1 ... 64", nullptr},
+    {"quadtree_threads", PG_OPT_AT(qtThreads), [](int v) { return v == 0 || v == 256 || v == 512 || v == 1024; },
+     "quadtree_threads must be 0 (automatic), 256, 512 or 1024", nullptr},
+    {"quadtree_split", PG_OPT_AT(qtSplit), [](int v) { return v >= 0 && v <= 2; },
+     "quadtree_split must be 0 (one launch), 1 (two) or 2 (automatic)", nullptr},
+    {"fused_levels", PG_OPT_AT(fused), nullptr, nullptr, [](int v) { return v ? 1 : 0; }},
+    {"pipeline_pyramid", PG_OPT_AT(pipePyr), nullptr, nullptr, [](int v) { return v ? 1 : 0; }},
+    {"pipeline_levels", PG_OPT_AT(pipeLev), nullptr, nullptr, [](int v) { return v & ((1 << PG_MAXL) - 2); }},
+    {"pipeline_levels_priority", PG_OPT_AT(pipeLevPrio), nullptr, nullptr, [](int v) { return v ? 1 : 0; }},
+};
+#undef PG_OPT_AT
+
+const PgOption* find_option(const char* key)
+{
+    for (const PgOption& o : kOptions)
+        if (!strcmp(key, o.key)) return &o;
+    return nullptr;
 }
 
 }  // namespace
@@ -868,8 +957,6 @@ int pgorb_create(const pgorb_params* p, pgorb_ctx** out)
     pgorb_ctx* c = new pgorb_ctx();
     c->prm = *p;
     c->mx = pg_match_default_opts();
-    if (const char* e = getenv("PGORB_EXTRACT_CHUNK_KB")) { const int kb = atoi(e); if (kb >= 16) c->chunkBytes = kb << 10; }
-    c->noStage = getenv("PGORB_EXTRACT_STAGE") == nullptr;
     c->useGraph = getenv("PGORB_EXTRACT_NO_GRAPH") == nullptr;
     if (const char* e = getenv("PGORB_QT_THREADS")) { const int v = atoi(e); if (v == 256 || v == 512 || v == 1024) c->qtThreads = v; }
     if (const char* e = getenv("PGORB_QT_SPLIT")) { const int v = atoi(e); if (v >= 0 && v <= 2) c->qtSplit = v; }      // A / B switch of K3's two forms (option "quadtree_split")
@@ -903,10 +990,8 @@ void pgorb_destroy(pgorb_ctx* c)
     if (!c) return;
     (void)hipSetDevice(c->prm.device);
     while (!c->streams.empty()) pgorb_stream_destroy(c->streams.back());      // a stream holds a pointer to its context
-    if (c->evPyrEnd) (void)hipEventDestroy(c->evPyrEnd);
-    if (c->evFastEnd) (void)hipEventDestroy(c->evFastEnd);
     Arena* all[] = {&c->cellTab, &c->cellTabBal, &c->cellCand, &c->cellCount, &c->pyr, &c->cand, &c->sel, &c->nodes, &c->counters, &c->tables, &c->qtTab, &c->qtLeaf,
-                    &c->outBlk, &c->stageA, &c->stageB, &c->stageOut, &c->stageSfi, &c->vocab, &c->xdesc};
+                    &c->outBlk, &c->stageA, &c->stageOut, &c->stageSfi, &c->vocab, &c->xdesc};
     for (Arena* a : all) if (a->p) (void)hipFree(a->p);
     if (c->sPyr) {
         (void)hipStreamSynchronize(c->sPyr); (void)hipStreamSynchronize(c->sFast);
@@ -921,7 +1006,6 @@ void pgorb_destroy(pgorb_ctx* c)
         for (int l = 0; l < PG_MAXL; l++) { (void)hipEventDestroy(c->evGrpFast[l]); (void)hipEventDestroy(c->evGrpQt[l]); }
     }
     if (c->pinned) (void)hipHostFree(c->pinned);
-    if (c->pinIn) (void)hipHostFree(c->pinIn);
     if (c->hg.exec) (void)hipGraphExecDestroy(c->hg.exec);
     if (c->hg.g) (void)hipGraphDestroy(c->hg.g);
     if (c->sHost) { (void)hipStreamSynchronize(c->sHost); (void)hipStreamDestroy(c->sHost); }
@@ -1033,7 +1117,7 @@ int pgorb_check_async(pgorb_ctx* c, void* stream)
 // one frame per synchronous call: Frame.cc:251-257, Tracking.cc:262-266).  Round 4 cut the call's fixed costs:
 //   * input: hipMemcpy2DAsync straight from the caller's (pageable) memory.  A page-locked staging buffer of the context's own,
 //     filled in row chunks while the DMA engine moves the previous chunk, measured 24 us SLOWER per 1080p frame than the
-//     runtime's pageable path (each extra copy command costs more than the overlap saves; PGORB_EXTRACT_STAGE=1 keeps the form);
+//     runtime's pageable path (each extra copy command costs more than the overlap saves);
 //   * output: status word, counts, keypoints and descriptors live in ONE device block (PgPlan::status points into it) and come
 //     back with one download and one synchronisation (there were two synchronous 4-byte copies in front of it).
 // Host phases of the last calls: pgorb_profile_host.
@@ -1051,7 +1135,6 @@ int pgorb_extract_batch(pgorb_ctx* c, const uint8_t* const* gray, int nframes, i
     int rc = make_plan(c, w, h, nframes);
     if (rc) return rc;
     for (int f = 0; f < nframes; f++) if (!gray[f]) return fail(c, PGORB_E_ARG, "null frame %d", f);
-    const PgLevel& L0 = c->plan.lvl[0];
     const int need = c->plan.selTotal;       // the device block always holds the full bound
     // device result block of this call: status (64 B) | n[nframes] | kps[nframes][need] | desc[nframes][need][32]
     auto al64 = [](size_t v) { return (v + 63) & ~(size_t)63; };
@@ -1063,41 +1146,9 @@ int pgorb_extract_batch(pgorb_ctx* c, const uint8_t* const* gray, int nframes, i
     if (!c->sHost) PG_HIP(c, hipStreamCreateWithFlags(&c->sHost, hipStreamNonBlocking));
     hipStream_t hs = c->sHost;
     // ---- upload ----
-    const size_t frameBytes = (size_t)w * h;
-    const bool stage = frameBytes * nframes <= ((size_t)64 << 20) && !c->noStage;
-    if (stage) {
-        if (c->pinInBytes < frameBytes * nframes) {
-            // an earlier call's chunk uploads out of the old buffer are complete (every call ends synchronised), but a caller
-            // that got an error return in between may have left copies queued: drain before the pages go away
-            if (c->pinIn) { (void)hipStreamSynchronize(hs); (void)hipHostFree(c->pinIn); }
-            c->pinIn = nullptr; c->pinInBytes = 0;
-            const size_t want = (frameBytes * std::min(nframes > 1 ? c->prm.max_batch : 1, (int)(((size_t)64 << 20) / frameBytes + 1)) + 4095) & ~(size_t)4095;
-            PG_HIP(c, hipHostMalloc((void**)&c->pinIn, std::max(want, frameBytes * nframes), hipHostMallocDefault));
-            c->pinInBytes = std::max(want, frameBytes * nframes);
-        }
-    }
-    const int rowsPer = std::max(1, (int)(((size_t)c->chunkBytes + w - 1) / w));
-    for (int f = 0; f < nframes; f++) {
-        bool direct = !stage;
-        if (stage) {
-            hipPointerAttribute_t at;
-            if (hipPointerGetAttributes(&at, gray[f]) == hipSuccess && at.type == hipMemoryTypeHost) direct = true;   // already page-locked
-            else (void)hipGetLastError();
-        }
-        uint8_t* dst = L0.img + (int64_t)f * L0.fstride;
-        if (direct) {
-            PG_HIP(c, hipMemcpy2DAsync(dst, L0.pitch, gray[f], stride, w, h, hipMemcpyHostToDevice, hs));
-            continue;
-        }
-        uint8_t* pin = c->pinIn + (size_t)f * frameBytes;
-        for (int r0 = 0; r0 < h; r0 += rowsPer) {
-            const int rows = std::min(rowsPer, h - r0);
-            if (stride == w) memcpy(pin + (size_t)r0 * w, gray[f] + (size_t)r0 * stride, (size_t)rows * w);
-            else for (int r = 0; r < rows; r++) memcpy(pin + (size_t)(r0 + r) * w, gray[f] + (size_t)(r0 + r) * stride, w);
-            if (L0.pitch == w) PG_HIP(c, hipMemcpyAsync(dst + (size_t)r0 * w, pin + (size_t)r0 * w, (size_t)rows * w, hipMemcpyHostToDevice, hs));
-            else PG_HIP(c, hipMemcpy2DAsync(dst + (size_t)r0 * L0.pitch, L0.pitch, pin + (size_t)r0 * w, w, w, rows, hipMemcpyHostToDevice, hs));
-        }
-    }
+    const PgLevel& L0 = c->plan.lvl[0];
+    for (int f = 0; f < nframes; f++)
+        PG_HIP(c, hipMemcpy2DAsync(L0.img + (int64_t)f * L0.fstride, L0.pitch, gray[f], stride, w, h, hipMemcpyHostToDevice, hs));
     const auto t1 = std::chrono::steady_clock::now();
     // ---- kernels ----
     // Direct launches the first time a (plan, batch size) is seen -- the launchers may still allocate or configure --, captured
@@ -1107,44 +1158,40 @@ int pgorb_extract_batch(pgorb_ctx* c, const uint8_t* const* gray, int nframes, i
     pgorb_ctx::HostGraph& G = c->hg;
     const bool graphable = c->useGraph && c->profExtract >= c->profMax && !c->pipePyr && !c->pipeLev;
     const bool replay = graphable && G.exec && G.nframes == nframes && G.epoch == c->planEpoch && G.pinned == hv && G.outBytes == outBytes;
-    if (replay) {
+    auto launch = [&] { return run_batch(c, nullptr, true, nframes, w, h, stride, 0, (pgorb_keypoint*)(blk + oK), blk + oD, need, (int32_t*)(blk + oN), hs); };
+    bool graph = replay;
+    if (!replay) {
+        const bool capture = graphable && G.seenFrames == nframes && G.seenEpoch == c->planEpoch;
+        G.seenFrames = nframes; G.seenEpoch = c->planEpoch;
+        if (capture) {
+            PG_HIP(c, hipStreamBeginCapture(hs, hipStreamCaptureModeRelaxed));
+            rc = launch();
+            const hipError_t e1 = rc ? hipSuccess : hipMemcpyAsync(hv, blk, outBytes, hipMemcpyDeviceToHost, hs);
+            hipGraph_t g = nullptr;
+            const hipError_t e2 = hipStreamEndCapture(hs, &g);
+            if (!rc && e1 == hipSuccess && e2 == hipSuccess && g) {
+                if (G.exec) { (void)hipGraphExecDestroy(G.exec); G.exec = nullptr; }
+                if (G.g) { (void)hipGraphDestroy(G.g); G.g = nullptr; }
+                hipGraphExec_t ex = nullptr;
+                graph = hipGraphInstantiate(&ex, g, nullptr, nullptr, 0) == hipSuccess;
+                if (graph) { G.g = g; G.exec = ex; G.nframes = nframes; G.epoch = c->planEpoch; G.pinned = hv; G.outBytes = outBytes; }
+            }
+            if (!graph) {
+                if (g) (void)hipGraphDestroy(g);
+                (void)hipGetLastError();
+                c->useGraph = 0;                               // capture or instantiation failed: direct launches, now and from here on
+                if (rc) return rc;
+            }
+        }
+    }
+    if (graph) {
         PG_HIP(c, hipGraphLaunch(G.exec, hs));
         c->lastFrames = nframes; c->lastAliased = false;
     } else {
-        const bool capture = graphable && G.seenFrames == nframes && G.seenEpoch == c->planEpoch;
-        G.seenFrames = nframes; G.seenEpoch = c->planEpoch;
-        if (capture) PG_HIP(c, hipStreamBeginCapture(hs, hipStreamCaptureModeRelaxed));
-        rc = run_batch(c, nullptr, true, nframes, w, h, stride, 0, (pgorb_keypoint*)(blk + oK), blk + oD, need, (int32_t*)(blk + oN), hs);
-        hipError_t e1 = rc ? hipSuccess : hipMemcpyAsync(hv, blk, outBytes, hipMemcpyDeviceToHost, hs);
-        if (capture) {
-            hipGraph_t g = nullptr;
-            const hipError_t e2 = hipStreamEndCapture(hs, &g);
-            if (rc || e1 != hipSuccess || e2 != hipSuccess || !g) {
-                if (g) (void)hipGraphDestroy(g);
-                (void)hipGetLastError();
-                c->useGraph = 0;                               // capture failed: direct launches, now and from here on
-                if (rc) return rc;
-                if ((rc = run_batch(c, nullptr, true, nframes, w, h, stride, 0, (pgorb_keypoint*)(blk + oK), blk + oD, need, (int32_t*)(blk + oN), hs))) return rc;
-                PG_HIP(c, hipMemcpyAsync(hv, blk, outBytes, hipMemcpyDeviceToHost, hs));
-                goto launched;
-            }
-            if (G.exec) { (void)hipGraphExecDestroy(G.exec); G.exec = nullptr; }
-            if (G.g) { (void)hipGraphDestroy(G.g); G.g = nullptr; }
-            hipGraphExec_t ex = nullptr;
-            if (hipGraphInstantiate(&ex, g, nullptr, nullptr, 0) != hipSuccess) {
-                (void)hipGraphDestroy(g); (void)hipGetLastError(); c->useGraph = 0;
-                if ((rc = run_batch(c, nullptr, true, nframes, w, h, stride, 0, (pgorb_keypoint*)(blk + oK), blk + oD, need, (int32_t*)(blk + oN), hs))) return rc;
-                PG_HIP(c, hipMemcpyAsync(hv, blk, outBytes, hipMemcpyDeviceToHost, hs));
-                goto launched;
-            }
-            G.g = g; G.exec = ex; G.nframes = nframes; G.epoch = c->planEpoch; G.pinned = hv; G.outBytes = outBytes;
-            PG_HIP(c, hipGraphLaunch(G.exec, hs));
-        } else {
-            if (rc) return rc;
-            if (e1 != hipSuccess) return fail(c, PGORB_E_HIP, "hipMemcpyAsync D2H failed: %s", hipGetErrorString(e1));
-        }
+        if ((rc = launch())) return rc;
+        const hipError_t e1 = hipMemcpyAsync(hv, blk, outBytes, hipMemcpyDeviceToHost, hs);
+        if (e1 != hipSuccess) return fail(c, PGORB_E_HIP, "hipMemcpyAsync D2H failed: %s", hipGetErrorString(e1));
     }
-launched:
     const auto t2 = std::chrono::steady_clock::now();
     PG_HIP(c, hipStreamSynchronize(hs));
     const auto t3 = std::chrono::steady_clock::now();
@@ -1231,13 +1278,16 @@ int pgorb_hamming_matrix(pgorb_ctx* c, const uint8_t* a, int na, const uint8_t* 
         return fail(c, PGORB_E_ARG, "bad argument to pgorb_hamming_matrix");
     if (!na || !nb) return 0;
     PG_HIP(c, hipSetDevice(c->prm.device));
+    // pageable copies, not PgHostCall: at 2000 x 2000 its page-locked download and host copy of the 8 MB matrix measured 531 us
+    // per call on an MI355X, these 213 us
+    const size_t offB = ((size_t)na * 32 + 63) & ~(size_t)63;
     int rc;
-    if ((rc = ensure(c, c->stageA, (size_t)na * 32))) return rc;
-    if ((rc = ensure(c, c->stageB, (size_t)nb * 32))) return rc;
+    if ((rc = ensure(c, c->stageA, offB + (size_t)nb * 32))) return rc;
     if ((rc = ensure(c, c->stageOut, (size_t)na * nb * 2))) return rc;
-    PG_HIP(c, hipMemcpy(c->stageA.p, a, (size_t)na * 32, hipMemcpyHostToDevice));
-    PG_HIP(c, hipMemcpy(c->stageB.p, b, (size_t)nb * 32, hipMemcpyHostToDevice));
-    pg_launch_hamming_matrix((uint8_t*)c->stageA.p, na, (uint8_t*)c->stageB.p, nb, (uint16_t*)c->stageOut.p, 0);
+    uint8_t* dA = (uint8_t*)c->stageA.p;
+    PG_HIP(c, hipMemcpy(dA, a, (size_t)na * 32, hipMemcpyHostToDevice));
+    PG_HIP(c, hipMemcpy(dA + offB, b, (size_t)nb * 32, hipMemcpyHostToDevice));
+    pg_launch_hamming_matrix(dA, na, dA + offB, nb, (uint16_t*)c->stageOut.p, 0);
     PG_HIP(c, hipGetLastError());
     PG_HIP(c, hipMemcpy(out, c->stageOut.p, (size_t)na * nb * 2, hipMemcpyDeviceToHost));
     return 0;
@@ -1253,20 +1303,20 @@ int pgorb_hamming_best2(pgorb_ctx* c, const uint8_t* a, int na, const uint8_t* b
     if (!na) return 0;
     PG_HIP(c, hipSetDevice(c->prm.device));
     int rc;
-    if ((rc = ensure(c, c->stageA, (size_t)na * 32))) return rc;
-    if ((rc = ensure(c, c->stageB, (size_t)nb * 32 + 32))) return rc;
-    if ((rc = ensure(c, c->stageOut, (size_t)na * 8 + 64))) return rc;
-    PG_HIP(c, hipMemcpy(c->stageA.p, a, (size_t)na * 32, hipMemcpyHostToDevice));
-    if (nb) PG_HIP(c, hipMemcpy(c->stageB.p, b, (size_t)nb * 32, hipMemcpyHostToDevice));
-    int32_t* d_idx = (int32_t*)c->stageOut.p;
-    uint16_t* d_b1 = (uint16_t*)(d_idx + na);
-    uint16_t* d_b2 = d_b1 + na;
     if ((rc = ensure(c, c->xdesc, pg_match_scratch_bytes(c->mx, nb, 1) + 16))) return rc;
-    pg_launch_best2(c->mx, (uint8_t*)c->stageA.p, na, (uint8_t*)c->stageB.p, nb, (uint8_t*)c->xdesc.p, d_idx, d_b1, d_b2, 0);
-    PG_HIP(c, hipGetLastError());
-    PG_HIP(c, hipMemcpy(best_idx, d_idx, (size_t)na * 4, hipMemcpyDeviceToHost));
-    PG_HIP(c, hipMemcpy(best, d_b1, (size_t)na * 2, hipMemcpyDeviceToHost));
-    PG_HIP(c, hipMemcpy(second, d_b2, (size_t)na * 2, hipMemcpyDeviceToHost));
+    PgHostCall s(c);
+    const size_t oA = s.region(PG_UP, (size_t)na * 32), oB = s.region(PG_UP, (size_t)nb * 32 + 32),
+                 oI = s.region(PG_DOWN, (size_t)na * 4), oB1 = s.region(PG_DOWN, (size_t)na * 2), oB2 = s.region(PG_DOWN, (size_t)na * 2);
+    if ((rc = s.begin())) return rc;
+    s.put(oA, a, (size_t)na * 32); s.put(oB, b, (size_t)nb * 32, 0, (size_t)nb * 32 + 32);
+    if ((rc = s.run([&] {
+            pg_launch_best2(c->mx, s.dev(oA), na, s.dev(oB), nb, (uint8_t*)c->xdesc.p, s.dev<int32_t>(oI), s.dev<uint16_t>(oB1),
+                            s.dev<uint16_t>(oB2), 0);
+            PG_HIP(c, hipGetLastError());
+            return 0; }))) return rc;
+    memcpy(best_idx, s.host(oI), (size_t)na * 4);
+    memcpy(best, s.host(oB1), (size_t)na * 2);
+    memcpy(second, s.host(oB2), (size_t)na * 2);
     return 0;
 }
 
@@ -1310,60 +1360,19 @@ int pgorb_set_option(pgorb_ctx* c, const char* key, int value)
     if (!c) return PGORB_E_ARG;                               // every option belongs to a context (round 4: no process-wide state)
     pg_forward_option_to_lanes(c, key, value);                // the sibling contexts of live multi-lane device streams follow
     c->planEpoch++;                                            // (a captured graph of the host-frame path holds the old settings)
-    if (!strcmp(key, "matcher")) { c->mx.popcount = value ? 1 : pg_match_default_opts().popcount; return 0; }     // 0 = what the environment says
-    if (!strcmp(key, "match_mode")) {
-        if (value < -1 || value > 2) return fail(c, PGORB_E_ARG, "match_mode must be -1, 0, 1 or 2");
-        c->mx.mode = value;
-        return 0;
-    }
-    if (!strcmp(key, "fast_tile_pitch")) {
-        if (value != 0 && (value < 48 || value > 128 || value % 16)) return fail(c, PGORB_E_ARG, "fast_tile_pitch must be 0 (automatic) or 48, 64, ... 128");
-        c->fastTilePitch = value; c->plan.fastTilePitch = value;
-        return 0;
-    }
-    if (!strcmp(key, "fast_waves_per_block")) {
-        if (value != 1 && value != 2 && value != 4) return fail(c, PGORB_E_ARG, "fast_waves_per_block must be 1, 2 or 4");
-        c->fastWpb = value; c->plan.fastWpb = value;
-        return 0;
-    }
-    if (!strcmp(key, "fast_cells_per_wave")) {
-        if (value < 1 || value > 64) return fail(c, PGORB_E_ARG, "fast_cells_per_wave must be 1 ... 64");
-        c->fastCpw = value; c->plan.fastCpw = value;
-        return 0;
-    }
-    if (!strcmp(key, "quadtree_threads")) {
-        if (value != 0 && value != 256 && value != 512 && value != 1024) return fail(c, PGORB_E_ARG, "quadtree_threads must be 0 (automatic), 256, 512 or 1024");
-        c->qtThreads = value; c->plan.qtThreads = value;
-        return 0;
-    }
-    if (!strcmp(key, "quadtree_split")) {
-        if (value < 0 || value > 2) return fail(c, PGORB_E_ARG, "quadtree_split must be 0 (one launch), 1 (two) or 2 (automatic)");
-        c->qtSplit = value; c->plan.qtSplit = value;
-        return 0;
-    }
-    if (!strcmp(key, "fused_levels")) { c->fused = value ? 1 : 0; c->fuse.enabled = c->fused; return 0; }
-    if (!strcmp(key, "pipeline_pyramid")) { c->pipePyr = value ? 1 : 0; return 0; }
-    if (!strcmp(key, "pipeline_levels")) { c->pipeLev = value & ((1 << PG_MAXL) - 2); return 0; }
-    if (!strcmp(key, "pipeline_levels_priority")) { c->pipeLevPrio = value ? 1 : 0; return 0; }
-    return fail(c, PGORB_E_ARG, "unknown option '%s'", key);
+    const PgOption* o = find_option(key);
+    if (!o) return fail(c, PGORB_E_ARG, "unknown option '%s'", key);
+    if (o->valid && !o->valid(value)) return fail(c, PGORB_E_ARG, "%s", o->error);
+    o->at(c) = o->store ? o->store(value) : value;
+    return 0;
 }
 
 int pgorb_get_option(const pgorb_ctx* c, const char* key)
 {
     if (!key || !c) return PGORB_OPTION_UNKNOWN;
-    if (!strcmp(key, "fast_tile_pitch")) return c->fastTilePitch;
-    if (!strcmp(key, "fast_waves_per_block")) return c->fastWpb;
-    if (!strcmp(key, "fast_cells_per_wave")) return c->fastCpw;
-    if (!strcmp(key, "quadtree_split")) return c->qtSplit;
-    if (!strcmp(key, "quadtree_threads")) return c->qtThreads;
-    if (!strcmp(key, "matcher")) return c->mx.popcount;
-    if (!strcmp(key, "match_mode")) return c->mx.mode;
-    if (!strcmp(key, "fused_levels")) return c->fused;
-    if (!strcmp(key, "fused_launches")) return c->lastFusedLaunches;
-    if (!strcmp(key, "pipeline_pyramid")) return c->pipePyr;
-    if (!strcmp(key, "pipeline_levels")) return c->pipeLev;
-    if (!strcmp(key, "pipeline_levels_priority")) return c->pipeLevPrio;
-    return PGORB_OPTION_UNKNOWN;
+    if (!strcmp(key, "fused_launches")) return c->lastFusedLaunches;      // (read-only)
+    const PgOption* o = find_option(key);
+    return o ? o->at(const_cast<pgorb_ctx*>(c)) : PGORB_OPTION_UNKNOWN;
 }
 
 int pgorb_matcher_is_popcount(const pgorb_ctx* c, int cap_per_frame) { return pg_match_uses_popcount(c ? c->mx : pg_match_default_opts(), cap_per_frame) ? 1 : 0; }
@@ -1485,9 +1494,6 @@ struct pgorb_stream {
     bool device = false;
     std::vector<pgorb_ctx*> lane;          // [0] = c
     std::vector<hipStream_t> sLane;        // [0] = sRun
-    int stagger = 0;                       // 0: lanes start their batches as soon as they can; 1: a batch's K1 starts when the previously
-                                           // submitted batch has finished ITS K1 (its K2 is starting); 2: ... has finished its K2
-    int lastLane = -1;                     // the lane the previously submitted batch runs on
     hipStream_t sChain = nullptr;          // the sections that cross batches, in submission order (several lanes: a stream of its own)
     int32_t* hStatus = nullptr;            // pinned, one word per slot (device form: the batch's status word)
     struct Slot {
@@ -1531,6 +1537,45 @@ static void stream_layout(pgorb_stream* s)
     }                                                        // (+ the status word behind it)
 }
 
+// what both stream forms allocate: the result-block layout, every slot's device result block and its upload / run events, the
+// pairs (f, f-1), the previous batch's last frame, and the matcher scratch of a batch
+static bool stream_alloc_common(pgorb_stream* s)
+{
+    pgorb_ctx* c = s->c;
+    const size_t cap = (size_t)s->cap, B = (size_t)s->B;
+    stream_layout(s);
+    s->slot.resize(s->depth);
+    bool ok = true;
+    for (auto& sl : s->slot) {
+        ok = ok && hipMalloc((void**)&sl.dOut, s->outBytes + 256) == hipSuccess;
+        ok = ok && hipEventCreateWithFlags(&sl.evIn, hipEventDisableTiming) == hipSuccess;
+        ok = ok && hipEventCreateWithFlags(&sl.evRun, hipEventDisableTiming) == hipSuccess;
+    }
+    std::vector<int32_t> pq(B), pt(B);
+    for (int f = 0; f < s->B; f++) { pq[f] = f + 1; pt[f] = f; }
+    ok = ok && hipMalloc((void**)&s->dPq, B * 4) == hipSuccess && hipMalloc((void**)&s->dPt, B * 4) == hipSuccess;
+    ok = ok && hipMalloc((void**)&s->dPrevDesc, cap * 32) == hipSuccess && hipMalloc((void**)&s->dPrevN, 4) == hipSuccess;
+    ok = ok && hipMalloc((void**)&s->dPrevKps, cap * sizeof(pgorb_keypoint)) == hipSuccess;
+    ok = ok && hipMemcpy(s->dPq, pq.data(), B * 4, hipMemcpyHostToDevice) == hipSuccess;
+    ok = ok && hipMemcpy(s->dPt, pt.data(), B * 4, hipMemcpyHostToDevice) == hipSuccess;
+    ok = ok && ensure(c, c->xdesc, pg_match_scratch_bytes(c->mx, s->cap, s->B) + 16) == 0;
+    return ok;
+}
+
+// the result pointers of a collected slot, into its host (pgorb_stream_wait) or device (pgorb_stream_wait_device) result block
+static int stream_results(const pgorb_stream* s, const pgorb_stream::Slot& sl, const uint8_t* base, const int32_t** n, const pgorb_keypoint** kps,
+                          const uint8_t** desc, const int32_t** best_idx, const uint16_t** best, const uint16_t** second, int* cap)
+{
+    if (n) *n = (const int32_t*)(base + s->offN) + 1;
+    if (kps) *kps = (const pgorb_keypoint*)(base + s->offK) + s->cap;
+    if (desc) *desc = base + s->offD + (size_t)s->cap * 32;
+    if (best_idx) *best_idx = (const int32_t*)(base + s->offI);
+    if (best) *best = (const uint16_t*)(base + s->offB1);
+    if (second) *second = (const uint16_t*)(base + s->offB2);
+    if (cap) *cap = s->cap;
+    return sl.frames;
+}
+
 extern "C" {
 
 int pgorb_stream_create_ingest(pgorb_ctx* c, int src_w, int src_h, int channels, int rgb_order, int rotate_degrees,
@@ -1555,12 +1600,11 @@ int pgorb_stream_create_ingest(pgorb_ctx* c, int src_w, int src_h, int channels,
     s->vflip = vertical_flip ? 1 : 0; s->hflip = horizontal_flip ? 1 : 0;
     s->ingest = channels != 1 || s->rot || s->vflip || s->hflip;
     s->inBytes = (size_t)src_w * src_h * channels;
-    const size_t cap = (size_t)s->cap, B = (size_t)batch;
-    stream_layout(s);
-    bool ok = hipStreamCreateWithFlags(&s->sIn, hipStreamNonBlocking) == hipSuccess &&
-              hipStreamCreateWithFlags(&s->sRun, hipStreamNonBlocking) == hipSuccess &&
-              hipStreamCreateWithFlags(&s->sOut, hipStreamNonBlocking) == hipSuccess;
-    s->slot.resize(depth);
+    const size_t B = (size_t)batch;
+    bool ok = stream_alloc_common(s);
+    ok = ok && hipStreamCreateWithFlags(&s->sIn, hipStreamNonBlocking) == hipSuccess &&
+         hipStreamCreateWithFlags(&s->sRun, hipStreamNonBlocking) == hipSuccess &&
+         hipStreamCreateWithFlags(&s->sOut, hipStreamNonBlocking) == hipSuccess;
     {
         // the page-locked input slots are the expensive part of a stream (0.3 ms per MB: 128 MB per slot of 64 1080p frames):
         // one thread per slot page-locks its buffers (round 4: the CLI's start-up; a third of the time with three slots)
@@ -1581,19 +1625,8 @@ int pgorb_stream_create_ingest(pgorb_ctx* c, int src_w, int src_h, int channels,
     }
     for (auto& sl : s->slot) {
         ok = ok && hipMalloc((void**)&sl.dIn, B * s->inBytes + 256) == hipSuccess;
-        ok = ok && hipMalloc((void**)&sl.dOut, s->outBytes + 256) == hipSuccess;
-        ok = ok && hipEventCreateWithFlags(&sl.evIn, hipEventDisableTiming) == hipSuccess;
-        ok = ok && hipEventCreateWithFlags(&sl.evRun, hipEventDisableTiming) == hipSuccess;
         ok = ok && hipEventCreateWithFlags(&sl.evOut, hipEventDisableTiming) == hipSuccess;
     }
-    std::vector<int32_t> pq(batch), pt(batch);
-    for (int f = 0; f < batch; f++) { pq[f] = f + 1; pt[f] = f; }
-    ok = ok && hipMalloc((void**)&s->dPq, B * 4) == hipSuccess && hipMalloc((void**)&s->dPt, B * 4) == hipSuccess;
-    ok = ok && hipMalloc((void**)&s->dPrevDesc, cap * 32) == hipSuccess && hipMalloc((void**)&s->dPrevN, 4) == hipSuccess;
-    ok = ok && hipMalloc((void**)&s->dPrevKps, cap * sizeof(pgorb_keypoint)) == hipSuccess;
-    ok = ok && hipMemcpy(s->dPq, pq.data(), B * 4, hipMemcpyHostToDevice) == hipSuccess;
-    ok = ok && hipMemcpy(s->dPt, pt.data(), B * 4, hipMemcpyHostToDevice) == hipSuccess;
-    ok = ok && ensure(c, c->xdesc, pg_match_scratch_bytes(c->mx, s->cap, batch) + 16) == 0;
     if (!ok) { pgorb_stream_destroy(s); return fail(c, PGORB_E_HIP, "pgorb_stream_create: allocation failed"); }
     s->lane.assign(1, c); s->sLane.assign(1, s->sRun); s->sChain = s->sRun;
     c->streams.push_back(s);
@@ -1609,13 +1642,11 @@ void pg_forward_option_to_lanes(pgorb_ctx* c, const char* key, int value)
             if (st->lane[l] && st->lane[l] != c) (void)pgorb_set_option(st->lane[l], key, value);
 }
 
-// every tunable of a context (pgorb_set_option), for the sibling contexts of a multi-lane device stream: "same parameters and
-// options" (pgorb.h) -- one list, used at lane creation; pgorb_set_option forwards later changes to the lanes of live streams
-static void copy_tunables(pgorb_ctx* dst, const pgorb_ctx* src)
+// every option of a context (kOptions), for the sibling contexts of a multi-lane device stream: "same parameters and options"
+// (pgorb.h) -- used at lane creation; pgorb_set_option forwards later changes to the lanes of live streams
+static void copy_tunables(pgorb_ctx* dst, pgorb_ctx* src)
 {
-    dst->mx = src->mx; dst->qtThreads = src->qtThreads; dst->qtSplit = src->qtSplit; dst->fastTilePitch = src->fastTilePitch;
-    dst->fastWpb = src->fastWpb; dst->fastCpw = src->fastCpw; dst->fused = src->fused; dst->pipePyr = src->pipePyr; dst->pipeLev = src->pipeLev;
-    dst->pipeLevPrio = src->pipeLevPrio;
+    for (const PgOption& o : kOptions) o.at(dst) = o.at(src);
 }
 
 int pgorb_stream_create_device(pgorb_ctx* c, int w, int h, int batch, int depth, int lanes, pgorb_stream** out)
@@ -1631,8 +1662,6 @@ int pgorb_stream_create_device(pgorb_ctx* c, int w, int h, int batch, int depth,
     s->c = c; s->w = w; s->h = h; s->B = batch; s->depth = depth; s->cap = c->plan.selTotal;
     s->srcW = w; s->srcH = h; s->ch = 1; s->device = true;
     s->inBytes = (size_t)w * h;
-    const size_t cap = (size_t)s->cap, B = (size_t)batch;
-    stream_layout(s);
     s->lane.assign(1, c);
     bool ok = hipStreamCreateWithFlags(&s->sRun, hipStreamNonBlocking) == hipSuccess;
     s->sLane.assign(1, s->sRun);
@@ -1648,30 +1677,11 @@ int pgorb_stream_create_device(pgorb_ctx* c, int w, int h, int batch, int depth,
             s->sLane.push_back(ls);
         }
     }
-    s->slot.resize(depth);
     ok = ok && hipHostMalloc((void**)&s->hStatus, 64 * sizeof(int32_t), hipHostMallocDefault) == hipSuccess;
     if (lanes > 1) ok = ok && hipStreamCreateWithFlags(&s->sChain, hipStreamNonBlocking) == hipSuccess;
     else s->sChain = s->sRun;
-    if (const char* e = getenv("PGORB_STREAM_STAGGER")) s->stagger = atoi(e);
-    if (lanes > 1)
-        for (pgorb_ctx* lc : s->lane) {
-            if (!lc->evPyrEnd) ok = ok && hipEventCreateWithFlags(&lc->evPyrEnd, hipEventDisableTiming) == hipSuccess;
-            if (!lc->evFastEnd) ok = ok && hipEventCreateWithFlags(&lc->evFastEnd, hipEventDisableTiming) == hipSuccess;
-        }
-    for (auto& sl : s->slot) {
-        ok = ok && hipMalloc((void**)&sl.dOut, s->outBytes + 256) == hipSuccess;
-        ok = ok && hipEventCreateWithFlags(&sl.evIn, hipEventDisableTiming) == hipSuccess;
-        ok = ok && hipEventCreateWithFlags(&sl.evRun, hipEventDisableTiming) == hipSuccess;
-        ok = ok && hipEventCreateWithFlags(&sl.evExt, hipEventDisableTiming) == hipSuccess;
-    }
-    std::vector<int32_t> pq(batch), pt(batch);
-    for (int f = 0; f < batch; f++) { pq[f] = f + 1; pt[f] = f; }
-    ok = ok && hipMalloc((void**)&s->dPq, B * 4) == hipSuccess && hipMalloc((void**)&s->dPt, B * 4) == hipSuccess;
-    ok = ok && hipMalloc((void**)&s->dPrevDesc, cap * 32) == hipSuccess && hipMalloc((void**)&s->dPrevN, 4) == hipSuccess;
-    ok = ok && hipMalloc((void**)&s->dPrevKps, cap * sizeof(pgorb_keypoint)) == hipSuccess;
-    ok = ok && hipMemcpy(s->dPq, pq.data(), B * 4, hipMemcpyHostToDevice) == hipSuccess;
-    ok = ok && hipMemcpy(s->dPt, pt.data(), B * 4, hipMemcpyHostToDevice) == hipSuccess;
-    ok = ok && ensure(c, c->xdesc, pg_match_scratch_bytes(c->mx, s->cap, batch) + 16) == 0;
+    ok = ok && stream_alloc_common(s);
+    for (auto& sl : s->slot) ok = ok && hipEventCreateWithFlags(&sl.evExt, hipEventDisableTiming) == hipSuccess;
     if (!ok) { pgorb_stream_destroy(s); return fail(c, PGORB_E_HIP, "pgorb_stream_create_device: allocation failed"); }
     c->streams.push_back(s);
     *out = s;
@@ -1810,16 +1820,9 @@ static int stream_submit_queue(pgorb_stream* s, pgorb_stream::Slot& sl, int nfra
         PG_HIP(c, hipEventRecord(sl.evIn, caller));
         PG_HIP(c, hipStreamWaitEvent(sr, sl.evIn, 0));
         PG_HIP(c, hipStreamWaitEvent(sr, sl.evRun, 0));
-        // stagger (PGORB_STREAM_STAGGER=1|2 at stream creation; off by default): hold a batch back until the previously submitted
-        // one (another lane) is past its pyramid (or past K2).  Measured on an MI355X (tools/experiments/r5_lanes.py,
-        // profiles/r05_lanes.txt; 1080p / 2000, batch 128): one lane 94-96 k frames/s, two lanes 101.3 k without stagger, 101.1 k /
-        // 99.0 k with 1 / 2, three lanes 99.0 k -- the hardware interleaves the lanes' kernels at workgroup granularity whatever
-        // the start offsets, and K2's one-wave workgroups take every wave slot they can get.  A never-recorded event does not wait.
-        if (s->stagger && s->lastLane >= 0 && s->lastLane != laneIx) {
-            pgorb_ctx* pl = s->lane[s->lastLane];
-            PG_HIP(c, hipStreamWaitEvent(sr, s->stagger == 2 ? pl->evFastEnd : pl->evPyrEnd, 0));
-        }
-        s->lastLane = laneIx;
+        // (holding a batch back until the previous lane's batch is past its pyramid or its K2 measured slower on an MI355X: 101.1 k /
+        // 99.0 k frames/s against 101.3 k at 1080p / 2000, batch 128 -- the hardware interleaves the lanes' kernels at workgroup
+        // granularity whatever the start offsets; tools/experiments/r5_lanes.py, profiles/r05_lanes.txt)
     }
     int32_t* dN = (int32_t*)(sl.dOut + s->offN);
     pgorb_keypoint* dK = (pgorb_keypoint*)(sl.dOut + s->offK);
@@ -1904,14 +1907,7 @@ int pgorb_stream_wait(pgorb_stream* s, int slot, const int32_t** n, const pgorb_
     sl.busy = false;
     const int32_t st = *(const int32_t*)(sl.hOut + s->outBytes);      // the batch's device status word
     if (st) return fail(c, st, "device reported status %d", st);
-    if (n) *n = (const int32_t*)(sl.hOut + s->offN) + 1;
-    if (kps) *kps = (const pgorb_keypoint*)(sl.hOut + s->offK) + s->cap;
-    if (desc) *desc = sl.hOut + s->offD + (size_t)s->cap * 32;
-    if (best_idx) *best_idx = (const int32_t*)(sl.hOut + s->offI);
-    if (best) *best = (const uint16_t*)(sl.hOut + s->offB1);
-    if (second) *second = (const uint16_t*)(sl.hOut + s->offB2);
-    if (cap) *cap = s->cap;
-    return sl.frames;
+    return stream_results(s, sl, sl.hOut, n, kps, desc, best_idx, best, second, cap);
 }
 
 // Device-resident form: the slot's batch is complete (host blocks on the batch's event, or -- hip_stream != NULL with
@@ -1934,14 +1930,7 @@ int pgorb_stream_wait_device(pgorb_stream* s, int slot, int wait_on_host, void* 
         PG_HIP(c, hipStreamWaitEvent((hipStream_t)hip_stream, sl.evRun, 0));        // (the status word: pgorb_check_async of the caller's choice)
     }
     sl.busy = false;
-    if (d_n) *d_n = (const int32_t*)(sl.dOut + s->offN) + 1;
-    if (d_kps) *d_kps = (const pgorb_keypoint*)(sl.dOut + s->offK) + s->cap;
-    if (d_desc) *d_desc = sl.dOut + s->offD + (size_t)s->cap * 32;
-    if (d_best_idx) *d_best_idx = (const int32_t*)(sl.dOut + s->offI);
-    if (d_best) *d_best = (const uint16_t*)(sl.dOut + s->offB1);
-    if (d_second) *d_second = (const uint16_t*)(sl.dOut + s->offB2);
-    if (cap) *cap = s->cap;
-    return sl.frames;
+    return stream_results(s, sl, sl.dOut, d_n, d_kps, d_desc, d_best_idx, d_best, d_second, cap);
 }
 
 int pgorb_stream_frontend(pgorb_stream* s, float min_x, float max_x, float min_y, float max_y, int window_size, float nnratio,

@@ -101,7 +101,6 @@ struct PgFuseLevel {
 };
 struct PgFusePlan {
     PgFuseLevel lvl[PG_MAXL];
-    int32_t  enabled;         // option "fused_levels": 1 = levels with fused tables take fused.hip's launch, 0 (default) = K1 + K2
 };
 
 #define PG_FAST_CPW_DEFAULT 1  // K2 cell records per wave

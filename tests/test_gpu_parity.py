@@ -881,12 +881,10 @@ def test_level_groups_beside_each_other_are_bit_exact(oracle, mask):
             assert np.array_equal(desc[f, :nh[f]].cpu().numpy(), odesc)
 
 
-def test_extract_through_the_staged_upload_twice(oracle, monkeypatch):
-    """PGORB_EXTRACT_STAGE=1 (the A/B form of the host-frame upload: page-locked staging buffer in chunks) grew its
-    buffer with three stray teardown lines that destroyed the stream and the graph in use.  Two frames of one size (the second
-    call replays the captured graph), then a larger batch through the same context (the staging buffer grows while the stream
-    and the graph exist), then the first frame again: every result equals the oracle."""
-    monkeypatch.setenv("PGORB_EXTRACT_STAGE", "1")
+def test_extract_replays_across_batch_growth(oracle):
+    """growing a host-frame call's buffers once destroyed the stream and the graph in use.  Two frames of one size
+    (the second call replays the captured graph), then a larger batch through the same context (its buffers grow while the
+    stream and the graph exist), then the first frame again: every result equals the oracle."""
     w, h, nf = 640, 480, 1000
     ride = synth_ride(2, w, h, 4)
     ora = oracle.OrbOracle(nf, 1.2, 8, 20, 7)

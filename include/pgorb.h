@@ -365,7 +365,8 @@ int  pgorb_search_by_bow_batch_device(pgorb_ctx* ctx,
  *       reference, a KF2 keypoint may be matched to several KF1 keypoints (vbMatched2 is never set, :679, :727), and among the
  *       candidates that pass the last one of the smallest distance wins (bestDist only moves on a passing candidate, :753-757).
  *       Each pair equals the reference called with those masks: CreateNewMapPoints adds map points to KF1 between neighbours
- *       (LocalMapping.cc:441), so reproducing that loop exactly means one call per neighbour with the updated has_point1. */
+ *       (LocalMapping.cc:441), so reproducing that loop exactly means one call per neighbour with the updated has_point1, or
+ *       pgorb_create_new_map_points for the whole loop. */
 int  pgorb_search_for_triangulation(pgorb_ctx* ctx,
         const pgorb_keypoint* kps1, const uint8_t* desc1, const uint8_t* has_point1, int n1,
         const uint32_t* fv1_node, const int32_t* fv1_start, const uint32_t* fv1_feat, int nfv1,
@@ -386,6 +387,68 @@ int  pgorb_search_for_triangulation_batch_device(pgorb_ctx* ctx,
         const int32_t* d_pair_kf1, const int32_t* d_pair_kf2, int npairs, const float* d_F12, const float* d_epipole,
         const uint8_t* d_has_point1, const uint8_t* d_has_point2, int check_orientation,
         int32_t* d_matches12, int32_t* d_nmatches, void* hip_stream);
+
+/* ---- Triangulation of the local-mapping thread -----------------------------------------------------------------------
+ *   pgorb_create_new_map_points   LocalMapping::CreateNewMapPoints() (src/LocalMapping.cc:209-454), monocular (mbMonocular,
+ *       mvuRight < 0): for every neighbour in the given order the baseline test (:243-262, baseline / medianDepthKF2 < 0.01),
+ *       ComputeF12 (:538-555) and the epipole (ORBmatcher.cc:665-672), SearchForTriangulation with ORBmatcher(0.6, false)
+ *       (:217, :266; rotation histogram off), then per match the parallax test, the linear triangulation (cv::SVD of a 4x4,
+ *       :311-327), the depth, reprojection and scale-consistency tests (:342-423) and, for a point that passes, what
+ *       MapPoint::UpdateNormalAndDepth (MapPoint.cc:347-387) stores.  The stereo branches and UnprojectStereo are out of scope.
+ *       The precision of every cv::Mat step is a recalled reading of OpenCV 2.4.9, listed in DESIGN.md section 4.
+ *   Inputs per key frame: keypoints (mvKeysUn), descriptors, FeatureVector CSR, has_point[i] = GetMapPoint(i) != NULL (NULL =
+ *   none), the pose and camera (pgorb_kf_pose), and per neighbour medianDepthKF2 = ComputeSceneMedianDepth(2) (it reads KF2's
+ *   map points, so the caller computes it).  Neighbours are distinct key frames other than KF1 (GetBestCovisibilityKeyFrames).
+ *   Equivalence with the reference's loop: the matcher has vbMatched2 never set (ORBmatcher.cc:679, 727) and no rotation
+ *   histogram, so KF1's mask only decides whether keypoint idx1 is searched, not which KF2 keypoint it takes; a pair's
+ *   triangulation depends only on the two key frames; a new point changes only KF1 and the current KF2.  So KF1 keypoint idx1
+ *   gets the point of the FIRST neighbour (in the given order) whose match for idx1 triangulates, provided idx1 had no point on
+ *   entry: every pair is matched and triangulated at once, then the first success per idx1 is kept.
+ *   Outputs: points[] in the reference's creation order (neighbour order, then ascending idx1), at most one per idx1, so at
+ *   most n1; count[s] = the points made with neighbour s, or PGORB_CNM_SKIPPED when the baseline test skipped it; F12 / epipole
+ *   (may be NULL) = ComputeF12 and the epipole of every neighbour, skipped or not; has_point1_out = KF1's mask afterwards.
+ *   Two KF1 keypoints may match one KF2 keypoint: both points are listed and KF2's slot ends with the later one (AddMapPoint
+ *   overwrites).  Left to the caller: AddObservation / AddMapPoint / Map::AddMapPoint / mlpRecentAddedMapPoints, and
+ *   ComputeDistinctiveDescriptors (with two observations the reference picks by KeyFrame* address).  CheckNewKeyFrames()'s
+ *   early return between neighbours (:240) is the caller's choice of how many neighbours to pass.
+ *   Returns the number of points, or a PGORB_E_* code.  At most PGORB_CNM_MAX_NEIGHBOURS neighbours, 16000 keypoints. */
+#define PGORB_CNM_MAX_NEIGHBOURS 64
+#define PGORB_CNM_SKIPPED (-1)
+typedef struct pgorb_kf_pose {
+    float Tcw[12];           /* [R | t] row-major, GetPose() rows 0-2 */
+    float Ow[3];             /* GetCameraCenter() */
+    float fx, fy, cx, cy, invfx, invfy;
+} pgorb_kf_pose;
+typedef struct pgorb_new_map_point {
+    int32_t neighbour;       /* slot of the neighbour (pKF2) in the given order */
+    int32_t idx1, idx2;      /* keypoint of KF1 and of the neighbour */
+    float pos[3];            /* mWorldPos = x3D */
+    float normal[3];         /* mNormalVector */
+    float min_distance, max_distance;   /* mfMinDistance, mfMaxDistance */
+} pgorb_new_map_point;
+int  pgorb_create_new_map_points(pgorb_ctx* ctx,
+        const pgorb_keypoint* kps1, const uint8_t* desc1, const uint8_t* has_point1, int n1,
+        const uint32_t* fv1_node, const int32_t* fv1_start, const uint32_t* fv1_feat, int nfv1, const pgorb_kf_pose* pose1,
+        int nneigh, const pgorb_keypoint* const* kps2, const uint8_t* const* desc2, const uint8_t* const* has_point2,
+        const int32_t* n2, const uint32_t* const* fv2_node, const int32_t* const* fv2_start, const uint32_t* const* fv2_feat,
+        const int32_t* nfv2, const pgorb_kf_pose* pose2 /*[nneigh]*/, const float* median_depth2 /*[nneigh]*/,
+        pgorb_new_map_point* points /*[n1]*/, int32_t* count /*[nneigh]*/, float* F12 /*[nneigh][9] or NULL*/,
+        float* epipole /*[nneigh][2] or NULL*/, uint8_t* has_point1_out /*[n1] or NULL*/);
+/* Batched, resident: problem k has current key frame d_kf1[k] and neighbours d_neigh[k][0 .. d_nneigh[k]) (frame indices of
+ * one batch in the layout of pgorb_extract_batch_device, FeatureVectors as pgorb_feature_vectors_batch_device writes them,
+ * unchecked as in pgorb_search_for_triangulation_batch_device).  d_pose [nframes], d_has_point [nframes][cap_per_frame] (NULL
+ * = none), d_median_depth [nkf][max_neigh].  Outputs: d_points [nkf][cap_per_frame], d_npoints [nkf], d_count
+ * [nkf][max_neigh] (0 past d_nneigh[k]), d_F12 [nkf][max_neigh][9] and d_epipole [nkf][max_neigh][2] (may be NULL),
+ * d_has_point1_out [nkf][cap_per_frame] (may be NULL).  Each problem equals the reference called with the masks it was
+ * given: the reference runs key frames one after another and each changes its neighbours' masks, so problems whose key frames
+ * neighbour each other are the caller's to order. */
+int  pgorb_create_new_map_points_batch_device(pgorb_ctx* ctx,
+        const pgorb_keypoint* d_kps, const uint8_t* d_desc, const int32_t* d_n, int cap_per_frame,
+        const uint32_t* d_fv_node, const int32_t* d_fv_start, const uint32_t* d_fv_feat, const int32_t* d_nfv,
+        const pgorb_kf_pose* d_pose, const uint8_t* d_has_point, const int32_t* d_kf1, int nkf, const int32_t* d_neigh,
+        const int32_t* d_nneigh, int max_neigh, const float* d_median_depth,
+        pgorb_new_map_point* d_points, int32_t* d_npoints, int32_t* d_count, float* d_F12, float* d_epipole,
+        uint8_t* d_has_point1_out, void* hip_stream);
 
 /* ---- ORB vocabulary (DBoW2 TemplatedVocabulary<FORB::TDescriptor, FORB>) -----------------
  *   pgorb_vocab_load_text     ORBVocabulary(text_file) -> TemplatedVocabulary::loadFromTextFile

@@ -5,3 +5,4 @@ the host-side mirror of the reference's ORBextractor / ORBmatcher interface (orb
 and the synthetic ride generator used by tests and bench (synth.py).
 """
 from .orb import KEYPOINT_DTYPE, DeviceFrameStream, Frame, FrameStream, MapPoints, ORBextractor, ORBmatcher  # noqa: F401
+from .orb import KF_POSE_DTYPE, NEW_MAP_POINT_DTYPE, LocalMapping, kf_pose  # noqa: F401

@@ -32,6 +32,7 @@ SYMBOLS = (
     "pgorb_search_by_projection_points_batch_device", "pgorb_search_by_projection_frame_batch_device",
     "pgorb_feature_vectors_batch_device", "pgorb_search_by_bow_batch_device",
     "pgorb_search_for_triangulation", "pgorb_search_for_triangulation_batch_device",
+    "pgorb_create_new_map_points", "pgorb_create_new_map_points_batch_device",
     "pgorb_search_by_projection_keyframe", "pgorb_search_by_projection_keyframe_batch_device",
     "pgorb_log_f", "pgorb_log_scale_factor", "pgorb_predict_scale",
     "pgorb_undistort_keypoints", "pgorb_undistort_keypoints_batch_device", "pgorb_image_bounds",
@@ -154,6 +155,8 @@ def lib():
     L.pgorb_search_for_triangulation.argtypes = [vp] + ([vp] * 3 + [C.c_int] + [vp] * 3 + [C.c_int]) * 2 + [vp, C.c_float, C.c_float, C.c_int, vp]
     L.pgorb_search_for_triangulation_batch_device.argtypes = [vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp, C.c_int] + [vp] * 4 + \
         [C.c_int, vp, vp, vp]
+    L.pgorb_create_new_map_points.argtypes = [vp] + [vp] * 3 + [C.c_int] + [vp] * 3 + [C.c_int, vp] + [C.c_int] + [vp] * 15
+    L.pgorb_create_new_map_points_batch_device.argtypes = [vp, vp, vp, vp, C.c_int] + [vp] * 7 + [C.c_int, vp, vp, C.c_int] + [vp] * 8
     L.pgorb_undistort_keypoints.argtypes = [vp, vp, C.c_int, vp, vp, vp]
     L.pgorb_undistort_keypoints_batch_device.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp]
     L.pgorb_image_bounds.argtypes = [C.c_int, C.c_int, vp, vp, vp]

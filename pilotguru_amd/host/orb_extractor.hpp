@@ -87,6 +87,22 @@ struct FeatureVector {
     int size() const { return (int)mNode.size(); }
 };
 
+namespace detail {
+inline void checkDescriptors(const Frame& F, const char* fn)
+{
+    if (F.mDescriptors.size() != (size_t)F.N() * 32) throw std::invalid_argument(std::string(fn) + ": descriptors are not N x 32 bytes");
+}
+// what the library reads of a key frame through its pointers: N descriptors, N mask entries (or none), mStart[n] feature indices
+inline void checkKeyFrame(const Frame& K, const FeatureVector& fv, const std::vector<uint8_t>& hasPoint, const char* fn)
+{
+    checkDescriptors(K, fn);
+    if (!hasPoint.empty() && hasPoint.size() != (size_t)K.N())
+        throw std::invalid_argument(std::string(fn) + ": a hasPoint mask is neither empty nor N entries long");
+    if (fv.mStart.size() != fv.mNode.size() + 1 || fv.mStart.back() < 0 || fv.mFeat.size() < (size_t)fv.mStart.back())
+        throw std::invalid_argument(std::string(fn) + ": FeatureVector arrays of inconsistent lengths");
+}
+}  // namespace detail
+
 class ORBmatcher {
  public:
     static const int TH_LOW = 50, TH_HIGH = 100, HISTO_LENGTH = 30;     // ORBmatcher.cc:38-40
@@ -98,8 +114,8 @@ class ORBmatcher {
                                 std::vector<int32_t>& vnMatches12, int windowSize = 10)
     {
         // the library reads N descriptors of each frame and 2 * N1 floats of vbPrevMatched through these pointers
-        checkDescriptors(F1, "SearchForInitialization");
-        checkDescriptors(F2, "SearchForInitialization");
+        detail::checkDescriptors(F1, "SearchForInitialization");
+        detail::checkDescriptors(F2, "SearchForInitialization");
         if (vbPrevMatched.size() != (size_t)F1.N() * 2)
             throw std::invalid_argument("SearchForInitialization: vbPrevMatched does not hold 2 floats per F1 keypoint");
         vnMatches12.assign(F1.N(), -1);
@@ -119,17 +135,8 @@ class ORBmatcher {
                                const std::vector<uint8_t>& hasPoint2, std::vector<std::pair<size_t, size_t> >& vMatchedPairs)
     {
         // the library reads N mask entries, N descriptors and mStart[n] feature indices through these pointers
-        const Frame* kf[2] = {&KF1, &KF2};
-        const std::vector<uint8_t>* has[2] = {&hasPoint1, &hasPoint2};
-        const FeatureVector* fv[2] = {&fv1, &fv2};
-        for (int k = 0; k < 2; k++) {
-            checkDescriptors(*kf[k], "SearchForTriangulation");
-            if (!has[k]->empty() && has[k]->size() != (size_t)kf[k]->N())
-                throw std::invalid_argument("SearchForTriangulation: a hasPoint mask is neither empty nor N entries long");
-            if (fv[k]->mStart.size() != fv[k]->mNode.size() + 1 || fv[k]->mStart.back() < 0 ||
-                fv[k]->mFeat.size() < (size_t)fv[k]->mStart.back())
-                throw std::invalid_argument("SearchForTriangulation: FeatureVector arrays of inconsistent lengths");
-        }
+        detail::checkKeyFrame(KF1, fv1, hasPoint1, "SearchForTriangulation");
+        detail::checkKeyFrame(KF2, fv2, hasPoint2, "SearchForTriangulation");
         vMatchedPairs.clear();
         std::vector<int32_t> m12(KF1.N() > 0 ? KF1.N() : 1, -1);
         const int rc = pgorb_search_for_triangulation(ctx_, KF1.mvKeysUndistorted.data(), KF1.mDescriptors.data(),
@@ -147,13 +154,68 @@ class ORBmatcher {
     }
 
  private:
-    static void checkDescriptors(const Frame& F, const char* fn)
-    {
-        if (F.mDescriptors.size() != (size_t)F.N() * 32) throw std::invalid_argument(std::string(fn) + ": descriptors are not N x 32 bytes");
-    }
     pgorb_ctx* ctx_;
     float mfNNratio;
     bool mbCheckOrientation;
+};
+
+// The slice of ORB_SLAM2::KeyFrame that CreateNewMapPoints reads: mvKeysUn and mDescriptors, mFeatVec, which keypoints have a map
+// point (empty = none), the pose and camera, and (for a neighbour) ComputeSceneMedianDepth(2).
+struct KeyFrame {
+    Frame frame;
+    FeatureVector featVec;
+    std::vector<uint8_t> hasPoint;
+    pgorb_kf_pose pose{};
+    float medianDepth = 0;
+};
+
+class LocalMapping {
+ public:
+    explicit LocalMapping(pgorb_ctx* ctx) : ctx_(ctx) {}
+    // CreateNewMapPoints() (LocalMapping.cc:209-454), monocular: neighbours in GetBestCovisibilityKeyFrames order.  points in
+    // the reference's creation order, count[s] per neighbour (PGORB_CNM_SKIPPED: the baseline test skipped it), hasPoint1Out KF1's
+    // mask afterwards.  The map bookkeeping is the caller's (include/pgorb.h).  Returns the number of points.
+    int CreateNewMapPoints(const KeyFrame& KF1, const std::vector<const KeyFrame*>& neighbours, std::vector<pgorb_new_map_point>& points,
+                           std::vector<int32_t>& count, std::vector<uint8_t>* hasPoint1Out = nullptr)
+    {
+        const size_t nn = neighbours.size();
+        if (nn > PGORB_CNM_MAX_NEIGHBOURS) throw std::invalid_argument("CreateNewMapPoints: more than 64 neighbours");
+        detail::checkKeyFrame(KF1.frame, KF1.featVec, KF1.hasPoint, "CreateNewMapPoints");
+        std::vector<const pgorb_keypoint*> kps(nn + 1);
+        std::vector<const uint8_t*> desc(nn + 1), has(nn + 1);
+        std::vector<const uint32_t*> node(nn + 1), feat(nn + 1);
+        std::vector<const int32_t*> start(nn + 1);
+        std::vector<int32_t> n(nn + 1), nfv(nn + 1);
+        std::vector<pgorb_kf_pose> pose(nn + 1);
+        std::vector<float> median(nn + 1);
+        for (size_t s = 0; s < nn; s++) {
+            if (!neighbours[s]) throw std::invalid_argument("CreateNewMapPoints: a neighbour is NULL");
+            const KeyFrame& K = *neighbours[s];
+            detail::checkKeyFrame(K.frame, K.featVec, K.hasPoint, "CreateNewMapPoints");
+            kps[s] = K.frame.mvKeysUndistorted.data(); desc[s] = K.frame.mDescriptors.data();
+            has[s] = K.hasPoint.empty() ? nullptr : K.hasPoint.data();
+            node[s] = K.featVec.mNode.data(); start[s] = K.featVec.mStart.data(); feat[s] = K.featVec.mFeat.data();
+            n[s] = K.frame.N(); nfv[s] = K.featVec.size(); pose[s] = K.pose; median[s] = K.medianDepth;
+        }
+        const int n1 = KF1.frame.N();
+        points.resize(n1 > 0 ? n1 : 1);
+        count.assign(nn > 0 ? nn : 1, 0);
+        std::vector<uint8_t> hout(n1 > 0 ? n1 : 1);
+        const int rc = pgorb_create_new_map_points(ctx_, KF1.frame.mvKeysUndistorted.data(), KF1.frame.mDescriptors.data(),
+                                                   KF1.hasPoint.empty() ? nullptr : KF1.hasPoint.data(), n1, KF1.featVec.mNode.data(),
+                                                   KF1.featVec.mStart.data(), KF1.featVec.mFeat.data(), KF1.featVec.size(), &KF1.pose,
+                                                   (int)nn, kps.data(), desc.data(), has.data(), n.data(), node.data(), start.data(),
+                                                   feat.data(), nfv.data(), pose.data(), median.data(), points.data(), count.data(),
+                                                   nullptr, nullptr, hout.data());
+        if (rc < 0) throw std::runtime_error(pgorb_last_error(ctx_));
+        points.resize(rc);
+        count.resize(nn);
+        if (hasPoint1Out) hasPoint1Out->assign(hout.begin(), hout.begin() + n1);
+        return rc;
+    }
+
+ private:
+    pgorb_ctx* ctx_;
 };
 
 }  // namespace pgorb

@@ -487,6 +487,76 @@ class ORBmatcher:
         return _lib.lib().pgorb_descriptor_distance(_p(a), _p(b))
 
 
+# pgorb_kf_pose: a key frame's GetPose() rows 0-2 ([R | t] row-major), GetCameraCenter() and camera (include/pgorb.h)
+KF_POSE_DTYPE = np.dtype([("Tcw", "<f4", (12,)), ("Ow", "<f4", (3,)), ("fx", "<f4"), ("fy", "<f4"), ("cx", "<f4"), ("cy", "<f4"),
+                          ("invfx", "<f4"), ("invfy", "<f4")])
+# pgorb_new_map_point: one point of CreateNewMapPoints
+NEW_MAP_POINT_DTYPE = np.dtype([("neighbour", "<i4"), ("idx1", "<i4"), ("idx2", "<i4"), ("pos", "<f4", (3,)), ("normal", "<f4", (3,)),
+                                ("min_distance", "<f4"), ("max_distance", "<f4")])
+CNM_SKIPPED = -1                 # count[s] of a neighbour the baseline test skipped
+CNM_MAX_NEIGHBOURS = 64
+
+
+def kf_pose(Tcw, Ow, fx, fy, cx, cy, invfx=None, invfy=None):
+    """A KF_POSE_DTYPE record; invfx / invfy default to 1.0f/fx, 1.0f/fy (Frame.cc:135-136 computes them in float)."""
+    r = np.zeros((), KF_POSE_DTYPE)
+    r["Tcw"] = np.asarray(Tcw, np.float32).reshape(3, 4).reshape(12)
+    r["Ow"] = np.asarray(Ow, np.float32).reshape(3)
+    fx, fy = np.float32(fx), np.float32(fy)
+    r["fx"], r["fy"], r["cx"], r["cy"] = fx, fy, np.float32(cx), np.float32(cy)
+    r["invfx"] = np.float32(1.0) / fx if invfx is None else np.float32(invfx)
+    r["invfy"] = np.float32(1.0) / fy if invfy is None else np.float32(invfy)
+    return r
+
+
+class LocalMapping:
+    """LocalMapping::CreateNewMapPoints (thirdparty/orb-slam2/src/LocalMapping.cc:209-454), monocular, on the GPU."""
+
+    @staticmethod
+    def CreateNewMapPoints(KF1, neighbours, fv1, fvs, pose1, poses, median_depths, has_point1=None, has_points=None):
+        """KF1 and each neighbour: a Frame-like object (ext, N, mvKeysUndistorted, mDescriptors); fv1 / fvs[s]: the (nodes,
+        starts, features) triples of ORBVocabulary.transform(); pose1 / poses[s]: KF_POSE_DTYPE records (kf_pose()); median_depths[s]
+        = neighbour s's ComputeSceneMedianDepth(2); has_point*[i] = GetMapPoint(i) != NULL (None = none).  Neighbours in the
+        order GetBestCovisibilityKeyFrames returns them.  Returns (points, count, F12, epipole, has_point1_out): points a
+        NEW_MAP_POINT_DTYPE array in the reference's creation order, count[s] the points made with neighbour s or CNM_SKIPPED,
+        F12 [nneigh, 3, 3], epipole [nneigh, 2], has_point1_out KF1's mask afterwards (pgorb.h states what is left to the caller)."""
+        nn = len(neighbours)
+        if len(fvs) != nn or len(poses) != nn or (has_points is not None and len(has_points) != nn):
+            raise ValueError("CreateNewMapPoints: neighbours, fvs, poses and has_points differ in length")
+        if nn > CNM_MAX_NEIGHBOURS:
+            raise ValueError("CreateNewMapPoints: more than %d neighbours" % CNM_MAX_NEIGHBOURS)
+        md = _arr(median_depths, np.float32, nn, "median_depths")
+        k1, d1 = _frame(KF1, "KF1")
+        h1 = _mask(has_point1, KF1.N, "KF1 has_point")
+        n1, s1, f1 = _featvec(fv1, "KF1")
+        p1 = np.ascontiguousarray(pose1, KF_POSE_DTYPE).reshape(())
+        keep = []
+        kps, descs, masks, nodes, starts, feats = [(C.c_void_p * max(nn, 1))() for _ in range(6)]
+        n2 = np.zeros(max(nn, 1), np.int32)
+        nfv2 = np.zeros(max(nn, 1), np.int32)
+        for s, K in enumerate(neighbours):
+            name = "neighbour %d" % s
+            kp, desc = _frame(K, name)
+            m = _mask(None if has_points is None else has_points[s], K.N, name + " has_point")
+            node, start, feat = _featvec(fvs[s], name)
+            keep += [kp, desc, m, node, start, feat]
+            kps[s], descs[s], masks[s], nodes[s], starts[s], feats[s] = (a.ctypes.data for a in (kp, desc, m, node, start, feat))
+            n2[s], nfv2[s] = K.N, len(node)
+        P2 = np.zeros(max(nn, 1), KF_POSE_DTYPE)
+        for s in range(nn):
+            P2[s] = np.asarray(poses[s], KF_POSE_DTYPE).reshape(())
+        ext = KF1.ext
+        pts = np.zeros(max(KF1.N, 1), NEW_MAP_POINT_DTYPE)
+        count = np.zeros(max(nn, 1), np.int32)
+        F12 = np.zeros((max(nn, 1), 9), np.float32)
+        ep = np.zeros((max(nn, 1), 2), np.float32)
+        hout = np.zeros(max(KF1.N, 1), np.uint8)
+        np_ = ext._check(ext._L.pgorb_create_new_map_points(
+            ext._h, _p(k1), _p(d1), _p(h1), KF1.N, _p(n1), _p(s1), _p(f1), len(n1), _p(p1), nn, kps, descs, masks, _p(n2), nodes,
+            starts, feats, _p(nfv2), _p(P2), _p(md), _p(pts), _p(count), _p(F12), _p(ep), _p(hout)))
+        return pts[:np_].copy(), count[:nn].copy(), F12[:nn].reshape(nn, 3, 3).copy(), ep[:nn].copy(), hout[:KF1.N].copy()
+
+
 class FrameStream:
     """Streamed ingest (include/pgorb.h, pgorb_stream_*): the frame loop around the extractor for frames that
     start in host memory -- ImageSequenceSource::next() -> System::TrackMonocular in the reference

@@ -1,0 +1,418 @@
+"""A plain, sequential restatement of LocalMapping::CreateNewMapPoints (thirdparty/orb-slam2/src/LocalMapping.cc:209-454),
+monocular, with ComputeF12 (:538-555), the epipole of ORBmatcher::SearchForTriangulation (ORBmatcher.cc:665-672) and
+MapPoint::UpdateNormalAndDepth (MapPoint.cc:347-387).  It is written from that upstream text and the table of cv::Mat readings
+in DESIGN.md section 4; it does not use oracle/ and was not derived from the HIP kernels (pilotguru_amd/csrc/frame.hip).
+
+The loop is the reference's: for every neighbour in order, the baseline test, F12, one call of
+tests/triangulation_reference.search_for_triangulation with KF1's mask as the earlier neighbours left it, then the triangulation
+of every match, and a passing match sets KF1's and KF2's masks before the next one.
+
+Every value the reference holds in `float` is an np.float32 scalar; what cv::Mat computes in double is np.float64.  `rules` (a
+Rules) switches one reading at a time; `hits` (a collections.Counter or None) counts the edges reached.
+"""
+import math
+import os
+import sys
+from dataclasses import dataclass
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import triangulation_reference as TR  # noqa: E402
+from matcher_reference import _hit  # noqa: E402
+
+f32, f64 = np.float32, np.float64
+FLT_EPSILON = f32(1.1920928955078125e-07)
+
+
+@dataclass(frozen=True)
+class Rules:
+    gemm: str = "float"          # the small-matrix gemm path (flags 0, 3x3 operands) sums in float | "double"
+    norm: str = "double"         # cv::norm and Mat::dot on CV_32F return double | "float": float sums
+    givensx: str = "double"      # the SVD's new row norms accumulated in double | "float": VBLAS<float>::givensx's float lanes
+    a_rows: str = "double"       # A's rows by addWeighted in double | "float"
+    divide: str = "scale"        # x3D.rowRange(0,3)/w: convertTo with the float scale (float)(1/w) | "divide": x/w in float
+    parallax: str = "strict"     # cosParallaxRays > 0 and < 0.9998 | "inclusive": >= 0, <= 0.9998
+    depth: str = "le"            # z <= 0 rejects | "lt": z < 0 rejects
+    chi2: str = "gt"             # err > 5.991*sigma2 rejects | "ge"
+    scale: str = "strict"        # ratioDist*ratioFactor < ratioOctave or ratioDist > ratioOctave*ratioFactor rejects | "inclusive"
+    baseline: str = "lt"         # ratioBaselineDepth < 0.01 skips | "le"
+    success: str = "first"       # KF1's mask is updated between neighbours, so the first success wins | "last": a later one replaces
+
+
+REFERENCE = Rules()
+# The mutants a float input can tell apart.  baseline=le, chi2=ge and the 0.9998 half of parallax=inclusive compare a float with a
+# double constant that no float equals (0.01, 5.991*sigma2, 0.9998), so no input separates them from the reference; depth=lt,
+# scale=inclusive and the 0 half of parallax need an exact tie, which the constructed scenes do not contain.
+MUTANTS = {
+    "gemm=double": Rules(gemm="double"),
+    "norm=float": Rules(norm="float"),
+    "givensx=float": Rules(givensx="float"),
+    "a_rows=float": Rules(a_rows="float"),
+    "divide=divide": Rules(divide="divide"),
+    "success=last": Rules(success="last"),
+}
+
+
+# ---------------------------------------------------------------- cv::Mat arithmetic
+def gemm3(a0, a1, a2, b0, b1, b2, rules=REFERENCE):
+    """One entry of the small gemm path: a0*b0 + a1*b1 + a2*b2 (float, or double under gemm=double), then + 0 in double."""
+    if rules.gemm == "double":
+        return f32(f64(a0) * f64(b0) + f64(a1) * f64(b1) + f64(a2) * f64(b2) + 0.0)
+    return f32(f64(f32(f32(f32(a0) * f32(b0)) + f32(f32(a1) * f32(b1))) + f32(f32(a2) * f32(b2))) + 0.0)
+
+
+def dotd(a, b, rules=REFERENCE):
+    """Mat::dot on CV_32F (double sum from 0), or the float sum under norm=float."""
+    if rules.norm == "float":
+        s = f32(0)
+        for x, y in zip(a, b):
+            s = f32(s + f32(f32(x) * f32(y)))
+        return f64(s)
+    s = f64(0)
+    for x, y in zip(a, b):
+        s = f64(s + f64(x) * f64(y))
+    return s
+
+
+def normd(a, rules=REFERENCE):
+    return f64(math.sqrt(dotd(a, a, rules))) if rules.norm != "float" else f64(np.sqrt(f32(dotd(a, a, rules))))
+
+
+def solve_lu(A, B):
+    """cv::solve(A, B, DECOMP_LU) on CV_32F 3x3 operands: LUImpl<float> with partial pivoting; a pivot below FLT_EPSILON fails (0)."""
+    A = [[f32(x) for x in r] for r in A]
+    B = [[f32(x) for x in r] for r in B]
+    m = 3
+    for i in range(m):
+        k = i
+        for j in range(i + 1, m):
+            if abs(A[j][i]) > abs(A[k][i]):
+                k = j
+        if abs(A[k][i]) < FLT_EPSILON:
+            return [[f32(0)] * 3 for _ in range(3)]
+        if k != i:
+            A[i], A[k] = A[k], A[i]
+            B[i], B[k] = B[k], B[i]
+        d = f32(f32(-1) / A[i][i])
+        for j in range(i + 1, m):
+            alpha = f32(A[j][i] * d)
+            for c in range(i + 1, m):
+                A[j][c] = f32(A[j][c] + f32(alpha * A[i][c]))
+            for c in range(3):
+                B[j][c] = f32(B[j][c] + f32(alpha * B[i][c]))
+        A[i][i] = f32(-d)
+    for i in range(m - 1, -1, -1):
+        for j in range(3):
+            s = B[i][j]
+            for c in range(i + 1, m):
+                s = f32(s - f32(A[i][c] * B[c][j]))
+            B[i][j] = f32(s * A[i][i])
+    return B
+
+
+def inv3(m):
+    """cv::invert(DECOMP_LU) of a CV_32F 3x3: the closed form with the determinant and cofactors in double."""
+    M = lambda a, b: f64(m[a][b])
+    C = lambda a, b, c, d: f64(M(a, b) * M(c, d) - M(a, d) * M(c, b))
+    det = f64(f64(f64(M(0, 0) * C(1, 1, 2, 2)) - f64(M(0, 1) * f64(M(1, 0) * M(2, 2) - M(1, 2) * M(2, 0))))
+              + f64(M(0, 2) * f64(M(1, 0) * M(2, 1) - M(1, 1) * M(2, 0))))
+    if det == 0:
+        return [[f32(0)] * 3 for _ in range(3)]
+    d = f64(1.0) / det
+    cof = [[C(1, 1, 2, 2), C(0, 2, 2, 1), C(0, 1, 1, 2)], [C(1, 2, 2, 0), C(0, 0, 2, 2), C(0, 2, 1, 0)], [C(1, 0, 2, 1), C(0, 1, 2, 0), C(0, 0, 1, 1)]]
+    return [[f32(cof[i][j] * d) for j in range(3)] for i in range(3)]
+
+
+def _pose(P):
+    T = np.asarray(P["Tcw"], np.float32).reshape(3, 4)
+    return T[:, :3], T[:, 3], np.asarray(P["Ow"], np.float32).reshape(3)
+
+
+def compute_f12(P1, P2, rules=REFERENCE):
+    """ComputeF12 (:538-555): K1.t().inv()*t12x*R12*K2.inv() as cv::Mat evaluates it."""
+    R1, t1, _ = _pose(P1)
+    R2, t2, _ = _pose(P2)
+    # R1w*R2w.t(): a transposed operand, GEMMSingleMul<float, double>; -R1w*R2w.t() is the same with alpha = -1
+    R12 = [[f32(_sumprod(R1[i], R2[j])) for j in range(3)] for i in range(3)]
+    t12 = []
+    for i in range(3):
+        if rules.gemm == "double":
+            t12.append(f32(f64(-R12[i][0]) * f64(t2[0]) + f64(-R12[i][1]) * f64(t2[1]) + f64(-R12[i][2]) * f64(t2[2]) + f64(t1[i])))
+        else:
+            t = f32(f32(f32(-R12[i][0] * t2[0]) + f32(-R12[i][1] * t2[1])) + f32(-R12[i][2] * t2[2]))
+            t12.append(f32(f64(t) + f64(t1[i])))
+    z = f32(0)
+    S = [[z, -t12[2], t12[1]], [t12[2], z, -t12[0]], [-t12[1], t12[0], z]]
+    K1t = [[P1["fx"], z, z], [z, P1["fy"], z], [P1["cx"], P1["cy"], f32(1)]]
+    X = solve_lu(K1t, S)
+    Y = [[gemm3(X[i][0], X[i][1], X[i][2], R12[0][j], R12[1][j], R12[2][j], rules) for j in range(3)] for i in range(3)]
+    Ki = inv3([[P2["fx"], z, P2["cx"]], [z, P2["fy"], P2["cy"]], [z, z, f32(1)]])
+    return np.array([[gemm3(Y[i][0], Y[i][1], Y[i][2], Ki[0][j], Ki[1][j], Ki[2][j], rules) for j in range(3)] for i in range(3)], np.float32)
+
+
+def epipole(P1, P2, rules=REFERENCE):
+    """ORBmatcher.cc:665-672: C2 = R2w*Cw + t2w, invz = 1.0f/C2.z, ex = fx*C2.x*invz + cx."""
+    R2, t2, _ = _pose(P2)
+    _, _, Ow1 = _pose(P1)
+    C2 = []
+    for i in range(3):
+        if rules.gemm == "double":
+            C2.append(f32(f64(R2[i][0]) * f64(Ow1[0]) + f64(R2[i][1]) * f64(Ow1[1]) + f64(R2[i][2]) * f64(Ow1[2]) + f64(t2[i])))
+        else:
+            t = f32(f32(f32(R2[i][0] * Ow1[0]) + f32(R2[i][1] * Ow1[1])) + f32(R2[i][2] * Ow1[2]))
+            C2.append(f32(f64(t) + f64(t2[i])))
+    with np.errstate(all="ignore"):
+        invz = f32(f32(1) / C2[2])
+        ex = f32(f32(f32(P2["fx"] * C2[0]) * invz) + P2["cx"])
+        ey = f32(f32(f32(P2["fy"] * C2[1]) * invz) + P2["cy"])
+    return ex, ey
+
+
+def svd_v3(A, rules=REFERENCE, hits=None):
+    """cv::SVD::compute(A, w, u, vt, MODIFY_A | FULL_UV) on a 4x4 CV_32F, as JacobiSVDImpl_<float>: returns vt.row(3)."""
+    At = [[f32(A[k][i]) for k in range(4)] for i in range(4)]
+    Vt = [[f32(1 if i == k else 0) for k in range(4)] for i in range(4)]
+    W = [f64(sum_sq) for sum_sq in (_sumsq(r) for r in At)]
+    eps = f32(FLT_EPSILON * f32(2))
+    sweeps = 0
+    for _ in range(30):
+        changed = False
+        sweeps += 1
+        for i in range(3):
+            for j in range(i + 1, 4):
+                a, b = W[i], W[j]
+                p = f64(0)
+                for k in range(4):
+                    p = f64(p + f64(At[i][k]) * f64(At[j][k]))
+                if abs(p) <= f64(eps) * math.sqrt(a * b):
+                    continue
+                p = p * 2
+                beta = f64(a - b)
+                gamma = _cv_hypot(p, beta)
+                if beta < 0:
+                    delta = f64((gamma - beta) * 0.5)
+                    s = f32(math.sqrt(delta / gamma))
+                    c = f32(p / (gamma * f64(s) * 2))
+                else:
+                    c = f32(math.sqrt((gamma + beta) / (gamma * 2)))
+                    s = f32(p / (gamma * f64(c) * 2))
+                na, nb = f64(0), f64(0)
+                qa, qb = [], []
+                for k in range(4):
+                    t0 = f32(f32(c * At[i][k]) + f32(s * At[j][k]))
+                    t1 = f32(f32(-s * At[i][k]) + f32(c * At[j][k]))
+                    At[i][k], At[j][k] = t0, t1
+                    na = f64(na + f64(t0) * f64(t0))
+                    nb = f64(nb + f64(t1) * f64(t1))
+                    qa.append(f32(t0 * t0))
+                    qb.append(f32(t1 * t1))
+                if rules.givensx == "float":
+                    na = f64(f32(f32(f32(qa[0] + qa[1]) + qa[2]) + qa[3]))
+                    nb = f64(f32(f32(f32(qb[0] + qb[1]) + qb[2]) + qb[3]))
+                W[i], W[j] = na, nb
+                changed = True
+                for k in range(4):
+                    t0 = f32(f32(c * Vt[i][k]) + f32(s * Vt[j][k]))
+                    t1 = f32(f32(-s * Vt[i][k]) + f32(c * Vt[j][k]))
+                    Vt[i][k], Vt[j][k] = t0, t1
+        if not changed:
+            break
+    if sweeps >= 5:
+        _hit(hits, "svd_5_sweeps")
+    W = [math.sqrt(_sumsq(r)) for r in At]
+    for i in range(3):
+        j = i
+        for k in range(i + 1, 4):
+            if W[j] < W[k]:
+                j = k
+        if j != i:
+            _hit(hits, "svd_sort_swap")
+            W[i], W[j] = W[j], W[i]
+            At[i], At[j] = At[j], At[i]
+            Vt[i], Vt[j] = Vt[j], Vt[i]
+    return Vt[3]
+
+
+def _sumprod(a, b):
+    """sum of a[k]*b[k] in double from 0 (gemm's double path; the SVD's sums)"""
+    s = f64(0)
+    for x, y in zip(a, b):
+        s = f64(s + f64(x) * f64(y))
+    return s
+
+
+def _sumsq(r):
+    s = f64(0)
+    for x in r:
+        s = f64(s + f64(x) * f64(x))
+    return s
+
+
+def _cv_hypot(a, b):
+    a, b = abs(f64(a)), abs(f64(b))
+    if a > b:
+        b = b / a
+        return f64(a * math.sqrt(1 + b * b))
+    if b > 0:
+        a = a / b
+        return f64(b * math.sqrt(1 + a * a))
+    return f64(0)
+
+
+def triangulate(kp1, kp2, P1, P2, sf, sigma2, nlevels, ratio_factor, rules=REFERENCE, hits=None):
+    """The body of the match loop (:282-423) and UpdateNormalAndDepth for one match: None, or (pos, normal, min_d, max_d)."""
+    R1, t1, Ow1 = _pose(P1)
+    R2, t2, Ow2 = _pose(P2)
+    xa = f32(f32(f32(kp1["x"]) - P1["cx"]) * P1["invfx"])
+    ya = f32(f32(f32(kp1["y"]) - P1["cy"]) * P1["invfy"])
+    xb = f32(f32(f32(kp2["x"]) - P2["cx"]) * P2["invfx"])
+    yb = f32(f32(f32(kp2["y"]) - P2["cy"]) * P2["invfy"])
+    one = f32(1)
+    ray1 = [gemm3(R1[0][i], R1[1][i], R1[2][i], xa, ya, one, rules) for i in range(3)]       # Rwc1*xn1
+    ray2 = [gemm3(R2[0][i], R2[1][i], R2[2][i], xb, yb, one, rules) for i in range(3)]
+    with np.errstate(all="ignore"):
+        cos_par = f32(dotd(ray1, ray2, rules) / (normd(ray1, rules) * normd(ray2, rules)))
+    cos_stereo = f32(cos_par + one)
+    if rules.parallax == "inclusive":
+        ok = cos_par < cos_stereo and cos_par >= 0 and float(cos_par) <= 0.9998
+    else:
+        ok = cos_par < cos_stereo and cos_par > 0 and float(cos_par) < 0.9998
+    if not ok:
+        _hit(hits, "parallax_low" if float(cos_par) >= 0.9998 else "parallax_negative")
+        return None
+    _hit(hits, "parallax_passed")
+    if float(cos_par) > 0.99979:
+        _hit(hits, "parallax_near_limit")
+    T1 = np.asarray(P1["Tcw"], np.float32).reshape(3, 4)
+    T2 = np.asarray(P2["Tcw"], np.float32).reshape(3, 4)
+    A = []
+    for x, T, r in ((xa, T1, 0), (ya, T1, 1), (xb, T2, 0), (yb, T2, 1)):
+        if rules.a_rows == "float":
+            A.append([f32(f32(x * T[2][c]) - T[r][c]) for c in range(4)])
+        else:
+            A.append([f32(f64(f64(T[2][c]) * f64(x) + (-f64(T[r][c]))) + 0.0) for c in range(4)])
+    v = svd_v3(A, rules, hits)
+    if v[3] == 0:
+        _hit(hits, "w_zero")
+        return None
+    with np.errstate(all="ignore"):
+        if rules.divide == "divide":
+            X = [f32(v[i] / v[3]) for i in range(3)]
+        else:
+            sc = f32(1.0 / f64(v[3]))
+            X = [f32(f32(v[i] * sc) + f32(0)) for i in range(3)]
+
+    def cam(R, t, row):
+        return f32(dotd(R[row], X, rules) + f64(t[row]))
+    reject_depth = (lambda z: z <= 0) if rules.depth == "le" else (lambda z: z < 0)
+    z1 = cam(R1, t1, 2)
+    if z1 == 0:
+        _hit(hits, "z1_zero")
+    if reject_depth(z1):
+        _hit(hits, "z1_behind")
+        return None
+    z2 = cam(R2, t2, 2)
+    if z2 == 0:
+        _hit(hits, "z2_zero")
+    if reject_depth(z2):
+        _hit(hits, "z2_behind")
+        return None
+    o1, o2 = int(kp1["octave"]), int(kp2["octave"])
+    for tag, R, t, z, P, kp, o in (("1", R1, t1, z1, P1, kp1, o1), ("2", R2, t2, z2, P2, kp2, o2)):
+        x, y = cam(R, t, 0), cam(R, t, 1)
+        with np.errstate(all="ignore"):
+            invz = f32(1.0 / f64(z))
+            u = f32(f32(f32(P["fx"] * x) * invz) + P["cx"])
+            vv = f32(f32(f32(P["fy"] * y) * invz) + P["cy"])
+            ex, ey = f32(u - f32(kp["x"])), f32(vv - f32(kp["y"]))
+            err = f32(f32(ex * ex) + f32(ey * ey))
+        lim = 5.991 * float(f32(sigma2[o]))
+        if float(err) > 0.98 * lim:
+            _hit(hits, "chi2_%s_near" % tag)
+        if (float(err) >= lim) if rules.chi2 == "ge" else (float(err) > lim):
+            _hit(hits, "chi2_%s_rejected" % tag)
+            return None
+    n1 = [f32(X[i] - Ow1[i]) for i in range(3)]
+    n2 = [f32(X[i] - Ow2[i]) for i in range(3)]
+    d1d, d2d = normd(n1, rules), normd(n2, rules)
+    dist1, dist2 = f32(d1d), f32(d2d)
+    if dist1 == 0 or dist2 == 0:
+        _hit(hits, "dist_zero")
+        return None
+    with np.errstate(all="ignore"):
+        ratio_dist = f32(dist2 / dist1)
+        ratio_oct = f32(f32(sf[o1]) / f32(sf[o2]))
+        lo, hi = f32(ratio_dist * ratio_factor), f32(ratio_oct * ratio_factor)
+    if rules.scale == "inclusive":
+        bad_lo, bad_hi = lo <= ratio_oct, ratio_dist >= hi
+    else:
+        bad_lo, bad_hi = lo < ratio_oct, ratio_dist > hi
+    if lo == ratio_oct or ratio_dist == hi:
+        _hit(hits, "scale_equal")
+    if bad_lo or bad_hi:
+        _hit(hits, "scale_low" if bad_lo else "scale_high")
+        return None
+    # UpdateNormalAndDepth: normali/cv::norm(normali) as convertTo with the float scale, a float sum, /2 (scale 0.5f)
+    with np.errstate(all="ignore"):
+        s1, s2 = f32(1.0 / d1d), f32(1.0 / d2d)
+        normal = [f32(f32(f32(n1[i] * s1) + f32(n2[i] * s2)) * f32(0.5)) for i in range(3)]
+        max_d = f32(dist1 * f32(sf[o1]))
+        min_d = f32(max_d / f32(sf[nlevels - 1]))
+    _hit(hits, "triangulated")
+    return np.array(X, np.float32), np.array(normal, np.float32), min_d, max_d
+
+
+def create_new_map_points(KF1, neighbours, sf, sigma2, nlevels, scale_factor, rules=REFERENCE, hits=None, pair_hook=None):
+    """KF1 / neighbours[s]: dicts with k (keypoints), d (descriptors), fv, h (has_point, uint8), pose (KF_POSE_DTYPE); a
+    neighbour also has median (ComputeSceneMedianDepth(2)).  Returns (points, count, F12, epipole, has_point1_out) as
+    pgorb_create_new_map_points does; points = list of (slot, idx1, idx2, pos, normal, min_d, max_d) in creation order.
+    pair_hook(s, matches12, results) sees every pair's matches and per-match results (for the parallel restatement)."""
+    ratio_factor = f32(f32(1.5) * f32(scale_factor))
+    has1 = np.array(KF1["h"], np.uint8).copy()
+    points, count, Fs, eps = [], [], [], []
+    for s, K2 in enumerate(neighbours):
+        _, _, Ow1 = _pose(KF1["pose"])
+        _, _, Ow2 = _pose(K2["pose"])
+        baseline = f32(normd([f32(Ow2[i] - Ow1[i]) for i in range(3)], rules))
+        with np.errstate(all="ignore"):
+            ratio = f32(baseline / f32(K2["median"]))
+        F = compute_f12(KF1["pose"], K2["pose"], rules)
+        ep = epipole(KF1["pose"], K2["pose"], rules)
+        Fs.append(F)
+        eps.append(ep)
+        skip = float(ratio) <= 0.01 if rules.baseline == "le" else float(ratio) < 0.01
+        if f32(ratio) == f32(0.01):
+            _hit(hits, "baseline_equal")
+        if skip:
+            _hit(hits, "baseline_skipped")
+            count.append(-1)
+            continue
+        mask1 = has1 if rules.success == "first" else np.array(KF1["h"], np.uint8)
+        _, m12 = TR.search_for_triangulation(KF1["k"], KF1["d"], mask1, KF1["fv"], K2["k"], K2["d"], K2["h"], K2["fv"], F, ep,
+                                             sf, sigma2, False, TR.REFERENCE, None)
+        results = {}
+        made = 0
+        for idx1 in range(len(m12)):
+            idx2 = int(m12[idx1])
+            if idx2 < 0:
+                continue
+            r = triangulate(KF1["k"][idx1], K2["k"][idx2], KF1["pose"], K2["pose"], sf, sigma2, nlevels, ratio_factor, rules, hits)
+            results[idx1] = r
+            if r is None:
+                continue
+            if has1[idx1]:
+                _hit(hits, "later_success_replaces")
+                points = [q for q in points if q[1] != idx1]
+            points.append((s, idx1, idx2) + tuple(r))
+            has1[idx1] = 1
+            made += 1
+        if pair_hook is not None:
+            pair_hook(s, m12, results)
+        taken = [q[2] for q in points if q[0] == s]
+        if len(set(taken)) < len(taken):
+            _hit(hits, "kf2_shared")
+        count.append(made)
+    if rules.success == "last":
+        count = [c if c < 0 else sum(1 for q in points if q[0] == s) for s, c in enumerate(count)]
+    return points, count, Fs, eps, has1

@@ -9,6 +9,8 @@ next to each, the oracle's CPU time for the same work (1 thread, a few frames, s
   bow          ORBVocabulary::transform (TemplatedVocabulary.h:1126-1259) on an ORBvoc-sized tree (k = 10, L = 6)
   triangulate  ORBmatcher::SearchForTriangulation (ORBmatcher.cc:659-825): one host pair, and key frames of the batch against
                20 neighbours each, as LocalMapping::CreateNewMapPoints calls it (LocalMapping.cc:212-270); no CPU column
+  map points   LocalMapping::CreateNewMapPoints (LocalMapping.cc:209-454, monocular) for the same key frames and neighbours in one
+               batched call, one key frame through the host API, and the 20 host matcher calls per key frame it replaces
 
 usage: python tools/next_tier_bench.py [--batch 128] [--out profiles/r02_next_tier.txt]"""
 import argparse, ctypes as C, os, sys, time
@@ -212,6 +214,38 @@ if ntri:
                  p(tA), p(tB), ntri, p(tF), p(tE), p(tH1), p(tH2), 1, p(tM), p(tN), s)))
     batch_rows.append(("SearchForTriangulation: %d key frames x 20 neighbours = %d pairs -> %d" % (ntri // 20, ntri, int(tN.float().mean())),
                        t_tr, float("nan"), ntri))
+    # CreateNewMapPoints (LocalMapping.cc:209-454) for the same key frames and neighbours in one call: the ride is a sideways camera over
+    # a fronto-parallel plane at depth 1 (frame k at (2k/f, k/f, 0), R = I), so matches triangulate; 30 % of the keypoints have a point
+    kfs = list(range(20, B, 5))
+    poses = np.zeros(B, pg.KF_POSE_DTYPE)
+    for k in range(B):
+        poses[k] = pg.kf_pose(np.hstack([np.eye(3), [[-2.0 * k / 500.0], [-1.0 * k / 500.0], [0.0]]]), (2.0 * k / 500.0, 1.0 * k / 500.0, 0.0),
+                              500.0, 500.0, w / 2.0, h / 2.0)
+    cP = torch.from_numpy(poses.view(np.uint8).copy()).cuda()
+    cH = torch.from_numpy((rng.uniform(size=(B, cap)) < 0.3).astype(np.uint8)).cuda()
+    cK = torch.tensor(kfs, dtype=torch.int32, device="cuda")
+    cN = torch.tensor([[k - d for d in range(1, 21)] for k in kfs], dtype=torch.int32, device="cuda")
+    cNN = torch.full((len(kfs),), 20, dtype=torch.int32, device="cuda"); cMD = torch.ones((len(kfs), 20), dtype=torch.float32, device="cuda")
+    cPts = torch.empty((len(kfs), cap * pg.NEW_MAP_POINT_DTYPE.itemsize), dtype=torch.uint8, device="cuda")
+    cNP = torch.empty(len(kfs), dtype=torch.int32, device="cuda"); cC = torch.empty((len(kfs), 20), dtype=torch.int32, device="cuda")
+    cHo = torch.empty((len(kfs), cap), dtype=torch.uint8, device="cuda")
+    t_cnm = timed(lambda: ext._check(ext._L.pgorb_create_new_map_points_batch_device(ext._h, p(kps), p(desc), p(n), cap, p(fvn), p(fvs), p(fvf), p(nfvd),
+                  p(cP), p(cH), p(cK), len(kfs), p(cN), p(cNN), 20, p(cMD), p(cPts), p(cNP), p(cC), None, None, p(cHo), s)))
+    batch_rows.append(("CreateNewMapPoints: %d key frames x 20 neighbours = %d pairs -> %d points / key frame" % (len(kfs), 20 * len(kfs), int(cNP.float().mean())),
+                       t_cnm, float("nan"), 20 * len(kfs)))
+    # ... one key frame through the host API, and the matcher-only host path it replaces: 20 single SearchForTriangulation calls
+    kf0 = kfs[-1]
+    KFs = {k: pg.Frame(ext, ride[k]) for k in [kf0] + [kf0 - d for d in range(1, 21)]}
+    fvh = {k: voc.transform(F.mDescriptors, 4)[1] for k, F in KFs.items()}
+    hh = {k: (rng.uniform(size=F.N) < 0.3).astype(np.uint8) for k, F in KFs.items()}
+    nb = [kf0 - d for d in range(1, 21)]
+    g_cnm = wall(lambda: pg.LocalMapping.CreateNewMapPoints(KFs[kf0], [KFs[k] for k in nb], fvh[kf0], [fvh[k] for k in nb], poses[kf0],
+                                                            [poses[k] for k in nb], np.ones(20, np.float32), hh[kf0], [hh[k] for k in nb]))
+    m = pg.ORBmatcher(0.6, False)
+    geoh = {k: sideways_geometry(kf0 - k) for k in nb}
+    g_loop = wall(lambda: [m.SearchForTriangulation(KFs[kf0], KFs[k], *geoh[k], fvh[kf0], fvh[k], hh[kf0], hh[k]) for k in nb])
+    host_rows.append(("CreateNewMapPoints(KF, 20 neighbours), one key frame", g_cnm, float("nan")))
+    host_rows.append(("20 x SearchForTriangulation, one key frame (matcher only; no triangulation)", g_loop, float("nan")))
 
 lines = ["# python tools/next_tier_bench.py --batch %d --features %d   (MI355X; ms per %d-frame 1080p batch; CPU = oracle, 1 thread, one frame or pair scaled to the batch)" % (B, nf, B),
          "# extraction alone (K1-K6): %.3f ms" % t_plain,

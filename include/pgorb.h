@@ -450,6 +450,77 @@ int  pgorb_create_new_map_points_batch_device(pgorb_ctx* ctx,
         pgorb_new_map_point* d_points, int32_t* d_npoints, int32_t* d_count, float* d_F12, float* d_epipole,
         uint8_t* d_has_point1_out, void* hip_stream);
 
+/* ---- Fusion of duplicate map points of the local-mapping thread -------------------------------------------------------
+ *   pgorb_fuse   ORBmatcher::Fuse(KeyFrame* pKF, const vector<MapPoint*>& vpMapPoints, float th) (src/ORBmatcher.cc:827-979),
+ *       monocular (mvuRight < 0), with KeyFrame::GetFeaturesInArea / IsInImage (src/KeyFrame.cc:672-716) and what Fuse reads
+ *       and changes of a MapPoint: Observations() (MapPoint.cc:119-130), Replace (:196-232), IsInKeyFrame and the distance
+ *       getters (:402-417 and :390-400).  Call sites: LocalMapping::SearchInNeighbors fuses the new key frame's points into
+ *       every target (src/LocalMapping.cc:491) and the targets' points back into the new key frame (:516).
+ *   The map points Fuse reads live in one TABLE shared by the queries and the key frame's slots: per point its pose fields
+ *   (pgorb_map_point: the plain mWorldPos, mNormalVector, mfMinDistance, mfMaxDistance, not the *Invariance() getters), its
+ *   32-byte descriptor, a bad flag and its observations as CSR: obs_kf[obs_start[i] .. obs_start[i + 1]) = the KeyFrame::mnId
+ *   of every key frame observing point i, ascending and without repeats (monocular: Observations() is their number).  The key
+ *   frame is its undistorted keypoints (mvKeysUn), descriptors, pose and camera, its mnId kf_id, and its slots:
+ *   kf_point[i] = the table index of GetMapPoint(i), or -1.  queries[q] = the table index of vpMapPoints[q], or -1 for NULL.
+ *   The bounds are the Frame's (the grid is built from them, Frame.cc:216-217); the key frame keeps them as int
+ *   (KeyFrame.h:195-198), and IsInImage (x >= minX && x < maxX, strict on the max side) and the search window read those.
+ *   Exact decomposition.  Given distinct non-NULL queries and consistent slots (a live point in slot i
+ *   lists kf_id, and no live point holds two slots): (1) what a query matches depends only on its own state and the key frame's,
+ *   and an earlier query changes another point's state only as the loser or survivor of a Replace -- the loser is the query or
+ *   the slot's occupant, the survivor's new descriptor is read by no later query (occupants are in pKF and so skipped) -- so
+ *   every query's (bestIdx, bestDist) comes from the state on entry, all at once; (2) a query with bestDist <= TH_LOW (50)
+ *   touches only slot bestIdx, so each slot's chain of queries is walked on its own, in query order.  Per query, action[q]:
+ *     PGORB_FUSE_SKIPPED            NULL, bad, already in pKF, or a test before the descriptor loop failed (no candidate);
+ *     PGORB_FUSE_NO_MATCH           candidates, but no distance <= 50 among those that pass the octave and chi-square tests;
+ *     PGORB_FUSE_ADDED              empty slot: pMP->AddObservation(pKF, bestIdx); pKF->AddMapPoint(pMP, bestIdx);
+ *     PGORB_FUSE_MERGED_INTO_KF_POINT   occupant.Observations() > query's: pMP->Replace(pMPinKF), the query becomes bad;
+ *     PGORB_FUSE_REPLACED_KF_POINT      otherwise (ties included): pMPinKF->Replace(pMP), the query takes the slot;
+ *     PGORB_FUSE_KF_POINT_BAD       the occupant is bad: nothing changes, but the query counts toward nFused.
+ *   After a Replace the survivor observes the UNION of both key-frame sets; a chain's counts follow those sets.
+ *   best_idx / best_dist (may be NULL) = -1 / -1 for a skipped query, -1 / 256 when no candidate passed; kf_point_out (may be
+ *   NULL) = the slots afterwards.  Returns nFused or a PGORB_E_* code.  The caller replays the actions in query order against
+ *   its own map: Replace, AddObservation / AddMapPoint, and what stays on the host -- ComputeDistinctiveDescriptors,
+ *   IncreaseFound / IncreaseVisible, Map::EraseMapPoint.  PGORB_E_ARG: an index out of range, an observation list unsorted or
+ *   with repeats, a repeated non-NULL query, a live (not bad) occupant that does not list kf_id or holds two slots, th <= 0.  The search
+ *   level comes from MapPoint::PredictScale under pgorb_log_f with the context's mfLogScaleFactor; octaves lie in [0, levels). */
+#define PGORB_FUSE_SKIPPED 0
+#define PGORB_FUSE_NO_MATCH 1
+#define PGORB_FUSE_ADDED 2
+#define PGORB_FUSE_MERGED_INTO_KF_POINT 3
+#define PGORB_FUSE_REPLACED_KF_POINT 4
+#define PGORB_FUSE_KF_POINT_BAD 5
+typedef struct pgorb_map_point {
+    float pos[3];            /* mWorldPos */
+    float normal[3];         /* mNormalVector */
+    float min_distance, max_distance;   /* mfMinDistance, mfMaxDistance */
+} pgorb_map_point;
+int  pgorb_fuse(pgorb_ctx* ctx,
+        const pgorb_keypoint* kps, const uint8_t* desc, int n, const pgorb_kf_pose* pose, uint64_t kf_id,
+        float min_x, float max_x, float min_y, float max_y, const int32_t* kf_point /*[n] or NULL = all empty*/,
+        int npoints, const pgorb_map_point* points, const uint8_t* point_desc /*[npoints][32]*/, const uint8_t* point_bad /*[npoints] or NULL*/,
+        const int32_t* obs_start /*[npoints + 1]*/, const uint64_t* obs_kf, int nq, const int32_t* queries /*[nq]*/, float th,
+        int32_t* action /*[nq]*/, int32_t* best_idx /*[nq] or NULL*/, int32_t* best_dist /*[nq] or NULL*/,
+        int32_t* kf_point_out /*[n] or NULL*/);
+/* Batched, resident: problem p fuses its queries d_queries[p][0 .. d_nq[p]) into key frame d_kf[p] of one batch in the layout of
+ * pgorb_extract_batch_device, grids as pgorb_frame_grid_batch_device writes them (with the same bounds).  d_kf_id and d_pose
+ * are [nframes], d_kf_point [nframes][cap_per_frame] (NULL = every slot empty); the map-point table as above, on the device.
+ * Outputs: d_action, d_best_idx, d_best_dist [nprob][qcap] (the last two may be NULL; entries past d_nq[p] are not written),
+ * d_kf_point_out [nprob][cap_per_frame] (may be NULL), d_nfused [nprob].  This form does not check its inputs: indices out of
+ * range count as NULL / empty, but the observation lists must be what the single call accepts.  Each problem equals the
+ * reference called on the state it was given: the reference runs the targets of SearchInNeighbors one after another and each
+ * changes bad flags, observation sets and (through ComputeDistinctiveDescriptors) descriptors of the points it fuses, so
+ * problems that share a key frame or a map point are the caller's to order.  One lane per query matches (k_fuse_match), then
+ * one workgroup per problem walks the slots' chains (k_fuse_resolve). */
+int  pgorb_fuse_batch_device(pgorb_ctx* ctx,
+        const pgorb_keypoint* d_kps, const uint8_t* d_desc, const int32_t* d_n, int cap_per_frame,
+        const int32_t* d_grid_start, const int32_t* d_grid_idx, const int32_t* d_kf /*[nprob]*/, int nprob,
+        const uint64_t* d_kf_id, const pgorb_kf_pose* d_pose, float min_x, float max_x, float min_y, float max_y,
+        const int32_t* d_kf_point, int npoints, const pgorb_map_point* d_points, const uint8_t* d_point_desc,
+        const uint8_t* d_point_bad, const int32_t* d_obs_start, const uint64_t* d_obs_kf,
+        int qcap, const int32_t* d_nq, const int32_t* d_queries, float th,
+        int32_t* d_action, int32_t* d_best_idx, int32_t* d_best_dist, int32_t* d_kf_point_out, int32_t* d_nfused,
+        void* hip_stream);
+
 /* ---- ORB vocabulary (DBoW2 TemplatedVocabulary<FORB::TDescriptor, FORB>) -----------------
  *   pgorb_vocab_load_text     ORBVocabulary(text_file) -> TemplatedVocabulary::loadFromTextFile
  *                             thirdparty/orb-slam2/src/ORBVocabulary.cc:7-9,

@@ -211,28 +211,6 @@ __device__ __forceinline__ uint32_t pg_list_reserve(const PgLists& L, int p, int
     return (uint32_t)base;
 }
 
-// GetFeaturesInArea's cell window (Frame.cc:336-350); false = the reference returns an empty vector
-__device__ __forceinline__ bool sfi_window(float x, float y, float r, float minX, float minY, float invW, float invH,
-                                           int& cx0, int& cx1, int& cy0, int& cy1)
-{
-    cx0 = max(0, (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(x, minX), r), invW)));
-    if (cx0 >= GRID_COLS) return false;
-    cx1 = min(GRID_COLS - 1, (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(x, minX), r), invW)));
-    if (cx1 < 0) return false;
-    cy0 = max(0, (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(y, minY), r), invH)));
-    if (cy0 >= GRID_ROWS) return false;
-    cy1 = min(GRID_ROWS - 1, (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(y, minY), r), invH)));
-    if (cy1 < 0) return false;
-    return cx1 >= cx0 && cy1 >= cy0;
-}
-
-__device__ __forceinline__ int sfi_distance(const uint4 q0, const uint4 q1, const uint8_t* d)
-{
-    const uint4 d0 = reinterpret_cast<const uint4*>(d)[0], d1 = reinterpret_cast<const uint4*>(d)[1];
-    return __popc(q0.x ^ d0.x) + __popc(q0.y ^ d0.y) + __popc(q0.z ^ d0.z) + __popc(q0.w ^ d0.w) +
-           __popc(q1.x ^ d1.x) + __popc(q1.y ^ d1.y) + __popc(q1.z ^ d1.z) + __popc(q1.w ^ d1.w);
-}
-
 // Phase 1: candidate lists.  Workgroup = 4 waves = 4 consecutive F1 keypoints of pair blockIdx.y.
 __global__ __launch_bounds__(256) void k_sfi_candidates(
     const pgorb_keypoint* __restrict__ kps, const uint8_t* __restrict__ desc, const int32_t* __restrict__ nper,
@@ -1490,20 +1468,6 @@ struct PgCnmBatch {
 struct PgCnmPairs { int32_t* state; int32_t* kf1; int32_t* kf2; float* F12; float* epi; uint8_t* has1; uint8_t* has2; };
 struct PgCnmRec { float pos[3], normal[3], minD, maxD; };
 
-__device__ __forceinline__ float cnm_f(double x) { return __double2float_rn(x); }
-// the small-matrix gemm path: t = a0*b0 + a1*b1 + a2*b2 in float, then (float)(t*1.0 + c*beta) in double
-__device__ __forceinline__ float cnm_dot3f(float a0, float a1, float a2, float b0, float b1, float b2)
-{
-    return __fadd_rn(__fadd_rn(__fmul_rn(a0, b0), __fmul_rn(a1, b1)), __fmul_rn(a2, b2));
-}
-// Mat::dot / the squared L2 norm of CV_32F data: double sums from 0
-__device__ __forceinline__ double cnm_dotd(float a0, float a1, float a2, float b0, float b1, float b2)
-{
-    double s = __dadd_rn(0.0, __dmul_rn((double)a0, (double)b0));
-    s = __dadd_rn(s, __dmul_rn((double)a1, (double)b1));
-    return __dadd_rn(s, __dmul_rn((double)a2, (double)b2));
-}
-__device__ __forceinline__ double cnm_normd(float a0, float a1, float a2) { return __dsqrt_rn(cnm_dotd(a0, a1, a2, a0, a1, a2)); }
 // OpenCV's hypot template (lapack.cpp) in double
 __device__ __forceinline__ double cnm_hypot(double a, double b)
 {

@@ -2,11 +2,12 @@
 // C ABI (include/pgorb.h).  Same names, argument meaning and error behaviour as
 //   thirdparty/orb-slam2/include/ORBextractor.h:44-110   (operator(), Get* accessors)
 //   thirdparty/orb-slam2/include/ORBmatcher.h:40-53      (DescriptorDistance, SearchForInitialization,
-//                                                          SearchForTriangulation)
+//                                                          SearchForTriangulation, Fuse)
 // but OpenCV-free: images are raw 8-bit planes, keypoints are pgorb_keypoint (the cv::KeyPoint
 // layout), descriptors are N x 32 bytes.  INTEGRATION.md shows the cv::Mat-typed variant a
 // pilotguru maintainer drops into Frame::ExtractORB.
 #pragma once
+#include <algorithm>
 #include <stdexcept>
 #include <string>
 #include <utility>
@@ -103,6 +104,55 @@ inline void checkKeyFrame(const Frame& K, const FeatureVector& fv, const std::ve
 }
 }  // namespace detail
 
+// The map points one Fuse call reads (include/pgorb.h): pose fields, 32-byte descriptors, bad flags (empty = none bad) and the
+// observations as CSR, obsKf[obsStart[i] .. obsStart[i + 1]) = the KeyFrame::mnId of every key frame observing point i, ascending.
+struct MapPointTable {
+    std::vector<pgorb_map_point> points;
+    std::vector<uint8_t> descriptors;
+    std::vector<uint8_t> bad;
+    std::vector<int32_t> obsStart{0};
+    std::vector<uint64_t> obsKf;
+    int size() const { return (int)points.size(); }
+};
+
+namespace detail {
+// everything pgorb_fuse rejects, and the lengths it reads through its pointers
+inline void checkFuse(const Frame& KF, uint64_t kfId, const std::vector<int32_t>& kfPoint, const MapPointTable& T,
+                      const std::vector<int32_t>& queries, float th)
+{
+    const char* fn = "Fuse";
+    checkDescriptors(KF, fn);
+    const int n = T.size();
+    if (!(th > 0.0f)) throw std::invalid_argument("Fuse: th must be positive");
+    if (T.descriptors.size() != (size_t)n * 32) throw std::invalid_argument("Fuse: point descriptors are not n x 32 bytes");
+    if (!T.bad.empty() && T.bad.size() != (size_t)n) throw std::invalid_argument("Fuse: bad flags are neither empty nor n entries long");
+    if (T.obsStart.size() != (size_t)n + 1 || T.obsStart[0] != 0 || T.obsKf.size() < (size_t)std::max(T.obsStart.back(), 0))
+        throw std::invalid_argument("Fuse: observation arrays of inconsistent lengths");
+    for (int i = 0; i < n; i++) {
+        if (T.obsStart[i + 1] < T.obsStart[i]) throw std::invalid_argument("Fuse: obsStart decreases");
+        for (int k = T.obsStart[i] + 1; k < T.obsStart[i + 1]; k++)
+            if (!(T.obsKf[k - 1] < T.obsKf[k])) throw std::invalid_argument("Fuse: an observation list is unsorted or repeats a key frame");
+    }
+    if (!kfPoint.empty() && kfPoint.size() != (size_t)KF.N()) throw std::invalid_argument("Fuse: kfPoint is neither empty nor N entries long");
+    std::vector<uint8_t> seen(n, 0);
+    for (int32_t o : kfPoint) {
+        if (o < -1 || o >= n) throw std::invalid_argument("Fuse: a slot names a point outside the table");
+        if (o < 0 || (!T.bad.empty() && T.bad[o])) continue;           // a bad occupant only makes its queries KF_POINT_BAD
+        if (seen[o]) throw std::invalid_argument("Fuse: a point holds two slots of the key frame");
+        seen[o] = 1;
+        if (!std::binary_search(T.obsKf.begin() + T.obsStart[o], T.obsKf.begin() + T.obsStart[o + 1], kfId))
+            throw std::invalid_argument("Fuse: the point in a slot does not list the key frame");
+    }
+    std::fill(seen.begin(), seen.end(), 0);
+    for (int32_t q : queries) {
+        if (q < -1 || q >= n) throw std::invalid_argument("Fuse: a query names a point outside the table");
+        if (q < 0) continue;
+        if (seen[q]) throw std::invalid_argument("Fuse: a map point is queried twice");
+        seen[q] = 1;
+    }
+}
+}  // namespace detail
+
 class ORBmatcher {
  public:
     static const int TH_LOW = 50, TH_HIGH = 100, HISTO_LENGTH = 30;     // ORBmatcher.cc:38-40
@@ -150,6 +200,30 @@ class ORBmatcher {
         vMatchedPairs.reserve(rc);
         for (int i = 0; i < KF1.N(); i++)                              // :814-822
             if (m12[i] >= 0) vMatchedPairs.push_back(std::make_pair((size_t)i, (size_t)m12[i]));
+        return rc;
+    }
+
+    // Fuse(pKF, vpMapPoints, th) (ORBmatcher.cc:827-979), monocular: KF's undistorted keypoints, descriptors and Frame bounds, its
+    // pose and mnId; kfPoint[i] = the table index of GetMapPoint(i) or -1 (empty = all empty); queries[q] = the table index of
+    // vpMapPoints[q] or -1 for NULL.  action[q] (PGORB_FUSE_*) says what the reference did with query q; the caller replays the
+    // actions in query order (include/pgorb.h).  Returns nFused.
+    int Fuse(const Frame& KF, const pgorb_kf_pose& pose, uint64_t kfId, const std::vector<int32_t>& kfPoint, const MapPointTable& table,
+             const std::vector<int32_t>& queries, std::vector<int32_t>& action, float th = 3.0f, std::vector<int32_t>* bestIdx = nullptr,
+             std::vector<int32_t>* bestDist = nullptr, std::vector<int32_t>* kfPointOut = nullptr)
+    {
+        detail::checkFuse(KF, kfId, kfPoint, table, queries, th);
+        const int nq = (int)queries.size(), N = KF.N();
+        action.assign(nq > 0 ? nq : 1, PGORB_FUSE_SKIPPED);
+        std::vector<int32_t> bi(nq > 0 ? nq : 1, -1), bd(nq > 0 ? nq : 1, -1), out(N > 0 ? N : 1, -1);
+        const int rc = pgorb_fuse(ctx_, KF.mvKeysUndistorted.data(), KF.mDescriptors.data(), N, &pose, kfId, KF.mnMinX, KF.mnMaxX,
+                                  KF.mnMinY, KF.mnMaxY, kfPoint.empty() ? nullptr : kfPoint.data(), table.size(), table.points.data(),
+                                  table.descriptors.data(), table.bad.empty() ? nullptr : table.bad.data(), table.obsStart.data(),
+                                  table.obsKf.data(), nq, queries.data(), th, action.data(), bi.data(), bd.data(), out.data());
+        if (rc < 0) throw std::runtime_error(pgorb_last_error(ctx_));
+        action.resize(nq);
+        if (bestIdx) bestIdx->assign(bi.begin(), bi.begin() + nq);
+        if (bestDist) bestDist->assign(bd.begin(), bd.begin() + nq);
+        if (kfPointOut) kfPointOut->assign(out.begin(), out.begin() + N);
         return rc;
     }
 

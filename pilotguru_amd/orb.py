@@ -478,6 +478,48 @@ class ORBmatcher:
         vbPrevMatched[...] = prev
         return nm, m12[:F1.N].copy()
 
+    def Fuse(self, KF, pose, kf_id, kf_point, table, queries, th=3.0, bounds=None):
+        """ORBmatcher::Fuse(pKF, vpMapPoints, th) (src/ORBmatcher.cc:827-979), monocular.  KF: a Frame-like object (ext, N,
+        mvKeysUndistorted, mDescriptors; bounds = the Frame's (min_x, max_x, min_y, max_y), default KF.bounds); pose: a
+        KF_POSE_DTYPE record; kf_id: KeyFrame::mnId; kf_point[i]: the table index of GetMapPoint(i) or -1 (None = all empty);
+        table: a MapPointTable; queries[q]: the table index of vpMapPoints[q] or -1 for NULL.  Returns (nfused, action,
+        best_idx, best_dist, kf_point_out) with action[q] one of FUSE_* (include/pgorb.h states how to replay them)."""
+        ext = KF.ext
+        kp, desc = _frame(KF, "KF")
+        bounds = KF.bounds if bounds is None else bounds
+        if len(bounds) != 4:
+            raise ValueError("Fuse: bounds must be (min_x, max_x, min_y, max_y)")
+        if not float(th) > 0:
+            raise ValueError("Fuse: th must be positive")
+        slots = np.full(max(KF.N, 1), -1, np.int32) if kf_point is None else _arr(kf_point, np.int32, KF.N, "kf_point")
+        q = np.ascontiguousarray(queries, np.int32).reshape(-1)
+        nq = len(q)
+        table.check_indices(q, "queries")
+        live = q[q >= 0]
+        if len(np.unique(live)) != len(live):
+            raise ValueError("Fuse: a map point is queried twice")
+        occ = slots[:KF.N]
+        table.check_indices(occ, "kf_point")
+        occ = occ[occ >= 0]
+        occ = occ[table.bad[occ] == 0]                     # a bad occupant only makes its queries FUSE_KF_POINT_BAD
+        if len(np.unique(occ)) != len(occ):
+            raise ValueError("Fuse: a point holds two slots of the key frame")
+        st = table.obs_start
+        owner = np.repeat(np.arange(table.n), np.diff(st))              # the point each observation belongs to
+        listing = owner[table.obs_kf[:int(st[-1])] == np.uint64(kf_id)]
+        if not np.all(np.isin(occ, listing)):
+            raise ValueError("Fuse: the point in a slot does not list key frame %d" % int(kf_id))
+        P = np.ascontiguousarray(pose, KF_POSE_DTYPE).reshape(())
+        action = np.zeros(max(nq, 1), np.int32)
+        bi = np.full(max(nq, 1), -1, np.int32)
+        bd = np.full(max(nq, 1), -1, np.int32)
+        out = np.full(max(KF.N, 1), -1, np.int32)
+        t = table
+        nf = ext._check(ext._L.pgorb_fuse(ext._h, _p(kp), _p(desc), KF.N, _p(P), int(kf_id), *[float(b) for b in bounds], _p(slots),
+                                          t.n, _p(t.points), _p(t.descriptors), _p(t.bad), _p(t.obs_start), _p(t.obs_kf), nq,
+                                          _p(q if nq else action), float(th), _p(action), _p(bi), _p(bd), _p(out)))
+        return nf, action[:nq].copy(), bi[:nq].copy(), bd[:nq].copy(), out[:KF.N].copy()
+
     @staticmethod
     def DescriptorDistance(a, b):
         a = np.frombuffer(bytes(a), np.uint8) if isinstance(a, (bytes, bytearray)) else a
@@ -495,6 +537,40 @@ NEW_MAP_POINT_DTYPE = np.dtype([("neighbour", "<i4"), ("idx1", "<i4"), ("idx2", 
                                 ("min_distance", "<f4"), ("max_distance", "<f4")])
 CNM_SKIPPED = -1                 # count[s] of a neighbour the baseline test skipped
 CNM_MAX_NEIGHBOURS = 64
+
+
+# pgorb_map_point: what ORBmatcher::Fuse reads of a MapPoint's pose fields (the plain mfMin/MaxDistance, not the getters)
+MAP_POINT_DTYPE = np.dtype([("pos", "<f4", (3,)), ("normal", "<f4", (3,)), ("min_distance", "<f4"), ("max_distance", "<f4")])
+# action codes of ORBmatcher.Fuse (include/pgorb.h)
+FUSE_SKIPPED, FUSE_NO_MATCH, FUSE_ADDED, FUSE_MERGED_INTO_KF_POINT, FUSE_REPLACED_KF_POINT, FUSE_KF_POINT_BAD = range(6)
+
+
+class MapPointTable:
+    """The map points one Fuse call reads, shared by its queries and the key frame's slots: points (MAP_POINT_DTYPE),
+    descriptors [n, 32], bad flags (None = none bad) and observations as CSR: obs_kf[obs_start[i]:obs_start[i + 1]] = the
+    KeyFrame::mnId of every key frame observing point i, ascending and without repeats."""
+
+    def __init__(self, points, descriptors, bad, obs_start, obs_kf):
+        self.points = np.ascontiguousarray(points, MAP_POINT_DTYPE).reshape(-1)
+        n = self.n = len(self.points)
+        self.descriptors = _arr(descriptors, np.uint8, n, "point descriptors", 32)
+        self.bad = _mask(bad, n, "point bad")
+        self.obs_start = _arr(obs_start, np.int32, n + 1, "obs_start")
+        self.obs_kf = np.ascontiguousarray(obs_kf, np.uint64).reshape(-1)
+        st = self.obs_start
+        if st[0] != 0 or np.any(np.diff(st) < 0) or len(self.obs_kf) < int(st[-1]):
+            raise ValueError("MapPointTable: obs_start must rise from 0 to at most len(obs_kf)")
+        k = self.obs_kf[:int(st[-1])]
+        inner = np.ones(len(k), bool)
+        inner[st[:-1][st[:-1] < len(k)]] = False           # the first entry of each list has no predecessor in it
+        if len(k) > 1 and np.any(inner[1:] & (k[1:] <= k[:-1])):
+            raise ValueError("MapPointTable: an observation list is unsorted or repeats a key frame")
+        if len(self.obs_kf) == 0:
+            self.obs_kf = np.zeros(1, np.uint64)
+
+    def check_indices(self, idx, name):
+        if len(idx) and (int(np.min(idx)) < -1 or int(np.max(idx)) >= self.n):
+            raise ValueError("Fuse: %s names a point outside the table (%d points)" % (name, self.n))
 
 
 def kf_pose(Tcw, Ow, fx, fy, cx, cy, invfx=None, invfy=None):

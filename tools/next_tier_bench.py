@@ -11,6 +11,9 @@ next to each, the oracle's CPU time for the same work (1 thread, a few frames, s
                20 neighbours each, as LocalMapping::CreateNewMapPoints calls it (LocalMapping.cc:212-270); no CPU column
   map points   LocalMapping::CreateNewMapPoints (LocalMapping.cc:209-454, monocular) for the same key frames and neighbours in one
                batched call, one key frame through the host API, and the 20 host matcher calls per key frame it replaces
+  fuse         ORBmatcher::Fuse (ORBmatcher.cc:827-979) as SearchInNeighbors calls it: one call of 1500 points through the host API,
+               and the same key frames x 20 targets as independent problems of the batched form; the CPU column is the Python
+               reference's matching step (tests/fuse_reference.py) for one call
 
 usage: python tools/next_tier_bench.py [--batch 128] [--out profiles/r02_next_tier.txt]"""
 import argparse, ctypes as C, os, sys, time
@@ -246,6 +249,76 @@ if ntri:
     g_loop = wall(lambda: [m.SearchForTriangulation(KFs[kf0], KFs[k], *geoh[k], fvh[kf0], fvh[k], hh[kf0], hh[k]) for k in nb])
     host_rows.append(("CreateNewMapPoints(KF, 20 neighbours), one key frame", g_cnm, float("nan")))
     host_rows.append(("20 x SearchForTriangulation, one key frame (matcher only; no triangulation)", g_loop, float("nan")))
+
+    # Fuse (ORBmatcher.cc:827-979) as SearchInNeighbors calls it (LocalMapping.cc:491): the key frame's points fused into each target.
+    # Map points are keypoints lifted onto the ride's plane at depth 1 (frame k's camera at (2k/f, k/f, 0)); every frame's slots hold
+    # a point for 30 % of its keypoints; one shared table
+    fuse_ids = np.arange(B, dtype=np.uint64) + 1000
+    kh, dh = kps.cpu().numpy().view(pg.KEYPOINT_DTYPE).reshape(B, cap), desc.cpu().numpy().reshape(B, cap, 32)
+    sfh = ext.GetScaleFactors()
+
+    def lift(f, idx):
+        k = kh[f, idx]
+        pt = np.zeros(len(idx), pg.MAP_POINT_DTYPE)
+        pt["pos"][:, 0] = (k["x"] - w / 2.0) / 500.0 + 2.0 * f / 500.0
+        pt["pos"][:, 1] = (k["y"] - h / 2.0) / 500.0 + 1.0 * f / 500.0
+        pt["pos"][:, 2] = 1.0
+        pt["normal"][:, 2] = 1.0
+        pt["max_distance"] = np.float32(np.sqrt(1 + ((k["x"] - w / 2.0) / 500.0) ** 2 + ((k["y"] - h / 2.0) / 500.0) ** 2)) * sfh[k["octave"]]
+        pt["min_distance"] = pt["max_distance"] / sfh[7]
+        return pt, dh[f, idx]
+    tp, td, tobs, qidx, slot = [], [], [], {}, np.full((B, cap), -1, np.int32)
+    base = 0
+    for f in range(B):
+        idx = np.nonzero(rng.uniform(size=int(nh[f])) < 0.3)[0]
+        pt, dd = lift(f, idx)
+        tp.append(pt); td.append(dd); tobs.append(np.full(len(idx), fuse_ids[f]))
+        slot[f, idx] = base + np.arange(len(idx)); base += len(idx)
+    for k in kfs:                                                      # the key frame's new points (not yet in any slot)
+        idx = np.arange(min(int(nh[k]), 1500))
+        pt, dd = lift(k, idx)
+        tp.append(pt); td.append(dd); tobs.append(np.full(len(idx), fuse_ids[k]))
+        qidx[k] = base + idx; base += len(idx)
+    tP, tD, tO = np.concatenate(tp), np.concatenate(td), np.concatenate(tobs).astype(np.uint64)
+    tS = np.arange(len(tP) + 1, dtype=np.int32)
+    # one call through the host API: key frame kf0's 1500 points into its predecessor, with a table of the points that call reads
+    tgt = kf0 - 1
+    Ft = KFs[tgt]
+    own = slot[tgt, :Ft.N]
+    used = np.concatenate([own[own >= 0], qidx[kf0]])
+    remap = np.full(len(tP), -1, np.int32); remap[used] = np.arange(len(used))
+    small = pg.MapPointTable(tP[used], tD[used], None, np.arange(len(used) + 1, dtype=np.int32), tO[used])
+    s_own, s_q = np.where(own >= 0, remap[np.maximum(own, 0)], -1).astype(np.int32), remap[qidx[kf0]]
+    g_fuse = wall(lambda: pg.ORBmatcher().Fuse(Ft, poses[tgt], int(fuse_ids[tgt]), s_own, small, s_q, 3.0))
+    nfz = pg.ORBmatcher().Fuse(Ft, poses[tgt], int(fuse_ids[tgt]), s_own, small, s_q, 3.0)[0]
+    # the sequential reference's matching step on the same inputs (tests/fuse_reference.py, Python), for scale
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import fuse_reference as FR
+    import matcher_cases as MCs
+    inv_s2 = np.array([np.float32(1.0) / np.float32(x * x) for x in sfh], np.float32)
+    rkf = FR.KeyFrame(int(fuse_ids[tgt]), Ft.mvKeysUndistorted, Ft.mDescriptors, poses[tgt], (0.0, float(w), 0.0, float(h)), sfh, inv_s2,
+                      np.float32(FR._LOG_F()(sfh[1])), 8)
+    rmp = [FR.MapPoint(i, tP[i]["pos"], tP[i]["normal"], tP[i]["min_distance"], tP[i]["max_distance"], tD[i]) for i in qidx[kf0]]
+    t0 = time.perf_counter(); [FR.match(rkf, mp_) for mp_ in rmp]; c_fuse = (time.perf_counter() - t0) * 1e3
+    host_rows.append(("Fuse(KF, %d points, th 3) -> %d fused, one call" % (len(qidx[kf0]), nfz), g_fuse, c_fuse))
+    # batched: every key frame's points into its 20 predecessors, 22 x 20 independent problems in one call
+    probs = [(k, k - d) for k in kfs for d in range(1, 21)]
+    qcap = 1500
+    Q = np.full((len(probs), qcap), -1, np.int32); NQ = np.zeros(len(probs), np.int32)
+    for i, (k, t) in enumerate(probs):
+        Q[i, :len(qidx[k])] = qidx[k]; NQ[i] = len(qidx[k])
+    G = lambda x: torch.from_numpy(np.ascontiguousarray(x)).cuda()
+    zgs = torch.empty((B, 3073), dtype=torch.int32, device="cuda"); zgi = torch.empty((B, cap), dtype=torch.int32, device="cuda")
+    ext._check(ext._L.pgorb_frame_grid_batch_device(ext._h, p(kps), p(n), B, cap, 0.0, float(w), 0.0, float(h), p(zgs), p(zgi), s))
+    zK, zId, zSl = G(np.array([t for _, t in probs], np.int32)), G(fuse_ids.view(np.int64)), G(slot)
+    zP, zD, zS, zO, zQ, zN = G(tP.view(np.uint8)), G(tD), G(tS), G(tO.view(np.int64)), G(Q), G(NQ)
+    zA = torch.empty((len(probs), qcap), dtype=torch.int32, device="cuda"); zNF = torch.empty(len(probs), dtype=torch.int32, device="cuda")
+    zSo = torch.empty((len(probs), cap), dtype=torch.int32, device="cuda")
+    t_fz = timed(lambda: ext._check(ext._L.pgorb_fuse_batch_device(ext._h, p(kps), p(desc), p(n), cap, p(zgs), p(zgi), p(zK), len(probs), p(zId), p(cP),
+                 0.0, float(w), 0.0, float(h), p(zSl), len(tP), p(zP), p(zD), None, p(zS), p(zO), qcap, p(zN), p(zQ), 3.0, p(zA), None, None,
+                 p(zSo), p(zNF), s)))
+    batch_rows.append(("Fuse: %d key frames x 20 targets = %d problems x %d points -> %d fused" % (len(kfs), len(probs), qcap, int(zNF.float().mean())),
+                       t_fz, c_fuse, len(probs)))
 
 lines = ["# python tools/next_tier_bench.py --batch %d --features %d   (MI355X; ms per %d-frame 1080p batch; CPU = oracle, 1 thread, one frame or pair scaled to the batch)" % (B, nf, B),
          "# extraction alone (K1-K6): %.3f ms" % t_plain,

@@ -14,11 +14,8 @@
 //                    slot (atomicMin) is decided against the slot's current occupant and observation union, so the chains
 //                    advance in query order, as many rounds as the longest chain.
 // Every float operation follows the reference's cv::Mat arithmetic under the readings of DESIGN.md section 4.
-#include "pgorb_internal.h"
-#include <algorithm>
-#include <vector>
+#include "match_common.h"
 
-#define FUSE_TH_LOW 50
 #define FUSE_T 1024
 #define FUSE_MATCHED (-3)                  // k_fuse_match's provisional action of a query with bestDist <= TH_LOW
 
@@ -119,7 +116,7 @@ __global__ __launch_bounds__(256) void k_fuse_match(PgFuseBatch B, PgFuseScratch
                 }
             if (any) {
                 bestIdx = bi; bestDist = bd;
-                act = bd <= FUSE_TH_LOW ? FUSE_MATCHED : PGORB_FUSE_NO_MATCH;
+                act = bd <= TH_LOW ? FUSE_MATCHED : PGORB_FUSE_NO_MATCH;
             }
         }
     }

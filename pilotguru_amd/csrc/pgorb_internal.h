@@ -1,4 +1,5 @@
-// pgorb_internal.h -- shared host/device declarations of libpgorb (gfx950 only).
+// pgorb_internal.h -- shared host/device declarations of libpgorb (gfx950 only).  What only the Frame side, the guided matchers,
+// CreateNewMapPoints and Fuse share (frame.hip, window_match.hip, node_match.hip, mapping.hip, fuse.hip) is in match_common.h.
 //
 // Data layout in HBM (all per context, sized for max_batch frames):
 //   pyramid arena   level l, frame f : u8 plane, row pitch = align64(w_l), at
@@ -238,60 +239,6 @@ __host__ __device__ inline float pg_log_f(float xf)
 #undef PGL_M
 #undef PGL_A
 #undef PGL_D
-}
-// ---- device helpers of the guided matchers (frame.hip, fuse.hip) ----
-// GetFeaturesInArea's cell window (Frame.cc:336-350); false = the reference returns an empty vector
-__device__ __forceinline__ bool sfi_window(float x, float y, float r, float minX, float minY, float invW, float invH,
-                                           int& cx0, int& cx1, int& cy0, int& cy1)
-{
-    cx0 = max(0, (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(x, minX), r), invW)));
-    if (cx0 >= PGORB_GRID_COLS) return false;
-    cx1 = min(PGORB_GRID_COLS - 1, (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(x, minX), r), invW)));
-    if (cx1 < 0) return false;
-    cy0 = max(0, (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(y, minY), r), invH)));
-    if (cy0 >= PGORB_GRID_ROWS) return false;
-    cy1 = min(PGORB_GRID_ROWS - 1, (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(y, minY), r), invH)));
-    if (cy1 < 0) return false;
-    return cx1 >= cx0 && cy1 >= cy0;
-}
-
-__device__ __forceinline__ int sfi_distance(const uint4 q0, const uint4 q1, const uint8_t* d)
-{
-    const uint4 d0 = reinterpret_cast<const uint4*>(d)[0], d1 = reinterpret_cast<const uint4*>(d)[1];
-    return __popc(q0.x ^ d0.x) + __popc(q0.y ^ d0.y) + __popc(q0.z ^ d0.z) + __popc(q0.w ^ d0.w) +
-           __popc(q1.x ^ d1.x) + __popc(q1.y ^ d1.y) + __popc(q1.z ^ d1.z) + __popc(q1.w ^ d1.w);
-}
-
-// cv::Mat arithmetic of the key-frame pose steps (CreateNewMapPoints, Fuse)
-__device__ __forceinline__ float cnm_f(double x) { return __double2float_rn(x); }
-// the small-matrix gemm path: t = a0*b0 + a1*b1 + a2*b2 in float, then (float)(t*1.0 + c*beta) in double
-__device__ __forceinline__ float cnm_dot3f(float a0, float a1, float a2, float b0, float b1, float b2)
-{
-    return __fadd_rn(__fadd_rn(__fmul_rn(a0, b0), __fmul_rn(a1, b1)), __fmul_rn(a2, b2));
-}
-// Mat::dot / the squared L2 norm of CV_32F data: double sums from 0
-__device__ __forceinline__ double cnm_dotd(float a0, float a1, float a2, float b0, float b1, float b2)
-{
-    double s = __dadd_rn(0.0, __dmul_rn((double)a0, (double)b0));
-    s = __dadd_rn(s, __dmul_rn((double)a1, (double)b1));
-    return __dadd_rn(s, __dmul_rn((double)a2, (double)b2));
-}
-__device__ __forceinline__ double cnm_normd(float a0, float a1, float a2) { return __dsqrt_rn(cnm_dotd(a0, a1, a2, a0, a1, a2)); }
-// MapPoint::PredictScale(currentDist, Frame*) (MapPoint.cc:516-531); (int)ceil(...) of a NaN / out-of-range value is what
-// x86-64's cvttss2si returns, INT_MIN, i.e. level 0 after the clamp
-__host__ __device__ inline int pg_predict_scale(float maxDistance, float currentDist, float logScaleFactor, int nlevels)
-{
-#ifdef __HIP_DEVICE_COMPILE__
-    const float ratio = __fdiv_rn(maxDistance, currentDist);
-    const float q = ceilf(__fdiv_rn(pg_log_f(ratio), logScaleFactor));
-#else
-    const float ratio = maxDistance / currentDist;
-    const float q = ceilf(pg_log_f(ratio) / logScaleFactor);
-#endif
-    int nScale = (q != q || q >= 2147483648.0f || q < -2147483648.0f) ? (-2147483647 - 1) : (int)q;
-    if (nScale < 0) nScale = 0;
-    else if (nScale >= nlevels) nScale = nlevels - 1;
-    return nScale;
 }
 
 // kernel launchers (each in its own .hip file)

@@ -1,4 +1,4 @@
-"""Constructed key frames for CreateNewMapPoints (pilotguru_amd/csrc/frame.hip, k_cnm_*) and the runners that put them through
+"""Constructed key frames for CreateNewMapPoints (pilotguru_amd/csrc/mapping.hip, k_cnm_*) and the runners that put them through
 the plain reference (tests/mapping_reference.py), the single-call ABI and the batched device form.  A helper module (no tests):
 tests/test_create_new_map_points.py uses it.
 

@@ -1,7 +1,7 @@
 """A plain, sequential restatement of LocalMapping::CreateNewMapPoints (thirdparty/orb-slam2/src/LocalMapping.cc:209-454),
 monocular, with ComputeF12 (:538-555), the epipole of ORBmatcher::SearchForTriangulation (ORBmatcher.cc:665-672) and
 MapPoint::UpdateNormalAndDepth (MapPoint.cc:347-387).  It is written from that upstream text and the table of cv::Mat readings
-in DESIGN.md section 4; it does not use oracle/ and was not derived from the HIP kernels (pilotguru_amd/csrc/frame.hip).
+in DESIGN.md section 4; it does not use oracle/ and was not derived from the HIP kernels (pilotguru_amd/csrc/mapping.hip).
 
 The loop is the reference's: for every neighbour in order, the baseline test, F12, one call of
 tests/triangulation_reference.search_for_triangulation with KF1's mask as the earlier neighbours left it, then the triangulation

@@ -1,4 +1,4 @@
-"""LocalMapping::CreateNewMapPoints on the GPU (pilotguru_amd/csrc/frame.hip, k_cnm_*; include/pgorb.h) against the plain
+"""LocalMapping::CreateNewMapPoints on the GPU (pilotguru_amd/csrc/mapping.hip, k_cnm_*; include/pgorb.h) against the plain
 sequential reference (tests/mapping_reference.py) on constructed scenes (tests/mapping_cases.py)."""
 import collections
 import ctypes as C

@@ -1,4 +1,4 @@
-"""Constructed edge cases of SearchForTriangulation (pilotguru_amd/csrc/frame.hip, k_search_for_triangulation) and the runners that
+"""Constructed edge cases of SearchForTriangulation (pilotguru_amd/csrc/node_match.hip, k_search_for_triangulation) and the runners that
 put them through the plain reference (tests/triangulation_reference.py), the single-call ABI and the batched device form.
 A helper module (no tests): tests/test_search_for_triangulation.py uses it.
 

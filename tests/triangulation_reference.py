@@ -1,6 +1,6 @@
 """A plain, sequential restatement of ORBmatcher::SearchForTriangulation (thirdparty/orb-slam2/src/ORBmatcher.cc:659-825) with
 CheckDistEpipolarLine (:142-159), written from that upstream text and nothing else: it does not use oracle/ and was not derived
-from the HIP kernel (pilotguru_amd/csrc/frame.hip), so a misreading shared by neither side shows up as a disagreement.
+from the HIP kernel (pilotguru_amd/csrc/node_match.hip), so a misreading shared by neither side shows up as a disagreement.
 
 Conventions (those of tests/matcher_reference.py):
 - Keypoints are KEYPOINT_DTYPE arrays (the undistorted mvKeysUn), descriptors [n, 32] uint8, feature vectors the

@@ -73,7 +73,7 @@ typedef uint32_t pg_u32x16 __attribute__((ext_vector_type(16)));
 template <int TPC, int MPC, bool NARROW, int WPB>
 __global__ __launch_bounds__(64 * WPB, 8) void k_fast_cells(const PgFastArgs KA)
 {
-    // Records [cell0, cellEnd) of `tab`.  The default table is in a BALANCED dispatch order (api.hip): XCD x -- the
+    // Records [cell0, cellEnd) of `tab`.  The default table is in a BALANCED dispatch order (plan.hip): XCD x -- the
     // dispatcher deals consecutive workgroups to consecutive XCDs -- gets the x-th eighth of EVERY level's cells, a
     // contiguous band per level, so neighbours still share L2 lines and every XCD sees the same mix of cheap cells
     // (level 0: ~15 candidates) and expensive ones (upper levels: 40..170 candidates, several score rounds).  In plain
@@ -111,7 +111,7 @@ __global__ __launch_bounds__(64 * WPB, 8) void k_fast_cells(const PgFastArgs KA)
     const uint32_t frame = blockIdx.y;                             // (unsigned: 32 x 32 -> 64-bit scalar multiplies, two instructions each)
     const int slot = ((int)(blockIdx.x >> 3) * WPB + wv) * cpw + j;           // within this XCD's run of records
     const int cell = cell0 + (int)(blockIdx.x & 7) * cellsPerXcd + slot;      // position in the table
-    const uint32_t* recp = tab + 16 * (int64_t)cell;               // (the tables end in 4 x 64 + 8 records of slack: api.hip)
+    const uint32_t* recp = tab + 16 * (int64_t)cell;               // (the tables end in 4 x 64 + 8 records of slack: plan.hip)
     pg_u32x16 rec;
     asm volatile("s_load_dwordx16 %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(rec) : "s"(recp) : "memory");
     if (cell >= cellEnd || slot >= cellsPerXcd) return cpw;

@@ -50,7 +50,7 @@ struct PgFuseArgs {
 };
 
 // The validity words of a cell's necessary test (fast_cell.inc, PgCellValid; the same arithmetic as PgPlan::cellTab w8-w15 in
-// api.hip) from the interior's size -- all scalar: a slot's cell is known from the slot's position, no record is loaded
+// plan.hip) from the interior's size -- all scalar: a slot's cell is known from the slot's position, no record is loaded
 __device__ __forceinline__ PgCellValid pg_cell_valid(int IW, int IH)
 {
     const int qFull = IW >> 2, rem = IW & 3, base = IH >> 3, rr = IH & 7;
@@ -125,7 +125,7 @@ __global__ __launch_bounds__(64, 8) void k_fast_resize(const PgFuseArgs A)
     // ... and, under the DMA, the lane's share of the resize: quad ql of the column's nq, group gl of the band's ng
     const int gBeg = A.bandTab[2 * b], ng = A.bandTab[2 * b + 1];
     const int qBeg = A.colTab[4 * (s + 1)], nq = A.colTab[4 * (s + 1) + 1], qMagic = A.colTab[4 * (s + 1) + 2];
-    const int gl = (lane * qMagic) >> 16, ql = lane - gl * nq;         // lane / nq, lane % nq (exact for lane < 64: api.hip checks)
+    const int gl = (lane * qMagic) >> 16, ql = lane - gl * nq;         // lane / nq, lane % nq (exact for lane < 64: plan.hip checks)
     const bool on = gl < ng;
     const int quad = qBeg + (on ? ql : 0), grp = gBeg + (on ? gl : 0);
     const PgQuadTab2 T = A.qtab[quad];

@@ -116,7 +116,7 @@ struct PgPlan {
     int64_t  cellCandFrame;   // u32 per frame in the per-cell slot slab
     uint32_t* cellCand;       // K2 output: [frame][level][cell][cellCap]
     int32_t*  cellCount;      // K2 output: [frame][totalCells]
-    // [totalCells] 64-byte record per cell, built with the plan (api.hip): everything K2 needs to
+    // [totalCells] 64-byte record per cell, built with the plan (plan.hip): everything K2 needs to
     // find its window in ONE scalar load -- the wave start used to be a chain of four dependent
     // scalar round trips (kernarg -> cell table -> level -> level fields).
     //   w0 level | cell index in the frame's cellCount array << 4      w1 iniX | iniY << 16
@@ -161,7 +161,7 @@ __host__ __device__ __forceinline__ int qt_pyr_depth(int nIni)
 }
 // One entry of K3's coordinate tables (quadtree.hip, the candidate pass): for region column c (isY = false) or row c (isY = true),
 // as K2 stores coordinates, {its bits of the depth-D descendant index, its part of the candidate-order rank}.  The same text builds
-// the tables with the plan on the host (api.hip) and inside k_quadtree on the device: single IEEE operations, nothing to contract.
+// the tables with the plan on the host (plan.hip) and inside k_quadtree on the device: single IEEE operations, nothing to contract.
 #if defined(__HIP_DEVICE_COMPILE__)
 #define PG_FDIV_RN(a, b) __fdiv_rn(a, b)
 #define PG_FMUL_RN(a, b) __fmul_rn(a, b)

@@ -3,7 +3,7 @@
 // Restates ORBextractor::ComputePyramid (thirdparty/orb-slam2/src/ORBextractor.cc:
 // 1106-1131): level l = cv::resize(level l-1, INTER_LINEAR) (:1119), no pre-blur.  The
 // 11-bit fixed-point arithmetic is OpenCV 2.4's; coefficient
-// tables are built once per frame size on the host (api.hip: build_resize_tables) with the
+// tables are built once per frame size on the host (plan.hip: build_resize_tables) with the
 // same float/double sequence as cv::resize.  The 19-px reflect border the reference adds
 // (:1121,:1126) is never read on the monocular path, so planes are stored unpadded.
 //

@@ -348,7 +348,7 @@ __global__ __launch_bounds__((WIDE == 1 || WIDE == 3) ? 512 : QT_TMAX, WIDE == 3
         // round; a cell rarely holds more) are in flight before the first is used, 16 bytes per load.  The first form of this pass
         // (16 lanes per cell, 32 cells per step, one round of 16 slots per trip) spent its 27 us per level-0 problem waiting: ten
         // dependent memory round trips per wave; this one makes three.  The 64 lanes of an LDS atomic now belong to 64 different
-        // cells -- mostly different leaves.  (A cell's slots are read up to 3 records past its count: inside the slab, api.hip.)
+        // cells -- mostly different leaves.  (A cell's slots are read up to 3 records past its count: inside the slab, plan.hip.)
         struct __attribute__((packed, aligned(4))) U4 { uint32_t e[4]; };
         if (ncells < QT_T) {
             // fewer cells than threads (the upper levels, small frames): 16 lanes per cell, 32 cells per wave step keeps the workgroup's
@@ -440,7 +440,7 @@ __global__ __launch_bounds__((WIDE == 1 || WIDE == 3) ? 512 : QT_TMAX, WIDE == 3
             PgSelRec* selE = reinterpret_cast<PgSelRec*>(P.sel) + ((int64_t)frame * P.selFrame + L.selOff);
             for (int p = tid; p < L.selCap; p += QT_T) selE[p].posLevel = 0xFFFFFFFFu;
             if (tid == 0) *kpc = 0;
-            if (ncand > 0 && tid == 0) atomicExch(P.status, PGORB_E_TOOSMALL);      // see api.hip level_geometry: reference UB, reported
+            if (ncand > 0 && tid == 0) atomicExch(P.status, PGORB_E_TOOSMALL);      // see plan.hip level_geometry: reference UB, reported
             return;
         }
         if (!rank24) {                                      // order ranks beyond 24 bits: the winners come from a key pass (64-bit bids)
@@ -846,7 +846,7 @@ __global__ __launch_bounds__(QTP_T) void k_qt_leaves(const PgPlan P, int level0,
     const PgLevel& L = P.lvl[l];
     const int nIni = L.nIni, nCols = L.nCols, ncells = nCols * L.nRows, cellCap = L.cellCap, hCell = L.hCell;
     const int32_t* cc = P.cellCount + (int64_t)frame * P.totalCells + L.cellBase;
-    if (nIni < 1) {                                          // no root: the reference's behaviour is undefined there (api.hip level_geometry), reported
+    if (nIni < 1) {                                          // no root: the reference's behaviour is undefined there (plan.hip level_geometry), reported
         if (rem == 0) {
             int any = 0;
             for (int i = tid; i < ncells; i += QTP_T) any |= cc[i];

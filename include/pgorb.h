@@ -408,8 +408,9 @@ int  pgorb_search_for_triangulation_batch_device(pgorb_ctx* ctx,
  *   most n1; count[s] = the points made with neighbour s, or PGORB_CNM_SKIPPED when the baseline test skipped it; F12 / epipole
  *   (may be NULL) = ComputeF12 and the epipole of every neighbour, skipped or not; has_point1_out = KF1's mask afterwards.
  *   Two KF1 keypoints may match one KF2 keypoint: both points are listed and KF2's slot ends with the later one (AddMapPoint
- *   overwrites).  Left to the caller: AddObservation / AddMapPoint / Map::AddMapPoint / mlpRecentAddedMapPoints, and
- *   ComputeDistinctiveDescriptors (with two observations the reference picks by KeyFrame* address).  CheckNewKeyFrames()'s
+ *   overwrites).  Left to the caller: AddObservation / AddMapPoint / Map::AddMapPoint / mlpRecentAddedMapPoints;
+ *   ComputeDistinctiveDescriptors (with two observations the reference picks by KeyFrame* address) is one
+ *   pgorb_refresh_map_points call over the new points, with the lists in that order.  CheckNewKeyFrames()'s
  *   early return between neighbours (:240) is the caller's choice of how many neighbours to pass.
  *   Returns the number of points, or a PGORB_E_* code.  At most PGORB_CNM_MAX_NEIGHBOURS neighbours, 16000 keypoints. */
 #define PGORB_CNM_MAX_NEIGHBOURS 64
@@ -479,8 +480,8 @@ int  pgorb_create_new_map_points_batch_device(pgorb_ctx* ctx,
  *   After a Replace the survivor observes the UNION of both key-frame sets; a chain's counts follow those sets.
  *   best_idx / best_dist (may be NULL) = -1 / -1 for a skipped query, -1 / 256 when no candidate passed; kf_point_out (may be
  *   NULL) = the slots afterwards.  Returns nFused or a PGORB_E_* code.  The caller replays the actions in query order against
- *   its own map: Replace, AddObservation / AddMapPoint, and what stays on the host -- ComputeDistinctiveDescriptors,
- *   IncreaseFound / IncreaseVisible, Map::EraseMapPoint.  PGORB_E_ARG: an index out of range, an observation list unsorted or
+ *   its own map: Replace, AddObservation / AddMapPoint, IncreaseFound / IncreaseVisible, Map::EraseMapPoint; the survivors'
+ *   ComputeDistinctiveDescriptors is pgorb_refresh_map_points (below).  PGORB_E_ARG: an index out of range, an observation list unsorted or
  *   with repeats, a repeated non-NULL query, a live (not bad) occupant that does not list kf_id or holds two slots, th <= 0.  The search
  *   level comes from MapPoint::PredictScale under pgorb_log_f with the context's mfLogScaleFactor; octaves lie in [0, levels). */
 #define PGORB_FUSE_SKIPPED 0
@@ -519,6 +520,66 @@ int  pgorb_fuse_batch_device(pgorb_ctx* ctx,
         const uint8_t* d_point_bad, const int32_t* d_obs_start, const uint64_t* d_obs_kf,
         int qcap, const int32_t* d_nq, const int32_t* d_queries, float th,
         int32_t* d_action, int32_t* d_best_idx, int32_t* d_best_dist, int32_t* d_kf_point_out, int32_t* d_nfused,
+        void* hip_stream);
+
+/* ---- Map-point refresh: the distinctive descriptor and the normal / depth range of many points --------------------------
+ *   pgorb_refresh_map_points   for every selected point what MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:259-324)
+ *       followed by MapPoint::UpdateNormalAndDepth (:347-388) would store, exactly.  The reference runs the pair once per point at
+ *       the end of CreateNewMapPoints (src/LocalMapping.cc:444-446), for every point of the new key frame after SearchInNeighbors'
+ *       two Fuse rounds (:519-532), in ProcessNewKeyFrame (:152-153), in Tracking (Tracking.cc:533-534, :664-665, :1108-1109) and,
+ *       one of the two only, after bundle adjustment and loop closing (Optimizer.cc:776, LoopClosing.cc:500, :534): `what`.
+ *   Key frames: nkf of them, each its undistorted keypoints (mvKeysUn; only `octave` is read), descriptors, n[f], its
+ *   pgorb_kf_pose (only Ow is read) and kf_bad[f] = pKF->isBad() (NULL = none).  Points: a table as pgorb_fuse's -- pose fields,
+ *   32-byte descriptor, bad flag (NULL = none) -- with the observations as CSR of (obs_frame, obs_idx) = (index of the key frame
+ *   in this call's list, keypoint index), and ref_obs[p] = the position of mpRefKF inside point p's own list.
+ *   THE LIST ORDER IS THE CONTRACT: it must be the order the caller's mObservations iterates, a std::map<KeyFrame*, size_t>,
+ *   i.e. key-frame ADDRESS order, which the library cannot know.  The first row with the smallest median wins and the normal is
+ *   a float sum in that order, so another order is another result.
+ *   ComputeDistinctiveDescriptors: a bad point or an empty list changes nothing.  The candidates are the observations whose key
+ *   frame is not bad, in list order (:278-284); none -> nothing changes.  Distances[i][j] = DescriptorDistance; per row the
+ *   median is sorted_row[(int)(0.5*(N-1))] (N = 4: index 1; N <= 2: the row's own 0, so the first candidate wins and no distance
+ *   is computed); the first row with the strictly smallest median wins (median < BestMedian, :313).  Out: the 32 descriptor bytes
+ *   and best_obs = the winner's position in the point's FULL list (bad key frames counted), -1 when nothing changed.
+ *   UpdateNormalAndDepth: a bad point or an empty list changes nothing; bad key frames are NOT skipped (:367-374).  normal = the
+ *   running float sum from 0, in list order, of normali/cv::norm(normali), normali = mWorldPos - Ow_i, then normal/n; dist =
+ *   cv::norm(Pos - Ow_ref), level = the octave of the reference key frame's keypoint, mfMaxDistance = dist*mvScaleFactors[level],
+ *   mfMinDistance = mfMaxDistance/mvScaleFactors[nLevels-1] with the context's tables, under the OpenCV 2.4.9 readings of
+ *   DESIGN.md section 4 (cv::norm in double, each term normali*(float)(1/norm) in float, float adds, normal*(float)(1.0/n)).
+ *   status[q] (q = position in `select`): bit 0 (PGORB_MP_DESCRIPTOR) = the descriptor was written, bit 1 (PGORB_MP_NORMAL_DEPTH)
+ *   = normal, min_distance, max_distance were written; PGORB_MP_LIMIT when the list of a live point is longer than
+ *   PGORB_MP_MAX_OBS (the reference's only limit is its stack, float Distances[N][N], :292): nothing is written for that point,
+ *   whatever `what` is.  Points that are not selected, and fields that are not written, keep their bytes.
+ *   select[nsel] = table indices (NULL = every point, nsel = npoints); best_obs may be NULL; ref_obs may be NULL when what =
+ *   PGORB_MP_DESCRIPTOR.  Returns the number of selected points with a positive status, or PGORB_E_ARG (an observation's key
+ *   frame or keypoint out of range, obs_start not rising from 0, a key frame twice in one list, ref_obs outside the list of a
+ *   live non-empty point that gets a normal / depth update, a selection index out of range or repeated, what outside 1..3) /
+ *   PGORB_E_LIMIT (more than 16000 keypoints in a key frame). */
+#define PGORB_MP_MAX_OBS 512
+#define PGORB_MP_DESCRIPTOR 1
+#define PGORB_MP_NORMAL_DEPTH 2
+#define PGORB_MP_BOTH 3
+#define PGORB_MP_LIMIT (-6)
+#define PGORB_MP_BAD_INDEX (-1)
+int  pgorb_refresh_map_points(pgorb_ctx* ctx,
+        int nkf, const pgorb_keypoint* const* kps, const uint8_t* const* desc, const int32_t* n /*[nkf]*/,
+        const pgorb_kf_pose* pose /*[nkf]*/, const uint8_t* kf_bad /*[nkf] or NULL*/,
+        int npoints, pgorb_map_point* points /*in: pos; out: normal, distances*/, uint8_t* point_desc /*[npoints][32] in/out*/,
+        const uint8_t* point_bad /*[npoints] or NULL*/, const int32_t* obs_start /*[npoints + 1]*/, const int32_t* obs_frame,
+        const int32_t* obs_idx, const int32_t* ref_obs /*[npoints]*/, int nsel, const int32_t* select /*[nsel] or NULL*/, int what,
+        int32_t* best_obs /*[nsel] or NULL*/, int32_t* status /*[nsel]*/);
+/* Batched, resident, asynchronous: the key frames are nframes frames of one batch in the layout of pgorb_extract_batch_device
+ * (d_kps / d_desc [nframes][cap_per_frame], d_n [nframes]), d_pose and d_kf_bad [nframes]; the table and the lists as above, on
+ * the device, nobs = the length of d_obs_frame / d_obs_idx.  This form does not check its inputs: a selection index outside the
+ * table, an obs_start pair outside [0, nobs], an observation outside the batch or a ref_obs outside its list makes THAT point a
+ * no-op with status PGORB_MP_BAD_INDEX, never an access out of bounds; a key frame listed twice and a point selected twice are
+ * not detected (the latter writes the same bytes twice).  Points are independent, so one call may refresh any subset.
+ * k_mp_bin bins the selection by list length, k_mp_seg<2 | 8 | 32 | 64> run 32 | 8 | 2 | 1 points per wave, k_mp_big one
+ * workgroup per longer list (csrc/map_point.hip). */
+int  pgorb_refresh_map_points_batch_device(pgorb_ctx* ctx,
+        const pgorb_keypoint* d_kps, const uint8_t* d_desc, const int32_t* d_n, int nframes, int cap_per_frame,
+        const pgorb_kf_pose* d_pose, const uint8_t* d_kf_bad, int npoints, pgorb_map_point* d_points, uint8_t* d_point_desc,
+        const uint8_t* d_point_bad, const int32_t* d_obs_start, const int32_t* d_obs_frame, const int32_t* d_obs_idx, int nobs,
+        const int32_t* d_ref_obs, int nsel, const int32_t* d_select, int what, int32_t* d_best_obs, int32_t* d_status,
         void* hip_stream);
 
 /* ---- ORB vocabulary (DBoW2 TemplatedVocabulary<FORB::TDescriptor, FORB>) -----------------

@@ -34,6 +34,7 @@ SYMBOLS = (
     "pgorb_search_for_triangulation", "pgorb_search_for_triangulation_batch_device",
     "pgorb_create_new_map_points", "pgorb_create_new_map_points_batch_device",
     "pgorb_fuse", "pgorb_fuse_batch_device",
+    "pgorb_refresh_map_points", "pgorb_refresh_map_points_batch_device",
     "pgorb_search_by_projection_keyframe", "pgorb_search_by_projection_keyframe_batch_device",
     "pgorb_log_f", "pgorb_log_scale_factor", "pgorb_predict_scale",
     "pgorb_undistort_keypoints", "pgorb_undistort_keypoints_batch_device", "pgorb_image_bounds",
@@ -163,6 +164,13 @@ def lib():
     L.pgorb_fuse.argtypes = [vp, vp, vp, C.c_int, vp, C.c_uint64] + f4 + [vp, C.c_int] + [vp] * 5 + [C.c_int, vp, C.c_float] + [vp] * 4
     L.pgorb_fuse_batch_device.argtypes = [vp, vp, vp, vp, C.c_int, vp, vp, vp, C.c_int, vp, vp] + f4 + [vp, C.c_int] + [vp] * 5 + \
         [C.c_int, vp, vp, C.c_float] + [vp] * 5 + [vp]
+    # (ctx, nkf, kps[], desc[], n, pose, kf_bad, npoints, points, point_desc, point_bad, obs_start, obs_frame, obs_idx, ref_obs, nsel,
+    #  select, what, best_obs, status)
+    L.pgorb_refresh_map_points.argtypes = [vp, C.c_int] + [vp] * 5 + [C.c_int] + [vp] * 7 + [C.c_int, vp, C.c_int, vp, vp]
+    # (ctx, kps, desc, n, nframes, cap, pose, kf_bad, npoints, points, point_desc, point_bad, obs_start, obs_frame, obs_idx, nobs,
+    #  ref_obs, nsel, select, what, best_obs, status, stream)
+    L.pgorb_refresh_map_points_batch_device.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, C.c_int] + [vp] * 6 + \
+        [C.c_int, vp, C.c_int, vp, C.c_int, vp, vp, vp]
     L.pgorb_undistort_keypoints.argtypes = [vp, vp, C.c_int, vp, vp, vp]
     L.pgorb_undistort_keypoints_batch_device.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp]
     L.pgorb_image_bounds.argtypes = [C.c_int, C.c_int, vp, vp, vp]

@@ -1,5 +1,5 @@
-// match_common.h -- what the Frame side, the guided matchers, CreateNewMapPoints and Fuse share: included by frame.hip,
-// window_match.hip, node_match.hip, mapping.hip and fuse.hip, and by no other translation unit.
+// match_common.h -- what the Frame side, the guided matchers, CreateNewMapPoints, Fuse and the map-point refresh share: included by
+// frame.hip, window_match.hip, node_match.hip, mapping.hip, fuse.hip and map_point.hip, and by no other translation unit.
 #pragma once
 #include "pgorb_internal.h"
 #include <algorithm>

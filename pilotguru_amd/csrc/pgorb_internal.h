@@ -1,5 +1,6 @@
 // pgorb_internal.h -- shared host/device declarations of libpgorb (gfx950 only).  What only the Frame side, the guided matchers,
-// CreateNewMapPoints and Fuse share (frame.hip, window_match.hip, node_match.hip, mapping.hip, fuse.hip) is in match_common.h.
+// CreateNewMapPoints, Fuse and the map-point refresh share (frame.hip, window_match.hip, node_match.hip, mapping.hip, fuse.hip,
+// map_point.hip) is in match_common.h.
 //
 // Data layout in HBM (all per context, sized for max_batch frames):
 //   pyramid arena   level l, frame f : u8 plane, row pitch = align64(w_l), at

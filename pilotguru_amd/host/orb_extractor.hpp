@@ -243,9 +243,56 @@ struct KeyFrame {
     float medianDepth = 0;
 };
 
+// The observation lists pgorb_refresh_map_points reads: point i observes key frame obsFrame[k] (a position in the call's key-frame
+// list) at keypoint obsIdx[k] for k in obsStart[i] .. obsStart[i + 1], IN THE ORDER THE CALLER'S mObservations ITERATES
+// (a std::map<KeyFrame*, size_t>: address order; include/pgorb.h); refObs[i] = the position of mpRefKF in point i's own list.
+struct MapPointObservations {
+    std::vector<int32_t> obsStart{0};
+    std::vector<int32_t> obsFrame, obsIdx, refObs;
+};
+
+namespace detail {
+// everything pgorb_refresh_map_points rejects, and the lengths it reads through its pointers
+inline void checkRefresh(const std::vector<const KeyFrame*>& kfs, const std::vector<uint8_t>& kfBad, size_t npoints, size_t ndesc,
+                         const std::vector<uint8_t>& pointBad, const MapPointObservations& O, const std::vector<int32_t>* select, int what);
+}  // namespace detail
+
 class LocalMapping {
  public:
     explicit LocalMapping(pgorb_ctx* ctx) : ctx_(ctx) {}
+    // MapPoint::ComputeDistinctiveDescriptors (MapPoint.cc:259-324) and MapPoint::UpdateNormalAndDepth (:347-388) of many points in
+    // one call, as LocalMapping.cc:444-446 and :519-532 run them.  keyFrames: frame (mvKeysUn, mDescriptors) and pose are read;
+    // kfBad[f] = isBad() (empty = none); points / descriptors (32 bytes each) / pointBad (empty = none) are the table, refreshed
+    // in place; select = table indices (NULL = all); what = PGORB_MP_DESCRIPTOR | PGORB_MP_NORMAL_DEPTH | PGORB_MP_BOTH.
+    // status[q] / bestObs[q] per selected point (include/pgorb.h).  Returns the number of points with a positive status.
+    int RefreshMapPoints(const std::vector<const KeyFrame*>& keyFrames, const std::vector<uint8_t>& kfBad,
+                         std::vector<pgorb_map_point>& points, std::vector<uint8_t>& descriptors, const std::vector<uint8_t>& pointBad,
+                         const MapPointObservations& obs, const std::vector<int32_t>* select, int what, std::vector<int32_t>& status,
+                         std::vector<int32_t>* bestObs = nullptr)
+    {
+        detail::checkRefresh(keyFrames, kfBad, points.size(), descriptors.size(), pointBad, obs, select, what);
+        const size_t nkf = keyFrames.size(), np = points.size();
+        std::vector<const pgorb_keypoint*> kps(nkf + 1);
+        std::vector<const uint8_t*> desc(nkf + 1);
+        std::vector<int32_t> n(nkf + 1);
+        std::vector<pgorb_kf_pose> pose(nkf + 1);
+        for (size_t f = 0; f < nkf; f++) {
+            kps[f] = keyFrames[f]->frame.mvKeysUndistorted.data(); desc[f] = keyFrames[f]->frame.mDescriptors.data();
+            n[f] = keyFrames[f]->frame.N(); pose[f] = keyFrames[f]->pose;
+        }
+        const int nsel = select ? (int)select->size() : (int)np;
+        status.assign(nsel > 0 ? nsel : 1, 0);
+        std::vector<int32_t> best(nsel > 0 ? nsel : 1, -1);
+        const int rc = pgorb_refresh_map_points(ctx_, (int)nkf, kps.data(), desc.data(), n.data(), pose.data(),
+                                                kfBad.empty() ? nullptr : kfBad.data(), (int)np, points.data(), descriptors.data(),
+                                                pointBad.empty() ? nullptr : pointBad.data(), obs.obsStart.data(), obs.obsFrame.data(),
+                                                obs.obsIdx.data(), obs.refObs.empty() ? nullptr : obs.refObs.data(), nsel,
+                                                select ? (nsel ? select->data() : best.data()) : nullptr, what, best.data(), status.data());
+        if (rc < 0) throw std::runtime_error(pgorb_last_error(ctx_));
+        status.resize(nsel);
+        if (bestObs) bestObs->assign(best.begin(), best.begin() + nsel);
+        return rc;
+    }
     // CreateNewMapPoints() (LocalMapping.cc:209-454), monocular: neighbours in GetBestCovisibilityKeyFrames order.  points in
     // the reference's creation order, count[s] per neighbour (PGORB_CNM_SKIPPED: the baseline test skipped it), hasPoint1Out KF1's
     // mask afterwards.  The map bookkeeping is the caller's (include/pgorb.h).  Returns the number of points.
@@ -291,5 +338,50 @@ class LocalMapping {
  private:
     pgorb_ctx* ctx_;
 };
+
+namespace detail {
+inline void checkRefresh(const std::vector<const KeyFrame*>& kfs, const std::vector<uint8_t>& kfBad, size_t npoints, size_t ndesc,
+                         const std::vector<uint8_t>& pointBad, const MapPointObservations& O, const std::vector<int32_t>* select, int what)
+{
+    const char* fn = "RefreshMapPoints";
+    const auto fail = [&](const char* m) { throw std::invalid_argument(std::string(fn) + ": " + m); };
+    if (what < PGORB_MP_DESCRIPTOR || what > PGORB_MP_BOTH) fail("what is not PGORB_MP_DESCRIPTOR, PGORB_MP_NORMAL_DEPTH or PGORB_MP_BOTH");
+    const int nkf = (int)kfs.size(), np = (int)npoints;
+    for (const KeyFrame* K : kfs) {
+        if (!K) fail("a key frame is NULL");
+        checkDescriptors(K->frame, fn);
+    }
+    if (!kfBad.empty() && kfBad.size() != kfs.size()) fail("kfBad is neither empty nor one entry per key frame");
+    if (ndesc != npoints * 32) fail("point descriptors are not n x 32 bytes");
+    if (!pointBad.empty() && pointBad.size() != npoints) fail("pointBad is neither empty nor n entries long");
+    if (O.obsStart.size() != npoints + 1 || O.obsStart[0] != 0) fail("obsStart is not n + 1 entries from 0");
+    for (int i = 0; i < np; i++) if (O.obsStart[i + 1] < O.obsStart[i]) fail("obsStart decreases");
+    const int m = O.obsStart[np];
+    if (O.obsFrame.size() < (size_t)m || O.obsIdx.size() < (size_t)m) fail("fewer observations than obsStart says");
+    for (int k = 0; k < m; k++)
+        if (O.obsFrame[k] < 0 || O.obsFrame[k] >= nkf || O.obsIdx[k] < 0 || O.obsIdx[k] >= kfs[O.obsFrame[k]]->frame.N())
+            fail("an observation names a key frame or keypoint out of range");
+    std::vector<int32_t> seen(nkf > 0 ? nkf : 1, -1);
+    for (int i = 0; i < np; i++)
+        for (int k = O.obsStart[i]; k < O.obsStart[i + 1]; k++) {
+            if (seen[O.obsFrame[k]] == i) fail("a list names a key frame twice");
+            seen[O.obsFrame[k]] = i;
+        }
+    if ((what & PGORB_MP_NORMAL_DEPTH) && O.refObs.size() != npoints) fail("refObs is not n entries long");
+    if (!(what & PGORB_MP_NORMAL_DEPTH) && !O.refObs.empty() && O.refObs.size() != npoints) fail("refObs is neither empty nor n entries long");
+    std::vector<uint8_t> chosen(np > 0 ? np : 1, 0);
+    const int nsel = select ? (int)select->size() : np;
+    for (int q = 0; q < nsel; q++) {
+        const int p = select ? (*select)[q] : q;
+        if (p < 0 || p >= np) fail("a selection index is out of range");
+        if (chosen[p]) fail("a point is selected twice");
+        chosen[p] = 1;
+        const int len = O.obsStart[p + 1] - O.obsStart[p];
+        if ((what & PGORB_MP_NORMAL_DEPTH) && !(!pointBad.empty() && pointBad[p]) && len > 0 && len <= PGORB_MP_MAX_OBS &&
+            (O.refObs[p] < 0 || O.refObs[p] >= len))
+            fail("refObs lies outside the point's list");
+    }
+}
+}  // namespace detail
 
 }  // namespace pgorb

@@ -585,6 +585,11 @@ def kf_pose(Tcw, Ow, fx, fy, cx, cy, invfx=None, invfy=None):
     return r
 
 
+# pgorb_refresh_map_points: what to refresh, the status word's bits, the limit (include/pgorb.h)
+MP_DESCRIPTOR, MP_NORMAL_DEPTH, MP_BOTH = 1, 2, 3
+MP_LIMIT, MP_BAD_INDEX, MP_MAX_OBS = -6, -1, 512
+
+
 class LocalMapping:
     """LocalMapping::CreateNewMapPoints (thirdparty/orb-slam2/src/LocalMapping.cc:209-454), monocular, on the GPU."""
 
@@ -631,6 +636,88 @@ class LocalMapping:
             ext._h, _p(k1), _p(d1), _p(h1), KF1.N, _p(n1), _p(s1), _p(f1), len(n1), _p(p1), nn, kps, descs, masks, _p(n2), nodes,
             starts, feats, _p(nfv2), _p(P2), _p(md), _p(pts), _p(count), _p(F12), _p(ep), _p(hout)))
         return pts[:np_].copy(), count[:nn].copy(), F12[:nn].reshape(nn, 3, 3).copy(), ep[:nn].copy(), hout[:KF1.N].copy()
+
+
+    @staticmethod
+    def RefreshMapPoints(key_frames, poses, points, descriptors, obs_start, obs_frame, obs_idx, ref_obs=None, point_bad=None,
+                         kf_bad=None, select=None, what=MP_BOTH, ext=None):
+        """MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:259-324) and MapPoint::UpdateNormalAndDepth (:347-388) of many
+        points in one call, as LocalMapping.cc:444-446 and :519-532 run them.  key_frames: Frame-like objects (ext, N,
+        mvKeysUndistorted, mDescriptors); poses[f]: KF_POSE_DTYPE; kf_bad[f] = isBad() (None = none).  points (MAP_POINT_DTYPE),
+        descriptors [n, 32], point_bad (None = none); point i observes (obs_frame[k], obs_idx[k]) = (position in key_frames,
+        keypoint) for k in obs_start[i]:obs_start[i + 1], IN THE ORDER mObservations ITERATES (include/pgorb.h); ref_obs[i] = the
+        position of mpRefKF in that list.  select: table indices (None = all); what: MP_DESCRIPTOR | MP_NORMAL_DEPTH | MP_BOTH.
+        Returns (points, descriptors, best_obs, status): copies with the refreshed fields, and per selected point the winning
+        observation's list position (-1: descriptor unchanged) and the status word (bits MP_DESCRIPTOR / MP_NORMAL_DEPTH, or
+        MP_LIMIT for a list longer than MP_MAX_OBS).  Raises ValueError for everything pgorb_refresh_map_points refuses."""
+        fn = "RefreshMapPoints"
+        nkf = len(key_frames)
+        if ext is None:
+            if not nkf:
+                raise ValueError(fn + ": no key frame and no ext")
+            ext = key_frames[0].ext
+        if what not in (MP_DESCRIPTOR, MP_NORMAL_DEPTH, MP_BOTH):
+            raise ValueError(fn + ": what must be MP_DESCRIPTOR, MP_NORMAL_DEPTH or MP_BOTH")
+        if len(poses) != nkf:
+            raise ValueError(fn + ": key_frames and poses differ in length")
+        P = np.zeros(max(nkf, 1), KF_POSE_DTYPE)
+        keep = []
+        kps, descs = [(C.c_void_p * max(nkf, 1))() for _ in range(2)]
+        nk = np.zeros(max(nkf, 1), np.int32)
+        for f, K in enumerate(key_frames):
+            kp, d = _frame(K, "key frame %d" % f)
+            keep += [kp, d]
+            kps[f], descs[f], nk[f] = kp.ctypes.data, d.ctypes.data, K.N
+            P[f] = np.asarray(poses[f], KF_POSE_DTYPE).reshape(())
+        kb = _mask(kf_bad, nkf, "kf_bad")
+        pts = np.array(np.ascontiguousarray(points, MAP_POINT_DTYPE).reshape(-1))       # a copy: refreshed in place
+        n = len(pts)
+        pd = np.array(_arr(descriptors, np.uint8, n, "point descriptors", 32))
+        pb = _mask(point_bad, n, "point_bad")
+        st = _arr(obs_start, np.int32, n + 1, "obs_start")
+        of = np.ascontiguousarray(obs_frame, np.int32).reshape(-1)
+        oi = np.ascontiguousarray(obs_idx, np.int32).reshape(-1)
+        if st[0] != 0 or np.any(np.diff(st) < 0) or len(of) < int(st[-1]) or len(oi) < int(st[-1]):
+            raise ValueError(fn + ": obs_start must rise from 0 to at most len(obs_frame), len(obs_idx)")
+        m = int(st[-1])
+        if m and (of[:m].min() < 0 or of[:m].max() >= nkf or oi[:m].min() < 0 or np.any(oi[:m] >= nk[np.clip(of[:m], 0, max(nkf - 1, 0))])):
+            raise ValueError(fn + ": an observation names a key frame or keypoint out of range")
+        owner = np.repeat(np.arange(n, dtype=np.int64), np.diff(st))
+        pair = owner * max(nkf, 1) + of[:m]
+        if len(np.unique(pair)) != m:
+            raise ValueError(fn + ": a list names a key frame twice")
+        if select is None:
+            sel, nsel = None, n
+            chosen = np.arange(n)
+        else:
+            sel = np.ascontiguousarray(select, np.int32).reshape(-1)
+            nsel = len(sel)
+            if nsel and (sel.min() < 0 or sel.max() >= n):
+                raise ValueError(fn + ": a selection index is out of range")
+            if len(np.unique(sel)) != nsel:
+                raise ValueError(fn + ": a point is selected twice")
+            chosen = sel
+        if what & MP_NORMAL_DEPTH:
+            ro = _arr(ref_obs if ref_obs is not None else [], np.int32, n, "ref_obs")
+            ln = np.diff(st)[chosen]
+            need = (pb[:n][chosen] == 0) & (ln > 0) & (ln <= MP_MAX_OBS)
+            if np.any(need & ((ro[chosen] < 0) | (ro[chosen] >= ln))):
+                raise ValueError(fn + ": ref_obs lies outside the point's list")
+        else:
+            ro = np.zeros(max(n, 1), np.int32) if ref_obs is None else _arr(ref_obs, np.int32, n, "ref_obs")
+        if len(of) == 0:
+            of, oi = np.zeros(1, np.int32), np.zeros(1, np.int32)
+        if len(ro) == 0:
+            ro = np.zeros(1, np.int32)
+        best = np.full(max(nsel, 1), -1, np.int32)
+        status = np.zeros(max(nsel, 1), np.int32)
+        pts_buf = pts if n else np.zeros(1, MAP_POINT_DTYPE)
+        pd_buf = pd if n else np.zeros((1, 32), np.uint8)
+        ext._check(ext._L.pgorb_refresh_map_points(ext._h, nkf, kps, descs, _p(nk), _p(P), _p(kb), n, _p(pts_buf), _p(pd_buf), _p(pb),
+                                                   _p(st), _p(of), _p(oi), _p(ro), nsel, None if sel is None else _p(sel if nsel else best),
+                                                   int(what), _p(best), _p(status)))
+        return pts, pd, best[:nsel].copy(), status[:nsel].copy()
+
 
 
 class FrameStream:

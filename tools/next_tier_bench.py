@@ -14,8 +14,12 @@ next to each, the oracle's CPU time for the same work (1 thread, a few frames, s
   fuse         ORBmatcher::Fuse (ORBmatcher.cc:827-979) as SearchInNeighbors calls it: one call of 1500 points through the host API,
                and the same key frames x 20 targets as independent problems of the batched form; the CPU column is the Python
                reference's matching step (tests/fuse_reference.py) for one call
+  refresh      MapPoint::ComputeDistinctiveDescriptors + UpdateNormalAndDepth (MapPoint.cc:259-388) of many points in one batched
+               call: a key frame's tail (1500 points) and a local-BA-sized set (20000 points) of the skewed list-length
+               distribution of tests/map_point_cases.py; beside it the download + host loop + upload it replaces, the host loop
+               being OUR restatement (tests/map_point_reference.py, Python, one core), not ORB-SLAM2.  --refresh-only runs this row alone
 
-usage: python tools/next_tier_bench.py [--batch 128] [--out profiles/r02_next_tier.txt]"""
+usage: python tools/next_tier_bench.py [--batch 128] [--out profiles/r02_next_tier.txt] [--refresh-only]"""
 import argparse, ctypes as C, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -30,13 +34,9 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--batch", type=int, default=128)
 ap.add_argument("--out", default="")
 ap.add_argument("--features", type=int, default=2000, help="4000 = the initialisation extractor (2 * nFeatures, Tracking.cc:143)")
+ap.add_argument("--refresh-only", action="store_true", help="the map-point refresh rows alone (no ride, no vocabulary)")
 a = ap.parse_args()
 w, h, nf, B = 1920, 1080, a.features, a.batch
-ride = synth_ride(0, w, h, B)
-ext = pg.ORBextractor(nf, 1.2, 8, 20, 7, max_width=w, max_height=h, max_batch=B)
-fr = torch.from_numpy(ride).cuda()
-p = lambda t: C.c_void_p(t.data_ptr())
-s = C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def timed(fn, reps=9):
@@ -47,6 +47,63 @@ def timed(fn, reps=9):
         e0.record(); fn(); e1.record(); torch.cuda.synchronize()
         ms.append(e0.elapsed_time(e1))
     return float(np.median(ms))
+
+
+def refresh_rows(ext):
+    """The map-point refresh: (name, batched GPU ms, replaced path ms = D2H + host loop + H2D, host loop ms, distances, points)."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import map_point_cases as PC
+    p = lambda t: C.c_void_p(t.data_ptr())
+    s = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    G = lambda x: torch.from_numpy(np.ascontiguousarray(x)).cuda()
+    out = []
+    for label, nkf, nkeys, npts in (("one key frame's tail", 260, 400, 1500), ("a local-BA-sized set", 260, 2000, 20000)):
+        c = PC.random_scene(5, nkf=nkf, nkeys=nkeys, npts=npts, bad_kf_share=0.02)
+        pts, pd, pb, st, of, oi, ref = PC.table_arrays(c.points)
+        kp = np.stack([k for k, _, _, _ in c.kfs]); ds = np.stack([d for _, d, _, _ in c.kfs])
+        poses = np.array([P for _, _, P, _ in c.kfs], pg.KF_POSE_DTYPE)
+        kb = np.array([b for _, _, _, b in c.kfs], np.uint8)
+        dK, dD, dN = G(kp.view(np.uint8).reshape(nkf, nkeys, 28)), G(ds), G(np.full(nkf, nkeys, np.int32))
+        dP, dKB, dPts, dPD, dPB = G(poses.view(np.uint8)), G(kb), G(pts.view(np.uint8)), G(pd), G(pb)
+        dS, dF, dI, dR = G(st), G(of), G(oi), G(ref)
+        best = torch.empty(npts, dtype=torch.int32, device="cuda"); status = torch.empty(npts, dtype=torch.int32, device="cuda")
+        call = lambda: ext._check(ext._L.pgorb_refresh_map_points_batch_device(ext._h, p(dK), p(dD), p(dN), nkf, nkeys, p(dP), p(dKB), npts, p(dPts),
+                                  p(dPD), p(dPB), p(dS), p(dF), p(dI), len(of), p(dR), npts, None, 3, p(best), p(status), s))
+        t_gpu = timed(call)
+        want = PC.run_reference(c)
+        assert np.array_equal(status.cpu().numpy(), want[3]) and np.array_equal(best.cpu().numpy(), want[2])
+        assert dPD.cpu().numpy().tobytes() == want[1].tobytes() and dPts.cpu().numpy().view(pg.MAP_POINT_DTYPE).tobytes() == want[0].tobytes()
+        # what the call replaces for a resident back end: the key frames' descriptors come down, the host loops, the points go up
+        t0 = time.perf_counter(); dD.cpu(); dK.cpu(); torch.cuda.synchronize(); t_down = (time.perf_counter() - t0) * 1e3
+        t0 = time.perf_counter(); PC.run_reference(c); t_loop = (time.perf_counter() - t0) * 1e3
+        t0 = time.perf_counter(); G(want[0].view(np.uint8)); G(want[1]); torch.cuda.synchronize(); t_up = (time.perf_counter() - t0) * 1e3
+        live = [(len(q["obs"]), sum(1 for f, _ in q["obs"] if not c.kfs[f][3])) for q in c.points if not q["bad"]]
+        ndist = sum(nc * nc for _, nc in live if nc > 2)
+        out.append(("refresh: %s, %d points over %d key frames (longest list %d)" % (label, npts, nkf, max(n for n, _ in live)),
+                    t_gpu, t_down + t_loop + t_up, t_loop, ndist, npts))
+    return out
+
+
+def refresh_lines(rows):
+    lines = ["# map-point refresh (ComputeDistinctiveDescriptors + UpdateNormalAndDepth), batched resident call, HIP events, median of 9;",
+             "# replaced = descriptors and keypoints D2H + the Python restatement on one core (NOT ORB-SLAM2) + points H2D, wall clock",
+             "%-86s %10s %12s %12s %14s" % ("call", "GPU ms", "replaced ms", "host loop ms", "Gdistances/s")]
+    for name, g, rep, loop, nd, _ in rows:
+        lines.append("%-86s %10.3f %12.1f %12.1f %14.2f" % (name, g, rep, loop, nd / g / 1e6))
+    return lines
+
+
+if a.refresh_only:
+    lines = ["# python tools/next_tier_bench.py --refresh-only   (MI355X)"] + refresh_lines(refresh_rows(pg.ORBextractor(nf, 1.2, 8, 20, 7, max_width=w, max_height=h)))
+    print("\n".join(lines))
+    if a.out:
+        open(a.out, "w").write("\n".join(lines) + "\n")
+    sys.exit(0)
+ride = synth_ride(0, w, h, B)
+ext = pg.ORBextractor(nf, 1.2, 8, 20, 7, max_width=w, max_height=h, max_batch=B)
+fr = torch.from_numpy(ride).cuda()
+p = lambda t: C.c_void_p(t.data_ptr())
+s = C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 rows = []
@@ -333,6 +390,7 @@ lines.append("# round 3: batched, resident forms (every frame vs its predecessor
 lines.append("%-86s %10s %12s %12s" % ("call", "GPU ms", "GPU ms/pair", "CPU ms/pair"))
 for name, g, cc, *np_ in batch_rows:
     lines.append("%-86s %10.3f %12.4f %12.2f" % (name, g, g / (np_[0] if np_ else npairs), cc))
+lines += refresh_lines(refresh_rows(ext))
 print("\n".join(lines))
 if a.out:
     open(a.out, "w").write("\n".join(lines) + "\n")

@@ -14,6 +14,8 @@
 //   int32 header[16] = {'PGVC', version, k, L, nnodes, nwords, scoring, weighting, 0...}
 //   u8  desc[nnodes][32]; f64 weight[nnodes]; i32 parent[nnodes]; i32 child0[nnodes];
 //   i32 nchild[nnodes]; i32 word[nnodes]; i32 children[nnodes-1]
+// word[i] is what a descent that ends at node i returns: the word id of a line flagged as a leaf, 0 for a childless node
+// whose line was not flagged (the reference's Node() default), -1 for an unflagged inner node (never returned).
 // One lane per feature; the 32-byte query stays in 8 VGPRs, children are gathered through L2
 // (node descriptors of one parent are 32-B records; 120 k distances per 2000-feature frame).
 #include "pgorb_internal.h"
@@ -98,6 +100,9 @@ std::vector<uint8_t> pack_blob(int k, int L, int scoring, int weighting, const s
     for (size_t i = 1; i < n; i++) { const int p = parent[i]; children[child0[p] + fill[p]++] = (int32_t)i; }
     int nwords = 0;
     for (size_t i = 1; i < n; i++) if (leafFlag[i]) word[i] = nwords++;     // :1408-1413
+    // a childless node whose line was not flagged ends a descent all the same (isLeaf() is children.empty(), :328) and still
+    // holds Node()'s word_id of 0 (:316): word[] is what the descent returns, so it is 0 there and -1 only on inner nodes
+    for (size_t i = 1; i < n; i++) if (!leafFlag[i] && nchild[i] == 0) word[i] = 0;
     *nwords_out = nwords;
     std::vector<uint8_t> out;
     auto put = [&](const void* p, size_t nb) {
@@ -288,7 +293,7 @@ int pgorb_vocab_load_cached(const char* path, pgorb_vocab** out, int* from_cache
     if (stat(path, &st) != 0) return PGORB_E_ARG;
     const int64_t srcSize = (int64_t)st.st_size, srcMtime = (int64_t)st.st_mtim.tv_sec * 1000000000ll + st.st_mtim.tv_nsec;
     const std::string cpath = std::string(path) + ".pgvoc";
-    const int64_t MAGIC = 0x32434F5647504750ll;                  // "PGPGVOC2": the trailing digit is the cache format's version word
+    const int64_t MAGIC = 0x33434F5647504750ll;                  // "PGPGVOC3": the trailing digit is the cache format's version word (3: word[] of an unflagged childless node is 0)
     if (FILE* fp = fopen(cpath.c_str(), "rb")) {
         int64_t hdr[4] = {0, 0, 0, 0};
         struct stat cst;

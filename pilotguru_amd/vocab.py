@@ -13,7 +13,8 @@ Blob layout (little endian), all sections 64-byte aligned:
   parent  int32 [nnodes]
   child0  int32 [nnodes]   index into `children` of the first child
   nchild  int32 [nnodes]
-  word    int32 [nnodes]   word id for leaves, -1 otherwise
+  word    int32 [nnodes]   what a descent ending at the node returns: the word id of a line flagged as a leaf,
+                           0 for a childless node whose line was not flagged, -1 for an unflagged inner node
   children int32[nnodes-1] child node ids, grouped by parent, in file order
 """
 import numpy as np
@@ -25,8 +26,10 @@ def _pad64(n):
     return (n + 63) // 64 * 64
 
 
-def pack_vocabulary(k, L, desc, weight, parent, scoring=0, weighting=0):
-    """desc [n,32] u8, weight [n] f64, parent [n] i32 (node 0 = root, parent[0] = -1)."""
+def pack_vocabulary(k, L, desc, weight, parent, scoring=0, weighting=0, leaf_flag=None):
+    """desc [n,32] u8, weight [n] f64, parent [n] i32 (node 0 = root, parent[0] = -1).  leaf_flag [n] is the isLeaf
+    column of the text format (entry 0, the root's, is ignored); None = the structure (a node is flagged iff it has no
+    children), which is what write_vocabulary_text emits.  With the file's flags the bytes equal the text loader's blob."""
     n = len(parent)
     parent = np.asarray(parent, np.int32)
     order = np.argsort(parent[1:], kind="stable") + 1          # children grouped by parent, file order
@@ -34,9 +37,12 @@ def pack_vocabulary(k, L, desc, weight, parent, scoring=0, weighting=0):
     child0 = np.zeros(n, np.int32)
     child0[1:] = np.cumsum(nchild)[:-1]
     word = np.full(n, -1, np.int32)
-    leaves = np.nonzero(nchild == 0)[0]
-    leaves = leaves[leaves != 0]
-    word[leaves] = np.arange(len(leaves), dtype=np.int32)      # word ids in file order (:1408-1413)
+    flag = nchild == 0 if leaf_flag is None else np.asarray(leaf_flag).astype(bool).copy()
+    flag[0] = False
+    leaves = np.nonzero(flag)[0]
+    word[(nchild == 0) & ~flag] = 0                            # unflagged and childless: Node()'s word_id (:316)
+    word[0] = -1
+    word[leaves] = np.arange(len(leaves), dtype=np.int32)      # word ids in file order of the flagged lines (:1408-1413)
     hdr = np.zeros(16, np.int32)
     hdr[:8] = [MAGIC, 1, k, L, n, len(leaves), scoring, weighting]
     parts = [hdr.tobytes(), np.ascontiguousarray(desc, np.uint8).tobytes(),

@@ -873,6 +873,16 @@ int  pgorb_debug_level_keypoints(pgorb_ctx* ctx, int frame, int level);
  * (tests/test_gpu_parity.py::test_device_sincos_equals_the_oracle_for_every_input).  Synchronous. */
 int  pgorb_debug_sincos_checksum(uint32_t first_bits, uint32_t count, int nblocks, unsigned long long* out);
 
+/* The shared arenas of a context, read-only, for tests that keep ONE context through many kinds of call and must see when an arena
+ * was reallocated (tests/test_context_session.py): address and size in bytes of arena `which` (null, 0: not allocated yet).
+ * PLAN_PYR and PLAN_TABLES stand for the per-frame-size plan arenas, which make_plan sizes together. */
+enum { PGORB_ARENA_STAGE_A = 0, PGORB_ARENA_PINNED = 1, PGORB_ARENA_SCRATCH = 2, PGORB_ARENA_STAGE_OUT = 3, PGORB_ARENA_XDESC = 4,
+       PGORB_ARENA_OUT_BLOCK = 5, PGORB_ARENA_VOCAB = 6, PGORB_ARENA_PLAN_PYR = 7, PGORB_ARENA_PLAN_TABLES = 8 };
+int  pgorb_debug_arena(const pgorb_ctx* ctx, int which, const void** ptr, int64_t* bytes);
+/* How the last pgorb_extract / pgorb_extract_batch ran its kernels: 0 direct launches, 1 captured into a graph and launched,
+ * 2 a replay of the captured graph; and the plan epoch (it moves with every new plan and every pgorb_set_option). */
+int  pgorb_debug_host_graph(const pgorb_ctx* ctx, int* last_call, int* plan_epoch);
+
 #ifdef __cplusplus
 }
 #endif

@@ -236,6 +236,7 @@ int pgorb_extract_batch(pgorb_ctx* c, const uint8_t* const* gray, int nframes, i
     const bool replay = graphable && G.exec && G.nframes == nframes && G.epoch == c->planEpoch && G.pinned == hv && G.outBytes == outBytes;
     auto launch = [&] { return run_batch(c, nullptr, true, nframes, w, h, stride, 0, (pgorb_keypoint*)(blk + oK), blk + oD, need, (int32_t*)(blk + oN), hs); };
     bool graph = replay;
+    G.last = replay ? 2 : 0;
     if (!replay) {
         const bool capture = graphable && G.seenFrames == nframes && G.seenEpoch == c->planEpoch;
         G.seenFrames = nframes; G.seenEpoch = c->planEpoch;
@@ -250,7 +251,7 @@ int pgorb_extract_batch(pgorb_ctx* c, const uint8_t* const* gray, int nframes, i
                 if (G.g) { (void)hipGraphDestroy(G.g); G.g = nullptr; }
                 hipGraphExec_t ex = nullptr;
                 graph = hipGraphInstantiate(&ex, g, nullptr, nullptr, 0) == hipSuccess;
-                if (graph) { G.g = g; G.exec = ex; G.nframes = nframes; G.epoch = c->planEpoch; G.pinned = hv; G.outBytes = outBytes; }
+                if (graph) { G.g = g; G.exec = ex; G.nframes = nframes; G.epoch = c->planEpoch; G.pinned = hv; G.outBytes = outBytes; G.last = 1; }
             }
             if (!graph) {
                 if (g) (void)hipGraphDestroy(g);
@@ -449,6 +450,24 @@ int pgorb_debug_level_keypoints(pgorb_ctx* c, int frame, int level)
     int32_t cnt = 0;
     PG_HIP(c, hipMemcpy(&cnt, c->plan.kpCount + frame * PG_MAXL + level, 4, hipMemcpyDeviceToHost));
     return cnt;
+}
+
+// ---- the context's shared arenas, for tests of one long-lived context (read-only; nothing in the library reads these) ------
+int pgorb_debug_arena(const pgorb_ctx* c, int which, const void** ptr, int64_t* bytes)
+{
+    if (!c || !ptr || !bytes) return PGORB_E_ARG;
+    if (which == PGORB_ARENA_PINNED) { *ptr = c->pinned; *bytes = (int64_t)c->pinnedBytes; return 0; }
+    const Arena* all[] = {&c->stageA, nullptr, &c->stageSfi, &c->stageOut, &c->xdesc, &c->outBlk, &c->vocab, &c->pyr, &c->tables};
+    if (which < 0 || which >= (int)(sizeof(all) / sizeof(all[0]))) return PGORB_E_ARG;
+    *ptr = all[which]->p; *bytes = (int64_t)all[which]->bytes;
+    return 0;
+}
+
+int pgorb_debug_host_graph(const pgorb_ctx* c, int* last_call, int* plan_epoch)
+{
+    if (!c || !last_call || !plan_epoch) return PGORB_E_ARG;
+    *last_call = c->hg.last; *plan_epoch = c->planEpoch;
+    return 0;
 }
 
 }  // extern "C"

@@ -52,7 +52,7 @@ struct pgorb_ctx {
     // as a HIP graph from the second call with the same plan / batch size on (PGORB_EXTRACT_NO_GRAPH=1: direct launches)
     hipStream_t sHost = nullptr;
     int useGraph = 1, planEpoch = 0;
-    struct HostGraph { hipGraph_t g = nullptr; hipGraphExec_t exec = nullptr; int nframes = 0, epoch = -1, seenFrames = 0, seenEpoch = -1; void* pinned = nullptr; size_t outBytes = 0; } hg;
+    struct HostGraph { hipGraph_t g = nullptr; hipGraphExec_t exec = nullptr; int nframes = 0, epoch = -1, seenFrames = 0, seenEpoch = -1; void* pinned = nullptr; size_t outBytes = 0; int last = 0; } hg;      // last: 0 direct, 1 captured, 2 replayed (pgorb_debug_host_graph)
     int vocabK = 0, vocabL = 0, vocabNodes = 0;
     int lastFrames = 0;
     bool lastAliased = false;

@@ -292,6 +292,20 @@ class ORBextractor:
     def debug_level_keypoints(self, frame, level):
         return self._check(self._L.pgorb_debug_level_keypoints(self._h, frame, level))
 
+    ARENAS = ("stageA", "pinned", "stageSfi", "stageOut", "xdesc", "outBlk", "vocab", "plan_pyr", "plan_tables")
+
+    def debug_arena(self, name):
+        """(address, bytes) of one of the context's shared arenas (pgorb_debug_arena; read-only, for the session tests)."""
+        ptr, n = C.c_void_p(), C.c_int64()
+        self._check(self._L.pgorb_debug_arena(self._h, self.ARENAS.index(name), C.byref(ptr), C.byref(n)))
+        return ptr.value or 0, n.value
+
+    def debug_host_graph(self):
+        """(how the last host-frame extract ran: 0 direct, 1 captured, 2 replayed; the plan epoch)."""
+        last, epoch = C.c_int32(), C.c_int32()
+        self._check(self._L.pgorb_debug_host_graph(self._h, C.byref(last), C.byref(epoch)))
+        return last.value, epoch.value
+
     # ---- Hamming (device) -------------------------------------------------------------------
     def hamming_matrix(self, a, b):
         a = np.ascontiguousarray(a, np.uint8).reshape(-1, 32)

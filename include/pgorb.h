@@ -662,6 +662,93 @@ int  pgorb_bow_vectors(int n, const uint32_t* word, const double* weight, const 
 double pgorb_bow_score_l1(const uint32_t* id1, const double* val1, int n1,
                           const uint32_t* id2, const double* val2, int n2);
 
+/* ---- Place recognition: KeyFrameDatabase candidate queries (csrc/place.hip) ---------------------------------------------------
+ * Reference (thirdparty/orb-slam2): Tracking::Relocalization asks KeyFrameDatabase::DetectRelocalizationCandidates
+ * (src/Tracking.cc:1330, src/KeyFrameDatabase.cc:212-310); LoopClosing::DetectLoop takes minScore as the lowest score against
+ * the connected key frames (src/LoopClosing.cc:120-141) and asks DetectLoopCandidates (src/KeyFrameDatabase.cc:89-210).
+ *
+ * BowVector table: frame f's BowVector is d_bow_id[f * cap .. f * cap + d_nbow[f]) (ascending word ids, no repeats) with its
+ * values at the same places of d_bow_val -- what TemplatedVocabulary::transform (TemplatedVocabulary.h:1126-1194) leaves in
+ * mBowVec.
+ *
+ * pgorb_bow_vectors_batch_device  the BowVector of every frame from pgorb_bow_transform_device's per-feature results
+ *   ([nframes][cap_per_frame], the first d_n[f] of each row), bit-equal to pgorb_bow_vectors: features with weight <= 0 are
+ *   skipped, a word's weights are added in feature order, the norm is the running double sum of fabs in ascending word order, every
+ *   value is divided by it when it is > 0.  One workgroup per frame: a stable sort by word id (ranks by counting on LDS), then
+ *   one sequential sum per word and one for the norm.  The context's vocabulary must be L1_NORM with TF_IDF or TF (else
+ *   PGORB_E_ARG); at most 8192 features per frame (PGORB_E_LIMIT).
+ * pgorb_bow_score_l1_batch_device  d_score[p] = L1Scoring::score(frame d_pair_a[p], frame d_pair_b[p]) (ScoringObject.cpp:23-60),
+ *   bit-equal to pgorb_bow_score_l1: one wave per pair, ONE running double sum over the common words in ascending word order.
+ *   This is the minScore loop of LoopClosing.cc:124-138; the caller takes the minimum over its non-bad connected key frames.
+ *   A pair index outside [0, nframes) reads as an empty vector.
+ *
+ * The two queries, over one table of frames:
+ *   d_in_db [nframes] u8      whether the frame is in the database.  Members must appear in the table in add() order
+ *                             (KeyFrameDatabase.cc:53-59 appends a key frame to every one of its words' lists, so all inverted
+ *                             lists share that order); other frames may sit anywhere and never share words.
+ *   d_neigh [nframes][10]     GetBestCovisibilityKeyFrames(10) in order, padded with -1; -1 and out-of-range indices are skipped
+ *   d_query [nq]              frame indices of the queries (out of range: an empty query)
+ *   d_score_state [nframes]   relocalisation form: the stored mRelocScore of every frame on entry; NULL = 0.0f.  The reference
+ *                             never initialises it (KeyFrame.cc:138), so ITS value for a never-scored key frame is
+ *                             indeterminate; here it is what the caller passes.  The loop form takes no state: every
+ *                             mLoopScore it reads was written by the same query.
+ *   loop form only            d_min_score [nq]; the connected sets (pKF->GetConnectedKeyFrames()) as CSR d_conn_start [nq + 1]
+ *                             into d_conn [nconn], in any order
+ *   d_cand [nq][ccap], d_ncand [nq]   the candidates in the reference's order; d_ncand is the full count, only the first ccap
+ *                             are written
+ *   d_common [nq][nframes]    (may be NULL) common words; 0 = the frame is not in lKFsSharingWords
+ *   d_score [nq][nframes]     (may be NULL) the stored scores afterwards: the state on entry, overwritten where a frame was scored
+ *   d_stats [nq][3]           (may be NULL) length of lKFsSharingWords, maxCommonWords, nscores
+ * Decomposition (proved in DESIGN.md section 4).  lKFsSharingWords (:99-117, :220-236) is the database members with a common word
+ * -- the loop form drops the connected key frames -- sorted by (smallest common word, table index), each with its number of
+ * common words.  k_place_overlap, one wave per (query, key frame), finds count, smallest common word and the score (one running
+ * double sum, rounded to float as `float si`).  k_place_decide, one workgroup per query: minCommonWords = (int)(max * 0.8f); a
+ * frame is scored iff count > minCommonWords; an entry of lScoreAndMatch (every scored frame; loop form: si >= minScore) reads
+ * only stored scores, so every entry accumulates on its own over its first 10 neighbours in order, in float, a strictly larger
+ * score moving pBestKF.  Relocalisation counts a neighbour with mnRelocQuery == id, i.e. every sharing frame: one that was not
+ * scored gives its STALE score from d_score_state.  The loop form also asks mnLoopWords > minCommonWords, so its reads are always
+ * fresh.  bestAccScore starts at 0 / minScore; entries with acc > 0.75f * best emit their pBestKF in list order, first
+ * occurrence only.
+ * Each query equals the reference called on the state it was given.  The reference runs queries one after another and the stale
+ * read sees earlier queries' scores: ordering queries that matter to each other is the caller's job -- feed d_score row q as the
+ * next call's d_score_state.  The batched forms do not check their inputs, but no index can cause an out-of-bounds access.
+ * Limits: PGORB_E_LIMIT above 65 536 frames, and above 65 535 queries in one batch.  Every per-query list lives in a global slab
+ * of 40 bytes per (query, frame) taken from the context's matcher scratch arena -- 40 * nq * nframes bytes, 167 MB for 64 queries
+ * over 65 536 frames --, so the scored set has no LDS bound, and what bounds nq is that arena's allocation (PGORB_E_HIP when the
+ * device cannot give it; split the batch).  The final ordering of the emitted candidates is by counting, quadratic in THEIR
+ * number.  The single host calls pad the CSR BowVectors to the longest one and refuse a padded table of more than 2^28 entries
+ * (nkf * longest BowVector) with PGORB_E_LIMIT.
+ * A context whose uploaded vocabulary is not L1_NORM refuses these calls (PGORB_E_ARG); without a vocabulary they run on the
+ * caller's BowVectors.
+ *
+ * Single host calls: BowVectors as CSR (bow_start [nkf + 1], bow_id, bow_val), neighbours as CSR (neigh_start [nkf + 1], neigh,
+ * at most 10 each), one query; staged as a one-query batch.  score_state [nkf] (may be NULL = zeros) is in/out; the loop form
+ * returns its stored scores in `score` (may be NULL).  They return the full candidate count (>= 0; the first ccap are written) and
+ * check their inputs: PGORB_E_ARG for unsorted or repeated word ids, indices out of range, a neighbour list longer than 10, start
+ * arrays that do not begin at 0 or that decrease. */
+int  pgorb_bow_vectors_batch_device(pgorb_ctx* ctx, const uint32_t* d_word, const double* d_weight, const int32_t* d_n, int nframes,
+                                    int cap_per_frame, uint32_t* d_bow_id, double* d_bow_val, int32_t* d_nbow, void* hip_stream);
+int  pgorb_bow_score_l1_batch_device(pgorb_ctx* ctx, const uint32_t* d_bow_id, const double* d_bow_val, const int32_t* d_nbow, int nframes,
+                                     int cap, const int32_t* d_pair_a, const int32_t* d_pair_b, int npairs, double* d_score,
+                                     void* hip_stream);
+int  pgorb_detect_relocalization_candidates_batch_device(pgorb_ctx* ctx, const uint32_t* d_bow_id, const double* d_bow_val,
+                                                         const int32_t* d_nbow, int nframes, int cap, const uint8_t* d_in_db,
+                                                         const int32_t* d_neigh, const int32_t* d_query, int nq,
+                                                         const float* d_score_state, int32_t* d_cand, int ccap, int32_t* d_ncand,
+                                                         int32_t* d_common, float* d_score, int32_t* d_stats, void* hip_stream);
+int  pgorb_detect_loop_candidates_batch_device(pgorb_ctx* ctx, const uint32_t* d_bow_id, const double* d_bow_val, const int32_t* d_nbow,
+                                               int nframes, int cap, const uint8_t* d_in_db, const int32_t* d_neigh,
+                                               const int32_t* d_query, int nq, const float* d_min_score, const int32_t* d_conn_start,
+                                               const int32_t* d_conn, int nconn, int32_t* d_cand, int ccap, int32_t* d_ncand,
+                                               int32_t* d_common, float* d_score, int32_t* d_stats, void* hip_stream);
+int  pgorb_detect_relocalization_candidates(pgorb_ctx* ctx, int nkf, const int32_t* bow_start, const uint32_t* bow_id,
+                                            const double* bow_val, const uint8_t* in_db, const int32_t* neigh_start, const int32_t* neigh,
+                                            int query, float* score_state, int32_t* cand, int ccap, int32_t* common, int32_t* stats);
+int  pgorb_detect_loop_candidates(pgorb_ctx* ctx, int nkf, const int32_t* bow_start, const uint32_t* bow_id, const double* bow_val,
+                                  const uint8_t* in_db, const int32_t* neigh_start, const int32_t* neigh, int query, float min_score,
+                                  const int32_t* conn, int nconn, int32_t* cand, int ccap, int32_t* common, float* score,
+                                  int32_t* stats);
+
 /* ---- after the path: what TrackImageSequence does to the finished trajectory ----
  * Host functions, double precision, no context needed (the reference runs them once per segment on
  * the CPU).  Quaternions are (w, x, y, z) like the JSON; all arrays are row-major.

@@ -35,6 +35,9 @@ SYMBOLS = (
     "pgorb_create_new_map_points", "pgorb_create_new_map_points_batch_device",
     "pgorb_fuse", "pgorb_fuse_batch_device",
     "pgorb_refresh_map_points", "pgorb_refresh_map_points_batch_device",
+    "pgorb_bow_vectors_batch_device", "pgorb_bow_score_l1_batch_device",
+    "pgorb_detect_relocalization_candidates", "pgorb_detect_relocalization_candidates_batch_device",
+    "pgorb_detect_loop_candidates", "pgorb_detect_loop_candidates_batch_device",
     "pgorb_search_by_projection_keyframe", "pgorb_search_by_projection_keyframe_batch_device",
     "pgorb_log_f", "pgorb_log_scale_factor", "pgorb_predict_scale",
     "pgorb_undistort_keypoints", "pgorb_undistort_keypoints_batch_device", "pgorb_image_bounds",
@@ -173,6 +176,18 @@ def lib():
     #  ref_obs, nsel, select, what, best_obs, status, stream)
     L.pgorb_refresh_map_points_batch_device.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, C.c_int] + [vp] * 6 + \
         [C.c_int, vp, C.c_int, vp, C.c_int, vp, vp, vp]
+    # (ctx, word, weight, n, nframes, cap, bow_id, bow_val, nbow, stream)
+    L.pgorb_bow_vectors_batch_device.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp]
+    # (ctx, bow_id, bow_val, nbow, nframes, cap, pair_a, pair_b, npairs, score, stream)
+    L.pgorb_bow_score_l1_batch_device.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp]
+    # (ctx, bow_id, bow_val, nbow, nframes, cap, in_db, neigh, query, nq, [state | min_score, conn_start, conn, nconn], cand, ccap, ncand,
+    #  common, score, stats, stream)
+    L.pgorb_detect_relocalization_candidates_batch_device.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, vp, C.c_int] + [vp] * 5
+    L.pgorb_detect_loop_candidates_batch_device.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp, C.c_int, vp, C.c_int] + \
+        [vp] * 5
+    # (ctx, nkf, bow_start, bow_id, bow_val, in_db, neigh_start, neigh, query, ...)
+    L.pgorb_detect_relocalization_candidates.argtypes = [vp, C.c_int] + [vp] * 6 + [C.c_int, vp, vp, C.c_int, vp, vp]
+    L.pgorb_detect_loop_candidates.argtypes = [vp, C.c_int] + [vp] * 6 + [C.c_int, C.c_float, vp, C.c_int, vp, C.c_int, vp, vp, vp]
     L.pgorb_undistort_keypoints.argtypes = [vp, vp, C.c_int, vp, vp, vp]
     L.pgorb_undistort_keypoints_batch_device.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp]
     L.pgorb_image_bounds.argtypes = [C.c_int, C.c_int, vp, vp, vp]

@@ -149,7 +149,7 @@ int pg_ctx_vocab_store(pgorb_ctx* c, const void* src, size_t nbytes, bool src_on
     if ((rc = ensure(c, c->vocab, nbytes))) return rc;
     if (src_on_device) PG_HIP(c, hipMemcpyAsync(c->vocab.p, src, nbytes, hipMemcpyDeviceToDevice, s));
     else PG_HIP(c, hipMemcpy(c->vocab.p, src, nbytes, hipMemcpyHostToDevice));
-    c->vocabK = hdr[2]; c->vocabL = hdr[3]; c->vocabNodes = hdr[4];
+    c->vocabK = hdr[2]; c->vocabL = hdr[3]; c->vocabNodes = hdr[4]; c->vocabScoring = hdr[6]; c->vocabWeighting = hdr[7];
     return 0;
 }
 // The receive side of the vocabulary broadcast (comm.hip): room for `nbytes` in the context's vocabulary arena (the collective
@@ -168,7 +168,7 @@ int pg_ctx_vocab_commit(pgorb_ctx* c, size_t nbytes, hipStream_t s)
     PG_HIP(c, hipSetDevice(c->prm.device));
     int32_t hdr[16];
     if (int rc = vocab_header_ok(c, c->vocab.p, nbytes, true, s, hdr)) return rc;
-    c->vocabK = hdr[2]; c->vocabL = hdr[3]; c->vocabNodes = hdr[4];
+    c->vocabK = hdr[2]; c->vocabL = hdr[3]; c->vocabNodes = hdr[4]; c->vocabScoring = hdr[6]; c->vocabWeighting = hdr[7];
     return 0;
 }
 void pg_ctx_vocab_drop(pgorb_ctx* c) { c->vocabK = c->vocabL = c->vocabNodes = 0; }
@@ -177,6 +177,12 @@ int pg_ctx_vocab_get(pgorb_ctx* c, const uint8_t** d_blob, int* k, int* L, int* 
     if (!c->vocab.p || !c->vocabNodes) return fail(c, PGORB_E_ARG, "no vocabulary uploaded");
     *d_blob = (const uint8_t*)c->vocab.p; *k = c->vocabK; *L = c->vocabL; *nnodes = c->vocabNodes;
     return 0;
+}
+bool pg_ctx_vocab_kind(pgorb_ctx* c, int* scoring, int* weighting)
+{
+    if (!c->vocab.p || !c->vocabNodes) return false;
+    *scoring = c->vocabScoring; *weighting = c->vocabWeighting;
+    return true;
 }
 
 extern "C" {

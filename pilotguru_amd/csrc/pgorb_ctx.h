@@ -54,6 +54,7 @@ struct pgorb_ctx {
     int useGraph = 1, planEpoch = 0;
     struct HostGraph { hipGraph_t g = nullptr; hipGraphExec_t exec = nullptr; int nframes = 0, epoch = -1, seenFrames = 0, seenEpoch = -1; void* pinned = nullptr; size_t outBytes = 0; int last = 0; } hg;      // last: 0 direct, 1 captured, 2 replayed (pgorb_debug_host_graph)
     int vocabK = 0, vocabL = 0, vocabNodes = 0;
+    int vocabScoring = 0, vocabWeighting = 0;  // the blob header's ScoringType / WeightingType (place.hip accepts L1_NORM with TF_IDF or TF)
     int lastFrames = 0;
     bool lastAliased = false;
     int lastFusedLaunches = 0;                // fused resize + detect launches the last batch issued (pgorb_get_option "fused_launches")

@@ -288,6 +288,7 @@ int pg_ctx_vocab_store(pgorb_ctx* c, const void* src, size_t nbytes, bool src_on
 int pg_ctx_vocab_reserve(pgorb_ctx* c, size_t nbytes, void** p);
 int pg_ctx_vocab_commit(pgorb_ctx* c, size_t nbytes, hipStream_t s);
 int pg_ctx_vocab_get(pgorb_ctx* c, const uint8_t** d_blob, int* k, int* L, int* nnodes);
+bool pg_ctx_vocab_kind(pgorb_ctx* c, int* scoring, int* weighting);             // false: no vocabulary uploaded
 void pg_ctx_vocab_drop(pgorb_ctx* c);
 
 // One synchronous host call of a batched device form.  Its arrays are 64-byte aligned regions at the same offsets in the

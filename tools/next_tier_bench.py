@@ -19,7 +19,12 @@ next to each, the oracle's CPU time for the same work (1 thread, a few frames, s
                distribution of tests/map_point_cases.py; beside it the download + host loop + upload it replaces, the host loop
                being OUR restatement (tests/map_point_reference.py, Python, one core), not ORB-SLAM2.  --refresh-only runs this row alone
 
-usage: python tools/next_tier_bench.py [--batch 128] [--out profiles/r02_next_tier.txt] [--refresh-only]"""
+  place        KeyFrameDatabase::DetectRelocalizationCandidates (KeyFrameDatabase.cc:212-310) as one batched resident call: 4096 key
+               frames of about 1500 words, 64 queries; beside it a plain C++ std::map / std::list restatement of the same queries
+               on one core (tools/place_comparator.py, compiled by the tool; OUR restatement, not ORB-SLAM2), whose results the
+               GPU's must equal.  --place-only runs this row alone
+
+usage: python tools/next_tier_bench.py [--batch 128] [--out profiles/r02_next_tier.txt] [--refresh-only | --place-only]"""
 import argparse, ctypes as C, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -35,6 +40,7 @@ ap.add_argument("--batch", type=int, default=128)
 ap.add_argument("--out", default="")
 ap.add_argument("--features", type=int, default=2000, help="4000 = the initialisation extractor (2 * nFeatures, Tracking.cc:143)")
 ap.add_argument("--refresh-only", action="store_true", help="the map-point refresh rows alone (no ride, no vocabulary)")
+ap.add_argument("--place-only", action="store_true", help="the place-recognition row alone (no ride, no vocabulary)")
 a = ap.parse_args()
 w, h, nf, B = 1920, 1080, a.features, a.batch
 
@@ -93,6 +99,59 @@ def refresh_lines(rows):
     return lines
 
 
+def place_lines(ext, nkf=4096, nwords=1500, nq=64, vocab=50000, ccap=256):
+    """The relocalisation candidate query, batched: GPU ms (HIP events, median of 9) beside the C++ comparator's seconds."""
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import place_comparator as CMP
+    rng = np.random.RandomState(12)
+    N = nkf + nq
+    cap = int(nwords * 1.1) + 1
+    ids, val, nb = np.zeros((N, cap), np.uint32), np.zeros((N, cap), np.float64), np.zeros(N, np.int32)
+    pool = vocab // 8                                       # half of every vector's words come from a small pool: dense sharing
+    for f in range(N):
+        n = int(rng.randint(int(nwords * 0.9), cap))
+        w = np.unique(np.concatenate([rng.randint(0, pool, n // 2), rng.randint(0, vocab, n - n // 2)]))
+        v = rng.uniform(0.05, 1.0, len(w))
+        nb[f] = len(w); ids[f, :len(w)] = w; val[f, :len(w)] = v / v.sum()
+    in_db = np.zeros(N, np.uint8); in_db[:nkf] = 1
+    neigh = np.full((N, 10), -1, np.int32)
+    neigh[:nkf] = rng.randint(0, nkf, (nkf, 10))
+    queries = np.arange(nkf, N, dtype=np.int32)
+    state = rng.uniform(0, 0.05, N).astype(np.float32)
+    G = lambda x: torch.from_numpy(np.ascontiguousarray(x)).cuda()
+    p = lambda t: C.c_void_p(t.data_ptr())
+    s = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    dI, dV, dN, dDb, dNe, dQ, dS = G(ids.view(np.int32)), G(val), G(nb), G(in_db), G(neigh), G(queries), G(state)
+    cand = torch.full((nq, ccap), -1, dtype=torch.int32, device="cuda"); ncand = torch.empty(nq, dtype=torch.int32, device="cuda")
+    common = torch.empty((nq, N), dtype=torch.int32, device="cuda"); score = torch.empty((nq, N), dtype=torch.float32, device="cuda")
+    stats = torch.empty((nq, 3), dtype=torch.int32, device="cuda")
+    call = lambda: ext._check(ext._L.pgorb_detect_relocalization_candidates_batch_device(ext._h, p(dI), p(dV), p(dN), N, cap, p(dDb), p(dNe), p(dQ), nq,
+                              p(dS), p(cand), ccap, p(ncand), p(common), p(score), p(stats), s))
+    t_gpu = timed(call)
+    start = np.zeros(N + 1, np.int32); start[1:] = np.cumsum(nb)
+    mask = np.arange(cap)[None, :] < nb[:, None]
+    nstart = np.zeros(N + 1, np.int32); nstart[1:nkf + 1] = 10 * np.arange(1, nkf + 1); nstart[nkf + 1:] = 10 * nkf
+    c_cand, c_ncand, c_common, c_score, c_stats, sec = CMP.run(False, start, ids[mask], val[mask], in_db, nstart, neigh[:nkf].reshape(-1), queries,
+                                                                state, ccap=ccap)
+    g_ncand = ncand.cpu().numpy()
+    assert np.array_equal(g_ncand, c_ncand) and np.array_equal(common.cpu().numpy(), c_common) and np.array_equal(stats.cpu().numpy(), c_stats)
+    assert score.cpu().numpy().tobytes() == c_score.tobytes()
+    g_cand = cand.cpu().numpy()
+    assert all(np.array_equal(g_cand[q, :min(n, ccap)], c_cand[q, :min(n, ccap)]) for q, n in enumerate(c_ncand))
+    return ["# place recognition (DetectRelocalizationCandidates), one batched resident call, HIP events, median of 9;",
+            "# CPU = the tool's C++ std::map / std::list restatement on one core (NOT ORB-SLAM2), its queries alone, results equal",
+            "%-86s %10s %12s %14s" % ("call", "GPU ms", "CPU ms", "candidates"),
+            "%-86s %10.3f %12.1f %14d" % ("place: %d key frames of %d words (mean), %d queries, sharing %d, scored %d per query" %
+                                          (nkf, int(nb.mean()), nq, int(c_stats[:, 0].mean()), int(c_stats[:, 2].mean())), t_gpu, sec * 1e3,
+                                          int(c_ncand.sum()))]
+
+
+if a.place_only:
+    lines = ["# python tools/next_tier_bench.py --place-only   (MI355X)"] + place_lines(pg.ORBextractor(nf, 1.2, 8, 20, 7, max_width=w, max_height=h))
+    print("\n".join(lines))
+    if a.out:
+        open(a.out, "w").write("\n".join(lines) + "\n")
+    sys.exit(0)
 if a.refresh_only:
     lines = ["# python tools/next_tier_bench.py --refresh-only   (MI355X)"] + refresh_lines(refresh_rows(pg.ORBextractor(nf, 1.2, 8, 20, 7, max_width=w, max_height=h)))
     print("\n".join(lines))

@@ -522,6 +522,133 @@ int  pgorb_fuse_batch_device(pgorb_ctx* ctx,
         int32_t* d_action, int32_t* d_best_idx, int32_t* d_best_dist, int32_t* d_kf_point_out, int32_t* d_nfused,
         void* hip_stream);
 
+/* ---- Loop closing: the two Scw matchers, then SearchByBoW(KF, KF) and SearchBySim3 -------------------------------------------------------------------------------------
+ * Both take the key frame as pgorb_fuse does (undistorted mvKeysUn, descriptors, the Frame's bounds, of which the key frame's
+ * int copies serve IsInImage -- strict on the max side -- and KeyFrame::GetFeaturesInArea, src/KeyFrame.cc:672-716), the
+ * map-point TABLE of pgorb_fuse without observation lists (pose fields with the plain mfMin/MaxDistance, descriptor, bad flag),
+ * and the DECOMPOSED Scw of :301-305 / :990-994 as a pgorb_kf_pose: Tcw = [Rcw | tcw] with Rcw = sRcw/scw and tcw =
+ * Scw(0..2, 3)/scw, Ow = -Rcw.t()*tcw, and the key frame's camera.  Those once-per-call cv::Mat steps stay with the owner of
+ * the Sim3.  Per query, in this order: bad or in spAlreadyFound; z < 0; IsInImage; the depth range 0.8f*mfMinDistance ..
+ * 1.2f*mfMaxDistance on cv::norm(p3Dw - Ow); PO.dot(Pn) < 0.5*dist in double; MapPoint::PredictScale under pgorb_log_f with the
+ * context's mfLogScaleFactor; radius th*mvScaleFactors[level]; octaves [level - 1, level], taken to lie in [0, levels); the
+ * first smallest descriptor distance (strict <); bestDist <= TH_LOW (50).  No chi-square test.  The float / double readings are
+ * Fuse's.  queries[q] = a table index; unlike pgorb_fuse a point MAY be queried twice (the reference
+ * does not forbid it).  spAlreadyFound is the state on entry and is never updated (:308, :997).
+ *
+ *   pgorb_search_by_projection_sim3   ORBmatcher::SearchByProjection(pKF, Scw, vpPoints, vpMatched, th) (src/ORBmatcher.cc:
+ *       292-405; LoopClosing::ComputeSim3, src/LoopClosing.cc:375, th = 10).  matched_in[i] = the table index of vpMatched[i] or
+ *       -1 (NULL = all -1); spAlreadyFound = the set of those.  Candidates whose vpMatched[idx] is set are skipped (:377), and an
+ *       accepted query sets it: THE ROUTINE DEPENDS ON ORDER, a later query takes its next best.  Outputs: assigned[i] = the
+ *       query index whose point this call wrote into vpMatched[i], or -1; matched_out (may be NULL) = vpMatched afterwards.
+ *       Returns nmatches.  Exact decomposition: a query takes its smallest-distance untaken candidate only if that distance is
+ *       <= 50, so candidates above 50 are dropped from the lists without changing any decision; the lists of all queries are
+ *       built in parallel in the reference's scan order, then one workgroup per problem decides the queries in rounds of
+ *       provably independent ones (a query is decided once no undecided earlier query lists any of its untaken candidates).
+ *   pgorb_fuse_sim3   ORBmatcher::Fuse(pKF, Scw, vpPoints, th, vpReplacePoint) (src/ORBmatcher.cc:981-1104;
+ *       LoopClosing::SearchAndFuse, src/LoopClosing.cc:601, th = 4, once per connected key frame).  kf_point[i] = the table index
+ *       of GetMapPoint(i) or -1 (NULL = all empty); spAlreadyFound = GetMapPoints() on entry.  IsInKeyFrame is not consulted and
+ *       no Replace happens here, so no observation lists.  action[q]: PGORB_FUSE_SKIPPED (bad, already found, or a test before
+ *       the descriptor loop failed), PGORB_FUSE_NO_MATCH, PGORB_FUSE_ADDED (the slot was empty: AddObservation + AddMapPoint),
+ *       PGORB_FUSE_KF_POINT_BAD (a bad occupant: nothing happens, but the query counts), and PGORB_FUSE_REPLACE_REQUESTED:
+ *       vpReplacePoint[q] = pMPinKF, with replace_point[q] = the occupant's table index (-1 for every other action).  Matching
+ *       never reads the slots, so it comes from the entry state, one lane per query; per slot the first matched query in list
+ *       order finds it empty and is ADDED (an atomicMin of the query index), every later one sees that query's point as the
+ *       occupant -- a repeated query then points at itself.  best_idx / best_dist (may be NULL) = -1 / -1 for a skipped query,
+ *       -1 / 256 when no candidate passed the octave test; kf_point_out (may be NULL) = the slots afterwards.  Returns nFused.
+ *       The caller replays ADDED and, under the map mutex, Replace of the requested points (LoopClosing.cc:607-615).
+ *   Single calls: PGORB_E_ARG on an index out of range (queries may not be NULL points: the reference dereferences them), th <= 0,
+ *   empty bounds; PGORB_E_LIMIT above 16000 keypoints.
+ *   Batched, resident forms: problem p runs its queries d_queries[p][0 .. d_nq[p]) against key frame d_kf[p] of one batch in the
+ *   layout of pgorb_extract_batch_device, grids as pgorb_frame_grid_batch_device writes them (same bounds); d_pose [nframes];
+ *   d_kf_point [nframes][cap_per_frame] but d_matched_in [nprob][cap_per_frame] (both may be NULL).  Outputs [nprob][qcap]
+ *   (action, replace_point, best_idx, best_dist; entries past d_nq[p] are not written) or [nprob][cap_per_frame] (assigned,
+ *   matched_out, kf_point_out), counts [nprob].  These forms do not check their inputs: indices out of range count as NULL /
+ *   empty.  Problems that share a key frame see the same entry state; ordering them is the caller's. */
+#define PGORB_FUSE_REPLACE_REQUESTED 6
+int  pgorb_search_by_projection_sim3(pgorb_ctx* ctx,
+        const pgorb_keypoint* kps, const uint8_t* desc, int n, const pgorb_kf_pose* scw_pose,
+        float min_x, float max_x, float min_y, float max_y, const int32_t* matched_in /*[n] or NULL*/,
+        int npoints, const pgorb_map_point* points, const uint8_t* point_desc /*[npoints][32]*/, const uint8_t* point_bad /*[npoints] or NULL*/,
+        int nq, const int32_t* queries /*[nq]*/, int th, int32_t* assigned /*[n]*/, int32_t* matched_out /*[n] or NULL*/);
+int  pgorb_search_by_projection_sim3_batch_device(pgorb_ctx* ctx,
+        const pgorb_keypoint* d_kps, const uint8_t* d_desc, const int32_t* d_n, int cap_per_frame,
+        const int32_t* d_grid_start, const int32_t* d_grid_idx, const int32_t* d_kf /*[nprob]*/, int nprob,
+        const pgorb_kf_pose* d_scw_pose, float min_x, float max_x, float min_y, float max_y,
+        const int32_t* d_matched_in, int npoints, const pgorb_map_point* d_points, const uint8_t* d_point_desc,
+        const uint8_t* d_point_bad, int qcap, const int32_t* d_nq, const int32_t* d_queries, int th,
+        int32_t* d_assigned, int32_t* d_matched_out, int32_t* d_nmatches, void* hip_stream);
+int  pgorb_fuse_sim3(pgorb_ctx* ctx,
+        const pgorb_keypoint* kps, const uint8_t* desc, int n, const pgorb_kf_pose* scw_pose,
+        float min_x, float max_x, float min_y, float max_y, const int32_t* kf_point /*[n] or NULL = all empty*/,
+        int npoints, const pgorb_map_point* points, const uint8_t* point_desc /*[npoints][32]*/, const uint8_t* point_bad /*[npoints] or NULL*/,
+        int nq, const int32_t* queries /*[nq]*/, float th, int32_t* action /*[nq]*/, int32_t* replace_point /*[nq]*/,
+        int32_t* best_idx /*[nq] or NULL*/, int32_t* best_dist /*[nq] or NULL*/, int32_t* kf_point_out /*[n] or NULL*/);
+int  pgorb_fuse_sim3_batch_device(pgorb_ctx* ctx,
+        const pgorb_keypoint* d_kps, const uint8_t* d_desc, const int32_t* d_n, int cap_per_frame,
+        const int32_t* d_grid_start, const int32_t* d_grid_idx, const int32_t* d_kf /*[nprob]*/, int nprob,
+        const pgorb_kf_pose* d_scw_pose, float min_x, float max_x, float min_y, float max_y,
+        const int32_t* d_kf_point, int npoints, const pgorb_map_point* d_points, const uint8_t* d_point_desc,
+        const uint8_t* d_point_bad, int qcap, const int32_t* d_nq, const int32_t* d_queries, float th,
+        int32_t* d_action, int32_t* d_replace_point, int32_t* d_best_idx, int32_t* d_best_dist, int32_t* d_kf_point_out,
+        int32_t* d_nfused, void* hip_stream);
+
+/*   pgorb_search_by_bow_keyframes   ORBmatcher::SearchByBoW(KeyFrame* pKF1, KeyFrame* pKF2, vpMatches12) (src/ORBmatcher.cc:
+ *       524-657; LoopClosing::ComputeSim3, src/LoopClosing.cc:265, once per loop candidate).  Both key frames come as descriptors,
+ *       the angles of mvKeysUn, and their FeatureVector CSR arrays (pgorb_bow_vectors / pgorb_feature_vectors_batch_device: node
+ *       ids ascending); point_valid1[i] / point_valid2[j] = the keypoint has a map point and it is not bad.  matches12[i1] = the
+ *       KF2 keypoint whose map point the reference writes to vpMatches12[i1], or -1; returns nmatches.  Unlike pgorb_search_by_bow:
+ *       bestDist1 < TH_LOW is STRICT (:600); the ratio test is on floats (:602); KF2's side is masked by validity and by
+ *       vbMatched2 (:578-582), which only an accepted match writes (:605); the rotation bin uses mvKeysUn angles of both.
+ *       A KF2 feature belongs to one vocabulary node, so nodes are independent and inside a node KF1's features go in
+ *       FeatureVector order: one wave per (pair, common node), then one finishing wave per pair (count, rotation histogram).
+ *       The single call checks its FeatureVectors (PGORB_E_ARG: starts not rising from 0, a feature index past n, node ids not
+ *       ascending).  THE BATCHED FORM TRUSTS ITS FeatureVectors, as pgorb_search_for_triangulation_batch_device does: d_nfv /
+ *       d_fv_* must be what pgorb_feature_vectors_batch_device writes.  d_point_valid1 / 2 and d_matches12 are
+ *       [npairs][cap_per_frame], d_nmatches [npairs]. */
+int  pgorb_search_by_bow_keyframes(pgorb_ctx* ctx,
+        const uint8_t* desc1, const float* angle1, const uint8_t* point_valid1, int n1,
+        const uint32_t* fv1_node, const int32_t* fv1_start, const uint32_t* fv1_feat, int nfv1,
+        const uint8_t* desc2, const float* angle2, const uint8_t* point_valid2, int n2,
+        const uint32_t* fv2_node, const int32_t* fv2_start, const uint32_t* fv2_feat, int nfv2,
+        float nnratio, int check_orientation, int32_t* matches12 /*[n1]*/);
+int  pgorb_search_by_bow_keyframes_batch_device(pgorb_ctx* ctx,
+        const pgorb_keypoint* d_kps, const uint8_t* d_desc, const int32_t* d_n, int cap_per_frame,
+        const uint32_t* d_fv_node, const int32_t* d_fv_start, const uint32_t* d_fv_feat, const int32_t* d_nfv,
+        const int32_t* d_pair_kf1, const int32_t* d_pair_kf2, int npairs, const uint8_t* d_point_valid1, const uint8_t* d_point_valid2,
+        float nnratio, int check_orientation, int32_t* d_matches12, int32_t* d_nmatches, void* hip_stream);
+
+/*   pgorb_search_by_sim3   ORBmatcher::SearchBySim3(pKF1, pKF2, vpMatches12, s12, R12, t12, th) (src/ORBmatcher.cc:1106-1330;
+ *       LoopClosing::ComputeSim3, src/LoopClosing.cc:323, th = 7.5).  Per key frame: undistorted keypoints, descriptors, the pose
+ *       (Tcw = GetRotation() | GetTranslation(); of pose2 only Tcw is read: BOTH projections use pKF1's fx, fy, cx, cy,
+ *       :1109-1112) and the slots kf_point[i] = a table index or -1 (NULL = none) into a pgorb_map_point table (the normal is
+ *       unused).  pgorb_sim3 holds the transform as the caller's own cv::Mat arithmetic of :1123-1125 produced it: sR12 = s12*R12,
+ *       t12, sR21 = (1.0/s12)*R12.t(), t21 = -sR21*t12 (row-major); those once-per-call products stay with the owner of the
+ *       poses.  already1[i] / already2[j] are vbAlreadyMatched1 / 2 of :1133-1146 (NULL = none); the caller owns
+ *       GetIndexInKeyFrame.  Per slot and direction: no point, already matched or bad -> nothing; p3Dc = Rw*p + tw, then sR*p3Dc
+ *       + t (gemm's small-matrix path, the translation as C); z < 0; IsInImage of the key frame's int bounds; dist3D = cv::norm
+ *       of the CAMERA-FRAME vector (double); the depth range 0.8f*mfMinDistance .. 1.2f*mfMaxDistance; PredictScale; radius
+ *       th*mvScaleFactors[level]; octaves [level - 1, level]; the first smallest distance; bestDist <= TH_HIGH (100).  No
+ *       viewing-angle and no chi-square test.  match12[i1] = the KF2 keypoint of every NEWLY found pair, those with
+ *       vnMatch2[vnMatch1[i1]] == i1 (:1314-1327), or -1; returns nFound.  Nothing depends on order: one lane per (pair,
+ *       direction, slot), then one agreement pass.  PGORB_E_ARG: a slot index out of range, th <= 0, empty bounds.
+ *       Batched: pair p matches key frames d_pair_kf1[p] and d_pair_kf2[p] of one batch (layout and grids as above);
+ *       d_pose and d_kf_point go by frame, d_sim3 [npairs], d_already1 / 2 and d_match12 [npairs][cap_per_frame] (entries past
+ *       the key frame's d_n are not written), d_nfound [npairs].  Unchecked: indices out of range count as empty. */
+typedef struct pgorb_sim3 { float sR12[9], t12[3], sR21[9], t21[3]; } pgorb_sim3;
+int  pgorb_search_by_sim3(pgorb_ctx* ctx,
+        const pgorb_keypoint* kps1, const uint8_t* desc1, int n1, const pgorb_kf_pose* pose1, const int32_t* kf_point1, const uint8_t* already1,
+        const pgorb_keypoint* kps2, const uint8_t* desc2, int n2, const pgorb_kf_pose* pose2, const int32_t* kf_point2, const uint8_t* already2,
+        float min_x, float max_x, float min_y, float max_y,
+        int npoints, const pgorb_map_point* points, const uint8_t* point_desc, const uint8_t* point_bad /*[npoints] or NULL*/,
+        const pgorb_sim3* sim3, float th, int32_t* match12 /*[n1]*/);
+int  pgorb_search_by_sim3_batch_device(pgorb_ctx* ctx,
+        const pgorb_keypoint* d_kps, const uint8_t* d_desc, const int32_t* d_n, int cap_per_frame,
+        const int32_t* d_grid_start, const int32_t* d_grid_idx, const int32_t* d_pair_kf1, const int32_t* d_pair_kf2, int npairs,
+        const pgorb_kf_pose* d_pose, float min_x, float max_x, float min_y, float max_y,
+        const int32_t* d_kf_point, int npoints, const pgorb_map_point* d_points, const uint8_t* d_point_desc, const uint8_t* d_point_bad,
+        const pgorb_sim3* d_sim3, const uint8_t* d_already1, const uint8_t* d_already2, float th,
+        int32_t* d_match12, int32_t* d_nfound, void* hip_stream);
+
 /* ---- Map-point refresh: the distinctive descriptor and the normal / depth range of many points --------------------------
  *   pgorb_refresh_map_points   for every selected point what MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:259-324)
  *       followed by MapPoint::UpdateNormalAndDepth (:347-388) would store, exactly.  The reference runs the pair once per point at

@@ -6,6 +6,6 @@ and the synthetic ride generator used by tests and bench (synth.py).
 """
 from .orb import KEYPOINT_DTYPE, DeviceFrameStream, Frame, FrameStream, MapPoints, ORBextractor, ORBmatcher  # noqa: F401
 from .orb import KF_POSE_DTYPE, NEW_MAP_POINT_DTYPE, LocalMapping, kf_pose  # noqa: F401
-from .orb import MAP_POINT_DTYPE, MapPointTable  # noqa: F401
+from .orb import MAP_POINT_DTYPE, MapPointTable, SIM3_DTYPE, sim3_pose, sim3_record  # noqa: F401
 from .orb import MP_BOTH, MP_DESCRIPTOR, MP_LIMIT, MP_MAX_OBS, MP_NORMAL_DEPTH  # noqa: F401
 from .place import KeyFrameDatabase  # noqa: F401

@@ -34,6 +34,10 @@ SYMBOLS = (
     "pgorb_search_for_triangulation", "pgorb_search_for_triangulation_batch_device",
     "pgorb_create_new_map_points", "pgorb_create_new_map_points_batch_device",
     "pgorb_fuse", "pgorb_fuse_batch_device",
+    "pgorb_search_by_projection_sim3", "pgorb_search_by_projection_sim3_batch_device",
+    "pgorb_fuse_sim3", "pgorb_fuse_sim3_batch_device",
+    "pgorb_search_by_sim3", "pgorb_search_by_sim3_batch_device",
+    "pgorb_search_by_bow_keyframes", "pgorb_search_by_bow_keyframes_batch_device",
     "pgorb_refresh_map_points", "pgorb_refresh_map_points_batch_device",
     "pgorb_bow_vectors_batch_device", "pgorb_bow_score_l1_batch_device",
     "pgorb_detect_relocalization_candidates", "pgorb_detect_relocalization_candidates_batch_device",
@@ -169,6 +173,24 @@ def lib():
     L.pgorb_fuse.argtypes = [vp, vp, vp, C.c_int, vp, C.c_uint64] + f4 + [vp, C.c_int] + [vp] * 5 + [C.c_int, vp, C.c_float] + [vp] * 4
     L.pgorb_fuse_batch_device.argtypes = [vp, vp, vp, vp, C.c_int, vp, vp, vp, C.c_int, vp, vp] + f4 + [vp, C.c_int] + [vp] * 5 + \
         [C.c_int, vp, vp, C.c_float] + [vp] * 5 + [vp]
+    # (ctx, kps, desc, n, scw_pose, bounds x 4, matched_in, npoints, points, point_desc, point_bad, nq, queries, th, assigned, matched_out)
+    L.pgorb_search_by_projection_sim3.argtypes = [vp, vp, vp, C.c_int, vp] + f4 + [vp, C.c_int, vp, vp, vp, C.c_int, vp, C.c_int, vp, vp]
+    L.pgorb_search_by_projection_sim3_batch_device.argtypes = [vp, vp, vp, vp, C.c_int, vp, vp, vp, C.c_int, vp] + f4 + \
+        [vp, C.c_int, vp, vp, vp, C.c_int, vp, vp, C.c_int] + [vp] * 4
+    # (ctx, [desc, angle, point_valid, n, fv x 3, nfv] x 2, nnratio, check, matches12)
+    L.pgorb_search_by_bow_keyframes.argtypes = [vp] + ([vp] * 3 + [C.c_int] + [vp] * 3 + [C.c_int]) * 2 + [C.c_float, C.c_int, vp]
+    # (ctx, kps, desc, n, cap, fv x 3, nfv, pair_kf1, pair_kf2, npairs, point_valid1, point_valid2, nnratio, check, matches12, nmatches, stream)
+    L.pgorb_search_by_bow_keyframes_batch_device.argtypes = [vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp, C.c_int, vp, vp, C.c_float,
+                                                             C.c_int, vp, vp, vp]
+    # (ctx, [kps, desc, n, pose, kf_point, already] x 2, bounds x 4, npoints, points, point_desc, point_bad, sim3, th, match12)
+    L.pgorb_search_by_sim3.argtypes = [vp] + [vp, vp, C.c_int, vp, vp, vp] * 2 + f4 + [C.c_int, vp, vp, vp, vp, C.c_float, vp]
+    L.pgorb_search_by_sim3_batch_device.argtypes = [vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, C.c_int, vp] + f4 + \
+        [vp, C.c_int, vp, vp, vp, vp, vp, vp, C.c_float, vp, vp, vp]
+    # (ctx, kps, desc, n, scw_pose, bounds x 4, kf_point, npoints, points, point_desc, point_bad, nq, queries, th, action, replace_point,
+    #  best_idx, best_dist, kf_point_out)
+    L.pgorb_fuse_sim3.argtypes = [vp, vp, vp, C.c_int, vp] + f4 + [vp, C.c_int, vp, vp, vp, C.c_int, vp, C.c_float] + [vp] * 5
+    L.pgorb_fuse_sim3_batch_device.argtypes = [vp, vp, vp, vp, C.c_int, vp, vp, vp, C.c_int, vp] + f4 + \
+        [vp, C.c_int, vp, vp, vp, C.c_int, vp, vp, C.c_float] + [vp] * 7
     # (ctx, nkf, kps[], desc[], n, pose, kf_bad, npoints, points, point_desc, point_bad, obs_start, obs_frame, obs_idx, ref_obs, nsel,
     #  select, what, best_obs, status)
     L.pgorb_refresh_map_points.argtypes = [vp, C.c_int] + [vp] * 5 + [C.c_int] + [vp] * 7 + [C.c_int, vp, C.c_int, vp, vp]

@@ -1,5 +1,6 @@
-// match_common.h -- what the Frame side, the guided matchers, CreateNewMapPoints, Fuse and the map-point refresh share: included by
-// frame.hip, window_match.hip, node_match.hip, mapping.hip, fuse.hip and map_point.hip, and by no other translation unit.
+// match_common.h -- what the Frame side, the guided matchers, CreateNewMapPoints, Fuse, loop closing's matchers and the map-point refresh
+// share: included by frame.hip, window_match.hip, node_match.hip, mapping.hip, fuse.hip, loop.hip and map_point.hip, and by no other
+// translation unit.
 #pragma once
 #include "pgorb_internal.h"
 #include <algorithm>

@@ -460,6 +460,26 @@ class ORBmatcher:
             self.mfNNratio, int(self.mbCheckOrientation), _p(out)))
         return nm, out[:F.N].copy()
 
+    def SearchByBoWKeyFrames(self, ext, desc1, angle1, point_valid1, featvec1, desc2, angle2, point_valid2, featvec2):
+        """ORBmatcher::SearchByBoW(pKF1, pKF2, vpMatches12) (src/ORBmatcher.cc:524-657).  Per key frame: descriptors, the angles
+        of mvKeysUn, point_valid[i] = the keypoint has a map point that is not bad, and the FeatureVector as the (nodes, starts,
+        features) triple of ORBVocabulary.transform().  Returns (nmatches, matches12) with matches12[i1] = the KF2 keypoint or -1."""
+        n1, n2 = len(angle1), len(angle2)
+        d1, d2 = _arr(desc1, np.uint8, n1, "desc1", 32), _arr(desc2, np.uint8, n2, "desc2", 32)
+        a1, a2 = _arr(angle1, np.float32, n1, "angle1"), _arr(angle2, np.float32, n2, "angle2")
+        v1, v2 = _arr(point_valid1, np.uint8, n1, "point_valid1"), _arr(point_valid2, np.uint8, n2, "point_valid2")
+        A, B = _featvec(featvec1, "featvec1"), _featvec(featvec2, "featvec2")
+        for fv, n, name in ((A, n1, "featvec1"), (B, n2, "featvec2")):
+            m = int(fv[1][-1])
+            if fv[1][0] != 0 or np.any(np.diff(fv[1]) < 0) or m > n or (m and int(fv[2][:m].max()) >= n) or np.any(np.diff(fv[0].astype(np.int64)) <= 0):
+                raise ValueError("SearchByBoWKeyFrames: %s is not a FeatureVector of %d features (ascending nodes, rising starts)" % (name, n))
+        out = np.full(max(n1, 1), -1, np.int32)
+        nm = ext._check(ext._L.pgorb_search_by_bow_keyframes(
+            ext._h, _p(d1), _p(a1), _p(v1), n1, _p(A[0]), _p(A[1]), _p(A[2]), len(A[0]),
+            _p(d2), _p(a2), _p(v2), n2, _p(B[0]), _p(B[1]), _p(B[2]), len(B[0]),
+            self.mfNNratio, int(self.mbCheckOrientation), _p(out)))
+        return nm, out[:n1].copy()
+
     def SearchForTriangulation(self, KF1, KF2, F12, epipole, fv1, fv2, has_point1=None, has_point2=None):
         """SearchForTriangulation(pKF1, pKF2, F12, vMatchedPairs, bOnlyStereo=false) (src/ORBmatcher.cc:659-825, 142-159) on
         the undistorted keypoints of two Frames.  F12: 3x3 (or 9) float32, F12.at<float>(r, c) row-major; epipole = (ex, ey) in
@@ -535,6 +555,87 @@ class ORBmatcher:
         return nf, action[:nq].copy(), bi[:nq].copy(), bd[:nq].copy(), out[:KF.N].copy()
 
     @staticmethod
+    def _loop_args(name, KF, slots, table, queries, bounds):
+        """The checked inputs FuseSim3 and SearchByProjectionSim3 share."""
+        kp, desc = _frame(KF, "KF")
+        bounds = KF.bounds if bounds is None else bounds
+        if len(bounds) != 4:
+            raise ValueError("%s: bounds must be (min_x, max_x, min_y, max_y)" % name)
+        sl = np.full(max(KF.N, 1), -1, np.int32) if slots is None else _arr(slots, np.int32, KF.N, name + " slots")
+        q = np.ascontiguousarray(queries, np.int32).reshape(-1)
+        if len(q) and int(np.min(q)) < 0:
+            raise ValueError("%s: a query is NULL or negative (the reference dereferences every point)" % name)
+        table.check_indices(q, "queries", name)
+        table.check_indices(sl[:KF.N], "slots", name)
+        return kp, desc, [float(b) for b in bounds], sl, q
+
+    def SearchBySim3(self, KF1, KF2, pose1, pose2, kf_point1, kf_point2, table, sim3, already1=None, already2=None, th=7.5,
+                     bounds=None):
+        """ORBmatcher::SearchBySim3(pKF1, pKF2, vpMatches12, s12, R12, t12, th) (src/ORBmatcher.cc:1106-1330), monocular.  KF1 /
+        KF2: Frame-like objects; pose1 / pose2: KF_POSE_DTYPE records (GetRotation() | GetTranslation(); both projections use
+        pose1's camera); kf_point1 / 2: table indices of the slots' points or -1 (None = none); table: a MapPointTable; sim3: a
+        SIM3_DTYPE record (sim3_record()); already1 / 2: vbAlreadyMatched1 / 2 (None = none).  Returns (nFound, match12) with
+        match12[i1] = the KF2 keypoint of every newly found pair, or -1."""
+        name = "SearchBySim3"
+        if not float(th) > 0:
+            raise ValueError("SearchBySim3: th must be positive")
+        k1, d1 = _frame(KF1, "KF1")
+        k2, d2 = _frame(KF2, "KF2")
+        bounds = KF1.bounds if bounds is None else bounds
+        if len(bounds) != 4:
+            raise ValueError("SearchBySim3: bounds must be (min_x, max_x, min_y, max_y)")
+        s1 = np.full(max(KF1.N, 1), -1, np.int32) if kf_point1 is None else _arr(kf_point1, np.int32, KF1.N, "kf_point1")
+        s2 = np.full(max(KF2.N, 1), -1, np.int32) if kf_point2 is None else _arr(kf_point2, np.int32, KF2.N, "kf_point2")
+        table.check_indices(s1[:KF1.N], "kf_point1", name)
+        table.check_indices(s2[:KF2.N], "kf_point2", name)
+        a1, a2 = _mask(already1, KF1.N, "already1"), _mask(already2, KF2.N, "already2")
+        X = np.ascontiguousarray(sim3, SIM3_DTYPE)
+        if X.size != 1:
+            raise ValueError("SearchBySim3: sim3 must be one SIM3_DTYPE record")
+        P1, P2 = (np.ascontiguousarray(P, KF_POSE_DTYPE).reshape(()) for P in (pose1, pose2))
+        ext, t = KF1.ext, table
+        m12 = np.full(max(KF1.N, 1), -1, np.int32)
+        nf = ext._check(ext._L.pgorb_search_by_sim3(ext._h, _p(k1), _p(d1), KF1.N, _p(P1), _p(s1), _p(a1), _p(k2), _p(d2), KF2.N, _p(P2),
+                                                    _p(s2), _p(a2), *[float(b) for b in bounds], t.n, _p(t.points), _p(t.descriptors),
+                                                    _p(t.bad), _p(X), float(th), _p(m12)))
+        return nf, m12[:KF1.N].copy()
+
+    def SearchByProjectionSim3(self, KF, scw_pose, matched_in, table, queries, th=10, bounds=None):
+        """ORBmatcher::SearchByProjection(pKF, Scw, vpPoints, vpMatched, th) (src/ORBmatcher.cc:292-405), monocular.  KF: a
+        Frame-like object; scw_pose: the decomposed Scw as a KF_POSE_DTYPE record (sim3_pose()); matched_in[i]: the table index
+        of vpMatched[i] or -1 (None = all -1); table: a MapPointTable (observations unused); queries: table indices, repeats
+        allowed; th: an int.  Returns (nmatches, assigned, matched_out): assigned[i] = the query written into vpMatched[i]."""
+        if int(th) != th or int(th) < 1:
+            raise ValueError("SearchByProjectionSim3: th must be a positive int")
+        kp, desc, b, sl, q = self._loop_args("SearchByProjectionSim3", KF, matched_in, table, queries, bounds)
+        ext, t, nq = KF.ext, table, len(q)
+        P = np.ascontiguousarray(scw_pose, KF_POSE_DTYPE).reshape(())
+        asg = np.full(max(KF.N, 1), -1, np.int32)
+        out = np.full(max(KF.N, 1), -1, np.int32)
+        nm = ext._check(ext._L.pgorb_search_by_projection_sim3(ext._h, _p(kp), _p(desc), KF.N, _p(P), *b, _p(sl), t.n, _p(t.points),
+                                                               _p(t.descriptors), _p(t.bad), nq, _p(q if nq else asg), int(th),
+                                                               _p(asg), _p(out)))
+        return nm, asg[:KF.N].copy(), out[:KF.N].copy()
+
+    def FuseSim3(self, KF, scw_pose, kf_point, table, queries, th=4.0, bounds=None):
+        """ORBmatcher::Fuse(pKF, Scw, vpPoints, th, vpReplacePoint) (src/ORBmatcher.cc:981-1104), monocular.  Arguments as
+        SearchByProjectionSim3's, with kf_point[i] = the table index of GetMapPoint(i) or -1.  Returns (nfused, action,
+        replace_point, best_idx, best_dist, kf_point_out); action[q] is FUSE_SKIPPED, FUSE_NO_MATCH, FUSE_ADDED,
+        FUSE_KF_POINT_BAD or FUSE_REPLACE_REQUESTED, the last with replace_point[q] = the table index of vpReplacePoint[q]."""
+        if not float(th) > 0:
+            raise ValueError("FuseSim3: th must be positive")
+        kp, desc, b, sl, q = self._loop_args("FuseSim3", KF, kf_point, table, queries, bounds)
+        ext, t, nq = KF.ext, table, len(q)
+        P = np.ascontiguousarray(scw_pose, KF_POSE_DTYPE).reshape(())
+        action = np.zeros(max(nq, 1), np.int32)
+        rep, bi, bd = (np.full(max(nq, 1), -1, np.int32) for _ in range(3))
+        out = np.full(max(KF.N, 1), -1, np.int32)
+        nf = ext._check(ext._L.pgorb_fuse_sim3(ext._h, _p(kp), _p(desc), KF.N, _p(P), *b, _p(sl), t.n, _p(t.points), _p(t.descriptors),
+                                               _p(t.bad), nq, _p(q if nq else action), float(th), _p(action), _p(rep), _p(bi), _p(bd),
+                                               _p(out)))
+        return nf, action[:nq].copy(), rep[:nq].copy(), bi[:nq].copy(), bd[:nq].copy(), out[:KF.N].copy()
+
+    @staticmethod
     def DescriptorDistance(a, b):
         a = np.frombuffer(bytes(a), np.uint8) if isinstance(a, (bytes, bytearray)) else a
         b = np.frombuffer(bytes(b), np.uint8) if isinstance(b, (bytes, bytearray)) else b
@@ -557,6 +658,7 @@ CNM_MAX_NEIGHBOURS = 64
 MAP_POINT_DTYPE = np.dtype([("pos", "<f4", (3,)), ("normal", "<f4", (3,)), ("min_distance", "<f4"), ("max_distance", "<f4")])
 # action codes of ORBmatcher.Fuse (include/pgorb.h)
 FUSE_SKIPPED, FUSE_NO_MATCH, FUSE_ADDED, FUSE_MERGED_INTO_KF_POINT, FUSE_REPLACED_KF_POINT, FUSE_KF_POINT_BAD = range(6)
+FUSE_REPLACE_REQUESTED = 6       # ORBmatcher.FuseSim3 only: vpReplacePoint[q] = the slot's occupant
 
 
 class MapPointTable:
@@ -582,9 +684,9 @@ class MapPointTable:
         if len(self.obs_kf) == 0:
             self.obs_kf = np.zeros(1, np.uint64)
 
-    def check_indices(self, idx, name):
+    def check_indices(self, idx, name, routine="Fuse"):
         if len(idx) and (int(np.min(idx)) < -1 or int(np.max(idx)) >= self.n):
-            raise ValueError("Fuse: %s names a point outside the table (%d points)" % (name, self.n))
+            raise ValueError("%s: %s names a point outside the table (%d points)" % (routine, name, self.n))
 
 
 def kf_pose(Tcw, Ow, fx, fy, cx, cy, invfx=None, invfy=None):
@@ -597,6 +699,40 @@ def kf_pose(Tcw, Ow, fx, fy, cx, cy, invfx=None, invfy=None):
     r["invfx"] = np.float32(1.0) / fx if invfx is None else np.float32(invfx)
     r["invfy"] = np.float32(1.0) / fy if invfy is None else np.float32(invfy)
     return r
+
+
+# pgorb_sim3: SearchBySim3's transform as the caller's cv::Mat arithmetic produced it (ORBmatcher.cc:1123-1125)
+SIM3_DTYPE = np.dtype([("sR12", "<f4", (9,)), ("t12", "<f4", (3,)), ("sR21", "<f4", (9,)), ("t21", "<f4", (3,))])
+
+
+def sim3_record(sR12, t12, sR21, t21):
+    """A SIM3_DTYPE record of sR12 = s12*R12, t12, sR21 = (1.0/s12)*R12.t() and t21 = -sR21*t12, each as the caller computed it."""
+    r = np.zeros((), SIM3_DTYPE)
+    r["sR12"], r["sR21"] = np.asarray(sR12, np.float32).reshape(9), np.asarray(sR21, np.float32).reshape(9)
+    r["t12"], r["t21"] = np.asarray(t12, np.float32).reshape(3), np.asarray(t21, np.float32).reshape(3)
+    return r
+
+
+def sim3_pose(Scw, fx, fy, cx, cy):
+    """The KF_POSE_DTYPE record of a 4x4 (or 3x4) float Scw as ORBmatcher.cc:301-305 / :990-994 decompose it:
+        scw = sqrt(sRcw.row(0).dot(sRcw.row(0)));  Rcw = sRcw/scw;  tcw = Scw.rowRange(0,3).col(3)/scw;  Ow = -Rcw.t()*tcw
+    under the project's cv::Mat readings (DESIGN.md section 4).  RECALLED, not checked against an OpenCV build: Mat::dot sums
+    in double and scw is its double sqrt rounded to float; Mat / double is the scaled copy Mat * (1/scw) with the factor 1.0/scw
+    formed in double and applied in float; -Rcw.t()*tcw is gemm's small-matrix path, float sums, then times alpha = -1 in
+    double."""
+    S = np.asarray(Scw, np.float32)
+    if S.shape not in ((4, 4), (3, 4)):
+        raise ValueError("sim3_pose: Scw must be 4x4 or 3x4")
+    f32, f64 = np.float32, np.float64
+    r0 = S[0, :3].astype(f64)
+    scw = f32(np.sqrt(f64(r0[0] * r0[0]) + f64(r0[1] * r0[1]) + f64(r0[2] * r0[2])))
+    if not scw > 0:
+        raise ValueError("sim3_pose: Scw has no scale")
+    a = f32(f64(1.0) / f64(scw))
+    R = (S[:3, :3] * a).astype(f32)
+    t = (S[:3, 3] * a).astype(f32)
+    Ow = [f32(f64(f32(f32(f32(R[0, i] * t[0]) + f32(R[1, i] * t[1])) + f32(R[2, i] * t[2]))) * f64(-1.0)) for i in range(3)]
+    return kf_pose(np.concatenate([R, t.reshape(3, 1)], 1), Ow, fx, fy, cx, cy)
 
 
 # pgorb_refresh_map_points: what to refresh, the status word's bits, the limit (include/pgorb.h)

@@ -24,7 +24,14 @@ next to each, the oracle's CPU time for the same work (1 thread, a few frames, s
                on one core (tools/place_comparator.py, compiled by the tool; OUR restatement, not ORB-SLAM2), whose results the
                GPU's must equal.  --place-only runs this row alone
 
-usage: python tools/next_tier_bench.py [--batch 128] [--out profiles/r02_next_tier.txt] [--refresh-only | --place-only]"""
+  loop         loop closing's four matchers (ORBmatcher.cc:524-657, 1106-1330, 292-405, 981-1104) as batched resident calls on constructed
+               scenes (tests/loop_cases.py): SearchByBoW(KF, KF) and SearchBySim3 on 8 pairs of about 2000 features,
+               SearchByProjection(KF, Scw) with 3000 points into one key frame, the Sim3 Fuse with 3000 points into 20 key frames
+               as one batch -- that row beside pgorb_fuse_batch_device at the same shape --; beside each the wall clock of the
+               sequential Python reference (tests/loop_reference.py, OUR restatement, not ORB-SLAM2) for ONE problem, whose results
+               the GPU's must equal.  --loop-only runs these rows alone
+
+usage: python tools/next_tier_bench.py [--batch 128] [--out profiles/r02_next_tier.txt] [--refresh-only | --place-only | --loop-only]"""
 import argparse, ctypes as C, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -41,6 +48,7 @@ ap.add_argument("--out", default="")
 ap.add_argument("--features", type=int, default=2000, help="4000 = the initialisation extractor (2 * nFeatures, Tracking.cc:143)")
 ap.add_argument("--refresh-only", action="store_true", help="the map-point refresh rows alone (no ride, no vocabulary)")
 ap.add_argument("--place-only", action="store_true", help="the place-recognition row alone (no ride, no vocabulary)")
+ap.add_argument("--loop-only", action="store_true", help="loop closing's four matchers alone (no ride, no vocabulary)")
 a = ap.parse_args()
 w, h, nf, B = 1920, 1080, a.features, a.batch
 
@@ -146,6 +154,71 @@ def place_lines(ext, nkf=4096, nwords=1500, nq=64, vocab=50000, ccap=256):
                                           int(c_ncand.sum()))]
 
 
+def loop_lines():
+    """Loop closing's four matchers, batched: GPU ms (HIP events, median of 9) beside the Python reference's ms for one problem."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import fuse_cases as FC
+    import loop_cases as LC
+    ext = pg.ORBextractor(2000, FC.MC.SCALE, FC.NLEVELS, 20, 7, max_width=640, max_height=480)      # the scale tables of the constructed scenes
+
+    def ref_ms(fn, c):
+        t0 = time.perf_counter(); r = fn(c); return r, (time.perf_counter() - t0) * 1e3
+    rows = []
+    # 1: SearchByBoW(KF, KF), 8 candidate pairs of about 2000 features
+    bows = [LC.bow_case(100 + k, n=1500, nodes=300) for k in range(8)]
+    got = LC.run_gpu1_batched(bows, ext, timer=timed)
+    want, ms = ref_ms(LC.run_ref1, bows[0])
+    assert LC.same(want, got[0])
+    rows.append(("SearchByBoW(KF, KF): 8 pairs of %d x %d features, %d matches in pair 0" % (len(bows[0].k1[1]), len(bows[0].k2[1]), want[0]), LC.LAST_MS[1], ms))
+    # 2: SearchBySim3, 8 pairs
+    pairs = [LC.pair_case(100 + k, npts=1800) for k in range(8)]
+    got = LC.run_gpu2_batched(pairs, ext, timer=timed)
+    want, ms = ref_ms(LC.run_ref2, pairs[0])
+    assert LC.same(want, got[0][:2])
+    rows.append(("SearchBySim3: 8 pairs of %d x %d features, %d found in pair 0" % (len(pairs[0].slots1), len(pairs[0].slots2), want[0]), LC.LAST_MS[2], ms))
+    # 3: SearchByProjection(KF, Scw), 3000 points into one key frame, th = 10
+    w = LC.wide_case(21, 3000)
+    w10 = LC.Case(w.name, w.kf, w.points, w.slots, w.queries, th=10)
+    got = LC.run_gpu_batched([w10], ext, 3, timer=timed)
+    want, ms = ref_ms(LC.run_ref3, w10)
+    assert LC.same(want, got[0][:-1])
+    rows.append(("SearchByProjection(KF, Scw): %d points into one key frame of %d keypoints, %d matches" % (3000, len(w.slots), want[0]), LC.LAST_MS[3], ms))
+    # 4: the Sim3 Fuse, 3000 points into 20 key frames as one batch (th = 4), every slot empty; beside it Fuse(KF, points) at the same shape
+    e = LC.Case(w.name, w.kf, w.points, np.full(len(w.slots), -1, np.int32), w.queries, th=4)
+    got = LC.run_gpu_batched([e] * 20, ext, 4, timer=timed)
+    want, ms = ref_ms(LC.run_ref4, e)
+    assert all(LC.same(want, g[:-1]) for g in got)
+    rows.append(("Fuse(KF, Scw): %d points into 20 key frames of %d keypoints as one batch, %d fused each" % (3000, len(w.slots), want[0]), LC.LAST_MS[4], ms))
+    # pgorb_fuse_batch_device on the same 20 problems (no observations, every slot empty, th = 4): it also runs the chi-square test
+    B, n, nq = 20, len(w.slots), len(w.queries)
+    G = lambda x: torch.from_numpy(np.ascontiguousarray(x)).cuda()
+    p = lambda t: C.c_void_p(t.data_ptr())
+    s = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    pts, pd, pb, st, ob = FC.table_arrays([dict(q, obs=[]) for q in w.points])
+    kid, k, d, P, b = w.kf
+    dK = G(np.tile(k.view(np.uint8).reshape(1, n, 28), (B, 1, 1))); dD = G(np.tile(d.reshape(1, n, 32), (B, 1, 1)))
+    dN = G(np.full(B, n, np.int32)); gs = torch.zeros((B, 3073), dtype=torch.int32, device="cuda"); gi = torch.zeros((B, n), dtype=torch.int32, device="cuda")
+    ext._check(ext._L.pgorb_frame_grid_batch_device(ext._h, p(dK), p(dN), B, n, *b, p(gs), p(gi), s))
+    dKf, dId, dP = G(np.arange(B, dtype=np.int32)), G(np.arange(B, dtype=np.int64)), G(np.tile(np.array(P, pg.KF_POSE_DTYPE).reshape(1).view(np.uint8), (B, 1)))
+    dPts, dPD, dPB, dSt, dOb = G(pts.view(np.uint8)), G(pd), G(pb), G(st), torch.zeros(1, dtype=torch.int64, device="cuda")
+    dNq, dQ = G(np.full(B, nq, np.int32)), G(np.tile(np.array(w.queries, np.int32), (B, 1)))
+    act = torch.empty((B, nq), dtype=torch.int32, device="cuda"); nfu = torch.empty(B, dtype=torch.int32, device="cuda")
+    fuse = lambda: ext._check(ext._L.pgorb_fuse_batch_device(ext._h, p(dK), p(dD), p(dN), n, p(gs), p(gi), p(dKf), B, p(dId), p(dP), *b, None,
+                              len(pts), p(dPts), p(dPD), p(dPB), p(dSt), p(dOb), nq, p(dNq), p(dQ), 4.0, p(act), None, None, None, p(nfu), s))
+    t_fuse = timed(fuse)
+    rows.append(("   beside it Fuse(KF, points), pgorb_fuse_batch_device, the same 20 problems, %d fused each" % int(nfu[0]), t_fuse, float("nan")))
+    lines = ["# loop closing's matchers, batched resident calls, HIP events, median of 9;",
+             "# reference = tests/loop_reference.py (Python, one core, NOT ORB-SLAM2) for ONE problem of the batch, wall clock, results equal",
+             "%-104s %10s %14s" % ("call", "GPU ms", "reference ms")]
+    return lines + ["%-104s %10.3f %14.1f" % r for r in rows]
+
+
+if a.loop_only:
+    lines = ["# python tools/next_tier_bench.py --loop-only   (MI355X)"] + loop_lines()
+    print("\n".join(lines))
+    if a.out:
+        open(a.out, "w").write("\n".join(lines) + "\n")
+    sys.exit(0)
 if a.place_only:
     lines = ["# python tools/next_tier_bench.py --place-only   (MI355X)"] + place_lines(pg.ORBextractor(nf, 1.2, 8, 20, 7, max_width=w, max_height=h))
     print("\n".join(lines))

@@ -14,20 +14,16 @@
 //                    slot (atomicMin) is decided against the slot's current occupant and observation union, so the chains
 //                    advance in query order, as many rounds as the longest chain.
 // Every float operation follows the reference's cv::Mat arithmetic under the readings of DESIGN.md section 4.
-#include "match_common.h"
+#include "kf_window.h"
 
 #define FUSE_T 1024
 #define FUSE_MATCHED (-3)                  // k_fuse_match's provisional action of a query with bestDist <= TH_LOW
 
 struct PgFuseBatch {
-    const pgorb_keypoint* K; const uint8_t* D; const int32_t* n; int cap;
-    const int32_t* gstart; const int32_t* gidx; const int32_t* kf; const uint64_t* kfId; const pgorb_kf_pose* pose;
-    const int32_t* kfPoint;
-    int npoints; const pgorb_map_point* pts; const uint8_t* pdesc; const uint8_t* pbad; const int32_t* obsStart; const uint64_t* obsKf;
+    PgKfBatch kb;
+    const int32_t* kf; const uint64_t* kfId; const int32_t* kfPoint; const int32_t* obsStart; const uint64_t* obsKf;
     int qcap; const int32_t* nq; const int32_t* queries;
-    float minX, minY, maxX, maxY;          // the key frame's int bounds (KeyFrame.h:195-198) as float
-    float invW, invH;                      // mfGridElementWidthInv / HeightInv of the Frame's float bounds
-    float sf[PG_MAXL + 1]; float invS2[PG_MAXL + 1]; int nlevels; float logSf; float th;
+    float invS2[PG_MAXL + 1];
 };
 // per problem scratch: [qcap] best index / distance / provisional action, chain links, two pending lists; [cap] slot state
 struct PgFuseScratch {
@@ -49,6 +45,7 @@ __device__ __forceinline__ bool fuse_lists(const PgFuseBatch& B, int mp, uint64_
 
 __global__ __launch_bounds__(256) void k_fuse_match(PgFuseBatch B, PgFuseScratch S)
 {
+    const PgKfBatch& W = B.kb;
     const int p = blockIdx.y, q = blockIdx.x * 256 + threadIdx.x;
     const int nq = min(max(B.nq[p], 0), B.qcap);
     if (q >= nq) return;
@@ -56,68 +53,19 @@ __global__ __launch_bounds__(256) void k_fuse_match(PgFuseBatch B, PgFuseScratch
     const int f = B.kf[p];
     int act = PGORB_FUSE_SKIPPED, bestIdx = -1, bestDist = -1;
     const int mp = B.queries[qi];
-    // :850-854: NULL, isBad(), IsInKeyFrame(pKF)
-    if (mp >= 0 && mp < B.npoints && !(B.pbad && B.pbad[mp]) && !fuse_lists(B, mp, B.kfId[f])) {
-        const pgorb_map_point P = B.pts[mp];
-        const float* T = B.pose[f].Tcw;
-        const pgorb_kf_pose& C = B.pose[f];
-        // p3Dc = Rcw*p3Dw + tcw: gemm's small-matrix path with tcw as C (:856-857)
-        const float zc = cnm_f(__dadd_rn((double)cnm_dot3f(T[8], T[9], T[10], P.pos[0], P.pos[1], P.pos[2]), (double)T[11]));
-        bool ok = !(zc < 0.0f);                                                          // :860-861
-        float u = 0.f, v = 0.f, dist3D = 0.f;
-        if (ok) {
-            const float xc = cnm_f(__dadd_rn((double)cnm_dot3f(T[0], T[1], T[2], P.pos[0], P.pos[1], P.pos[2]), (double)T[3]));
-            const float yc = cnm_f(__dadd_rn((double)cnm_dot3f(T[4], T[5], T[6], P.pos[0], P.pos[1], P.pos[2]), (double)T[7]));
-            const float invz = __fdiv_rn(1.0f, zc);                                     // :863-868
-            u = __fadd_rn(__fmul_rn(C.fx, __fmul_rn(xc, invz)), C.cx);
-            v = __fadd_rn(__fmul_rn(C.fy, __fmul_rn(yc, invz)), C.cy);
-            ok = u >= B.minX && u < B.maxX && v >= B.minY && v < B.maxY;                  // IsInImage (:871, KeyFrame.cc:713-716)
-        }
-        if (ok) {
-            const float po0 = __fsub_rn(P.pos[0], C.Ow[0]), po1 = __fsub_rn(P.pos[1], C.Ow[1]), po2 = __fsub_rn(P.pos[2], C.Ow[2]);
-            dist3D = cnm_f(cnm_normd(po0, po1, po2));                                     // cv::norm(PO) (:879-880)
-            ok = !(dist3D < __fmul_rn(0.8f, P.min_distance) || dist3D > __fmul_rn(1.2f, P.max_distance));      // :883-884
-            // PO.dot(Pn) < 0.5*dist3D, in double (:889-890)
-            if (ok) ok = !(cnm_dotd(po0, po1, po2, P.normal[0], P.normal[1], P.normal[2]) < __dmul_rn(0.5, (double)dist3D));
-        }
-        int cx0 = 0, cx1 = -1, cy0 = 0, cy1 = -1, lvl = 0;
-        float r = 0.f;
-        if (ok) {
-            lvl = pg_predict_scale(P.max_distance, dist3D, B.logSf, B.nlevels);           // :892
-            r = __fmul_rn(B.th, B.sf[lvl]);                                             // :897
-            ok = sfi_window(u, v, r, B.minX, B.minY, B.invW, B.invH, cx0, cx1, cy0, cy1);
-        }
-        if (ok) {
-            const int cap = B.cap;
-            const pgorb_keypoint* __restrict__ K = B.K + (int64_t)f * cap;
-            const uint8_t* __restrict__ D = B.D + (int64_t)f * cap * 32;
-            const int32_t* __restrict__ gstart = B.gstart + (int64_t)f * (PGORB_GRID_CELLS + 1);
-            const int32_t* __restrict__ gidx = B.gidx + (int64_t)f * cap;
-            const uint4 q0 = reinterpret_cast<const uint4*>(B.pdesc + (int64_t)mp * 32)[0];
-            const uint4 q1 = reinterpret_cast<const uint4*>(B.pdesc + (int64_t)mp * 32)[1];
-            bool any = false;
-            int bd = 256, bi = -1;
-            for (int ix = cx0; ix <= cx1; ix++)                                           // KeyFrame::GetFeaturesInArea
-                for (int iy = cy0; iy <= cy1; iy++) {
-                    const int c = ix * PGORB_GRID_ROWS + iy;
-                    for (int j = gstart[c], je = gstart[c + 1]; j < je; j++) {
-                        const int idx = gidx[j];
-                        const pgorb_keypoint kp = K[idx];
-                        const float ex = __fsub_rn(u, kp.x), ey = __fsub_rn(v, kp.y);
-                        if (!(fabsf(ex) < r && fabsf(ey) < r)) continue;                   // fabs(kp - x) < r, the same values
-                        any = true;
-                        const int o = kp.octave;                                          // :921-924 (upper end: the level itself)
-                        if (o < lvl - 1 || o > lvl || o < 0) continue;
-                        const float e2 = __fadd_rn(__fmul_rn(ex, ex), __fmul_rn(ey, ey)); // :941-948
-                        if ((double)__fmul_rn(e2, B.invS2[o]) > 5.99) continue;
-                        const int dist = sfi_distance(q0, q1, D + (int64_t)idx * 32);
-                        if (dist < bd) { bd = dist; bi = idx; }                           // :955-959
-                    }
-                }
-            if (any) {
-                bestIdx = bi; bestDist = bd;
-                act = bd <= TH_LOW ? FUSE_MATCHED : PGORB_FUSE_NO_MATCH;
-            }
+    KfQuery Q;
+    // :850-854: NULL, isBad(), IsInKeyFrame(pKF); then the front part (:856-897)
+    if (mp >= 0 && mp < W.npoints && !(W.pbad && W.pbad[mp]) && !fuse_lists(B, mp, B.kfId[f]) && kf_point_query(W, f, mp, Q)) {
+        int bd = 256, bi = -1;
+        const bool any = kf_scan(W, f, mp, Q,
+                                 [&](int, const pgorb_keypoint& kp) {                          // the chi-square test (:941-948)
+                                     const float ex = __fsub_rn(Q.u, kp.x), ey = __fsub_rn(Q.v, kp.y);
+                                     const float e2 = __fadd_rn(__fmul_rn(ex, ex), __fmul_rn(ey, ey));
+                                     return (double)__fmul_rn(e2, B.invS2[kp.octave]) > 5.99; },
+                                 [&](int idx, int dist) { if (dist < bd) { bd = dist; bi = idx; } });     // :955-959
+        if (any) {
+            bestIdx = bi; bestDist = bd;
+            act = bd <= TH_LOW ? FUSE_MATCHED : PGORB_FUSE_NO_MATCH;
         }
     }
     S.best[qi] = bestIdx; S.dist[qi] = bestDist; S.act[qi] = act;
@@ -142,15 +90,16 @@ __global__ __launch_bounds__(FUSE_T) void k_fuse_resolve(PgFuseBatch B, PgFuseSc
                                                          int32_t* __restrict__ bestOut, int32_t* __restrict__ distOut,
                                                          int32_t* __restrict__ slotsOut, int32_t* __restrict__ nfused)
 {
-    const int p = blockIdx.x, tid = threadIdx.x, f = B.kf[p], cap = B.cap;
-    const int n = min(max(B.n[f], 0), cap), nq = min(max(B.nq[p], 0), B.qcap);
+    const PgKfBatch& W = B.kb;
+    const int p = blockIdx.x, tid = threadIdx.x, f = B.kf[p], cap = W.cap;
+    const int n = min(max(W.n[f], 0), cap), nq = min(max(B.nq[p], 0), B.qcap);
     const int64_t rowQ = (int64_t)p * B.qcap, rowS = (int64_t)p * cap;
     const uint64_t kfId = B.kfId[f];
     __shared__ int sNext, sFused;
     if (tid == 0) { sNext = 0; sFused = 0; }
     for (int s = tid; s < n; s += FUSE_T) {
         int o = B.kfPoint ? B.kfPoint[(int64_t)f * cap + s] : -1;
-        if (o >= B.npoints) o = -1;
+        if (o >= W.npoints) o = -1;
         S.occ[rowS + s] = o;
         S.cnt[rowS + s] = o >= 0 ? B.obsStart[o + 1] - B.obsStart[o] : 0;
         S.last[rowS + s] = -1;
@@ -179,11 +128,11 @@ __global__ __launch_bounds__(FUSE_T) void k_fuse_resolve(PgFuseBatch B, PgFuseSc
             fuse_store(&S.head[rowS + s], 0x7FFFFFFF);                     // this thread alone owns slot s in this round
             fused++;
             const int o0 = B.kfPoint ? B.kfPoint[(int64_t)f * cap + s] : -1;
-            const int o0v = o0 < B.npoints ? o0 : -1;
+            const int o0v = o0 < W.npoints ? o0 : -1;
             const int mp = B.queries[rowQ + q];
             const int nobs = B.obsStart[mp + 1] - B.obsStart[mp];
             int act;
-            if (o0v >= 0 && B.pbad && B.pbad[o0v]) {
+            if (o0v >= 0 && W.pbad && W.pbad[o0v]) {
                 act = PGORB_FUSE_KF_POINT_BAD;                                 // :966-967: nothing changes
             } else if (S.occ[rowS + s] < 0) {
                 act = PGORB_FUSE_ADDED;                                        // :974-976: AddObservation(pKF) + AddMapPoint
@@ -220,19 +169,39 @@ __global__ __launch_bounds__(FUSE_T) void k_fuse_resolve(PgFuseBatch B, PgFuseSc
     if (tid == 0) nfused[p] = sFused;
 }
 
-static bool pg_fuse_tables(pgorb_ctx* c, PgFuseBatch& B, float min_x, float max_x, float min_y, float max_y, float th)
+PgKfPack::PgKfPack(PgHostCall& s, const PgKfFrame* f, int nframes, int npoints) : nframes(nframes), cap(1), npoints(npoints)
 {
-    float s2[PG_MAXL + 1] = {0};
-    pgorb_scale_tables(c, B.sf, nullptr, s2, B.invS2);
-    (void)s2;
-    B.nlevels = pgorb_levels(c);
-    B.logSf = pgorb_log_scale_factor(c);
-    B.th = th;
-    B.invW = (float)PGORB_GRID_COLS / (max_x - min_x);                 // Frame.cc:216-217, copied by the KeyFrame
-    B.invH = (float)PGORB_GRID_ROWS / (max_y - min_y);
-    B.minX = (float)(int)min_x; B.maxX = (float)(int)max_x;            // KeyFrame's const int mnMinX .. mnMaxY
-    B.minY = (float)(int)min_y; B.maxY = (float)(int)max_y;
-    return B.nlevels > 0;
+    for (int k = 0; k < nframes; k++) cap = std::max(cap, f[k].n);
+    const size_t slots = (size_t)nframes * cap, np = std::max(npoints, 1);
+    K = s.region(PG_UP, slots * sizeof(pgorb_keypoint)); D = s.region(PG_UP, slots * 32); S = s.region(PG_UP, slots * 4);
+    Pose = s.region(PG_UP, nframes * sizeof(pgorb_kf_pose)); N = s.region(PG_UP, (size_t)nframes * 4); F = s.region(PG_UP, (size_t)nframes * 4);
+    P = s.region(PG_UP, np * sizeof(pgorb_map_point)); PD = s.region(PG_UP, np * 32); B = s.region(PG_UP, np);
+    GS = GI = 0;
+}
+void PgKfPack::device(PgHostCall& s)
+{
+    GS = s.region(PG_DEV, (size_t)nframes * (PGORB_GRID_CELLS + 1) * 4); GI = s.region(PG_DEV, (size_t)nframes * cap * 4);
+}
+void PgKfPack::pack(PgHostCall& s, const PgKfFrame* f, const pgorb_map_point* points, const uint8_t* point_desc, const uint8_t* point_bad) const
+{
+    const size_t kb = sizeof(pgorb_keypoint);
+    for (int k = 0; k < nframes; k++) {
+        const size_t n = f[k].n, slot = (size_t)k * cap;
+        s.host<int32_t>(N)[k] = f[k].n; s.host<int32_t>(F)[k] = k;
+        s.put(K, f[k].kps, n * kb, slot * kb, cap * kb);
+        s.put(D, f[k].desc, n * 32, slot * 32, (size_t)cap * 32);
+        memset(s.host(S) + slot * 4, 0xFF, (size_t)cap * 4);
+        s.put(S, f[k].slots, n * 4, slot * 4);
+        s.put(Pose, f[k].pose, sizeof(pgorb_kf_pose), k * sizeof(pgorb_kf_pose));
+    }
+    s.put(P, points, (size_t)npoints * sizeof(pgorb_map_point));
+    s.put(PD, point_desc, (size_t)npoints * 32);
+    s.put(B, point_bad, npoints, 0, npoints);
+}
+int PgKfPack::grid(pgorb_ctx* c, PgHostCall& s, float min_x, float max_x, float min_y, float max_y) const
+{
+    return pgorb_frame_grid_batch_device(c, s.dev<pgorb_keypoint>(K), s.dev<int32_t>(N), nframes, cap, min_x, max_x, min_y, max_y,
+                                         s.dev<int32_t>(GS), s.dev<int32_t>(GI), nullptr);
 }
 
 extern "C" {
@@ -246,28 +215,20 @@ int pgorb_fuse_batch_device(pgorb_ctx* c, const pgorb_keypoint* d_kps, const uin
                             int32_t* d_action, int32_t* d_best_idx, int32_t* d_best_dist, int32_t* d_kf_point_out, int32_t* d_nfused,
                             void* stream)
 {
-    if (!c) return PGORB_E_ARG;
-    if (!d_kps || !d_desc || !d_n || cap < 1 || !d_grid_start || !d_grid_idx || nprob < 0 || npoints < 0 || qcap < 1 ||
-        !(max_x > min_x) || !(max_y > min_y) || !(th > 0.0f) ||
-        (nprob && (!d_kf || !d_kf_id || !d_pose || !d_nq || !d_queries || !d_action || !d_nfused || !d_obs_start)) ||
-        (npoints && (!d_points || !d_point_desc || !d_obs_kf)))
-        return pg_ctx_fail(c, PGORB_E_ARG, "bad argument to pgorb_fuse_batch_device");
-    if (cap > 16000) return pg_ctx_fail(c, PGORB_E_LIMIT, "more than 16000 keypoints per frame");
-    if (!nprob) return 0;
-    if (hipSetDevice(pg_ctx_device(c)) != hipSuccess) return pg_ctx_fail(c, PGORB_E_HIP, "hipSetDevice failed");
+    PgFuseBatch B = {{d_kps, d_desc, d_n, cap, d_grid_start, d_grid_idx, d_pose, npoints, d_points, d_point_desc, d_point_bad},
+                     d_kf, d_kf_id, d_kf_point, d_obs_start, d_obs_kf, qcap, d_nq, d_queries};
+    int rc;
+    if (pg_kf_begin(c, "bad argument to pgorb_fuse_batch_device",
+                    qcap >= 1 && (!nprob || (d_kf && d_kf_id && d_nq && d_queries && d_action && d_nfused && d_obs_start)) &&
+                        (!npoints || d_obs_kf), B.kb, nprob, min_x, max_x, min_y, max_y, th, rc)) return rc;
+    pgorb_scale_tables(c, nullptr, nullptr, nullptr, B.invS2);
     const hipStream_t s = (hipStream_t)stream;
-    PgFuseBatch B = {d_kps, d_desc, d_n, cap, d_grid_start, d_grid_idx, d_kf, d_kf_id, d_pose, d_kf_point, npoints, d_points,
-                     d_point_desc, d_point_bad, d_obs_start, d_obs_kf, qcap, d_nq, d_queries};
-    if (!pg_fuse_tables(c, B, min_x, max_x, min_y, max_y, th)) return pg_ctx_fail(c, PGORB_E_ARG, "context has no levels");
     const size_t rq = (size_t)nprob * qcap * 4, rs = (size_t)nprob * cap * 4;
-    size_t o = 0;
-    auto take = [&](size_t bytes) { const size_t r = o; o += (bytes + 255) & ~(size_t)255; return r; };
+    PgCarve cv;
     size_t off[10];
-    for (int k = 0; k < 6; k++) off[k] = take(rq);
-    for (int k = 6; k < 10; k++) off[k] = take(rs);
+    for (int k = 0; k < 10; k++) off[k] = cv.take(k < 6 ? rq : rs);
     void* scr;
-    int rc = pg_ctx_scratch(c, o, s, &scr);
-    if (rc) return rc;
+    if ((rc = pg_ctx_scratch(c, cv.o, s, &scr))) return rc;
     int32_t* a[10];
     for (int k = 0; k < 10; k++) a[k] = (int32_t*)((uint8_t*)scr + off[k]);
     const PgFuseScratch S = {a[0], a[1], a[2], a[3], a[4], a[5], a[6], a[7], a[8], a[9]};
@@ -322,42 +283,30 @@ int pgorb_fuse(pgorb_ctx* c, const pgorb_keypoint* kps, const uint8_t* desc, int
     if (kf_point_out) for (int i = 0; i < n; i++) kf_point_out[i] = kf_point ? kf_point[i] : -1;
     if (!nq) return 0;
     for (int q = 0; q < nq; q++) { action[q] = PGORB_FUSE_SKIPPED; if (best_idx) best_idx[q] = -1; if (best_dist) best_dist[q] = -1; }
-    const int cap = std::max(n, 1), np = std::max(npoints, 1);
+    const PgKfFrame f = {kps, desc, kf_point, pose, n};
     PgHostCall hc(c);
-    const size_t kb = sizeof(pgorb_keypoint);
-    const size_t oN = hc.region(PG_UP, 8), oK = hc.region(PG_UP, (size_t)cap * kb), oD = hc.region(PG_UP, (size_t)cap * 32),
-                 oS = hc.region(PG_UP, (size_t)cap * 4), oPose = hc.region(PG_UP, sizeof(pgorb_kf_pose)), oId = hc.region(PG_UP, 8),
-                 oF = hc.region(PG_UP, 4), oP = hc.region(PG_UP, (size_t)np * sizeof(pgorb_map_point)), oPD = hc.region(PG_UP, (size_t)np * 32),
-                 oB = hc.region(PG_UP, np), oOS = hc.region(PG_UP, (size_t)(npoints + 1) * 4), oOK = hc.region(PG_UP, (size_t)std::max(nobs, 1) * 8),
-                 oQ = hc.region(PG_UP, (size_t)nq * 4),
+    PgKfPack pk(hc, &f, 1, npoints);
+    const int cap = pk.cap;
+    const size_t oId = hc.region(PG_UP, 8), oOS = hc.region(PG_UP, (size_t)(npoints + 1) * 4),
+                 oOK = hc.region(PG_UP, (size_t)std::max(nobs, 1) * 8), oNQ = hc.region(PG_UP, 4), oQ = hc.region(PG_UP, (size_t)nq * 4),
                  oA = hc.region(PG_DOWN, (size_t)nq * 4), oBI = hc.region(PG_DOWN, (size_t)nq * 4), oBD = hc.region(PG_DOWN, (size_t)nq * 4),
-                 oSO = hc.region(PG_DOWN, (size_t)cap * 4), oNF = hc.region(PG_DOWN, 4),
-                 oGS = hc.region(PG_DEV, (size_t)(PGORB_GRID_CELLS + 1) * 4), oGI = hc.region(PG_DEV, (size_t)cap * 4);
+                 oSO = hc.region(PG_DOWN, (size_t)cap * 4), oNF = hc.region(PG_DOWN, 4);
+    pk.device(hc);
     int rc = hc.begin();
     if (rc) return rc;
-    const int32_t cnt[2] = {n, nq};
-    hc.put(oN, cnt, 8);
-    hc.put(oK, kps, (size_t)n * kb, 0, (size_t)cap * kb);
-    hc.put(oD, desc, (size_t)n * 32, 0, (size_t)cap * 32);
-    if (kf_point) hc.put(oS, kf_point, (size_t)n * 4);
-    else memset(hc.host(oS), 0xFF, (size_t)cap * 4);
-    hc.put(oPose, pose, sizeof(pgorb_kf_pose));
+    pk.pack(hc, &f, points, point_desc, point_bad);
     hc.put(oId, &kf_id, 8);
-    hc.put(oF, nullptr, 0, 0, 4);
-    hc.put(oP, points, (size_t)npoints * sizeof(pgorb_map_point));
-    hc.put(oPD, point_desc, (size_t)npoints * 32);
-    hc.put(oB, point_bad, npoints, 0, npoints);
     hc.put(oOS, obs_start, (size_t)(npoints + 1) * 4);
     hc.put(oOK, obs_kf, (size_t)nobs * 8);
+    hc.put(oNQ, &nq, 4);
     hc.put(oQ, queries, (size_t)nq * 4);
     if ((rc = hc.run([&] {
-            int r = pgorb_frame_grid_batch_device(c, hc.dev<pgorb_keypoint>(oK), hc.dev<int32_t>(oN), 1, cap, min_x, max_x, min_y, max_y,
-                                                  hc.dev<int32_t>(oGS), hc.dev<int32_t>(oGI), nullptr);
-            return r ? r : pgorb_fuse_batch_device(c, hc.dev<pgorb_keypoint>(oK), hc.dev(oD), hc.dev<int32_t>(oN), cap, hc.dev<int32_t>(oGS),
-                                                   hc.dev<int32_t>(oGI), hc.dev<int32_t>(oF), 1, hc.dev<uint64_t>(oId), hc.dev<pgorb_kf_pose>(oPose),
-                                                   min_x, max_x, min_y, max_y, hc.dev<int32_t>(oS), npoints, hc.dev<pgorb_map_point>(oP),
-                                                   hc.dev(oPD), hc.dev(oB), hc.dev<int32_t>(oOS), hc.dev<uint64_t>(oOK), nq,
-                                                   hc.dev<int32_t>(oN) + 1, hc.dev<int32_t>(oQ), th, hc.dev<int32_t>(oA), hc.dev<int32_t>(oBI),
+            const int r = pk.grid(c, hc, min_x, max_x, min_y, max_y);
+            return r ? r : pgorb_fuse_batch_device(c, hc.dev<pgorb_keypoint>(pk.K), hc.dev(pk.D), hc.dev<int32_t>(pk.N), cap, hc.dev<int32_t>(pk.GS),
+                                                   hc.dev<int32_t>(pk.GI), hc.dev<int32_t>(pk.F), 1, hc.dev<uint64_t>(oId), hc.dev<pgorb_kf_pose>(pk.Pose),
+                                                   min_x, max_x, min_y, max_y, hc.dev<int32_t>(pk.S), npoints, hc.dev<pgorb_map_point>(pk.P),
+                                                   hc.dev(pk.PD), hc.dev(pk.B), hc.dev<int32_t>(oOS), hc.dev<uint64_t>(oOK), nq,
+                                                   hc.dev<int32_t>(oNQ), hc.dev<int32_t>(oQ), th, hc.dev<int32_t>(oA), hc.dev<int32_t>(oBI),
                                                    hc.dev<int32_t>(oBD), hc.dev<int32_t>(oSO), hc.dev<int32_t>(oNF), nullptr); }))) return rc;
     memcpy(action, hc.host(oA), (size_t)nq * 4);
     if (best_idx) memcpy(best_idx, hc.host(oBI), (size_t)nq * 4);

@@ -1,6 +1,6 @@
 // match_common.h -- what the Frame side, the guided matchers, CreateNewMapPoints, Fuse, loop closing's matchers and the map-point refresh
-// share: included by frame.hip, window_match.hip, node_match.hip, mapping.hip, fuse.hip, loop.hip and map_point.hip, and by no other
-// translation unit.
+// share: included by frame.hip, window_match.hip, node_match.hip, mapping.hip, fuse.hip, loop.hip (the last two through kf_window.h)
+// and map_point.hip, and by no other translation unit.
 #pragma once
 #include "pgorb_internal.h"
 #include <algorithm>
@@ -72,6 +72,12 @@ template <auto K> static bool pg_raise_lds(pgorb_ctx* c, size_t lds)
     }
     return true;
 }
+
+// offsets of 256-byte aligned arrays inside one block of the matchers' scratch arena; `o` ends as the block's size
+struct PgCarve {
+    size_t o = 0;
+    size_t take(size_t bytes) { const size_t r = o; o += (bytes + 255) & ~(size_t)255; return r; }
+};
 
 // GetFeaturesInArea's cell window (Frame.cc:336-350); false = the reference returns an empty vector
 __device__ __forceinline__ bool sfi_window(float x, float y, float r, float minX, float minY, float invW, float invH,
@@ -196,4 +202,18 @@ struct PgFvPack {
     size_t K, D, H, N, FN, FS, FF, NF, P;
     PgFvPack(PgHostCall& s, const PgFvFrame* f, int nframes);
     void pack(PgHostCall& s, const PgFvFrame* f) const;
+};
+
+// One key frame of a single host call of a projection matcher (Fuse, the Scw forms, SearchBySim3); slots null: every slot empty
+struct PgKfFrame { const pgorb_keypoint* kps; const uint8_t* desc; const int32_t* slots; const pgorb_kf_pose* pose; int n; };
+// ... and `nframes` of them as one batch: keypoints, descriptors and slot rows (filled with -1 past n) in slots of cap = max(n, 1)
+// entries, the poses, n[nframes] and the frame numbers F = {0, 1, ...}; the map-point table (points, descriptors, bad mask) in
+// max(npoints, 1) entries; and, declared by device() after the caller's own uploads and downloads, the two grid arrays grid() fills.
+struct PgKfPack {
+    int nframes, cap, npoints;
+    size_t K, D, S, Pose, N, F, P, PD, B, GS, GI;
+    PgKfPack(PgHostCall& s, const PgKfFrame* f, int nframes, int npoints);
+    void device(PgHostCall& s);
+    void pack(PgHostCall& s, const PgKfFrame* f, const pgorb_map_point* points, const uint8_t* point_desc, const uint8_t* point_bad) const;
+    int grid(pgorb_ctx* c, PgHostCall& s, float min_x, float max_x, float min_y, float max_y) const;      // the frames' grids, on the null stream
 };

@@ -1,11 +1,12 @@
-// node_match.hip -- the BoW-node matchers on gfx950: the FeatureVector of a frame, SearchByBoW and SearchForTriangulation.
+// node_match.hip -- the BoW-node matchers on gfx950: the FeatureVector of a frame, both SearchByBoW forms and SearchForTriangulation.
 //
 // Restates (thirdparty/orb-slam2):
 //   DBoW2 FeatureVector::addFeature           Thirdparty/DBoW2/DBoW2/FeatureVector.cpp:31-45
 //   ORBmatcher::SearchByBoW(KeyFrame*, Frame&) src/ORBmatcher.cc:161-290
+//   ORBmatcher::SearchByBoW(KeyFrame*, KeyFrame*) src/ORBmatcher.cc:524-657
 //   ORBmatcher::SearchForTriangulation        src/ORBmatcher.cc:659-825, 142-159
 //   ORBmatcher::ComputeThreeMaxima            src/ORBmatcher.cc:1605-1646 (match_common.h)
-// Both matchers walk the vocabulary nodes two frames share, one wave per node, and end in k_match_finish.  mapping.hip reaches
+// All three walk the vocabulary nodes two frames share, one wave per node, and end in k_match_finish.  mapping.hip reaches
 // SearchForTriangulation through pg_tri_launch.
 #include "match_common.h"
 
@@ -270,8 +271,63 @@ __global__ __launch_bounds__(64) void k_search_by_bow(PgBowBatch B, float nnrati
     }
 }
 
+// ---- SearchByBoW(pKF1, pKF2, vpMatches12), src/ORBmatcher.cc:524-657 (loop closing) ----
+// Differences from SearchByBoW(KeyFrame*, Frame&): bestDist1 < TH_LOW is strict (:600); KF2's side is masked by validity AND
+// vbMatched2 (:578-582), and vbMatched2 is written only by an accepted match (:605); the output goes by KF1's feature.  A KF2 feature
+// belongs to one vocabulary node, so vbMatched2 never crosses a node: one wave per (pair, common node) walks KF1's features of the
+// node in FeatureVector order, KF2's features of it one per lane.  The finishing pass is k_match_finish over KF1's side with no drop
+// mask: it histograms every bin >= 0 without looking at the matches, and this kernel writes a bin only together with its match and
+// never clears either, so that is the histogram of the matches (:636-654).
+struct PgKfBowBatch { PgFvBatch fv; const int32_t* kf1; const int32_t* kf2; const uint8_t* valid1; const uint8_t* valid2; };
+#define KFBOW_WAVES 64           // waves per pair, each takes KF1's nodes a = wave, wave + 64, ...
+
+__global__ __launch_bounds__(64) void k_bow_keyframes(PgKfBowBatch B, float nnratio, int checkOrientation, int32_t* __restrict__ m12,
+                                                      int8_t* __restrict__ bins, uint8_t* matched2)
+{
+    const int p = blockIdx.y, cap = B.fv.cap, lane = threadIdx.x;
+    const int f1 = B.kf1[p], f2 = B.kf2[p];
+    PgFvView v1 = pg_fv_view(B.fv, f1), v2 = pg_fv_view(B.fv, f2);
+    // the batched form trusts its FeatureVectors: it only clamps the counts here and the nodes' starts below
+    v1.nfv = min(max(v1.nfv, 0), cap); v2.nfv = min(max(v2.nfv, 0), cap);
+    const int n1 = min(max(B.fv.n[f1], 0), cap), n2 = min(max(B.fv.n[f2], 0), cap);
+    const int64_t row = (int64_t)p * cap;
+    for (int a = blockIdx.x; a < v1.nfv; a += KFBOW_WAVES) {
+        const int lo = pg_fv_find_node(v2, v1.node[a]);                      // KF2's entry of the same node
+        if (lo < 0) continue;
+        const int a0 = max(v1.start[a], 0), a1 = min(v1.start[a + 1], cap), b0 = max(v2.start[lo], 0), b1 = min(v2.start[lo + 1], cap);
+        for (int ia = a0; ia < a1; ia++) {                                    // KF1's features of the node, in order (:556)
+            const int idx1 = (int)v1.feat[ia];
+            if ((unsigned)idx1 >= (unsigned)n1 || !B.valid1[row + idx1]) continue;     // !pMP1 || pMP1->isBad() (:560-564)
+            const uint4 q0 = reinterpret_cast<const uint4*>(v1.D + (int64_t)idx1 * 32)[0];
+            const uint4 q1 = reinterpret_cast<const uint4*>(v1.D + (int64_t)idx1 * 32)[1];
+            unsigned k1 = 0xFFFFFFFFu, k2 = 0xFFFFFFFFu;                      // the lane's two smallest (distance << 16 | list position)
+            for (int k = lane; b0 + k < b1; k += 64) {
+                const int idx2 = (int)v2.feat[b0 + k];
+                if ((unsigned)idx2 >= (unsigned)n2) continue;
+                if (matched2[row + idx2] || !B.valid2[row + idx2]) continue;  // vbMatched2[idx2] || !pMP2 || pMP2->isBad() (:578-582)
+                const unsigned key = ((unsigned)sfi_distance(q0, q1, v2.D + (int64_t)idx2 * 32) << 16) | (unsigned)k;
+                if (key < k1) { k2 = k1; k1 = key; } else if (key < k2) k2 = key;
+            }
+            const unsigned w1 = wave_min_u32(k1);
+            if (w1 == 0xFFFFFFFFu) continue;
+            const unsigned w2 = wave_min_u32(k1 == w1 ? k2 : k1);
+            const int bestDist1 = (int)(w1 >> 16), bestDist2 = w2 == 0xFFFFFFFFu ? 256 : (int)(w2 >> 16);
+            if (bestDist1 < TH_LOW && (float)bestDist1 < __fmul_rn(nnratio, (float)bestDist2)) {     // :600-602
+                const int kbest = (int)(w1 & 0xFFFFu);
+                if ((kbest & 63) == lane) {
+                    const int idx2 = (int)v2.feat[b0 + kbest];
+                    m12[row + idx1] = idx2;                                   // :604-605
+                    matched2[row + idx2] = 1;
+                    bins[row + idx1] = (int8_t)(checkOrientation ? pg_rot_bin(v1.K[idx1].angle, v2.K[idx2].angle) : -1);
+                }
+                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");        // the next feature's scan reads matched2 from other lanes
+            }
+        }
+    }
+}
+
 // after the nodes: count the matches of a pair and apply the rotation histogram.  The output side of pair p is frame
-// pairSide[p] (SearchByBoW: the frame; SearchForTriangulation: key frame 1).  drop ([npairs][cap] or null) clears the entries
+// pairSide[p] (SearchByBoW: the frame; SearchByBoW(KF, KF) and SearchForTriangulation: key frame 1).  drop ([npairs][cap] or null) clears the entries
 // it marks before anything is counted: SearchForTriangulation's "KF1 keypoint already has a map point" (ORBmatcher.cc:701-705).
 __global__ __launch_bounds__(64) void k_match_finish(const int32_t* __restrict__ pairSide, const int32_t* __restrict__ nper, int cap,
                                                      const uint8_t* __restrict__ drop, int checkOrientation, int32_t* __restrict__ matchesOut,
@@ -588,6 +644,77 @@ int pgorb_search_by_bow_batch_device(pgorb_ctx* c, const pgorb_keypoint* d_kps, 
     return pg_ctx_scratch_done(c, (hipStream_t)stream);
 }
 
+int pgorb_search_by_bow_keyframes_batch_device(pgorb_ctx* c, const pgorb_keypoint* d_kps, const uint8_t* d_desc, const int32_t* d_n, int cap,
+                                               const uint32_t* d_fv_node, const int32_t* d_fv_start, const uint32_t* d_fv_feat,
+                                               const int32_t* d_nfv, const int32_t* d_pair_kf1, const int32_t* d_pair_kf2, int npairs,
+                                               const uint8_t* d_point_valid1, const uint8_t* d_point_valid2, float nnratio,
+                                               int check_orientation, int32_t* d_matches12, int32_t* d_nmatches, void* stream)
+{
+    if (!c) return PGORB_E_ARG;
+    if (!d_kps || !d_desc || !d_n || cap < 1 || !d_fv_node || !d_fv_start || !d_fv_feat || !d_nfv || npairs < 0 ||
+        (npairs && (!d_pair_kf1 || !d_pair_kf2 || !d_point_valid1 || !d_point_valid2 || !d_matches12 || !d_nmatches)))
+        return pg_ctx_fail(c, PGORB_E_ARG, "bad argument to pgorb_search_by_bow_keyframes_batch_device");
+    if (cap > 16000) return pg_ctx_fail(c, PGORB_E_LIMIT, "more than 16000 keypoints per frame");
+    if (!npairs) return 0;
+    if (hipSetDevice(pg_ctx_device(c)) != hipSuccess) return pg_ctx_fail(c, PGORB_E_HIP, "hipSetDevice failed");
+    const hipStream_t s = (hipStream_t)stream;
+    const size_t rb = (size_t)npairs * cap;                                  // the rotation bins (i8) and vbMatched2 (u8) of every pair
+    PgCarve cv;
+    const size_t oBins = cv.take(rb), oM2 = cv.take(rb);
+    void* scr;
+    int rc = pg_ctx_scratch(c, cv.o, s, &scr);
+    if (rc) return rc;
+    int8_t* bins = (int8_t*)scr + oBins;
+    uint8_t* matched2 = (uint8_t*)scr + oM2;
+    const PgKfBowBatch B = {{d_kps, d_desc, d_n, cap, d_fv_node, d_fv_start, d_fv_feat, d_nfv}, d_pair_kf1, d_pair_kf2, d_point_valid1,
+                            d_point_valid2};
+    bool cleared = false;
+    rc = pg_node_match_launch(c, npairs, cap, d_pair_kf1, d_n, nullptr, check_orientation, d_matches12, bins, d_nmatches, s, [&] {
+        if ((cleared = hipMemsetAsync(matched2, 0, rb, s) == hipSuccess))
+            hipLaunchKernelGGL(k_bow_keyframes, dim3(KFBOW_WAVES, (unsigned)npairs), dim3(64), 0, s, B, nnratio, check_orientation, d_matches12, bins, matched2); });
+    if (rc) return rc;
+    if (!cleared) return pg_ctx_fail(c, PGORB_E_HIP, "hipMemsetAsync failed");
+    if (hipGetLastError() != hipSuccess) return pg_ctx_fail(c, PGORB_E_HIP, "k_bow_keyframes launch failed");
+    return pg_ctx_scratch_done(c, s);
+}
+
+// single pair through host buffers: a two-frame batch (KF1 = frame 0, KF2 = frame 1); the FeatureVectors are checked here
+int pgorb_search_by_bow_keyframes(pgorb_ctx* c, const uint8_t* desc1, const float* angle1, const uint8_t* point_valid1, int n1,
+                                  const uint32_t* fv1_node, const int32_t* fv1_start, const uint32_t* fv1_feat, int nfv1,
+                                  const uint8_t* desc2, const float* angle2, const uint8_t* point_valid2, int n2,
+                                  const uint32_t* fv2_node, const int32_t* fv2_start, const uint32_t* fv2_feat, int nfv2,
+                                  float nnratio, int check_orientation, int32_t* matches12)
+{
+    if (!c) return PGORB_E_ARG;
+    if (n1 < 0 || n2 < 0 || nfv1 < 0 || nfv2 < 0 || (n1 && !matches12) || (n1 && (!desc1 || !angle1 || !point_valid1)) ||
+        (n2 && (!desc2 || !angle2 || !point_valid2)) || (nfv1 && (!fv1_node || !fv1_start || !fv1_feat)) ||
+        (nfv2 && (!fv2_node || !fv2_start || !fv2_feat)))
+        return pg_ctx_fail(c, PGORB_E_ARG, "bad argument to pgorb_search_by_bow_keyframes");
+    for (int i = 0; i < n1; i++) matches12[i] = -1;
+    if (!n1 || !n2 || !nfv1 || !nfv2) return 0;
+    if (n1 > 16000 || n2 > 16000) return pg_ctx_fail(c, PGORB_E_LIMIT, "more than 16000 keypoints");
+    if (!pg_fv_ok(fv1_start, fv1_feat, nfv1, n1) || !pg_fv_ok(fv2_start, fv2_feat, nfv2, n2))
+        return pg_ctx_fail(c, PGORB_E_ARG, "pgorb_search_by_bow_keyframes: FeatureVector names more features than the key frame has");
+    for (int a = 1; a < nfv1; a++) if (!(fv1_node[a - 1] < fv1_node[a])) return pg_ctx_fail(c, PGORB_E_ARG, "pgorb_search_by_bow_keyframes: node ids must ascend");
+    for (int a = 1; a < nfv2; a++) if (!(fv2_node[a - 1] < fv2_node[a])) return pg_ctx_fail(c, PGORB_E_ARG, "pgorb_search_by_bow_keyframes: node ids must ascend");
+    const PgFvFrame f[2] = {{nullptr, angle1, desc1, point_valid1, n1, fv1_node, fv1_start, fv1_feat, nfv1},
+                            {nullptr, angle2, desc2, point_valid2, n2, fv2_node, fv2_start, fv2_feat, nfv2}};
+    PgHostCall hc(c);
+    const PgFvPack pk(hc, f, 2);
+    const size_t oM = hc.region(PG_DOWN, (size_t)pk.cap * 4), oNM = hc.region(PG_DOWN, 4);
+    int rc = hc.begin();
+    if (rc) return rc;
+    pk.pack(hc, f);
+    if ((rc = hc.run([&] {
+            return pgorb_search_by_bow_keyframes_batch_device(c, hc.dev<pgorb_keypoint>(pk.K), hc.dev(pk.D), hc.dev<int32_t>(pk.N), pk.cap,
+                                                              hc.dev<uint32_t>(pk.FN), hc.dev<int32_t>(pk.FS), hc.dev<uint32_t>(pk.FF),
+                                                              hc.dev<int32_t>(pk.NF), hc.dev<int32_t>(pk.P), hc.dev<int32_t>(pk.P) + 1, 1,
+                                                              hc.dev(pk.H), hc.dev(pk.H) + pk.cap, nnratio, check_orientation,
+                                                              hc.dev<int32_t>(oM), hc.dev<int32_t>(oNM), nullptr); }))) return rc;
+    memcpy(matches12, hc.host(oM), (size_t)n1 * 4);
+    return *hc.host<int32_t>(oNM);
+}
+
 // single pair through host buffers: the pair becomes a two-frame batch (KF1 = frame 0, KF2 = frame 1)
 int pgorb_search_for_triangulation(pgorb_ctx* c, const pgorb_keypoint* kps1, const uint8_t* desc1, const uint8_t* has_point1, int n1,
                                    const uint32_t* fv1_node, const int32_t* fv1_start, const uint32_t* fv1_feat, int nfv1,
@@ -640,13 +767,14 @@ int pgorb_search_for_triangulation_batch_device(pgorb_ctx* c, const pgorb_keypoi
     PgTriBatch T = {{d_kps, d_desc, d_n, cap, d_fv_node, d_fv_start, d_fv_feat, d_nfv}, d_pair_kf1, d_pair_kf2, d_F12, d_epipole, d_has_point2, {0}, {0}};
     // scratch: the rotation bin of every matched KF1 keypoint [npairs][cap] i8, then (no d_has_point2) an all-zero mask
     void* scratch;
-    const size_t binBytes = ((size_t)npairs * cap + 255) & ~(size_t)255;
-    int rcs = pg_ctx_scratch(c, binBytes + (d_has_point2 ? 0 : (size_t)npairs * cap) + 256, (hipStream_t)stream, &scratch);
+    PgCarve cv;
+    const size_t oBins = cv.take((size_t)npairs * cap), oHas = cv.take(d_has_point2 ? 0 : (size_t)npairs * cap);
+    int rcs = pg_ctx_scratch(c, cv.o, (hipStream_t)stream, &scratch);
     if (rcs) return rcs;
-    int8_t* bins = (int8_t*)scratch;
+    int8_t* bins = (int8_t*)scratch + oBins;
     if (!d_has_point2) {
-        T.hasPoint2 = (const uint8_t*)scratch + binBytes;
-        if (hipMemsetAsync((uint8_t*)scratch + binBytes, 0, (size_t)npairs * cap, (hipStream_t)stream) != hipSuccess)
+        T.hasPoint2 = (const uint8_t*)scratch + oHas;
+        if (hipMemsetAsync((uint8_t*)scratch + oHas, 0, (size_t)npairs * cap, (hipStream_t)stream) != hipSuccess)
             return pg_ctx_fail(c, PGORB_E_HIP, "hipMemsetAsync failed");
     }
     if ((rcs = pg_tri_launch(c, T, npairs, d_has_point1, check_orientation, d_matches12, bins, d_nmatches, (hipStream_t)stream)))

@@ -49,8 +49,10 @@ enum {
     PGORB_E_CAP = -3,        /* output capacity too small; nothing truncated silently   */
     PGORB_E_NODEVICE = -4,   /* no HIP device / wrong architecture                      */
     PGORB_E_HIP = -5,        /* HIP runtime error (see pgorb_last_error)                */
-    PGORB_E_LIMIT = -6,      /* exceeds max_width/max_height/max_batch of the context, or a
-                              * level larger than 4095 px a side                          */
+    PGORB_E_LIMIT = -6,      /* exceeds max_width/max_height/max_batch of the context, a
+                              * level larger than 4095 px a side, more than 65533 keypoints
+                              * on one level (the level's share of nfeatures), or a size
+                              * limit stated at the call (DESIGN.md section 7 lists all)   */
     PGORB_E_OVERFLOW = -7    /* internal candidate capacity exceeded                    */
 };
 
@@ -160,7 +162,8 @@ int  pgorb_hamming_matrix(pgorb_ctx* ctx, const uint8_t* a, int na, const uint8_
                           uint16_t* out);
 /* Best and second-best train descriptor per query (first minimum wins, strict <, like
  * the bestDist/bestDist2 scans in src/ORBmatcher.cc:438-459).  best_idx = -1 and
- * best = second = 65535 when nb == 0; second = 65535 when nb == 1. */
+ * best = second = 65535 when nb == 0; second = 65535 when nb == 1.  PGORB_E_LIMIT for nb >= 2^20 (the popcount
+ * kernel's key is distance << 20 | train index); the batched form below refuses cap_per_frame >= 2^20 likewise. */
 int  pgorb_hamming_best2(pgorb_ctx* ctx, const uint8_t* a, int na, const uint8_t* b, int nb,
                          int32_t* best_idx, uint16_t* best, uint16_t* second);
 /* Batched, resident: pair p matches descriptors of frame qa[p] (queries) against frame
@@ -211,7 +214,8 @@ int  pgorb_frame_grid_batch_device(pgorb_ctx* ctx, const pgorb_keypoint* d_kps, 
                                    int32_t* d_grid_start /*[nframes][3073]*/,
                                    int32_t* d_grid_idx /*[nframes][cap]*/, void* hip_stream);
 /* prev_matched: float[2*n1] in/out (vbPrevMatched); matches12: int32[n1] out (-1 = none);
- * returns nmatches (>= 0) or an error code. */
+ * returns nmatches (>= 0) or an error code.  PGORB_E_LIMIT above 16000 keypoints in either frame (cap_per_frame in the batched
+ * form); the grid calls above have no limit of their own. */
 int  pgorb_search_for_initialization(pgorb_ctx* ctx,
                                      const pgorb_keypoint* kps1, const uint8_t* desc1, int n1,
                                      const pgorb_keypoint* kps2, const uint8_t* desc2, int n2,
@@ -247,7 +251,11 @@ int  pgorb_search_for_initialization_batch_device(pgorb_ctx* ctx, const pgorb_ke
  * Observations() > 0 before the call (:79-81 / :1397-1399); assigned[i] receives the index of the
  * query (map point) written to F.mvpMapPoints[i] by this call, or -1.  Queries are processed in
  * order (each assignment changes what later queries may take): the results equal the reference's
- * sequence; since round 4 the device decides provably independent queries together. */
+ * sequence; since round 4 the device decides provably independent queries together.
+ * Limits (all three forms, single and batched; PGORB_E_LIMIT): the deciding kernel keeps keypoints and queries in LDS, so what
+ * bounds a call is  keypoints * 13 + queries * 10 + 256 <= 163840 bytes  (n and the number of queries in a single call,
+ * cap_per_frame and qcap in a batched one), and 16000 for each count alone: 12582 keypoints with one query, 7112 with 7112
+ * queries, 1000 with 15058.  Split the query list to match a larger frame. */
 int  pgorb_search_by_projection_points(pgorb_ctx* ctx,
         const pgorb_keypoint* kps, const uint8_t* desc, int n,            /* the frame F             */
         float min_x, float max_x, float min_y, float max_y,
@@ -297,7 +305,8 @@ int   pgorb_predict_scale(const pgorb_ctx* ctx, float max_distance, float curren
  *       src/Tracking.cc:758; relocalisation :1359).  Both FeatureVectors come as the CSR arrays
  *       pgorb_bow_vectors produces (ascending node ids).  kf_point_valid[i] = the key frame's
  *       keypoint i has a map point that is not bad.  matches[j] = key-frame keypoint index whose
- *       map point was written to vpMapPointMatches[j], or -1.  Returns nmatches. */
+ *       map point was written to vpMapPointMatches[j], or -1.  Returns nmatches.  PGORB_E_LIMIT above 16000 features in
+ *       either frame. */
 int  pgorb_search_by_bow(pgorb_ctx* ctx,
         const uint8_t* kf_desc, const float* kf_angle, const uint8_t* kf_point_valid, int nkf,
         const uint32_t* kf_fv_node, const int32_t* kf_fv_start, const uint32_t* kf_fv_feat, int kf_nfv,

@@ -766,6 +766,15 @@ static int pg_lists_acquire(pgorb_ctx* c, int npairs, int rowsPerPair, hipStream
     return 0;
 }
 
+// The dynamic LDS of k_search_by_projection for `cap` keypoints and `qcap` queries: minq, minAny, asg (4 B each) and taken (1 B) per
+// keypoint; listA, listB, cntL, qBest (2 B each), rotBin and done (1 B each) per query; the counters and the histogram.  This line, not
+// the 16 000 of the other matchers, is the family's limit: 12 582 keypoints with one query, 7 112 with as many queries, 16 358 queries
+// with one keypoint (the 16 000 gate comes first there).
+static size_t pg_sbp_lds(int cap, int qcap) { return (size_t)cap * 13 + (size_t)qcap * 10 + 256; }
+static const size_t PG_SBP_LDS_MAX = (size_t)160 * 1024;      // what pg_raise_lds grants a workgroup (match_common.h)
+static const char* const PG_SBP_LDS_MSG =
+    "SearchByProjection: keypoints * 13 + queries * 10 + 256 bytes exceed the 163840 B of LDS (e.g. 12582 keypoints with 1 query, 7112 with 7112)";
+
 // what the key-frame form (mode 2) takes beyond the common query arrays
 struct PgProjKeyFrame { const uint8_t* found; const float* dist3d; const float* minDist; const float* maxDist; float logSf; int orbDist; };
 
@@ -796,9 +805,9 @@ static int pg_search_by_projection_batch(pgorb_ctx* c, int mode, const pgorb_key
     pgorb_scale_tables(c, B.sf, nullptr, nullptr, nullptr);
     const float invW = (float)GRID_COLS / (max_x - min_x), invH = (float)GRID_ROWS / (max_y - min_y);
     const size_t ldsA = (size_t)4 * cap * 2;
-    const size_t lds = (size_t)cap * 13 + (size_t)qcap * 10 + 256;
+    const size_t lds = pg_sbp_lds(cap, qcap);
     if (!pg_raise_lds<k_search_by_projection>(c, lds) ||
-        !pg_raise_lds<k_proj_candidates>(c, ldsA)) return pg_ctx_fail(c, PGORB_E_LIMIT, "SearchByProjection state exceeds the LDS (keypoints * 13 + queries * 10 bytes, 160 KB)");
+        !pg_raise_lds<k_proj_candidates>(c, ldsA)) return pg_ctx_fail(c, PGORB_E_LIMIT, PG_SBP_LDS_MSG);
     PgLists Ls;                                                                    // of every query of every pair
     const int rcs = pg_lists_acquire(c, npairs, std::max(qcap, 1), stream, &Ls);
     if (rcs) return rcs;
@@ -825,6 +834,7 @@ static int pg_search_by_projection_host(pgorb_ctx* c, int mode, const pgorb_keyp
     for (int i = 0; i < n; i++) assigned[i] = -1;
     if (!n || !nq) return 0;
     if (n > 16000 || nq > 16000) return pg_ctx_fail(c, PGORB_E_LIMIT, "more than 16000 keypoints / queries");
+    if (pg_sbp_lds(n, nq) > PG_SBP_LDS_MAX) return pg_ctx_fail(c, PGORB_E_LIMIT, PG_SBP_LDS_MSG);      // (before anything is staged)
     const size_t q4 = (size_t)nq * 4, k4 = m2 ? q4 : 0;
     PgHostCall s(c);
     const size_t oN = s.region(PG_UP, 8), oK = s.region(PG_UP, (size_t)n * sizeof(pgorb_keypoint)), oD = s.region(PG_UP, (size_t)n * 32),
@@ -864,6 +874,7 @@ int pgorb_search_for_initialization(pgorb_ctx* c, const pgorb_keypoint* kps1, co
         return pg_ctx_fail(c, PGORB_E_ARG, "bad argument to pgorb_search_for_initialization");
     if (n1 == 0) return 0;
     const int cap = std::max(n1, n2);
+    if (cap > 16000) return pg_ctx_fail(c, PGORB_E_LIMIT, "more than 16000 keypoints per frame");      // (before anything is staged)
     const size_t kb = sizeof(pgorb_keypoint);
     PgHostCall s(c);
     const size_t oMisc = s.region(PG_UP, 16), oK = s.region(PG_UP, (size_t)2 * cap * kb), oD = s.region(PG_UP, (size_t)2 * cap * 32),

@@ -613,8 +613,9 @@ def _pack_frames(frames, extra, poison):
     return dk, torch.from_numpy(ds).cuda(), torch.from_numpy(n).cuda(), cap
 
 
-def run_gpu_batched(cases, ext, poison):
-    """Every case of one kind in one launch of the *_batch_device form; returns the per-case results."""
+def run_gpu_batched(cases, ext, poison, extra=7, qextra=3):
+    """Every case of one kind in one launch of the *_batch_device form; returns the per-case results.  cap = the largest
+    frame + extra, qcap = the longest query list + qextra (tests/capacity_cases.py passes 0: the caps themselves are the case)."""
     import torch
     L, h = ext._L, ext._h
     keep = []                                   # device tensors stay referenced until the launch has finished
@@ -635,7 +636,7 @@ def run_gpu_batched(cases, ext, poison):
         frames = [(a["keys"], a["desc"]) for a in A]
         bounds = A[0]["bounds"]
     B, P = len(frames), len(cases)
-    dk, dd, dn, cap = _pack_frames(frames, 7, poison)
+    dk, dd, dn, cap = _pack_frames(frames, extra, poison)
     gs = torch.empty((B, 64 * 48 + 1), dtype=torch.int32, device="cuda")
     gi = torch.full((B, cap), -7, dtype=torch.int32, device="cuda")
     ext._check(L.pgorb_frame_grid_batch_device(h, p(dk), p(dn), B, cap, *bounds, p(gs), p(gi), s))
@@ -667,7 +668,7 @@ def run_gpu_batched(cases, ext, poison):
                                                      p(pair + P), P, p(T(kv)), A[0]["ratio"], int(A[0]["ori"]), p(asg), p(nm), s))
         torch.cuda.synchronize()
         return grids, [(int(nm[j]), asg[j, :len(a["fk"])].cpu().numpy()) for j, a in enumerate(A)]
-    qcap = max(len(a["valid"]) for a in A) + 3
+    qcap = max(len(a["valid"]) for a in A) + qextra
 
     def qpack(key, dtype, width=None):
         x = np.zeros((P, qcap) + ((width,) if width else ()), dtype)

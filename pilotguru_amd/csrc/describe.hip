@@ -21,47 +21,60 @@
 // Algorithmic bytes per keypoint: 43*43 window read + 60 B written.
 #include "pgorb_internal.h"
 
-// bit_pattern_31_ (ORBextractor.cc:150-408) as floats: the test points are only ever used as
-// float factors of the rotation (:119-120), so the table holds them converted once at compile time
-struct PgPatternF { float v[256 * 4]; };
-constexpr PgPatternF pg_make_pattern_f()
+struct PgGauss7 { int k0, k1, k2, k3; };     // K[0]=K[6]=k0 ... K[3]=k3 (8-bit fixed point)
+// cv::getGaussianKernel(7, 2, CV_32F) in Q8 (Appendix A4) is a fixed set of four integers: compile-time constants here, so the
+// accumulator start value and the packed tap pairs are immediates.  pg_gauss7() below still derives them the way the reference
+// does, and the launcher refuses to run when the two disagree.
+constexpr PgGauss7 PG_G7 = {18, 34, 49, 55};
+
+#define DH_N 37               // blurred side
+
+// Everything constant a wave reads, in ONE object (one address computation, immediate offsets).  A wave pulls its share of it
+// through the CU's vector-memory path once per keypoint, and that path, not HBM, is what the table costs: the layouts below are the
+// ones with the fewest bytes per lane (9.7 KB per wave became 5.3 KB; DESIGN_HISTORY.md, "K4-6 front").
+//   mom   per round `it` and lane: task i = lane + 64 it = (disc row v+15, window dword q+1) -> four byte weights for v_dot4_u32_u8:
+//         u + 16 inside the disc, 0 outside, so the 0/1 disc mask is "byte != 0" and needs no table of its own; tasks past 31 * 9
+//         are zero.  (The circular patch row half-widths umax, ORBextractor.cc:452-469, are baked in.)
+//   btab  B operand of the row-pass MFMAs: the banded Toeplitz matrix of the 7 taps as i8, [column block cb][lane l][16 bytes]:
+//         byte j of an entry is T[k][n] = K[k - n] (0 <= k - n <= 6, n < 37) for k = 16 (l >> 4) + j, n = 16 cb + (l & 15)
+//   pat   bit_pattern_31_ (ORBextractor.cc:150-408) as it is, signed bytes, [lane][round r][x0 y0 x1 y1] = test pair 64 r + lane: one
+//         16-byte load per lane; the bytes become the float factors of the rotation (:119-120) by v_cvt_f32_i32 with a byte select
+struct PgDescTab { uint32_t mom[5 * 64]; uint32_t btab[3 * 64 * 4]; int8_t pat[64 * 4 * 4]; };
+constexpr PgDescTab pg_make_desc_tab()
 {
+    constexpr int umax[16] = {15, 15, 15, 15, 14, 14, 14, 13, 13, 12, 11, 10, 9, 8, 6, 3};
     constexpr int8_t p[256 * 4] = {
 #include "orb_pattern31.inc"
     };
-    PgPatternF t = {};
-    for (int i = 0; i < 256 * 4; i++) t.v[i] = (float)p[i];
-    return t;
-}
-__device__ static const PgPatternF pg_pattern31f = pg_make_pattern_f();
-
-// (circular patch row half-widths umax, ORBextractor.cc:452-469, are baked into pg_make_moment_tab)
-
-struct PgMomentTab { uint32_t wu[31 * 9], wm[31 * 9]; };
-// per (disc row v+15, window dword q+1): packed byte weights (u+15 inside the disc, else 0) and
-// the 0/1 disc mask, for v_dot4_u32_u8
-constexpr PgMomentTab pg_make_moment_tab()
-{
-    constexpr int umax[16] = {15, 15, 15, 15, 14, 14, 14, 13, 13, 12, 11, 10, 9, 8, 6, 3};
-    PgMomentTab t = {};
+    constexpr int K[7] = {PG_G7.k0, PG_G7.k1, PG_G7.k2, PG_G7.k3, PG_G7.k2, PG_G7.k1, PG_G7.k0};
+    PgDescTab t = {};
     for (int r = 0; r < 31; r++)
         for (int q = 0; q < 9; q++) {
             const int vy = r - 15, dmax = umax[vy < 0 ? -vy : vy];
-            uint32_t wu = 0, wm = 0;
+            uint32_t wu = 0;
             for (int k = 0; k < 4; k++) {
                 const int ux = 4 * (q + 1) + k - 21;
-                if ((ux < 0 ? -ux : ux) <= dmax) { wu |= (uint32_t)(ux + 15) << (8 * k); wm |= 1u << (8 * k); }
+                if ((ux < 0 ? -ux : ux) <= dmax) wu |= (uint32_t)(ux + 16) << (8 * k);
             }
-            t.wu[r * 9 + q] = wu; t.wm[r * 9 + q] = wm;
+            t.mom[r * 9 + q] = wu;
         }
+    for (int cb = 0; cb < 3; cb++)
+        for (int l = 0; l < 64; l++)
+            for (int j = 0; j < 16; j++) {
+                const int k = 16 * (l >> 4) + j, n = 16 * cb + (l & 15), d = k - n;
+                const uint32_t v = (d >= 0 && d <= 6 && n < DH_N) ? (uint32_t)K[d] : 0u;
+                t.btab[(cb * 64 + l) * 4 + j / 4] |= v << (8 * (j % 4));
+            }
+    for (int l = 0; l < 64; l++)
+        for (int r = 0; r < 4; r++)
+            for (int k = 0; k < 4; k++) t.pat[(l * 4 + r) * 4 + k] = p[(64 * r + l) * 4 + k];
     return t;
 }
-__device__ static const PgMomentTab pg_moment_tab = pg_make_moment_tab();
+__device__ static const __attribute__((aligned(16))) PgDescTab pg_desc_tab = pg_make_desc_tab();
 
 #define DW_R 21               // window radius: 18 (taps) + 3 (blur)
 #define DW_N 43               // window side
 #define DW_PITCH 48
-#define DH_N 37               // blurred side
 #define DH_PITCH 40           // columns per packed row pair of the horizontal pass
 #define DB_PITCH 40
 
@@ -131,8 +144,6 @@ __device__ __forceinline__ void pg_sincos_f(float angle, float* s_out, float* c_
     *c_out = (float)c;
 }
 
-struct PgGauss7 { int k0, k1, k2, k3; };     // K[0]=K[6]=k0 ... K[3]=k3 (8-bit fixed point)
-
 // sum over the 64 lanes, returned wave-uniform: DPP row shifts inside each row of 16, row
 // broadcasts across rows, then lane 63 (six cross-lane moves instead of six LDS-crossbar shuffles)
 __device__ __forceinline__ int pg_wave_sum(int x)
@@ -152,19 +163,18 @@ typedef __attribute__((address_space(1))) const void* pg_gptr_t;
 typedef __attribute__((address_space(3))) void* pg_lptr_t;
 typedef unsigned short pg_us2 __attribute__((ext_vector_type(2)));
 typedef int pg_v4i __attribute__((ext_vector_type(4)));
-
-// B operand of the row-pass MFMAs: the banded Toeplitz matrix of the 7 taps as i8, [column block
-// cb][lane l][16 bytes]: byte j of an entry is T[k][n] = K[k - n] (0 <= k - n <= 6, n < 37) for
-// k = 16 (l >> 4) + j, n = 16 cb + (l & 15).  Filled once by pg_launch_describe.
-__device__ uint32_t pg_blur_btab[3 * 64 * 4];
+#define PG_GLOBAL __attribute__((address_space(1)))
+typedef PG_GLOBAL const uint8_t* pg_gbytes_t;
 
 // Column pass of the separable blur for ONE output pixel (Y, X) of the 37x37 blurred tile, from
 // the row-pass sums hT[row pair][column] = (row 2p | row 2p+1 << 16): rows Y .. Y+6 are three
 // packed pairs and a single, shifted by 16 bits when Y is odd.  FixedPtCastEx rounding (half
 // up) and the SSE2 tie rule of the reference build (tie -> even for x < (w & ~3)).
-__device__ __forceinline__ int pg_blur_at(const uint32_t* hT, int Y, int X, const PgGauss7& G,
-                                          pg_us2 K01, pg_us2 K23, pg_us2 K45, bool tieEven)
+__device__ __forceinline__ int pg_blur_at(const uint32_t* hT, int Y, int X, bool tieEven)
 {
+    constexpr PgGauss7 G = PG_G7;
+    const pg_us2 K01 = {(unsigned short)G.k0, (unsigned short)G.k1}, K23 = {(unsigned short)G.k2, (unsigned short)G.k3},
+                 K45 = {(unsigned short)G.k2, (unsigned short)G.k1};
     const uint32_t* s = hT + (Y >> 1) * 40 + X;
     const uint32_t p0 = s[0], p1 = s[40], p2 = s[80], p3 = s[120];
     const uint32_t sh = (uint32_t)(Y & 1) << 4;
@@ -184,10 +194,16 @@ __device__ __forceinline__ int pg_blur_at(const uint32_t* hT, int Y, int X, cons
 #define PG_WAVE_SYNC() do { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); \
                             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); } while (0)
 
-__global__ __launch_bounds__(64) void k_describe(const PgPlan P, const PgGauss7 G,
-                                                  pgorb_keypoint* __restrict__ kps,
-                                                  uint8_t* __restrict__ desc, int cap_per_frame,
-                                                  int32_t* __restrict__ n_out, int slotBeg, int slotEnd, int writeTotal, int argPad)
+// Everything a K4-6 wave reads from its argument block: 96 bytes = one s_load_dwordx16 + one s_load_dwordx8, as K2 does
+// (PgFastArgs, fast.hip).  PgPlan by value was a 3.8 KB block read by ten separate scalar loads, and gridDim a hidden argument.
+struct PgDescArgs {
+    const int32_t* kpCount;  const PgSelRec* sel;  int64_t selFrame;  pgorb_keypoint* kps;                          // dwords 0-7
+    uint8_t* desc;  int32_t* n_out;  int32_t nlevels, tieMode, cap_per_frame, slotBeg;                              // 8-15
+    int32_t slotEnd, writeTotal, slotsPerXcd, pad[5];                                                               // 16-23
+};
+static_assert(sizeof(PgDescArgs) == 96 && sizeof(PgDescArgs) <= 128, "one s_load_dwordx16 + one s_load_dwordx8");
+
+__global__ __launch_bounds__(64) void k_describe(const PgDescArgs KA)
 {
     // one 3520-byte LDS buffer per wave: first the raw window (43 rows x 48 B), then -- once the
     // moments and the row-pass operands have been read from it -- the row sums [row pair][column]
@@ -196,43 +212,56 @@ __global__ __launch_bounds__(64) void k_describe(const PgPlan P, const PgGauss7 
     uint8_t* raw = reinterpret_cast<uint8_t*>(hbuf);
 
     const int lane = threadIdx.x;
-    const int frame = blockIdx.y;
+    const uint32_t frame = blockIdx.y;
+    typedef int32_t pg_i32x16 __attribute__((ext_vector_type(16)));
+    typedef uint32_t pg_u32x16 __attribute__((ext_vector_type(16)));
+    typedef uint32_t pg_u32x8 __attribute__((ext_vector_type(8)));
+    // The wave is one long dependent chain and lives ~8 us; every load that does not depend on the keypoint is issued here,
+    // before the chain starts, and has landed when the window fetch is issued two scalar round trips later (the memory pipe is
+    // in order: the window must not queue behind them): the lane's five entries of the moment table, the Toeplitz operands of the
+    // row pass and its four test-point pairs.  The table's address goes through an opaque copy, as a global-address-space
+    // pointer in SGPRs: every load is that base + the lane's 32-bit offset + an immediate (one s_getpc instead of one per
+    // load), and the loads stay in front of the scalar loads below (left to itself the compiler sank fourteen of them behind
+    // the record's arrival, in front of the window fetch).  Placement checked in the generated code, not here.
+    pg_gbytes_t tb = (pg_gbytes_t)(const void*)&pg_desc_tab;
+    asm volatile("" : "+s"(tb));
+    const uint32_t o4 = 4u * (uint32_t)lane, o16 = 16u * (uint32_t)lane;
+    uint32_t mt[5];
+#pragma unroll
+    for (int it = 0; it < 5; it++) mt[it] = *(const PG_GLOBAL uint32_t*)(tb + (offsetof(PgDescTab, mom) + 256 * it) + o4);
+    pg_v4i Bop[3];
+#pragma unroll
+    for (int cb = 0; cb < 3; cb++) Bop[cb] = *(const PG_GLOBAL pg_v4i*)(tb + (offsetof(PgDescTab, btab) + 1024 * cb) + o16);
+    const pg_v4i pat = *(const PG_GLOBAL pg_v4i*)(tb + offsetof(PgDescTab, pat) + o16);
+    // Two scalar round trips to the window address: (1) the argument block, (2) the record + the frame's counts.
+    pg_u32x16 a0;
+    pg_u32x8 a1;
+    asm volatile("s_load_dwordx16 %0, %2, 0x0\n\ts_load_dwordx8 %1, %2, 0x40\n\ts_waitcnt lgkmcnt(0)"
+                 : "=&s"(a0), "=&s"(a1) : "s"(__builtin_amdgcn_kernarg_segment_ptr()) : "memory");
+#define PG_A64(T, v, k) reinterpret_cast<T>((uintptr_t)(((uint64_t)(v)[(k) + 1] << 32) | (v)[k]))
+    const int32_t* kpCount = PG_A64(const int32_t*, a0, 0);
+    const PgSelRec* sel = PG_A64(const PgSelRec*, a0, 2);
+    const int64_t selFrame = (int64_t)(((uint64_t)a0[5] << 32) | a0[4]);
+    pgorb_keypoint* kps = PG_A64(pgorb_keypoint*, a0, 6);
+    uint8_t* desc = PG_A64(uint8_t*, a0, 8);
+    int32_t* n_out = PG_A64(int32_t*, a0, 10);
+#undef PG_A64
+    const int nlevels = (int)a0[12], tieMode = (int)a0[13], cap_per_frame = (int)a0[14], slotBeg = (int)a0[15];
+    const int slotEnd = (int)a1[0], writeTotal = (int)a1[1], slotsPerXcd = (int)a1[2];
     // XCD-contiguous keypoint ranges: consecutive workgroups go to consecutive XCDs, so give XCD x
     // the x-th eighth of the frame's keypoint list (neighbours in the list are neighbours in the
     // image: their 43x43 windows share L2 lines)
     // (the launch covers slots [slotBeg, slotEnd) -- the slabs of a range of levels; writeTotal: this launch reports the
-    //  frame's keypoint count, i.e. K3 has finished for every level)
-    const int slot = slotBeg + (blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3);
-    // The wave is one long dependent chain and lives ~8 us; every load that does not depend on
-    // the keypoint is issued here, before the chain starts: the lane's entries of the moment
-    // table, the Toeplitz operands of the row pass and its four test-point pairs.
-    uint32_t mtU[5], mtM[5];
-#pragma unroll
-    for (int it = 0; it < 5; it++) {
-        const int i = min(lane + 64 * it, 31 * 9 - 1);
-        mtU[it] = pg_moment_tab.wu[i]; mtM[it] = pg_moment_tab.wm[i];
-    }
-    pg_v4i Bop[3];
-#pragma unroll
-    for (int cb = 0; cb < 3; cb++) Bop[cb] = reinterpret_cast<const pg_v4i*>(pg_blur_btab)[cb * 64 + lane];
-    float4 pat[4];
-#pragma unroll
-    for (int r = 0; r < 4; r++) pat[r] = *reinterpret_cast<const float4*>(pg_pattern31f.v + 4 * (64 * r + lane));
+    //  frame's keypoint count, i.e. K3 has finished for every level; slotsPerXcd: an eighth of the grid's x extent)
+    const int slot = slotBeg + (int)(blockIdx.x & 7) * slotsPerXcd + (int)(blockIdx.x >> 3);
     // Slot s of a frame IS entry s of the frame's selection slab (the levels' slabs lie back to back, K3 writes them in
     // dispatch order), and the 32-byte record holds the keypoint AND what the wave needs of its level (PgSelRec): the
     // record and the frame's per-level counts load in ONE scalar trip behind the arguments.  (The first version searched
     // the counts for the slot's level, loaded the record, then the level's fields: three dependent round trips were
     // 2.6 of the wave's 8.1 us.)  A level that kept fewer keypoints than its capacity (~1 % of the slots) leaves marked
     // records behind; their waves return after the loads.
-    const int32_t* kpc = P.kpCount + frame * PG_MAXL;
-    const int nlevels = P.nlevels;
-    const PgSelRec* recp = reinterpret_cast<const PgSelRec*>(P.sel) + ((int64_t)frame * P.selFrame + slot);
-    const int tieMode = P.tieMode;
-    asm volatile("" :: "s"(kpc), "s"(nlevels), "s"(recp), "s"(n_out), "s"(kps), "s"(desc), "s"(cap_per_frame), "s"(tieMode),
-                 "s"(slotBeg), "s"(slotEnd), "s"(writeTotal), "s"(argPad));     // (argPad completes the 16-byte group of the three ints: with
-                 // a dead fourth dword the allocator reused its register for another argument load and split the batch in two)
-    typedef int32_t pg_i32x16 __attribute__((ext_vector_type(16)));
-    typedef uint32_t pg_u32x8 __attribute__((ext_vector_type(8)));
+    const int32_t* kpc = kpCount + frame * PG_MAXL;
+    const PgSelRec* recp = sel + ((int64_t)frame * selFrame + slot);
     pg_i32x16 kc;
     pg_u32x8 rec;
     asm volatile("s_load_dwordx16 %0, %2, 0x0\n\ts_load_dwordx8 %1, %3, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=&s"(kc), "=&s"(rec) : "s"(kpc), "s"(recp) : "memory");
@@ -281,7 +310,7 @@ __global__ __launch_bounds__(64) void k_describe(const PgPlan P, const PgGauss7 
 
     // ---- IC_Angle: integer moments over the radius-15 disc (:77-104) -------------------
     // One task = one aligned dword (4 pixels) of one disc row; v_dot4_u32_u8 against the
-    // precomputed per-(row, dword) weights: (u+15) inside the disc / 0 outside, and the disc mask.
+    // precomputed per-(row, dword) weights: (u+16) inside the disc / 0 outside, and the disc mask made from them.
     int m10 = 0, m01 = 0;
 #pragma unroll
     for (int it = 0; it < 5; it++) {
@@ -289,8 +318,9 @@ __global__ __launch_bounds__(64) void k_describe(const PgPlan P, const PgGauss7 
         if (i >= 31 * 9) break;
         const int r = i / 9, q = i - r * 9;                     // r = v+15, dword q+1 = columns 4q+4 ..
         const uint32_t val = *reinterpret_cast<const uint32_t*>(raw + (DW_R - 15 + r) * DW_PITCH + 4 * (q + 1));
-        const int sv = (int)__builtin_amdgcn_udot4(val, mtM[it], 0u, false);                   // sum of disc pixels
-        m10 += (int)__builtin_amdgcn_udot4(val, mtU[it], 0u, false) - 15 * sv;                 // sum u * I
+        const uint32_t wm = ((mt[it] + 0x7F7F7F7Fu) >> 7) & 0x01010101u;                       // weights are <= 31: bit 7 of byte + 127 = "byte != 0"
+        const int sv = (int)__builtin_amdgcn_udot4(val, wm, 0u, false);                         // sum of disc pixels
+        m10 += (int)__builtin_amdgcn_udot4(val, mt[it], 0u, false) - 16 * sv;                   // sum u * I
         m01 += (r - 15) * sv;                                                                   // sum v * I
     }
     m10 = pg_wave_sum(m10);
@@ -307,7 +337,7 @@ __global__ __launch_bounds__(64) void k_describe(const PgPlan P, const PgGauss7 
     // pass can use v_dot2_u32_u16.  (The VALU version was 185 instructions per keypoint.)
     uint32_t* hT = hbuf;                                       // [22 row pairs][DH_PITCH columns]
     {
-        const int cinit = 128 * (2 * (G.k0 + G.k1 + G.k2) + G.k3);
+        constexpr int cinit = 128 * (2 * (PG_G7.k0 + PG_G7.k1 + PG_G7.k2) + PG_G7.k3);
         pg_v4i Aop[3];
         // ALL row operands leave the raw window before the first row sum is written over it
 #pragma unroll
@@ -334,9 +364,6 @@ __global__ __launch_bounds__(64) void k_describe(const PgPlan P, const PgGauss7 
     // column pass: on demand.  Only the 512 rotated tap positions of the 37x37 blurred tile are
     // ever read, so each lane blurs its own 8 taps from the row-pass sums (4 LDS dwords, 3
     // v_dot2_u32_u16 each) instead of the wave producing all 1369 pixels.
-    const pg_us2 K01 = __builtin_bit_cast(pg_us2, (uint32_t)G.k0 | ((uint32_t)G.k1 << 16));
-    const pg_us2 K23 = __builtin_bit_cast(pg_us2, (uint32_t)G.k2 | ((uint32_t)G.k3 << 16));
-    const pg_us2 K45 = __builtin_bit_cast(pg_us2, (uint32_t)G.k2 | ((uint32_t)G.k1 << 16));
     const int wvec = w & ~3;
 
     // ---- rBRIEF-256 (:107-147) ------------------------------------------------------------
@@ -346,13 +373,15 @@ __global__ __launch_bounds__(64) void k_describe(const PgPlan P, const PgGauss7 
     unsigned long long bits[4];
 #pragma unroll
     for (int r = 0; r < 4; r++) {
-        const float px0 = pat[r].x, py0 = pat[r].y, px1 = pat[r].z, py1 = pat[r].w;
+        const uint32_t pw = (uint32_t)pat[r];
+        const float px0 = (float)(int8_t)(pw & 0xFF), py0 = (float)(int8_t)((pw >> 8) & 0xFF);
+        const float px1 = (float)(int8_t)((pw >> 16) & 0xFF), py1 = (float)(int8_t)(pw >> 24);
         const int r0 = __float2int_rn(__fadd_rn(__fmul_rn(px0, b), __fmul_rn(py0, a)));
         const int c0 = __float2int_rn(__fsub_rn(__fmul_rn(px0, a), __fmul_rn(py0, b)));
         const int r1 = __float2int_rn(__fadd_rn(__fmul_rn(px1, b), __fmul_rn(py1, a)));
         const int c1 = __float2int_rn(__fsub_rn(__fmul_rn(px1, a), __fmul_rn(py1, b)));
-        const int t0 = pg_blur_at(hT, 18 + r0, 18 + c0, G, K01, K23, K45, tieMode == 0 && x + c0 < wvec);
-        const int t1 = pg_blur_at(hT, 18 + r1, 18 + c1, G, K01, K23, K45, tieMode == 0 && x + c1 < wvec);
+        const int t0 = pg_blur_at(hT, 18 + r0, 18 + c0, tieMode == 0 && x + c0 < wvec);
+        const int t1 = pg_blur_at(hT, 18 + r1, 18 + c1, tieMode == 0 && x + c1 < wvec);
         bits[r] = __ballot(t0 < t1);
     }
 
@@ -393,41 +422,33 @@ static PgGauss7 pg_gauss7()
     return g;
 }
 
-void pg_launch_describe(const PgPlan& P, int nframes, pgorb_keypoint* d_kps, uint8_t* d_desc,
+bool pg_launch_describe(const PgPlan& P, int nframes, pgorb_keypoint* d_kps, uint8_t* d_desc,
                         int cap_per_frame, int32_t* d_n, hipStream_t s)
 {
-    pg_launch_describe_levels(P, nframes, d_kps, d_desc, cap_per_frame, d_n, 0, P.nlevels, s);
+    return pg_launch_describe_levels(P, nframes, d_kps, d_desc, cap_per_frame, d_n, 0, P.nlevels, s);
 }
 
 // K4-6 for the keypoints of levels [levelBeg, levelEnd): their slots are one contiguous range of a frame's selection slab,
 // and a keypoint's output position needs the counts of the levels BELOW its own only.  The launch that contains the last
 // level also writes the frame's keypoint count (K3 must have finished for all levels by then).
-void pg_launch_describe_levels(const PgPlan& P, int nframes, pgorb_keypoint* d_kps, uint8_t* d_desc,
+// false (nothing launched): the taps derived the reference's way are not the constants the kernel was compiled with.
+bool pg_launch_describe_levels(const PgPlan& P, int nframes, pgorb_keypoint* d_kps, uint8_t* d_desc,
                                int cap_per_frame, int32_t* d_n, int levelBeg, int levelEnd, hipStream_t s)
 {
     static const PgGauss7 G = pg_gauss7();
-    static bool tabReady[64] = {};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev >= 0 && dev < 64 && !tabReady[dev]) {
-        const int K[7] = {G.k0, G.k1, G.k2, G.k3, G.k2, G.k1, G.k0};
-        uint32_t tab[3 * 64 * 4] = {};
-        for (int cb = 0; cb < 3; cb++)
-            for (int l = 0; l < 64; l++)
-                for (int j = 0; j < 16; j++) {
-                    const int k = 16 * (l >> 4) + j, n = 16 * cb + (l & 15), t = k - n;
-                    const uint32_t v = (t >= 0 && t <= 6 && n < DH_N) ? (uint32_t)K[t] : 0u;
-                    tab[(cb * 64 + l) * 4 + j / 4] |= v << (8 * (j % 4));
-                }
-        (void)hipMemcpyToSymbolAsync(HIP_SYMBOL(pg_blur_btab), tab, sizeof(tab), 0, hipMemcpyHostToDevice, s);
-        (void)hipStreamSynchronize(s);                           // tab is a stack array
-        tabReady[dev] = true;
-    }
-    const int slotBeg = (int)P.lvl[levelBeg].selOff;
-    const int slotEnd = (levelEnd < P.nlevels) ? (int)P.lvl[levelEnd].selOff : P.selTotal;
-    dim3 grid((slotEnd - slotBeg + 7) & ~7, nframes), block(64);
-    hipLaunchKernelGGL(k_describe, grid, block, 0, s, P, G, d_kps, d_desc, cap_per_frame, d_n, slotBeg, slotEnd,
-                       levelEnd == P.nlevels ? 1 : 0, 0);
+    static const bool tapsOk = G.k0 == PG_G7.k0 && G.k1 == PG_G7.k1 && G.k2 == PG_G7.k2 && G.k3 == PG_G7.k3;
+    if (!tapsOk) return false;
+    PgDescArgs KA = {};
+    KA.kpCount = P.kpCount; KA.sel = reinterpret_cast<const PgSelRec*>(P.sel); KA.selFrame = P.selFrame;
+    KA.kps = d_kps; KA.desc = d_desc; KA.n_out = d_n;
+    KA.nlevels = P.nlevels; KA.tieMode = P.tieMode; KA.cap_per_frame = cap_per_frame;
+    KA.slotBeg = (int)P.lvl[levelBeg].selOff;
+    KA.slotEnd = (levelEnd < P.nlevels) ? (int)P.lvl[levelEnd].selOff : P.selTotal;
+    KA.writeTotal = levelEnd == P.nlevels ? 1 : 0;
+    dim3 grid((KA.slotEnd - KA.slotBeg + 7) & ~7, nframes), block(64);
+    KA.slotsPerXcd = (int)(grid.x >> 3);
+    hipLaunchKernelGGL(k_describe, grid, block, 0, s, KA);
+    return true;
 }
 
 // ---- exhaustive check of the sin/cos contract (tests/test_gpu_parity.py, SURVEY.md hard part 4) --------

@@ -114,7 +114,7 @@ int run_batch(pgorb_ctx* c, const uint8_t* d_gray, bool resident_in_level0, int 
             pg_launch_quadtree_levels(P, nframes, beg, end, c->sQt);
             PG_HIP(c, hipEventRecord(c->evGrpQt[beg], c->sQt));
             PG_HIP(c, hipStreamWaitEvent(c->sDesc, c->evGrpQt[beg], 0));
-            pg_launch_describe_levels(P, nframes, d_kps, d_desc, cap_per_frame, d_n, beg, end, c->sDesc);
+            if (!pg_launch_describe_levels(P, nframes, d_kps, d_desc, cap_per_frame, d_n, beg, end, c->sDesc)) return fail(c, PGORB_E_HIP, "K4-6: the Gaussian taps derived on this host differ from the kernel's compiled-in constants");
             beg = end;
         }
         if (ev) PG_HIP(c, hipEventRecord(ev[2], s));
@@ -155,7 +155,7 @@ int run_batch(pgorb_ctx* c, const uint8_t* d_gray, bool resident_in_level0, int 
     pg_launch_quadtree(P, nframes, s);
     PG_DBG_SYNC("K3 quadtree");
     if (ev) PG_HIP(c, hipEventRecord(ev[3], s));
-    pg_launch_describe(P, nframes, d_kps, d_desc, cap_per_frame, d_n, s);
+    if (!pg_launch_describe(P, nframes, d_kps, d_desc, cap_per_frame, d_n, s)) return fail(c, PGORB_E_HIP, "K4-6: the Gaussian taps derived on this host differ from the kernel's compiled-in constants");
     PG_DBG_SYNC("K4-6 describe");
     if (ev) { PG_HIP(c, hipEventRecord(ev[4], s)); c->profExtract++; }
     PG_HIP(c, hipGetLastError());

@@ -359,6 +359,111 @@ int  pgorb_search_by_bow_batch_device(pgorb_ctx* ctx,
         const int32_t* d_pair_kf, const int32_t* d_pair_f, int npairs, const uint8_t* d_kf_point_valid,
         float nnratio, int check_orientation, int32_t* d_matches, int32_t* d_nmatches, void* hip_stream);
 
+/* ---- The tracking thread's projection matchers with the projection on the device (csrc/track.hip) ---------------------------
+ * The three pgorb_search_by_projection_* calls above take the projections as inputs; these three take what the rest of the
+ * library takes -- poses, the resident map-point table of pgorb_fuse and table indices -- and run the front part on the device too:
+ *   pgorb_search_local_points                  Tracking::SearchLocalPoints (src/Tracking.cc:1134-1184) from its first loop to the
+ *       matcher's return, with Frame::isInFrustum (src/Frame.cc:273-329) and SearchByProjection(F, points, th) (ORBmatcher.cc:46-131);
+ *   pgorb_search_by_projection_last_frame      all of SearchByProjection(CurrentFrame, LastFrame, th, bMono = true)
+ *       (src/ORBmatcher.cc:1342-1474; Tracking::TrackWithMotionModel; the 2*th retry stays with the caller);
+ *   pgorb_search_by_projection_keyframe_pose   all of SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist)
+ *       (src/ORBmatcher.cc:1476-1603; Tracking::Relocalization).
+ * Common inputs.  The frame as above: keypoints (mvKeysUn), descriptors, n and the Frame's float bounds.  pose: the frame's pose
+ * and camera as ONE pgorb_kf_pose (declared with pgorb_create_new_map_points below): Tcw = rows 0-2 of mTcw, Ow = mOw =
+ * -Rcw.t()*tcw formed by the caller exactly as for pgorb_fuse, fx, fy, cx, cy; invfx / invfy are not read.  The table: points
+ * (pgorb_map_point: the plain mWorldPos, mNormalVector, mfMinDistance, mfMaxDistance), point_desc [npoints][32], point_bad
+ * [npoints] (NULL = none bad) and point_has_obs [npoints] (Observations() > 0; NULL = all 1); no observation lists.  Queries are
+ * table indices.  assigned[i] = the index of the QUERY written to mvpMapPoints[i] by this call, or -1; the return value is
+ * nmatches.
+ *   (a) pgorb_search_local_points.  kp_point[i] = the table index of mCurrentFrame.mvpMapPoints[i] on entry or -1 (NULL = all
+ *       -1); queries[q] = mvpLocalMapPoints as table indices, distinct; query_seen[q] (NULL = none) is set for a point whose
+ *       mnLastFrameSeen already equals this frame's id for a reason the slots do not show (the outliers discarded at
+ *       Tracking.cc:781 and :904); viewing_cos_limit 0.5f, th 1, 3 or 5, nnratio 0.8f.  First loop (:1137-1153): a slot holding a
+ *       bad point is cleared, any other slot marks its point as seen.  Second loop (:1158-1171): a seen or bad query is skipped,
+ *       every other query runs isInFrustum.  in_view[q] = mbTrackInView (the caller does IncreaseVisible from it and from the
+ *       slots); proj_x, proj_y, level, view_cos [nq] (each may be NULL) = mTrackProjX / Y, mnTrackScaleLevel, mTrackViewCos of an
+ *       in-view query and 0 for any other; kp_point_out [n] (may be NULL) = the slots after the first loop; *n_to_match (may be
+ *       NULL) = nToMatch.  The matcher then runs with those values, kp_has_point[i] = the slot's point after clearing has
+ *       point_has_obs set.  (The reference skips the matcher when nToMatch == 0; the result, all -1 and 0, is the same.)
+ *   (b) pgorb_search_by_projection_last_frame.  Query i is the last frame's keypoint i (assigned holds last-frame keypoint
+ *       indices): last_kps[i].octave is read as mvKeys[i].octave and .angle as mvKeysUn[i].angle; last_point[i] = table index or
+ *       -1; last_outlier [nlast] (NULL = none); kp_has_point [n] as in pgorb_search_by_projection_frame (NULL after
+ *       TrackWithMotionModel's fill(NULL)).  As in the reference there is NO isBad() test (a bad point is projected and matched),
+ *       invzc = (float)(1.0 / z) and invzc < 0 skips, the bounds test is inclusive on both sides, and for mono neither bForward
+ *       nor bBackward holds, so tlc is not formed.  valid, u, v [nlast] (each may be NULL): valid[i] = the point went on to the
+ *       window search; (u, v) its projection, 0 when not valid.
+ *   (c) pgorb_search_by_projection_keyframe_pose.  kf_kps[i].angle is pKF->mvKeysUn[i].angle; kf_point[i] = the table index of
+ *       GetMapPointMatches()[i] or -1; already_found [nkf] (NULL = none); kp_has_point as in pgorb_search_by_projection_keyframe
+ *       (any point blocks a keypoint).  Bad and found points are skipped; there is NO depth-sign test (a point behind the camera
+ *       whose projection lands inside the bounds goes on, as in the reference); dist3D = cv::norm(x3Dw - Ow); the depth test and
+ *       PredictScale are those of pgorb_search_by_projection_keyframe.  u, v, dist3d [nkf] (each may be NULL): the projection
+ *       and distance of every point that is not NULL, bad or found and projects inside the bounds, 0 for any other.
+ * Float readings: DESIGN.md section 4 (the Fuse rows and the tracking rows).  A NaN projection (z = +-0 with a zero numerator, or
+ * inf - inf) makes the reference convert NaN to int inside GetFeaturesInArea, which is undefined; pgorb skips such a point (not in
+ * view / not valid).  An infinite u fails the bounds test as written.
+ * PGORB_E_ARG (single calls, checked on the host before anything else): a negative count, a NULL array that is read, empty bounds,
+ * th <= 0, a table index outside [-1, npoints) -- for the queries of (a) outside [0, npoints) -- and in (a) a repeated query.  The
+ * batched forms do not check: an index outside [0, npoints) counts as NULL.
+ * Limits (PGORB_E_LIMIT): those of the deciding kernel above, keypoints * 13 + queries * 10 + 256 <= 163840 bytes and 16000 for
+ * each count (queries = nq, nlast, nkf; in the batched forms of (b) and (c) a pair's queries are a frame of the batch, so
+ * cap_per_frame * 23 + 256 <= 163840: 7112); and in (a) npoints <= 1048576: the seen marks are one bit per table point and pair
+ * (npairs * 128 KiB of the context's scratch arena at that size). */
+struct pgorb_kf_pose;
+struct pgorb_map_point;
+int  pgorb_search_local_points(pgorb_ctx* ctx,
+        const pgorb_keypoint* kps, const uint8_t* desc, int n, float min_x, float max_x, float min_y, float max_y,
+        const struct pgorb_kf_pose* pose, const int32_t* kp_point /*[n] or NULL*/,
+        int npoints, const struct pgorb_map_point* points, const uint8_t* point_desc, const uint8_t* point_bad,
+        const uint8_t* point_has_obs, int nq, const int32_t* queries, const uint8_t* query_seen,
+        float viewing_cos_limit, float th, float nnratio,
+        uint8_t* in_view /*[nq]*/, float* proj_x, float* proj_y, int32_t* level, float* view_cos,
+        int32_t* kp_point_out /*[n] or NULL*/, int32_t* n_to_match, int32_t* assigned /*[n]*/);
+int  pgorb_search_by_projection_last_frame(pgorb_ctx* ctx,
+        const pgorb_keypoint* kps, const uint8_t* desc, int n, float min_x, float max_x, float min_y, float max_y,
+        const struct pgorb_kf_pose* pose, const uint8_t* kp_has_point,
+        const pgorb_keypoint* last_kps, int nlast, const int32_t* last_point, const uint8_t* last_outlier,
+        int npoints, const struct pgorb_map_point* points, const uint8_t* point_desc, const uint8_t* point_has_obs,
+        float th, int check_orientation, uint8_t* valid, float* u, float* v, int32_t* assigned /*[n]*/);
+int  pgorb_search_by_projection_keyframe_pose(pgorb_ctx* ctx,
+        const pgorb_keypoint* kps, const uint8_t* desc, int n, float min_x, float max_x, float min_y, float max_y,
+        const struct pgorb_kf_pose* pose, const uint8_t* kp_has_point,
+        const pgorb_keypoint* kf_kps, int nkf, const int32_t* kf_point, const uint8_t* already_found,
+        int npoints, const struct pgorb_map_point* points, const uint8_t* point_desc, const uint8_t* point_bad,
+        float th, int orb_dist, int check_orientation, float* u, float* v, float* dist3d, int32_t* assigned /*[n]*/);
+/* Batched, resident forms (the single calls are one-pair batches of these).  Frames and grids as for the batched matchers above;
+ * pair p matches into frame d_pair_frame[p] (NULL: frame p) under d_pose[p]; the table is shared by all pairs.  (a): d_kp_point,
+ * d_kp_point_out [npairs][cap_per_frame]; d_queries, d_query_seen and the per-query outputs [npairs][qcap] with d_nq[p] entries in
+ * use (entries past d_nq[p] are not written); d_n_to_match [npairs]; d_in_view and d_n_to_match are required here.  (b), (c): the last frame / key frame of pair p is frame
+ * d_pair_last[p] / d_pair_kf[p] of the same batch; d_last_point, d_last_outlier, d_kf_point, d_already_found and the per-query
+ * outputs are [npairs][cap_per_frame], d_kp_has_point [npairs][cap_per_frame] (NULL = none).  d_assigned [npairs][cap_per_frame],
+ * d_nmatches [npairs].  One lane per (pair, query) projects (k_track_front) and writes the query arrays the two passes of
+ * SearchByProjection read, in the context's scratch arena. */
+int  pgorb_search_local_points_batch_device(pgorb_ctx* ctx,
+        const pgorb_keypoint* d_kps, const uint8_t* d_desc, const int32_t* d_n, int cap_per_frame,
+        const int32_t* d_grid_start, const int32_t* d_grid_idx, const int32_t* d_pair_frame, int npairs,
+        float min_x, float max_x, float min_y, float max_y, const struct pgorb_kf_pose* d_pose, const int32_t* d_kp_point,
+        int npoints, const struct pgorb_map_point* d_points, const uint8_t* d_point_desc, const uint8_t* d_point_bad,
+        const uint8_t* d_point_has_obs, int qcap, const int32_t* d_nq, const int32_t* d_queries, const uint8_t* d_query_seen,
+        float viewing_cos_limit, float th, float nnratio,
+        uint8_t* d_in_view, float* d_proj_x, float* d_proj_y, int32_t* d_level, float* d_view_cos,
+        int32_t* d_kp_point_out, int32_t* d_n_to_match, int32_t* d_assigned, int32_t* d_nmatches, void* hip_stream);
+int  pgorb_search_by_projection_last_frame_batch_device(pgorb_ctx* ctx,
+        const pgorb_keypoint* d_kps, const uint8_t* d_desc, const int32_t* d_n, int cap_per_frame,
+        const int32_t* d_grid_start, const int32_t* d_grid_idx, const int32_t* d_pair_frame, const int32_t* d_pair_last, int npairs,
+        float min_x, float max_x, float min_y, float max_y, const struct pgorb_kf_pose* d_pose, const uint8_t* d_kp_has_point,
+        const int32_t* d_last_point, const uint8_t* d_last_outlier,
+        int npoints, const struct pgorb_map_point* d_points, const uint8_t* d_point_desc, const uint8_t* d_point_has_obs,
+        float th, int check_orientation, uint8_t* d_valid, float* d_u, float* d_v,
+        int32_t* d_assigned, int32_t* d_nmatches, void* hip_stream);
+int  pgorb_search_by_projection_keyframe_pose_batch_device(pgorb_ctx* ctx,
+        const pgorb_keypoint* d_kps, const uint8_t* d_desc, const int32_t* d_n, int cap_per_frame,
+        const int32_t* d_grid_start, const int32_t* d_grid_idx, const int32_t* d_pair_frame, const int32_t* d_pair_kf, int npairs,
+        float min_x, float max_x, float min_y, float max_y, const struct pgorb_kf_pose* d_pose, const uint8_t* d_kp_has_point,
+        const int32_t* d_kf_point, const uint8_t* d_already_found,
+        int npoints, const struct pgorb_map_point* d_points, const uint8_t* d_point_desc, const uint8_t* d_point_bad,
+        float th, int orb_dist, int check_orientation, float* d_u, float* d_v, float* d_dist3d,
+        int32_t* d_assigned, int32_t* d_nmatches, void* hip_stream);
+
 /* ---- Matcher of the local-mapping thread ------------------------------------------------------------------------------
  *   pgorb_search_for_triangulation   ORBmatcher::SearchForTriangulation(pKF1, pKF2, F12, vMatchedPairs, bOnlyStereo = false)
  *       src/ORBmatcher.cc:659-825 with CheckDistEpipolarLine :142-159, monocular (mvuRight < 0) -- called by

@@ -44,6 +44,9 @@ SYMBOLS = (
     "pgorb_detect_loop_candidates", "pgorb_detect_loop_candidates_batch_device",
     "pgorb_search_by_projection_keyframe", "pgorb_search_by_projection_keyframe_batch_device",
     "pgorb_log_f", "pgorb_log_scale_factor", "pgorb_predict_scale",
+    "pgorb_search_local_points", "pgorb_search_local_points_batch_device",
+    "pgorb_search_by_projection_last_frame", "pgorb_search_by_projection_last_frame_batch_device",
+    "pgorb_search_by_projection_keyframe_pose", "pgorb_search_by_projection_keyframe_pose_batch_device",
     "pgorb_undistort_keypoints", "pgorb_undistort_keypoints_batch_device", "pgorb_image_bounds",
     "pgorb_host_alloc", "pgorb_host_free", "pgorb_host_register", "pgorb_host_unregister", "pgorb_stream_create", "pgorb_stream_create_ingest", "pgorb_stream_create_device", "pgorb_stream_submit_device", "pgorb_stream_wait_device", "pgorb_stream_lanes", "pgorb_stream_destroy", "pgorb_stream_input", "pgorb_stream_reset", "pgorb_stream_submit",
     "pgorb_stream_wait", "pgorb_stream_frontend", "pgorb_stream_frontend_results", "pgorb_set_option", "pgorb_get_option", "pgorb_matcher_is_popcount",
@@ -157,6 +160,26 @@ def lib():
     L.pgorb_search_by_projection_keyframe.argtypes = [vp, vp, vp, C.c_int] + f4 + [vp, C.c_int] + [vp] * 9 + [C.c_float, C.c_float, C.c_int, C.c_int, vp]
     L.pgorb_search_by_projection_keyframe_batch_device.argtypes = [vp, vp, vp, vp, C.c_int, vp, vp, vp, C.c_int] + f4 + [vp, C.c_int, vp] + [vp] * 9 + \
         [C.c_float, C.c_float, C.c_int, C.c_int, vp, vp, vp]
+    # the tracking thread's matchers with the projection on the device
+    # (ctx, kps, desc, n, bounds x 4, pose, kp_point, npoints, points, point_desc, point_bad, point_has_obs, nq, queries, query_seen,
+    #  viewing_cos_limit, th, nnratio, in_view, proj_x, proj_y, level, view_cos, kp_point_out, n_to_match, assigned)
+    L.pgorb_search_local_points.argtypes = [vp, vp, vp, C.c_int] + f4 + [vp, vp, C.c_int] + [vp] * 4 + [C.c_int, vp, vp] + [C.c_float] * 3 + [vp] * 8
+    # (ctx, kps, desc, n, bounds x 4, pose, kp_has_point, last_kps, nlast, last_point, last_outlier, npoints, points, point_desc,
+    #  point_has_obs, th, check, valid, u, v, assigned)
+    L.pgorb_search_by_projection_last_frame.argtypes = [vp, vp, vp, C.c_int] + f4 + [vp, vp, vp, C.c_int, vp, vp, C.c_int, vp, vp, vp,
+                                                        C.c_float, C.c_int] + [vp] * 4
+    # (..., kf_kps, nkf, kf_point, already_found, npoints, points, point_desc, point_bad, th, orb_dist, check, u, v, dist3d, assigned)
+    L.pgorb_search_by_projection_keyframe_pose.argtypes = [vp, vp, vp, C.c_int] + f4 + [vp, vp, vp, C.c_int, vp, vp, C.c_int, vp, vp, vp,
+                                                           C.c_float, C.c_int, C.c_int] + [vp] * 4
+    # (ctx, kps, desc, n, cap, grid_start, grid_idx, pair_frame, npairs, bounds x 4, pose, kp_point, npoints, 4 table arrays, qcap, nq,
+    #  queries, query_seen, viewing_cos_limit, th, nnratio, 5 query outputs, kp_point_out, n_to_match, assigned, nmatches, stream)
+    L.pgorb_search_local_points_batch_device.argtypes = [vp, vp, vp, vp, C.c_int, vp, vp, vp, C.c_int] + f4 + [vp, vp, C.c_int] + [vp] * 4 + \
+        [C.c_int, vp, vp, vp] + [C.c_float] * 3 + [vp] * 10
+    # (ctx, kps, desc, n, cap, grid_start, grid_idx, pair_frame, pair_last | pair_kf, npairs, bounds x 4, pose, kp_has_point, ...)
+    L.pgorb_search_by_projection_last_frame_batch_device.argtypes = [vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, C.c_int] + f4 + \
+        [vp, vp, vp, vp, C.c_int, vp, vp, vp, C.c_float, C.c_int] + [vp] * 6
+    L.pgorb_search_by_projection_keyframe_pose_batch_device.argtypes = [vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, C.c_int] + f4 + \
+        [vp, vp, vp, vp, C.c_int, vp, vp, vp, C.c_float, C.c_int, C.c_int] + [vp] * 6
     L.pgorb_log_f.argtypes = [C.c_float]
     L.pgorb_log_scale_factor.argtypes = [vp]
     L.pgorb_predict_scale.argtypes = [vp, C.c_float, C.c_float]

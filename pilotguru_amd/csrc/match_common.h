@@ -1,6 +1,7 @@
 // match_common.h -- what the Frame side, the guided matchers, CreateNewMapPoints, Fuse, loop closing's matchers and the map-point refresh
-// share: included by frame.hip, window_match.hip, node_match.hip, mapping.hip, fuse.hip, loop.hip (the last two through kf_window.h)
-// and map_point.hip, and by no other translation unit.
+// share: included by frame.hip, window_match.hip, node_match.hip, mapping.hip, fuse.hip, loop.hip (the last two through kf_window.h),
+// track.hip (through kf_window.h and proj_match.h, which window_match.hip includes too) and map_point.hip, and by no other
+// translation unit.
 #pragma once
 #include "pgorb_internal.h"
 #include <algorithm>

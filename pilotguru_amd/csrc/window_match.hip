@@ -26,25 +26,8 @@
 //       cell by cell.  The rotation histogram only needs (i1, the i2 it was matched to when pushed):
 //       the bins are computed after the loop, in parallel.
 // All per-pair state (vMatchedDistance, vnMatches21, vnMatches12) lives in LDS.
-#include "match_common.h"
+#include "proj_match.h"
 
-// ---- candidate lists of the two-pass matchers (round 4: variable length) -----------------------------------------------
-// Pass A stores EVERY surviving candidate of a query in the reference's scan order: the first LIST_K in the query's fixed slots,
-// the rest in the pair's pool (one atomic per query that needs it).  Rounds 2-3 capped the lists at 64 and re-evaluated denser
-// queries in place inside the sequential pass -- the initialisation workload's cliff.  Only when a pair's pool is full (an
-// average of LIST_K + LIST_POOL candidates per query) is a query still evaluated in place (count LIST_OVER).
-#define LIST_K 64
-#define LIST_POOL 256
-#define LIST_OVER 0xFFFFu
-#define SFI_K LIST_K
-struct PgLists {
-    uint32_t* fixed;             // [rows][LIST_K]
-    uint16_t* cnt;               // [rows]   survivors of the query (LIST_OVER: evaluate in place)
-    uint32_t* ovf;               // [rows]   where the query's entries LIST_K.. start in its pair's pool
-    uint32_t* pool;              // [npairs][poolPerPair]
-    int32_t*  poolTop;           // [npairs] (zeroed before pass A)
-    uint32_t  poolPerPair;
-};
 // scratch layout for npairs x rowsPerPair rows; returns the bytes needed
 static size_t pg_lists_layout(void* scratch, int npairs, int rowsPerPair, PgLists* L)
 {
@@ -394,19 +377,6 @@ __global__ __launch_bounds__(64) void k_search_for_initialization(
 // (keypoints / descriptors `cap` apart, grids (GRID_CELLS + 1) / cap apart); query arrays are [npairs][qcap].  The search
 // radius and the level window of a query are derived here from what the caller holds (predicted level + viewing cosine,
 // or the last frame's octave) exactly as the reference does, so the host never touches the queries.
-struct PgProjBatch {
-    const pgorb_keypoint* K; const uint8_t* D; const int32_t* n; int cap;
-    const int32_t* gstart; const int32_t* gidx; const int32_t* pairFrame;
-    const uint8_t* kpHasPoint;             // [npairs][cap] or null
-    int qcap; const int32_t* nq;
-    const uint8_t* valid; const float* x; const float* y; const int32_t* level; const float* aux;   // aux: view cos (mode 0) / angle (mode 1)
-    const uint8_t* desc; const uint8_t* hasObs;
-    float sf[PG_MAXL + 1]; int nlevels; float th;
-    // mode 2 (key frame, relocalisation): level = PredictScale(dist3d), aux = the key frame keypoint's angle
-    const uint8_t* found; const float* dist3d; const float* minDist; const float* maxDist; float logSf; int orbDist;
-    float maxX, maxY;                      // mnMaxX / mnMaxY (the kernels derive everything else from minX / minY and the inverse cell sizes)
-};
-
 // Round 3, two passes like SearchForInitialization: the candidates of a query and their distances do not depend on the
 // assignments made so far (only `taken` does), so pass A computes them for every query of every pair in parallel and
 // pass B -- one wave per pair, the reference's order -- only filters the stored candidates by `taken` and picks.
@@ -766,17 +736,37 @@ static int pg_lists_acquire(pgorb_ctx* c, int npairs, int rowsPerPair, hipStream
     return 0;
 }
 
-// The dynamic LDS of k_search_by_projection for `cap` keypoints and `qcap` queries: minq, minAny, asg (4 B each) and taken (1 B) per
-// keypoint; listA, listB, cntL, qBest (2 B each), rotBin and done (1 B each) per query; the counters and the histogram.  This line, not
-// the 16 000 of the other matchers, is the family's limit: 12 582 keypoints with one query, 7 112 with as many queries, 16 358 queries
-// with one keypoint (the 16 000 gate comes first there).
-static size_t pg_sbp_lds(int cap, int qcap) { return (size_t)cap * 13 + (size_t)qcap * 10 + 256; }
-static const size_t PG_SBP_LDS_MAX = (size_t)160 * 1024;      // what pg_raise_lds grants a workgroup (match_common.h)
-static const char* const PG_SBP_LDS_MSG =
-    "SearchByProjection: keypoints * 13 + queries * 10 + 256 bytes exceed the 163840 B of LDS (e.g. 12582 keypoints with 1 query, 7112 with 7112)";
+int pg_proj_begin(pgorb_ctx* c, int cap, int qcap, int npairs, size_t extraBytes, hipStream_t stream, PgLists* Ls, void** extra)
+{
+    if (cap > 16000 || qcap > 16000) return pg_ctx_fail(c, PGORB_E_LIMIT, "more than 16000 keypoints / queries");
+    if (hipSetDevice(pg_ctx_device(c)) != hipSuccess) return pg_ctx_fail(c, PGORB_E_HIP, "hipSetDevice failed");
+    if (!pg_raise_lds<k_search_by_projection>(c, pg_sbp_lds(cap, qcap)) ||
+        !pg_raise_lds<k_proj_candidates>(c, (size_t)4 * cap * 2)) return pg_ctx_fail(c, PGORB_E_LIMIT, PG_SBP_LDS_MSG);
+    const int rows = std::max(qcap, 1);
+    const size_t lists = pg_lists_layout(nullptr, npairs, rows, Ls) + 256;
+    void* scratch;
+    const int rc = pg_ctx_scratch(c, lists + extraBytes, stream, &scratch);
+    if (rc) return rc;
+    pg_lists_layout(scratch, npairs, rows, Ls);
+    if (extra) *extra = (uint8_t*)scratch + lists;
+    if (hipMemsetAsync(Ls->poolTop, 0, (size_t)npairs * 4, stream) != hipSuccess) return pg_ctx_fail(c, PGORB_E_HIP, "hipMemsetAsync failed");
+    return 0;
+}
 
-// what the key-frame form (mode 2) takes beyond the common query arrays
-struct PgProjKeyFrame { const uint8_t* found; const float* dist3d; const float* minDist; const float* maxDist; float logSf; int orbDist; };
+int pg_proj_run(pgorb_ctx* c, PgProjBatch& B, int npairs, float min_x, float max_x, float min_y, float max_y, int mode, float nnratio,
+                int check_orientation, const PgLists& Ls, int32_t* d_assigned, int32_t* d_nmatches, hipStream_t stream)
+{
+    B.nlevels = pgorb_levels(c); B.maxX = max_x; B.maxY = max_y;
+    pgorb_scale_tables(c, B.sf, nullptr, nullptr, nullptr);
+    const float invW = (float)GRID_COLS / (max_x - min_x), invH = (float)GRID_ROWS / (max_y - min_y);
+    const int cap = B.cap, qcap = B.qcap;
+    if (qcap) hipLaunchKernelGGL(k_proj_candidates, dim3((qcap + 3) / 4, npairs), dim3(256), (size_t)4 * cap * 2, stream, B, min_x, min_y, invW,
+                                 invH, mode, Ls);
+    hipLaunchKernelGGL(k_search_by_projection, dim3(npairs), dim3(RR_T), pg_sbp_lds(cap, qcap), stream, B, min_x, min_y, invW, invH, mode,
+                       nnratio, check_orientation, Ls, d_assigned, d_nmatches);
+    if (hipGetLastError() != hipSuccess) return pg_ctx_fail(c, PGORB_E_HIP, "k_search_by_projection launch failed");
+    return pg_ctx_scratch_done(c, stream);
+}
 
 static int pg_search_by_projection_batch(pgorb_ctx* c, int mode, const pgorb_keypoint* d_kps, const uint8_t* d_desc, const int32_t* d_n, int cap,
                                          const int32_t* d_grid_start, const int32_t* d_grid_idx, const int32_t* d_pair_frame, int npairs,
@@ -795,27 +785,16 @@ static int pg_search_by_projection_batch(pgorb_ctx* c, int mode, const pgorb_key
         return pg_ctx_fail(c, PGORB_E_ARG, "bad argument to pgorb_search_by_projection_*");
     if (cap > 16000 || qcap > 16000) return pg_ctx_fail(c, PGORB_E_LIMIT, "more than 16000 keypoints / queries");
     if (!npairs) return 0;
-    if (hipSetDevice(pg_ctx_device(c)) != hipSuccess) return pg_ctx_fail(c, PGORB_E_HIP, "hipSetDevice failed");
+    PgLists Ls;                                                                    // of every query of every pair
+    const int rcs = pg_proj_begin(c, cap, qcap, npairs, 0, stream, &Ls, nullptr);
+    if (rcs) return rcs;
     PgProjBatch B;
     B.K = d_kps; B.D = d_desc; B.n = d_n; B.cap = cap; B.gstart = d_grid_start; B.gidx = d_grid_idx; B.pairFrame = d_pair_frame;
     B.kpHasPoint = d_kp_has_point; B.qcap = qcap; B.nq = d_nq; B.valid = d_valid; B.x = d_x; B.y = d_y; B.level = d_level; B.aux = d_aux;
-    B.desc = d_qdesc; B.hasObs = d_qobs; B.nlevels = pgorb_levels(c); B.th = th;
-    B.found = nullptr; B.dist3d = B.minDist = B.maxDist = nullptr; B.logSf = 1.0f; B.orbDist = TH_HIGH; B.maxX = max_x; B.maxY = max_y;
+    B.desc = d_qdesc; B.hasObs = d_qobs; B.th = th;
+    B.found = nullptr; B.dist3d = B.minDist = B.maxDist = nullptr; B.logSf = 1.0f; B.orbDist = TH_HIGH;
     if (m2) { B.found = kf->found; B.dist3d = kf->dist3d; B.minDist = kf->minDist; B.maxDist = kf->maxDist; B.logSf = kf->logSf; B.orbDist = kf->orbDist; }
-    pgorb_scale_tables(c, B.sf, nullptr, nullptr, nullptr);
-    const float invW = (float)GRID_COLS / (max_x - min_x), invH = (float)GRID_ROWS / (max_y - min_y);
-    const size_t ldsA = (size_t)4 * cap * 2;
-    const size_t lds = pg_sbp_lds(cap, qcap);
-    if (!pg_raise_lds<k_search_by_projection>(c, lds) ||
-        !pg_raise_lds<k_proj_candidates>(c, ldsA)) return pg_ctx_fail(c, PGORB_E_LIMIT, PG_SBP_LDS_MSG);
-    PgLists Ls;                                                                    // of every query of every pair
-    const int rcs = pg_lists_acquire(c, npairs, std::max(qcap, 1), stream, &Ls);
-    if (rcs) return rcs;
-    if (qcap) hipLaunchKernelGGL(k_proj_candidates, dim3((qcap + 3) / 4, npairs), dim3(256), ldsA, stream, B, min_x, min_y, invW, invH, mode, Ls);
-    hipLaunchKernelGGL(k_search_by_projection, dim3(npairs), dim3(RR_T), lds, stream, B, min_x, min_y, invW, invH, mode, nnratio,
-                       check_orientation, Ls, d_assigned, d_nmatches);
-    if (hipGetLastError() != hipSuccess) return pg_ctx_fail(c, PGORB_E_HIP, "k_search_by_projection launch failed");
-    return pg_ctx_scratch_done(c, stream);
+    return pg_proj_run(c, B, npairs, min_x, max_x, min_y, max_y, mode, nnratio, check_orientation, Ls, d_assigned, d_nmatches, stream);
 }
 
 // single frame through host buffers: a one-pair batch

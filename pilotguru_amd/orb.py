@@ -442,6 +442,102 @@ class ORBmatcher:
             ext.log_scale_factor(), float(th), int(ORBdist), int(self.mbCheckOrientation), _p(out)))
         return nm, out[:F.N].copy()
 
+    @staticmethod
+    def _track_args(name, F, pose, table, idx, idx_name, lo, th, bounds, has_obs):
+        """The checked inputs the three pose forms share: the frame, its bounds and pose, the table's Observations() > 0 flags
+        (default: from the table's observation lists) and one index array into the table, every entry in [lo, table.n)."""
+        kp, desc = _frame(F, name)
+        bounds = F.bounds if bounds is None else bounds
+        if len(bounds) != 4 or not (float(bounds[1]) > float(bounds[0]) and float(bounds[3]) > float(bounds[2])):
+            raise ValueError("%s: bounds must be (min_x, max_x, min_y, max_y) with max > min" % name)
+        if not float(th) > 0:
+            raise ValueError("%s: th must be positive" % name)
+        idx = np.ascontiguousarray(idx, np.int32).reshape(-1)
+        if len(idx) and (int(np.min(idx)) < lo or int(np.max(idx)) >= table.n):
+            raise ValueError("%s: %s names a point outside the table (%d points)" % (name, idx_name, table.n))
+        obs = (np.diff(table.obs_start) > 0).astype(np.uint8) if has_obs is None else _arr(has_obs, np.uint8, table.n, "point_has_obs")
+        if table.n == 0:
+            obs = np.zeros(1, np.uint8)
+        P = np.ascontiguousarray(pose, KF_POSE_DTYPE).reshape(())
+        return kp, desc, [float(b) for b in bounds], idx, obs, P
+
+    def SearchLocalPoints(self, F, pose, kp_point, table, queries, query_seen=None, th=1.0, viewing_cos_limit=0.5, bounds=None,
+                          point_has_obs=None):
+        """Tracking::SearchLocalPoints (src/Tracking.cc:1134-1184) with Frame::isInFrustum (src/Frame.cc:273-329) and
+        SearchByProjection(F, points, th) (src/ORBmatcher.cc:46-131) on the device.  pose: the frame's KF_POSE_DTYPE record;
+        kp_point[i]: the table index of mvpMapPoints[i] or -1 (None = all -1); table: a MapPointTable; queries: mvpLocalMapPoints
+        as distinct table indices; query_seen: see include/pgorb.h.  Returns a dict: nmatches, assigned, in_view, proj_x, proj_y,
+        level, view_cos, kp_point_out, n_to_match."""
+        name = "SearchLocalPoints"
+        kp, desc, b, q, obs, P = self._track_args(name, F, pose, table, queries, "queries", 0, th, bounds, point_has_obs)
+        nq = len(q)
+        if len(np.unique(q)) != nq:
+            raise ValueError("%s: a map point is queried twice" % name)
+        slots = None if kp_point is None else _arr(kp_point, np.int32, F.N, "kp_point")
+        if slots is not None:
+            table.check_indices(slots, "kp_point", name)
+        seen = None if query_seen is None else _arr(query_seen, np.uint8, nq, "query_seen")
+        ext = F.ext
+        m = max(nq, 1)
+        iv, px, py = np.zeros(m, np.uint8), np.zeros(m, np.float32), np.zeros(m, np.float32)
+        lv, vc = np.zeros(m, np.int32), np.zeros(m, np.float32)
+        out, kpo, ntm = np.full(max(F.N, 1), -1, np.int32), np.full(max(F.N, 1), -1, np.int32), np.zeros(1, np.int32)
+        t = table
+        nm = ext._check(ext._L.pgorb_search_local_points(
+            ext._h, _p(kp), _p(desc), F.N, *b, _p(P), None if slots is None else _p(slots), t.n, _p(t.points), _p(t.descriptors),
+            _p(t.bad), _p(obs), nq, _p(q if nq else lv), None if seen is None else _p(seen), float(viewing_cos_limit), float(th),
+            self.mfNNratio, _p(iv), _p(px), _p(py), _p(lv), _p(vc), _p(kpo), _p(ntm), _p(out)))
+        return dict(nmatches=nm, assigned=out[:F.N].copy(), in_view=iv[:nq].copy(), proj_x=px[:nq].copy(), proj_y=py[:nq].copy(),
+                    level=lv[:nq].copy(), view_cos=vc[:nq].copy(), kp_point_out=kpo[:F.N].copy(), n_to_match=int(ntm[0]))
+
+    def SearchByProjectionLastFramePose(self, CurrentFrame, pose, last_keys, last_point, table, th, last_outlier=None,
+                                        kp_has_point=None, bounds=None, point_has_obs=None):
+        """All of SearchByProjection(CurrentFrame, LastFrame, th, bMono=true) (src/ORBmatcher.cc:1342-1474) on the device.
+        last_keys: the last frame's keypoints (octave and angle are read); last_point[i]: the table index of
+        LastFrame.mvpMapPoints[i] or -1; last_outlier: mvbOutlier (None = none).  Returns a dict: nmatches, assigned (last-frame
+        keypoint indices), valid, u, v."""
+        name = "SearchByProjectionLastFramePose"
+        F = CurrentFrame
+        kp, desc, b, lp, obs, P = self._track_args(name, F, pose, table, last_point, "last_point", -1, th, bounds, point_has_obs)
+        nl = len(lp)
+        lk = _arr(last_keys, KEYPOINT_DTYPE, nl, "last_keys")
+        outl = None if last_outlier is None else _arr(last_outlier, np.uint8, nl, "last_outlier")
+        has = None if kp_has_point is None else _arr(kp_has_point, np.uint8, F.N, "kp_has_point")
+        ext = F.ext
+        m = max(nl, 1)
+        va, u, v = np.zeros(m, np.uint8), np.zeros(m, np.float32), np.zeros(m, np.float32)
+        out = np.full(max(F.N, 1), -1, np.int32)
+        t = table
+        nm = ext._check(ext._L.pgorb_search_by_projection_last_frame(
+            ext._h, _p(kp), _p(desc), F.N, *b, _p(P), None if has is None else _p(has), _p(lk if nl else out), nl,
+            _p(lp if nl else out), None if outl is None else _p(outl), t.n, _p(t.points), _p(t.descriptors), _p(obs), float(th),
+            int(self.mbCheckOrientation), _p(va), _p(u), _p(v), _p(out)))
+        return dict(nmatches=nm, assigned=out[:F.N].copy(), valid=va[:nl].copy(), u=u[:nl].copy(), v=v[:nl].copy())
+
+    def SearchByProjectionKeyFramePose(self, CurrentFrame, pose, kf_keys, kf_point, table, th, ORBdist, already_found=None,
+                                       kp_has_point=None, bounds=None):
+        """All of SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist) (src/ORBmatcher.cc:1476-1603) on the device.
+        kf_keys: pKF->mvKeysUn (the angle is read); kf_point[i]: the table index of GetMapPointMatches()[i] or -1;
+        already_found: per key-frame keypoint (None = none).  Returns a dict: nmatches, assigned (key-frame keypoint indices), u,
+        v, dist3d."""
+        name = "SearchByProjectionKeyFramePose"
+        F = CurrentFrame
+        kp, desc, b, kfp, _, P = self._track_args(name, F, pose, table, kf_point, "kf_point", -1, th, bounds, None)
+        nk = len(kfp)
+        kk = _arr(kf_keys, KEYPOINT_DTYPE, nk, "kf_keys")
+        found = None if already_found is None else _arr(already_found, np.uint8, nk, "already_found")
+        has = None if kp_has_point is None else _arr(kp_has_point, np.uint8, F.N, "kp_has_point")
+        ext = F.ext
+        m = max(nk, 1)
+        u, v, d3 = np.zeros(m, np.float32), np.zeros(m, np.float32), np.zeros(m, np.float32)
+        out = np.full(max(F.N, 1), -1, np.int32)
+        t = table
+        nm = ext._check(ext._L.pgorb_search_by_projection_keyframe_pose(
+            ext._h, _p(kp), _p(desc), F.N, *b, _p(P), None if has is None else _p(has), _p(kk if nk else out), nk,
+            _p(kfp if nk else out), None if found is None else _p(found), t.n, _p(t.points), _p(t.descriptors), _p(t.bad), float(th),
+            int(ORBdist), int(self.mbCheckOrientation), _p(u), _p(v), _p(d3), _p(out)))
+        return dict(nmatches=nm, assigned=out[:F.N].copy(), u=u[:nk].copy(), v=v[:nk].copy(), dist3d=d3[:nk].copy())
+
     def SearchByBoW(self, ext, kf_desc, kf_angle, kf_point_valid, kf_featvec, F, f_featvec):
         """SearchByBoW(KeyFrame* pKF, Frame &F, vpMapPointMatches) (src/ORBmatcher.cc:161-290).
         Feature vectors are the (nodes, starts, features) triples of ORBVocabulary.transform().

@@ -31,7 +31,14 @@ next to each, the oracle's CPU time for the same work (1 thread, a few frames, s
                sequential Python reference (tests/loop_reference.py, OUR restatement, not ORB-SLAM2) for ONE problem, whose results
                the GPU's must equal.  --loop-only runs these rows alone
 
-usage: python tools/next_tier_bench.py [--batch 128] [--out profiles/r02_next_tier.txt] [--refresh-only | --place-only | --loop-only]"""
+  tracking     Tracking::SearchLocalPoints (Tracking.cc:1134-1184) as ONE batched resident call with the projection on the device
+               (pgorb_search_local_points_batch_device): 127 pairs at 1080p bounds, 2000 keypoints a frame, 3000 local points of a
+               resident table; beside it pgorb_search_by_projection_points_batch_device at the same shape, which starts from the
+               projections, and the host front part that call needs first: isInFrustum for every point as vectorised numpy on one
+               core (OUR restatement, not ORB-SLAM2), the descriptor gather and the upload of the seven arrays, wall clock.  The
+               two device calls must assign the same points.  --track-only runs these rows alone
+
+usage: python tools/next_tier_bench.py [--batch 128] [--out profiles/r02_next_tier.txt] [--refresh-only | --place-only | --loop-only | --track-only]"""
 import argparse, ctypes as C, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -49,6 +56,7 @@ ap.add_argument("--features", type=int, default=2000, help="4000 = the initialis
 ap.add_argument("--refresh-only", action="store_true", help="the map-point refresh rows alone (no ride, no vocabulary)")
 ap.add_argument("--place-only", action="store_true", help="the place-recognition row alone (no ride, no vocabulary)")
 ap.add_argument("--loop-only", action="store_true", help="loop closing's four matchers alone (no ride, no vocabulary)")
+ap.add_argument("--track-only", action="store_true", help="the tracking thread's SearchLocalPoints rows alone (no ride, no vocabulary)")
 a = ap.parse_args()
 w, h, nf, B = 1920, 1080, a.features, a.batch
 
@@ -213,6 +221,115 @@ def loop_lines():
     return lines + ["%-104s %10.3f %14.1f" % r for r in rows]
 
 
+def track_lines(npairs=127, cap=2000, npts=3000):
+    """SearchLocalPoints, batched and resident, with the front part on the device; beside it the matcher that starts from the
+    projections and the host front part it needs."""
+    ext = pg.ORBextractor(2000, 1.2, 8, 20, 7, max_width=640, max_height=480)
+    rng = np.random.RandomState(9)
+    f, cx, cy = 1400.0, w / 2.0, h / 2.0
+    bnd = (0.0, float(w), 0.0, float(h))
+    sf = ext.GetScaleFactors()
+    # the table: points on a slab 4 .. 9 in front of the first camera, seen head-on; the cameras move sideways, 0.004 a frame
+    z = rng.uniform(4.0, 9.0, npts)
+    pts = np.zeros(npts, pg.MAP_POINT_DTYPE)
+    pts["pos"] = np.stack([(rng.uniform(-80, w + 330, npts) - cx) * z / f, (rng.uniform(-60, h + 60, npts) - cy) * z / f, z], 1)
+    pts["normal"] = [0.0, 0.0, 1.0]
+    pts["max_distance"] = (z * sf[rng.randint(1, 8, npts)]).astype(np.float32)
+    pts["min_distance"] = pts["max_distance"] / sf[7]
+    pdesc = rng.randint(0, 256, (npts, 32)).astype(np.uint8)
+    pbad = (rng.uniform(size=npts) < 0.02).astype(np.uint8)
+    pobs = (rng.uniform(size=npts) > 0.1).astype(np.uint8)
+    B_ = npairs + 1
+    poses = np.zeros(B_, pg.KF_POSE_DTYPE)
+    kp = np.zeros((B_, cap), pg.KEYPOINT_DTYPE)
+    ds = rng.randint(0, 256, (B_, cap, 32)).astype(np.uint8)
+    slots = np.full((npairs, cap), -1, np.int32)
+    for k in range(B_):
+        c = np.array([0.004 * k, 0.002 * k, 0.0])
+        poses[k] = pg.kf_pose(np.hstack([np.eye(3), -c[:, None]]), c, f, f, cx, cy)
+        pc = pts["pos"].astype(np.float64) - c
+        u, v = f * pc[:, 0] / pc[:, 2] + cx, f * pc[:, 1] / pc[:, 2] + cy
+        vis = np.flatnonzero((u > 1) & (u < w - 1) & (v > 1) & (v < h - 1))
+        own = rng.permutation(vis)[:int(cap * 0.75)]                      # three quarters of the keypoints sit on a point's projection
+        m = len(own)
+        kp[k]["x"], kp[k]["y"] = rng.uniform(0, w - 1, cap), rng.uniform(0, h - 1, cap)
+        kp[k]["x"][:m], kp[k]["y"][:m] = u[own] + rng.uniform(-1, 1, m), v[own] + rng.uniform(-1, 1, m)
+        kp[k]["octave"] = rng.randint(0, 8, cap)
+        lvl = np.clip(np.ceil(np.log(pts["max_distance"][own] / np.linalg.norm(pc[own], axis=1)) / np.log(1.2)), 0, 7).astype(np.int32)
+        kp[k]["octave"][:m] = lvl
+        kp[k]["angle"], kp[k]["size"] = rng.uniform(0, 360, cap), 31.0
+        flip = rng.randint(0, 256, (m, 3))                                # the keypoint's descriptor: the point's with up to 24 bits flipped
+        d = pdesc[own].copy()
+        for j in range(3):
+            d[np.arange(m), flip[:, j] % 32] ^= (flip[:, j] & 0xFF).astype(np.uint8)
+        ds[k, :m] = d
+        if k >= 1:
+            slots[k - 1, :m:5] = own[::5]                                 # a fifth of them already hold their point (tracked from the last frame)
+    G = lambda x: torch.from_numpy(np.ascontiguousarray(x)).cuda()
+    p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+    s = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    dK, dD, dN = G(kp.view(np.uint8).reshape(B_, cap, 28)), G(ds), G(np.full(B_, cap, np.int32))
+    gs = torch.empty((B_, 3073), dtype=torch.int32, device="cuda"); gi = torch.empty((B_, cap), dtype=torch.int32, device="cuda")
+    ext._check(ext._L.pgorb_frame_grid_batch_device(ext._h, p(dK), p(dN), B_, cap, *bnd, p(gs), p(gi), s))
+    pairF = torch.arange(1, B_, dtype=torch.int32, device="cuda")
+    dPose = G(poses[1:].view(np.uint8).reshape(npairs, -1))
+    dPts, dPD, dPB, dPO, dSl = G(pts.view(np.uint8).reshape(npts, 32)), G(pdesc), G(pbad), G(pobs), G(slots)
+    q = np.stack([rng.permutation(npts) for _ in range(npairs)]).astype(np.int32)
+    dQ, dNq = G(q), G(np.full(npairs, npts, np.int32))
+    I32 = lambda *sh: torch.empty(sh, dtype=torch.int32, device="cuda")
+    F32 = lambda *sh: torch.empty(sh, dtype=torch.float32, device="cuda")
+    iv = torch.empty((npairs, npts), dtype=torch.uint8, device="cuda")
+    px, py, lv, vc = F32(npairs, npts), F32(npairs, npts), I32(npairs, npts), F32(npairs, npts)
+    kpo, ntm, asg, nm = I32(npairs, cap), I32(npairs), I32(npairs, cap), I32(npairs)
+    new = lambda: ext._check(ext._L.pgorb_search_local_points_batch_device(ext._h, p(dK), p(dD), p(dN), cap, p(gs), p(gi), p(pairF), npairs, *bnd,
+                             p(dPose), p(dSl), npts, p(dPts), p(dPD), p(dPB), p(dPO), npts, p(dNq), p(dQ), None, 0.5, 1.0, 0.8, p(iv), p(px),
+                             p(py), p(lv), p(vc), p(kpo), p(ntm), p(asg), p(nm), s))
+    t_new = timed(new)
+    # the matcher that starts from the projections, fed with what the new call computed (its front part's outputs)
+    has = ((kpo >= 0) & (dPO[kpo.clamp(min=0).long()] != 0)).to(torch.uint8).contiguous()
+    qd, qo = dPD[dQ.long()].contiguous(), dPO[dQ.long()].contiguous()
+    asg2, nm2 = I32(npairs, cap), I32(npairs)
+    old = lambda: ext._check(ext._L.pgorb_search_by_projection_points_batch_device(ext._h, p(dK), p(dD), p(dN), cap, p(gs), p(gi), p(pairF), npairs,
+                             *bnd, p(has), npts, p(dNq), p(iv), p(px), p(py), p(lv), p(vc), p(qd), p(qo), 1.0, 0.8, p(asg2), p(nm2), s))
+    t_old = timed(old)
+    assert torch.equal(asg, asg2) and torch.equal(nm, nm2)
+    # the host front part that call needs first, for ONE pair: isInFrustum vectorised in float32 numpy, the gather, the upload
+    def host_front(j):
+        P_, T_ = pts["pos"][q[j]], poses[j + 1]["Tcw"].reshape(3, 4)
+        pc = P_ @ T_[:, :3].T + T_[:, 3]
+        with np.errstate(all="ignore"):
+            invz = np.float32(1) / pc[:, 2]
+            u, v = np.float32(f) * pc[:, 0] * invz + np.float32(cx), np.float32(f) * pc[:, 1] * invz + np.float32(cy)
+            po = P_ - poses[j + 1]["Ow"]
+            dist = np.sqrt((po.astype(np.float64) ** 2).sum(1)).astype(np.float32)
+            vcos = ((po.astype(np.float64) * pts["normal"][q[j]]).sum(1) / dist).astype(np.float32)
+            mx, mn = pts["max_distance"][q[j]], pts["min_distance"][q[j]]
+            lvl = np.clip(np.ceil(np.log(mx / dist) / np.log(np.float32(1.2))), 0, 7).astype(np.int32)
+        ok = (pc[:, 2] >= 0) & (u >= 0) & (u <= w) & (v >= 0) & (v <= h) & (dist >= np.float32(0.8) * mn) & (dist <= np.float32(1.2) * mx) & \
+            (vcos >= 0.5) & (pbad[q[j]] == 0)
+        arrs = [ok.astype(np.uint8), u, v, lvl, vcos, pdesc[q[j]], pobs[q[j]]]
+        return [G(x) for x in arrs]
+    host_front(0); torch.cuda.synchronize()
+    ts = []
+    for j in range(9):
+        t0 = time.perf_counter(); host_front(j); torch.cuda.synchronize(); ts.append((time.perf_counter() - t0) * 1e3)
+    t_host = float(np.median(ts))
+    nin, nmm = float(ntm.float().mean()), float(nm.float().mean())
+    head = "%d pairs x %d keypoints x %d local points (%d in view, %d matches a pair)" % (npairs, cap, npts, nin, nmm)
+    return ["# the tracking thread's SearchLocalPoints, batched resident calls, HIP events, median of 9; host front part = isInFrustum of one pair's",
+            "# points as vectorised numpy on one core (OUR restatement, NOT ORB-SLAM2) + descriptor gather + upload of the 7 arrays, wall clock, median of 9",
+            "%-118s %10s %12s" % ("call", "GPU ms", "GPU ms/pair"),
+            "%-118s %10.3f %12.4f" % ("search_local_points (front part on the device): " + head, t_new, t_new / npairs),
+            "%-118s %10.3f %12.4f" % ("search_by_projection_points (starts from the projections), the same shape and arrays", t_old, t_old / npairs),
+            "%-118s %10.3f %12.4f" % ("   the host front part search_by_projection_points needs first: ms per pair, x %d pairs" % npairs, t_host * npairs, t_host)]
+
+
+if a.track_only:
+    lines = ["# python tools/next_tier_bench.py --track-only   (MI355X)"] + track_lines()
+    print("\n".join(lines))
+    if a.out:
+        open(a.out, "w").write("\n".join(lines) + "\n")
+    sys.exit(0)
 if a.loop_only:
     lines = ["# python tools/next_tier_bench.py --loop-only   (MI355X)"] + loop_lines()
     print("\n".join(lines))
@@ -523,6 +640,7 @@ lines.append("%-86s %10s %12s %12s" % ("call", "GPU ms", "GPU ms/pair", "CPU ms/
 for name, g, cc, *np_ in batch_rows:
     lines.append("%-86s %10.3f %12.4f %12.2f" % (name, g, g / (np_[0] if np_ else npairs), cc))
 lines += refresh_lines(refresh_rows(ext))
+lines += track_lines()
 print("\n".join(lines))
 if a.out:
     open(a.out, "w").write("\n".join(lines) + "\n")

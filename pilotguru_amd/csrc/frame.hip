@@ -4,7 +4,7 @@
 //   Frame::AssignFeaturesToGrid / PosInGrid   src/Frame.cc:234-249, 386-396
 //   Frame::UndistortKeyPoints                 src/Frame.cc:398-437 (cv::undistortPoints)
 //   Frame::ComputeImageBounds                 src/Frame.cc:439-467
-// The matchers that read the grid are in window_match.hip (GetFeaturesInArea's window: match_common.h) and fuse.hip.
+// The matchers that read the grid are in init_match.hip, window_match.hip (GetFeaturesInArea's window: match_common.h) and fuse.hip.
 #include "match_common.h"
 
 __device__ __forceinline__ int grid_cell_of(const pgorb_keypoint& kp, float minX, float minY, float invW, float invH)

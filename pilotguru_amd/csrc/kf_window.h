@@ -82,7 +82,7 @@ __device__ __forceinline__ bool kf_query(const PgKfBatch& B, const pgorb_kf_pose
     if (!depth(dist3D)) return false;
     Q.lvl = pg_predict_scale(P.max_distance, dist3D, B.logSf, B.nlevels);
     Q.r = __fmul_rn(B.th, B.sf[Q.lvl]);
-    return sfi_window(Q.u, Q.v, Q.r, B.minX, B.minY, B.invW, B.invH, Q.cx0, Q.cx1, Q.cy0, Q.cy1);
+    return sfi_window(Q.u, Q.v, Q.r, PgGridWin{B.minX, B.minY, B.invW, B.invH}, Q.cx0, Q.cx1, Q.cy0, Q.cy1);
 }
 // the depth test every form makes: dist3D inside [0.8*minDistance, 1.2*maxDistance]
 __device__ __forceinline__ bool kf_depth_ok(const pgorb_map_point& P, float dist3D)

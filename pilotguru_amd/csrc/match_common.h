@@ -1,7 +1,7 @@
 // match_common.h -- what the Frame side, the guided matchers, CreateNewMapPoints, Fuse, loop closing's matchers and the map-point refresh
-// share: included by frame.hip, window_match.hip, node_match.hip, mapping.hip, fuse.hip, loop.hip (the last two through kf_window.h),
-// track.hip (through kf_window.h and proj_match.h, which window_match.hip includes too) and map_point.hip, and by no other
-// translation unit.
+// share: included by frame.hip, init_match.hip (through cand_lists.h), window_match.hip (through proj_match.h, which includes
+// cand_lists.h), node_match.hip, mapping.hip, fuse.hip, loop.hip (the last two through kf_window.h), track.hip (through kf_window.h
+// and proj_match.h) and map_point.hip, and by no other translation unit.
 #pragma once
 #include "pgorb_internal.h"
 #include <algorithm>
@@ -80,10 +80,12 @@ struct PgCarve {
     size_t take(size_t bytes) { const size_t r = o; o += (bytes + 255) & ~(size_t)255; return r; }
 };
 
+// the Frame's grid as GetFeaturesInArea sees it: mnMinX, mnMinY, mfGridElementWidthInv, mfGridElementHeightInv
+struct PgGridWin { float minX, minY, invW, invH; };
 // GetFeaturesInArea's cell window (Frame.cc:336-350); false = the reference returns an empty vector
-__device__ __forceinline__ bool sfi_window(float x, float y, float r, float minX, float minY, float invW, float invH,
-                                           int& cx0, int& cx1, int& cy0, int& cy1)
+__device__ __forceinline__ bool sfi_window(float x, float y, float r, const PgGridWin& G, int& cx0, int& cx1, int& cy0, int& cy1)
 {
+    const float minX = G.minX, minY = G.minY, invW = G.invW, invH = G.invH;
     cx0 = max(0, (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(x, minX), r), invW)));
     if (cx0 >= PGORB_GRID_COLS) return false;
     cx1 = min(PGORB_GRID_COLS - 1, (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(x, minX), r), invW)));

@@ -1,5 +1,5 @@
 // pgorb_internal.h -- shared host/device declarations of libpgorb (gfx950 only).  What only the Frame side, the guided matchers,
-// CreateNewMapPoints, Fuse and the map-point refresh share (frame.hip, window_match.hip, node_match.hip, mapping.hip, fuse.hip,
+// CreateNewMapPoints, Fuse and the map-point refresh share (frame.hip, init_match.hip, window_match.hip, node_match.hip, mapping.hip, fuse.hip,
 // map_point.hip) is in match_common.h.
 //
 // Data layout in HBM (all per context, sized for max_batch frames):

@@ -1,26 +1,9 @@
 // proj_match.h -- what the projection matchers given their projections (window_match.hip) and the tracking thread's matchers that
-// project on the device (track.hip) share: the query arrays the two passes of SearchByProjection read, the candidate lists between
-// them, the family's LDS limit and the launch of the two passes.  Included by those two translation units only.
+// project on the device (track.hip) share: the query arrays the two passes of SearchByProjection read, the family's LDS limit and the
+// launch of the two passes; the candidate lists between the passes are cand_lists.h.  Included by those two translation units only.
 #pragma once
-#include "match_common.h"
+#include "cand_lists.h"
 
-// ---- candidate lists of the two-pass matchers (round 4: variable length) -----------------------------------------------
-// Pass A stores EVERY surviving candidate of a query in the reference's scan order: the first LIST_K in the query's fixed slots,
-// the rest in the pair's pool (one atomic per query that needs it).  Rounds 2-3 capped the lists at 64 and re-evaluated denser
-// queries in place inside the sequential pass -- the initialisation workload's cliff.  Only when a pair's pool is full (an
-// average of LIST_K + LIST_POOL candidates per query) is a query still evaluated in place (count LIST_OVER).
-#define LIST_K 64
-#define LIST_POOL 256
-#define LIST_OVER 0xFFFFu
-#define SFI_K LIST_K
-struct PgLists {
-    uint32_t* fixed;             // [rows][LIST_K]
-    uint16_t* cnt;               // [rows]   survivors of the query (LIST_OVER: evaluate in place)
-    uint32_t* ovf;               // [rows]   where the query's entries LIST_K.. start in its pair's pool
-    uint32_t* pool;              // [npairs][poolPerPair]
-    int32_t*  poolTop;           // [npairs] (zeroed before pass A)
-    uint32_t  poolPerPair;
-};
 // Batch layout of SearchByProjection's two passes (k_proj_candidates, k_search_by_projection; window_match.hip): pair p matches its
 // nq[p] queries against frame pairFrame[p] of an extract batch (keypoints / descriptors `cap` apart, grids (GRID_CELLS + 1) / cap
 // apart); query arrays are [npairs][qcap].
@@ -49,11 +32,10 @@ static const char* const PG_SBP_LDS_MSG =
 // what the key-frame form (mode 2) takes beyond the common query arrays
 struct PgProjKeyFrame { const uint8_t* found; const float* dist3d; const float* minDist; const float* maxDist; float logSf; int orbDist; };
 
-
-// The two passes behind a front part that fills the query arrays on the device.  pg_proj_begin: the family's limits for `cap`
-// keypoints and `qcap` queries a pair, the device, and ONE block of the matchers' scratch arena holding the candidate lists of
-// npairs x qcap queries and, behind them, `extraBytes` for the caller's own arrays (*extra, 256-byte aligned).  pg_proj_run: pass A,
-// pass B and the arena's event, on `stream`; B's sf / nlevels are filled here.
+// The two passes behind a front part that fills the query arrays on the device.  pg_proj_begin: the family's LDS limit for `cap`
+// keypoints and `qcap` queries a pair (neither above LIST_MAX_N: the caller's check, asserted here), the device, and ONE block of the
+// matchers' scratch arena holding the candidate lists of npairs x qcap queries and, behind them, `extraBytes` for the caller's own
+// arrays (*extra, 256-byte aligned).  pg_proj_run: pass A, pass B and the arena's event, on `stream`; B's sf / nlevels are filled here.
 int pg_proj_begin(pgorb_ctx* c, int cap, int qcap, int npairs, size_t extraBytes, hipStream_t stream, PgLists* Ls, void** extra);
 int pg_proj_run(pgorb_ctx* c, PgProjBatch& B, int npairs, float min_x, float max_x, float min_y, float max_y, int mode, float nnratio,
                 int check_orientation, const PgLists& Ls, int32_t* d_assigned, int32_t* d_nmatches, hipStream_t stream);

@@ -157,7 +157,7 @@ static int pg_track_batch(pgorb_ctx* c, const char* bad, const pgorb_keypoint* d
         (npairs && qcap && !t.queries) || (npairs && mode == TRACK_LOCAL && (!t.nq || !t.oValid || !t.nToMatch)) ||
         (npairs && mode != TRACK_LOCAL && (!t.pairOther || !t.otherK || !t.otherN)) || !(max_x > min_x) || !(max_y > min_y) || !(t.th > 0.0f))
         return pg_ctx_fail(c, PGORB_E_ARG, bad);
-    if (cap > 16000 || qcap > 16000) return pg_ctx_fail(c, PGORB_E_LIMIT, "more than 16000 keypoints / queries");
+    if (cap > LIST_MAX_N || qcap > LIST_MAX_N) return pg_ctx_fail(c, PGORB_E_LIMIT, "more than 16000 keypoints / queries");
     if (mode == TRACK_LOCAL && npoints > TRACK_MAX_POINTS)
         return pg_ctx_fail(c, PGORB_E_LIMIT, "pgorb_search_local_points: more than 1048576 table points (the seen marks of a pair)");
     if (!npairs) return 0;
@@ -257,7 +257,7 @@ static int pg_track_host(pgorb_ctx* c, const char* bad, int mode, const PgTrackH
     if (kpOut) for (int i = 0; i < n; i++) kpOut[i] = h.kpPoint ? ((h.pbad && h.kpPoint[i] >= 0 && h.pbad[h.kpPoint[i]]) ? -1 : h.kpPoint[i]) : -1;
     if (!nq) return 0;
     const int cap = std::max(n, 1), ocap = std::max(h.nother, 1), np = std::max(npoints, 1);
-    if (n > 16000 || nq > 16000) return pg_ctx_fail(c, PGORB_E_LIMIT, "more than 16000 keypoints / queries");
+    if (n > LIST_MAX_N || nq > LIST_MAX_N) return pg_ctx_fail(c, PGORB_E_LIMIT, "more than 16000 keypoints / queries");
     if (pg_sbp_lds(n, nq) > PG_SBP_LDS_MAX) return pg_ctx_fail(c, PGORB_E_LIMIT, PG_SBP_LDS_MSG);      // (before anything is staged)
     if (mode == TRACK_LOCAL && npoints > TRACK_MAX_POINTS)
         return pg_ctx_fail(c, PGORB_E_LIMIT, "pgorb_search_local_points: more than 1048576 table points (the seen marks of a pair)");

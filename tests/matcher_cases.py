@@ -1,5 +1,5 @@
-"""Constructed edge cases of the Frame grid and the guided matchers (pilotguru_amd/csrc/frame.hip, window_match.hip, node_match.hip) and the runners that put
-them through the plain reference (tests/matcher_reference.py), the oracle, the single-call ABI and the batched device forms.
+"""Constructed edge cases of the Frame grid and the guided matchers (pilotguru_amd/csrc/frame.hip, init_match.hip, window_match.hip,
+node_match.hip) and the runners that put them through the plain reference (tests/matcher_reference.py), the oracle, the single-call ABI and the batched device forms.
 A helper module (no tests): tests/test_matcher_edges.py and the matcher_edges fuzzer of tests/fuzzers.py use it.
 
 Frames are built straight from arrays, with descriptors at exact Hamming distances from their queries.  Families:

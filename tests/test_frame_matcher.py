@@ -247,6 +247,17 @@ def test_gpu_search_by_projection_last_frame(oracle, th, ori):
     assert nm == onm and np.array_equal(asg, oasg) and nm > 100
 
 
+def _assert_lists_overflow(oracle, keys, bounds, windows, rows):
+    """The premise of the pool-overflow test, from the oracle's GetFeaturesInArea alone: `windows` = (x, y, r, minLevel, maxLevel) of
+    every query the reference evaluates against `keys`.  Some query has more survivors than the 64 fixed slots of its list, and the
+    survivors beyond them, summed over the pair, exceed the pair's pool of rows * 256 entries.  (A query reserves pool space for an
+    upper bound of its count, so the pool runs out no later than this sum says, and the queries behind are evaluated in place.)"""
+    grid = oracle.frame_grid(keys, bounds)
+    counts = np.array([len(oracle.features_in_area(keys, grid, bounds, *win)) for win in windows])
+    assert counts.max() > 64
+    assert int(np.maximum(counts - 64, 0).sum()) > rows * 256
+
+
 @pytest.mark.gpu
 def test_gpu_search_by_projection_when_the_list_pool_overflows(oracle):
     """One pyramid level, > 1 200 keypoints on 640 x 480 and search radii of 160 px: a query's window holds a third of the frame's
@@ -262,6 +273,12 @@ def test_gpu_search_by_projection_when_the_list_pool_overflows(oracle):
     sf = ext.GetScaleFactors()
     sel, valid, px, py, lvl, vc, pd, obs = _synthetic_map_points(F1.mvKeys, F1.mDescriptors, (5, 2), rng)
     has = (rng.uniform(size=F2.N) > 0.9).astype(np.uint8)
+    f32, live, osf = np.float32, np.flatnonzero(valid), oracle.OrbOracle(nf, 1.2, 1, 20, 7).scale_factors
+    rvc = [f32(2.5) if float(vc[q]) > 0.998 else f32(4.0) for q in live]                     # RadiusByViewingCos (ORBmatcher.cc:133-139), then r*th, then * scale (:65-69)
+    _assert_lists_overflow(oracle, F2.mvKeys, F2.bounds, [(px[q], py[q], f32(f32(r * f32(40.0)) * osf[lvl[q]]), int(lvl[q]) - 1, int(lvl[q]))
+                                                          for q, r in zip(live, rvc)], len(valid))
+    _assert_lists_overflow(oracle, F2.mvKeys, F2.bounds, [(px[q], py[q], f32(f32(160.0) * osf[lvl[q]]), int(lvl[q]) - 1, int(lvl[q]) + 1)
+                                                          for q in live], len(valid))
     onm, oasg = oracle.search_by_projection_points(F2.mvKeys, F2.mDescriptors, F2.bounds, sf, has, valid, px, py, lvl, vc, pd, obs, 40.0, 0.7)
     nm, asg = pg.ORBmatcher(0.7, True).SearchByProjection(F2, pg.MapPoints(valid, px, py, lvl, vc, pd, obs), 40.0, has)
     assert nm == onm and np.array_equal(asg, oasg) and nm > 100
@@ -271,6 +288,8 @@ def test_gpu_search_by_projection_when_the_list_pool_overflows(oracle):
     assert nm == onm and np.array_equal(asg, oasg) and nm > 100
     # SearchForInitialization with a 250-px window on the same frames: lists beyond the fixed slots and, late in the pair, beyond the pool
     prev = np.stack([F1.mvKeys["x"], F1.mvKeys["y"]], 1).astype(np.float32)
+    _assert_lists_overflow(oracle, F2.mvKeys, F2.bounds, [(x, y, f32(250), 0, 0) for (x, y), o in zip(prev, F1.mvKeys["octave"]) if o == 0],
+                           max(F1.N, F2.N))
     onm, om12, oprev = oracle.search_for_initialization(F1.mvKeys, F1.mDescriptors, F2.mvKeys, F2.mDescriptors, F2.bounds, prev.copy(), 250, 0.9, True)
     nm, m12 = pg.ORBmatcher(0.9, True).SearchForInitialization(F1, F2, prev, 250)
     assert nm == onm and np.array_equal(m12, om12) and prev.tobytes() == oprev.tobytes() and nm > 100

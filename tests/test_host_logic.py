@@ -71,7 +71,8 @@ def test_bench_cpu_core_count_respects_the_cgroup_quota(tmp_path, monkeypatch):
 
 
 def test_round_scheduling_rule_of_the_guided_matchers_equals_the_sequence():
-    """The guided matchers (window_match.hip, round 4) decide a pair's queries in ROUNDS instead of one after the other.  The rule --
+    """The guided matchers (window_match.hip, round 4; init_match.hip keeps the sequence) decide a pair's queries in ROUNDS
+    instead of one after the other.  The rule --
     query q is ready when no undecided EARLIER query can take a keypoint of q's list, and no undecided earlier query lists a
     keypoint q can take -- must reproduce the plain sequence of ORBmatcher.cc:46-131 (taken flags, ratio test with levels) and of
     :407-522 (vMatchedDistance, matches taken over): checked here on random candidate lists, without the GPU."""

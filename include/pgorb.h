@@ -464,6 +464,56 @@ int  pgorb_search_by_projection_keyframe_pose_batch_device(pgorb_ctx* ctx,
         float th, int orb_dist, int check_orientation, float* d_u, float* d_v, float* d_dist3d,
         int32_t* d_assigned, int32_t* d_nmatches, void* hip_stream);
 
+/* ---- Motion-only pose refinement of the tracking thread (csrc/pose_opt.hip) ---------------------------------------------------
+ *   pgorb_pose_optimization   Optimizer::PoseOptimization(pFrame) (src/Optimizer.cc:239-451) with the g2o path under it (the vertex
+ *       SE3Quat, EdgeSE3ProjectXYZOnlyPose, RobustKernelHuber, OptimizationAlgorithmLevenberg, LinearSolverDense), monocular
+ *       (mvuRight < 0), in double.  It is this project's READING of g2o and Eigen (DESIGN.md section 4 lists it), anchored by the
+ *       CPU tests of tests/test_pose_optimization.py and not pinned to a g2o build.
+ * Inputs.  kps = mvKeysUn (pt and octave are read), pose = the frame's pose and camera as for the matchers above (Tcw, fx, fy, cx,
+ * cy are read; invfx / invfy / Ow are not), kp_point[i] = the table index of mvpMapPoints[i] or -1, the table as above (pos is
+ * read), point_has_obs [npoints] (NULL = all 1).  invSigma2 is the context's float mvInvLevelSigma2[octave].
+ * Outputs.  pose_out = the input with Tcw and Ow = -Rcw.t()*tcw replaced (a complete pgorb_kf_pose for the next call);
+ * outlier[i] = mvbOutlier[i] (0 where there is no point); chi2[i] (may be NULL) = the float chi2 of the last classification, 0
+ * where there is no point; info (may be NULL) = PGORB_PO_INFO int32: status bits, rounds run, iterations of rounds 0..3, Levenberg
+ * trials, edges.  The return value is nInitialCorrespondences - nBad of the last round run.
+ *   discard_outliers = 1: the loop after the call in TrackReferenceKeyFrame / TrackWithMotionModel (Tracking.cc:768-787, :891-911)
+ *       runs too: kp_point_out[i] = -1 for an outlier slot and its flag is cleared.
+ *   discard_outliers = 0: kp_point_out = kp_point (TrackLocalMap, :932-950).
+ *   *nmatches_map (may be NULL) = the slots that are not outliers and whose point has point_has_obs, in both forms.
+ * PGORB_PO_FEW: fewer than 3 correspondences -- returns 0, pose_out = pose byte for byte, the flags are cleared.
+ * PGORB_PO_NONFINITE: the active chi2 a Levenberg iteration starts from, or an edge's chi2 at a classification, is not finite (a
+ * point at z = 0; the reference's behaviour there is undefined) -- pose_out = pose byte for byte, every flag and chi2 0, returns 0.
+ * Determinism: a problem's result depends on its inputs only, not on its place in a batch, the number of problems, the stream or a
+ * repeat; the single call equals the batched one byte for byte (DESIGN.md section 4 states the summation order).
+ * PGORB_E_ARG (single call, checked on the host before anything else): a negative count, a NULL array that is read, a slot index
+ * outside [-1, npoints), the octave of a slot that holds a point outside the context's levels, a value of Tcw, fx, fy, cx, cy or of
+ * a referenced point that is not finite, fx or fy zero.  The batched form does not check: a bad index or octave counts as no point.
+ * PGORB_E_LIMIT: more than 16000 keypoints per frame (cap_per_frame in the batched form).
+ *   pgorb_slots_from_assignment   kp_point[i] = source[assigned[i]] where assigned[i] >= 0 and untouched elsewhere: the matchers'
+ *       `assigned` (indices of queries) back to table indices; source = last_point after the last-frame search, queries after
+ *       pgorb_search_local_points.  PGORB_E_ARG: an assignment outside [-1, nsource).  The batched form reads source
+ *       [npairs][source_stride] and skips an assignment outside [0, source_stride). */
+#define PGORB_PO_FEW        1
+#define PGORB_PO_NONFINITE  2
+#define PGORB_PO_INFO       8
+int  pgorb_pose_optimization(pgorb_ctx* ctx, const pgorb_keypoint* kps, int n,
+        const struct pgorb_kf_pose* pose, const int32_t* kp_point /*[n]*/,
+        int npoints, const struct pgorb_map_point* points, const uint8_t* point_has_obs, int discard_outliers,
+        struct pgorb_kf_pose* pose_out, uint8_t* outlier /*[n]*/, int32_t* kp_point_out /*[n] or NULL*/,
+        int32_t* nmatches_map, float* chi2 /*[n] or NULL*/, int32_t* info);
+/* pair p refines frame d_pair_frame[p] (NULL: frame p) from d_pose[p]; d_kp_point, d_outlier, d_kp_point_out, d_chi2
+ * [npairs][cap_per_frame] (every entry is written), d_pose_out, d_nmatches_map, d_ninliers [npairs], d_info [npairs][PGORB_PO_INFO].
+ * One workgroup per pair; the edge records live in the context's scratch arena (32 bytes per pair and keypoint). */
+int  pgorb_pose_optimization_batch_device(pgorb_ctx* ctx, const pgorb_keypoint* d_kps, const int32_t* d_n, int cap_per_frame,
+        const int32_t* d_pair_frame, int npairs, const struct pgorb_kf_pose* d_pose, const int32_t* d_kp_point,
+        int npoints, const struct pgorb_map_point* d_points, const uint8_t* d_point_has_obs, int discard_outliers,
+        struct pgorb_kf_pose* d_pose_out, uint8_t* d_outlier, int32_t* d_kp_point_out, int32_t* d_nmatches_map, float* d_chi2,
+        int32_t* d_info, int32_t* d_ninliers, void* hip_stream);
+int  pgorb_slots_from_assignment(pgorb_ctx* ctx, const int32_t* assigned, const int32_t* source, int nsource,
+        int32_t* kp_point /*[n] in/out*/, int n);
+int  pgorb_slots_from_assignment_batch_device(pgorb_ctx* ctx, const int32_t* d_assigned, const int32_t* d_source, int source_stride,
+        int32_t* d_kp_point /*in/out*/, int cap_per_frame, int npairs, void* hip_stream);
+
 /* ---- Matcher of the local-mapping thread ------------------------------------------------------------------------------
  *   pgorb_search_for_triangulation   ORBmatcher::SearchForTriangulation(pKF1, pKF2, F12, vMatchedPairs, bOnlyStereo = false)
  *       src/ORBmatcher.cc:659-825 with CheckDistEpipolarLine :142-159, monocular (mvuRight < 0) -- called by

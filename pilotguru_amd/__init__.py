@@ -8,4 +8,5 @@ from .orb import KEYPOINT_DTYPE, DeviceFrameStream, Frame, FrameStream, MapPoint
 from .orb import KF_POSE_DTYPE, NEW_MAP_POINT_DTYPE, LocalMapping, kf_pose  # noqa: F401
 from .orb import MAP_POINT_DTYPE, MapPointTable, SIM3_DTYPE, sim3_pose, sim3_record  # noqa: F401
 from .orb import MP_BOTH, MP_DESCRIPTOR, MP_LIMIT, MP_MAX_OBS, MP_NORMAL_DEPTH  # noqa: F401
+from .orb import PO_FEW, PO_INFO, PO_NONFINITE, Optimizer  # noqa: F401
 from .place import KeyFrameDatabase  # noqa: F401

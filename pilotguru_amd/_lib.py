@@ -47,6 +47,8 @@ SYMBOLS = (
     "pgorb_search_local_points", "pgorb_search_local_points_batch_device",
     "pgorb_search_by_projection_last_frame", "pgorb_search_by_projection_last_frame_batch_device",
     "pgorb_search_by_projection_keyframe_pose", "pgorb_search_by_projection_keyframe_pose_batch_device",
+    "pgorb_pose_optimization", "pgorb_pose_optimization_batch_device",
+    "pgorb_slots_from_assignment", "pgorb_slots_from_assignment_batch_device",
     "pgorb_undistort_keypoints", "pgorb_undistort_keypoints_batch_device", "pgorb_image_bounds",
     "pgorb_host_alloc", "pgorb_host_free", "pgorb_host_register", "pgorb_host_unregister", "pgorb_stream_create", "pgorb_stream_create_ingest", "pgorb_stream_create_device", "pgorb_stream_submit_device", "pgorb_stream_wait_device", "pgorb_stream_lanes", "pgorb_stream_destroy", "pgorb_stream_input", "pgorb_stream_reset", "pgorb_stream_submit",
     "pgorb_stream_wait", "pgorb_stream_frontend", "pgorb_stream_frontend_results", "pgorb_set_option", "pgorb_get_option", "pgorb_matcher_is_popcount",
@@ -180,6 +182,14 @@ def lib():
         [vp, vp, vp, vp, C.c_int, vp, vp, vp, C.c_float, C.c_int] + [vp] * 6
     L.pgorb_search_by_projection_keyframe_pose_batch_device.argtypes = [vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, C.c_int] + f4 + \
         [vp, vp, vp, vp, C.c_int, vp, vp, vp, C.c_float, C.c_int, C.c_int] + [vp] * 6
+    # (ctx, kps, n, pose, kp_point, npoints, points, point_has_obs, discard_outliers, pose_out, outlier, kp_point_out, nmatches_map, chi2, info)
+    L.pgorb_pose_optimization.argtypes = [vp, vp, C.c_int, vp, vp, C.c_int, vp, vp, C.c_int] + [vp] * 6
+    # (ctx, kps, n, cap, pair_frame, npairs, pose, kp_point, npoints, points, point_has_obs, discard_outliers, pose_out, outlier,
+    #  kp_point_out, nmatches_map, chi2, info, ninliers, stream)
+    L.pgorb_pose_optimization_batch_device.argtypes = [vp, vp, vp, C.c_int, vp, C.c_int, vp, vp, C.c_int, vp, vp, C.c_int] + [vp] * 8
+    # (ctx, assigned, source, nsource | source_stride, kp_point, n | cap, [npairs, stream])
+    L.pgorb_slots_from_assignment.argtypes = [vp, vp, vp, C.c_int, vp, C.c_int]
+    L.pgorb_slots_from_assignment_batch_device.argtypes = [vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, vp]
     L.pgorb_log_f.argtypes = [C.c_float]
     L.pgorb_log_scale_factor.argtypes = [vp]
     L.pgorb_predict_scale.argtypes = [vp, C.c_float, C.c_float]

@@ -8,6 +8,7 @@
 // pilotguru maintainer drops into Frame::ExtractORB.
 #pragma once
 #include <algorithm>
+#include <cmath>
 #include <stdexcept>
 #include <string>
 #include <utility>
@@ -335,6 +336,58 @@ class LocalMapping {
         return rc;
     }
 
+ private:
+    pgorb_ctx* ctx_;
+};
+
+// What Optimizer::PoseOptimization returns beside the pose (include/pgorb.h).
+struct PoseOptimizationResult {
+    int inliers = 0;                       // the reference's return value
+    pgorb_kf_pose pose{};                  // a complete record: Tcw, Ow, the input's camera
+    std::vector<uint8_t> outlier;          // mvbOutlier
+    std::vector<int32_t> kpPoint;          // the slots afterwards (discardOutliers empties the outliers')
+    std::vector<float> chi2;
+    int nmatchesMap = 0;
+    int32_t info[PGORB_PO_INFO] = {};      // status, rounds, iterations of rounds 0..3, trials, edges
+};
+
+class Optimizer {
+ public:
+    explicit Optimizer(pgorb_ctx* ctx) : ctx_(ctx) {}
+    // Optimizer::PoseOptimization(pFrame) (Optimizer.cc:239-451), monocular, on the GPU.  F: mvKeysUn (pt and octave are read); pose:
+    // the frame's pose and camera; kpPoint[i] = the table index of mvpMapPoints[i] or -1; points: the table (pos is read);
+    // pointHasObs: Observations() > 0 per point (empty = all).  discardOutliers: the loop of Tracking.cc:768-787 runs too.
+    // Everything pgorb_pose_optimization refuses is a std::invalid_argument here, before the library is called.
+    PoseOptimizationResult PoseOptimization(const Frame& F, const pgorb_kf_pose& pose, const std::vector<int32_t>& kpPoint,
+                                            const std::vector<pgorb_map_point>& points, const std::vector<uint8_t>& pointHasObs,
+                                            bool discardOutliers = false)
+    {
+        const auto fail = [](const char* m) { throw std::invalid_argument(std::string("PoseOptimization: ") + m); };
+        const int n = F.N(), np = (int)points.size(), levels = pgorb_levels(ctx_);
+        if (kpPoint.size() != (size_t)n) fail("kpPoint is not N entries long");
+        if (!pointHasObs.empty() && pointHasObs.size() != (size_t)np) fail("pointHasObs is neither empty nor one entry per point");
+        for (int k = 0; k < 12; k++)
+            if (!std::isfinite(pose.Tcw[k])) fail("the pose is not finite");
+        if (!std::isfinite(pose.fx) || !std::isfinite(pose.fy) || !std::isfinite(pose.cx) || !std::isfinite(pose.cy)) fail("the camera is not finite");
+        if (pose.fx == 0.0f || pose.fy == 0.0f) fail("fx or fy is zero");
+        for (int i = 0; i < n; i++) {
+            const int s = kpPoint[i];
+            if (s < -1 || s >= np) fail("a slot names a point outside the table");
+            if (s < 0) continue;
+            const int o = F.mvKeysUndistorted[i].octave;
+            if (levels > 0 && (o < 0 || o >= levels)) fail("an octave is outside the context's levels");      // (no context: the library's error)
+            if (!std::isfinite(points[s].pos[0]) || !std::isfinite(points[s].pos[1]) || !std::isfinite(points[s].pos[2])) fail("a referenced point is not finite");
+        }
+        PoseOptimizationResult r;
+        r.outlier.assign(n > 0 ? n : 1, 0); r.kpPoint.assign(n > 0 ? n : 1, -1); r.chi2.assign(n > 0 ? n : 1, 0.0f);
+        const int rc = pgorb_pose_optimization(ctx_, F.mvKeysUndistorted.data(), n, &pose, kpPoint.data(), np, points.data(),
+                                               pointHasObs.empty() ? nullptr : pointHasObs.data(), discardOutliers ? 1 : 0, &r.pose, r.outlier.data(),
+                                               r.kpPoint.data(), &r.nmatchesMap, r.chi2.data(), r.info);
+        if (rc < 0) throw std::runtime_error(pgorb_last_error(ctx_));
+        r.outlier.resize(n); r.kpPoint.resize(n); r.chi2.resize(n);
+        r.inliers = rc;
+        return r;
+    }
  private:
     pgorb_ctx* ctx_;
 };

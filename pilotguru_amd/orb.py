@@ -831,6 +831,56 @@ def sim3_pose(Scw, fx, fy, cx, cy):
     return kf_pose(np.concatenate([R, t.reshape(3, 1)], 1), Ow, fx, fy, cx, cy)
 
 
+# pgorb_pose_optimization: the status bits and the length of its info record (include/pgorb.h)
+PO_FEW, PO_NONFINITE, PO_INFO = 1, 2, 8
+
+
+class Optimizer:
+    """Optimizer::PoseOptimization (thirdparty/orb-slam2/src/Optimizer.cc:239-451), monocular, on the GPU."""
+
+    @staticmethod
+    def PoseOptimization(frame_keys, pose, kp_point, table, discard_outliers=False, point_has_obs=None):
+        """frame_keys: a Frame-like object (ext, N, mvKeysUndistorted: pt and octave are read); pose: the frame's KF_POSE_DTYPE
+        record (Tcw and the camera are read); kp_point[i]: the table index of mvpMapPoints[i] or -1; table: a MapPointTable (pos is
+        read; point_has_obs defaults to its observation lists).  discard_outliers: run the loop of Tracking.cc:768-787 too.  Every
+        input the library's checked call refuses is a ValueError here, before the library is called.  Returns a dict: ret (the
+        reference's return value), pose (a complete KF_POSE_DTYPE record), outlier, kp_point_out, nmatches_map, chi2, status
+        (PO_FEW | PO_NONFINITE bits), rounds, iterations (of rounds 0..3), trials, edges."""
+        name = "PoseOptimization"
+        F = frame_keys
+        n = int(F.N)
+        if n < 0:
+            raise ValueError("%s: a negative keypoint count" % name)
+        kp = _arr(F.mvKeysUndistorted, KEYPOINT_DTYPE, n, name + " keypoints")
+        slots = _arr(kp_point, np.int32, n, "kp_point")
+        table.check_indices(slots, "kp_point", name)
+        P = np.ascontiguousarray(pose, KF_POSE_DTYPE).reshape(())
+        cam = [float(P[k]) for k in ("fx", "fy", "cx", "cy")]
+        if not (np.isfinite(P["Tcw"]).all() and np.isfinite(cam).all()):
+            raise ValueError("%s: the pose or the camera is not finite" % name)
+        if cam[0] == 0.0 or cam[1] == 0.0:
+            raise ValueError("%s: fx or fy is zero" % name)
+        held = slots >= 0
+        if held.any() and not np.isfinite(table.points["pos"][slots[held]]).all():
+            raise ValueError("%s: a referenced point is not finite" % name)
+        obs = (np.diff(table.obs_start) > 0).astype(np.uint8) if point_has_obs is None else _arr(point_has_obs, np.uint8, table.n, "point_has_obs")
+        if table.n == 0:
+            obs = np.zeros(1, np.uint8)
+        ext = F.ext
+        levels = ext.GetLevels()
+        if held.any() and (int(kp["octave"][held].min()) < 0 or int(kp["octave"][held].max()) >= levels):
+            raise ValueError("%s: an octave is outside the extractor's %d levels" % (name, levels))
+        m = max(n, 1)
+        out = np.zeros((), KF_POSE_DTYPE)
+        fl, ko, chi = np.zeros(m, np.uint8), np.full(m, -1, np.int32), np.zeros(m, np.float32)
+        nmap, info = np.zeros(1, np.int32), np.zeros(PO_INFO, np.int32)
+        ret = ext._check(ext._L.pgorb_pose_optimization(
+            ext._h, _p(kp if n else chi), n, _p(P), _p(slots if n else ko), table.n, _p(table.points), _p(obs), int(bool(discard_outliers)),
+            _p(out), _p(fl), _p(ko), _p(nmap), _p(chi), _p(info)))
+        return dict(ret=ret, pose=out, outlier=fl[:n].copy(), kp_point_out=ko[:n].copy(), nmatches_map=int(nmap[0]), chi2=chi[:n].copy(),
+                    status=int(info[0]), rounds=int(info[1]), iterations=[int(x) for x in info[2:6]], trials=int(info[6]), edges=int(info[7]))
+
+
 # pgorb_refresh_map_points: what to refresh, the status word's bits, the limit (include/pgorb.h)
 MP_DESCRIPTOR, MP_NORMAL_DEPTH, MP_BOTH = 1, 2, 3
 MP_LIMIT, MP_BAD_INDEX, MP_MAX_OBS = -6, -1, 512

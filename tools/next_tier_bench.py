@@ -38,7 +38,13 @@ next to each, the oracle's CPU time for the same work (1 thread, a few frames, s
                core (OUR restatement, not ORB-SLAM2), the descriptor gather and the upload of the seven arrays, wall clock.  The
                two device calls must assign the same points.  --track-only runs these rows alone
 
-usage: python tools/next_tier_bench.py [--batch 128] [--out profiles/r02_next_tier.txt] [--refresh-only | --place-only | --loop-only | --track-only]"""
+  pose         Optimizer::PoseOptimization (Optimizer.cc:239-451) on the device (pgorb_pose_optimization, csrc/pose_opt.hip): the
+               single call at 300 edges of 2000 keypoints (wall clock, staging included) and the batched resident call at 128
+               problems x 300 edges and x 2000 edges (HIP events); beside them the wall clock of the sequential Python reference
+               of the tests (tests/pose_reference.py, OUR restatement on one core, NOT g2o) for ONE such problem.  There is no
+               g2o build to hold these times against and no earlier path in this library.  --pose-only runs these rows alone
+
+usage: python tools/next_tier_bench.py [--batch 128] [--out profiles/r02_next_tier.txt] [--refresh-only | --place-only | --loop-only | --track-only | --pose-only]"""
 import argparse, ctypes as C, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -57,6 +63,7 @@ ap.add_argument("--refresh-only", action="store_true", help="the map-point refre
 ap.add_argument("--place-only", action="store_true", help="the place-recognition row alone (no ride, no vocabulary)")
 ap.add_argument("--loop-only", action="store_true", help="loop closing's four matchers alone (no ride, no vocabulary)")
 ap.add_argument("--track-only", action="store_true", help="the tracking thread's SearchLocalPoints rows alone (no ride, no vocabulary)")
+ap.add_argument("--pose-only", action="store_true", help="the pose-optimisation rows alone (no ride, no vocabulary)")
 a = ap.parse_args()
 w, h, nf, B = 1920, 1080, a.features, a.batch
 
@@ -324,6 +331,59 @@ def track_lines(npairs=127, cap=2000, npts=3000):
             "%-118s %10.3f %12.4f" % ("   the host front part search_by_projection_points needs first: ms per pair, x %d pairs" % npairs, t_host * npairs, t_host)]
 
 
+def pose_lines(npairs=128, cap=2000):
+    """PoseOptimization: the single call and the batched resident call, beside the Python reference of the tests."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import pose_cases as PC
+    ext = pg.ORBextractor(2000, 1.2, 8, 20, 7, max_width=640, max_height=480)
+    p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+    G = lambda x: torch.from_numpy(np.ascontiguousarray(x)).cuda()
+    s = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    out = ["# Optimizer::PoseOptimization on the device; single call = wall clock with staging, median of 9; batched resident call = HIP events, median of 9;",
+           "# reference = tests/pose_reference.py for ONE problem, wall clock: OUR restatement in numpy on one core, NOT g2o (no g2o build exists here to time)",
+           "%-96s %10s %14s %16s" % ("call", "GPU ms", "GPU ms/problem", "reference ms (1)")]
+    for edges in (300, cap):
+        cs = [PC.scene("bench", 1000 + j, edges, cap, noise=0.5, outliers=0.2, extra_points=0) for j in range(8)]
+        t0 = time.perf_counter(); ref = PC.run_reference(cs[0]); t_ref = (time.perf_counter() - t0) * 1e3
+        if edges == 300:
+            ts = []
+            for j in range(10):
+                t0 = time.perf_counter(); got = PC.run_gpu(cs[0], ext); ts.append((time.perf_counter() - t0) * 1e3)
+            assert got["ret"] == ref["ret"] and np.array_equal(got["outlier"], ref["outlier"])
+            t1 = float(np.median(ts[1:]))
+            out.append("%-96s %10.3f %14.4f %16.1f" % ("pose_optimization (single call): %d edges of %d keypoints, %d inliers" % (edges, cap, ref["ret"]), t1, t1, t_ref))
+        # the batch: 128 problems, 8 distinct scenes repeated, each its own frame and table slice
+        kp = np.zeros((npairs, cap), pg.KEYPOINT_DTYPE)
+        slots = np.zeros((npairs, cap), np.int32)
+        poses = np.zeros(npairs, pg.KF_POSE_DTYPE)
+        pts = np.concatenate([PC.table(c.points) for c in cs])
+        off = np.cumsum([0] + [len(c.points) for c in cs])
+        for j in range(npairs):
+            c = cs[j % 8]
+            kp[j] = PC.keypoints(c.keys_xy, c.octaves)
+            slots[j] = np.where(c.kp_point >= 0, c.kp_point + off[j % 8], -1)
+            poses[j] = PC.pose_record(c.pose)
+        dK, dN, dS = G(kp.view(np.uint8).reshape(npairs, cap, 28)), G(np.full(npairs, cap, np.int32)), G(slots)
+        dP, dT = G(poses.view(np.uint8).reshape(npairs, -1)), G(pts.view(np.uint8).reshape(len(pts), 32))
+        oP = torch.empty((npairs, pg.KF_POSE_DTYPE.itemsize), dtype=torch.uint8, device="cuda")
+        oF = torch.empty((npairs, cap), dtype=torch.uint8, device="cuda")
+        oK, oI, oN = (torch.empty(sh, dtype=torch.int32, device="cuda") for sh in ((npairs, cap), (npairs, 8), (npairs,)))
+        run = lambda: ext._check(ext._L.pgorb_pose_optimization_batch_device(ext._h, p(dK), p(dN), cap, None, npairs, p(dP), p(dS), len(pts), p(dT), None, 1,
+                                 p(oP), p(oF), p(oK), None, None, p(oI), p(oN), s))
+        t = timed(run)
+        assert int(oN[0]) == ref["ret"] and torch.equal(oN[:8], oN[8:16])
+        info = oI.cpu().numpy()
+        out.append("%-96s %10.3f %14.4f %16.1f" % ("pose_optimization_batch_device: %d problems x %d edges of %d keypoints (%.1f iterations, %.1f trials a problem)" % (
+            npairs, edges, cap, info[:, 2:6].sum(1).mean(), info[:, 6].mean()), t, t / npairs, t_ref))
+    return out
+
+
+if a.pose_only:
+    lines = ["# python tools/next_tier_bench.py --pose-only   (MI355X)"] + pose_lines()
+    print("\n".join(lines))
+    if a.out:
+        open(a.out, "w").write("\n".join(lines) + "\n")
+    sys.exit(0)
 if a.track_only:
     lines = ["# python tools/next_tier_bench.py --track-only   (MI355X)"] + track_lines()
     print("\n".join(lines))

@@ -813,6 +813,82 @@ int  pgorb_search_by_sim3_batch_device(pgorb_ctx* ctx,
         const pgorb_sim3* d_sim3, const uint8_t* d_already1, const uint8_t* d_already2, float th,
         int32_t* d_match12, int32_t* d_nfound, void* hip_stream);
 
+/*   pgorb_sim3_solver   Sim3Solver (src/Sim3Solver.cc:37-423; LoopClosing::ComputeSim3, src/LoopClosing.cc:274-342): the constructor,
+ *       SetRansacParameters and ONE call of iterate(niterations) -- or find(), with niterations >= max_iterations -- of a solver whose
+ *       mnIterations and mnBestInliers are first_iteration and best_inliers_in.  It is the step between pgorb_search_by_bow_keyframes
+ *       and pgorb_search_by_sim3: matches12 [n1] is exactly what the former writes (the KF2 keypoint or -1), found_sim3 and
+ *       already1 / already2 are what the latter reads.  Key frames and the table as for pgorb_search_by_sim3: of the poses Tcw, fx, fy,
+ *       cx, cy are read (each key frame's OWN camera, :105-109), kf_point the slots; the caller owns GetIndexInKeyFrame and passes -1
+ *       where it would be negative.  Sigma2 is the context's mvLevelSigma2[octave].
+ *   The constructor (:37-112).  A correspondence is kept where matches12[i1] = i2 >= 0, kf_point1[i1] and kf_point2[i2] hold points and
+ *       neither is bad; kept ones are compacted IN i1 ORDER (the draws index this order): X3Dc = Rcw*P + tcw per key frame, its image
+ *       under that key frame's K, and the thresholds: mvnMaxError1/2 are vector<size_t> (Sim3Solver.h:78-79), so 9.210*sigma2 is
+ *       evaluated in double, TRUNCATED to an integer and compared as float -- 9 for octave 0, not 9.21.
+ *   SetRansacParameters (:114-138).  mRansacMaxIts(N) is evaluated on the host with the reference's own expression (the host's log;
+ *       pow of the float epsilon promoted to double) and kept as a table by N in the context, re-made when probability, min_inliers
+ *       or max_iterations change; pgorb_sim3_max_iterations returns one entry.  No device logarithm decides a ceil.  nIterations is
+ *       an int there: a quotient that is NaN or not below 2^31 becomes INT_MIN (x86-64's cvttsd2si) and the cap 1, so with 20
+ *       inliers asked of more than about 15500 correspondences the reference runs one iteration, and so does the library.
+ *   iterate (:140-207).  draws [max_iterations][3] are raw rand() values in [0, 2^31); iteration t uses draws[t].  The library applies
+ *       RandomInt's formula int((double)r/((double)RAND_MAX + 1.0)*size) (DUtils/Random.cpp:47-50) and the swap-with-back selection of
+ *       :166-177, so a caller who seeds rand() as the reference does reproduces it.  All iterations of the window [first_iteration,
+ *       min(first_iteration + niterations, mRansacMaxIts)) are evaluated at once; with inl[t] the inlier count of iteration t and
+ *       b[t] = max(best_inliers_in, inl[first .. t-1]) the call returns the first t with inl[t] > min_inliers && inl[t] >= b[t]
+ *       (PGORB_S3_FOUND), and otherwise `best` is the LAST t with inl[t] >= b[t] -- the reference's `>=` at :183.
+ *   ComputeSim3 (:226-337) and CheckInliers (:340-364) follow the cv::Mat readings of DESIGN.md section 4.  cv::eigen is READ as a
+ *       cyclic Jacobi in double on the float N with the eigenvector's sign as it falls out (the rotation does not depend on it);
+ *       OpenCV 2.4.9 cannot be built here, so this is a reading and not a pin.  A hypothesis with a non-finite
+ *       quantity (norm(vec) == 0, den == 0, a point at z == 0) gets what the reference's comparisons give: a NaN compares false.
+ * Outputs.  The return value is nInliers (0 without PGORB_S3_FOUND).  found = R12, t12, s12 of the returned hypothesis; found_sim3 the
+ * same as the pgorb_sim3 record above (s*R, (1.0/s)*R.t(), -sR21*t12, as :323-335 form them); best = mBestRotation / Translation /
+ * Scale after the call (zero when no iteration of the call reached the carried best); inlier [n1] = vbInliers; matches12_out [n1] =
+ * matches12 where inlier is set, else -1 (LoopClosing.cc:313-318); already1 [n1] / already2 [n2] (may be NULL) = what SearchBySim3
+ * derives from that vector (ORBmatcher.cc:1133-1146).  info (may be NULL) = PGORB_S3_INFO int32: status bits, N, mRansacMaxIts,
+ * mnIterations after the call, nInliers, mnBestInliers after the call, the iteration of `best` (-1: none), 0.
+ * Without PGORB_S3_FOUND: returns 0, inlier all 0, matches12_out all -1, already1 / 2 all 0, found and found_sim3 zeroed; best and
+ * info are still written.  PGORB_S3_FEW: N < min_inliers (bNoMore; nothing evaluated).  PGORB_S3_NO_MORE: not found and mnIterations
+ * reached mRansacMaxIts.
+ * Determinism: a pair's result depends on its inputs only, not on its place in a batch, the number of pairs, the stream or a repeat;
+ * every lane of a hypothesis' wave runs Horn in one fixed operation order, counts are sums of ballot popcounts, there are no atomics;
+ * the single call equals the batched one byte for byte.
+ * PGORB_E_ARG (single call, checked on the host before anything else): a negative count, a NULL array that is read, a slot outside
+ * [-1, npoints), matches12 outside [-1, n2), the octave of a used keypoint outside the context's levels, a value of Tcw, fx, fy, cx,
+ * cy or of a referenced point that is not finite, min_inliers < 3, probability outside (0, 1), max_iterations < 1, first_iteration
+ * < 0, niterations < 1, a draw >= 2^31.  PGORB_E_LIMIT: more than 16000 keypoints in a key frame (cap_per_frame), max_iterations >
+ * PGORB_SIM3_MAX_ITERATIONS.  The batched form checks the parameters and the limits only: a bad index or octave counts as no
+ * correspondence.
+ *   Batched: pair p aligns key frames d_pair_kf1[p] and d_pair_kf2[p] of one batch; d_pose and d_kf_point go by frame; d_matches12,
+ *       d_inlier, d_matches12_out, d_already1 / 2 are [npairs][cap_per_frame] (every entry is written), d_draws
+ *       [npairs][max_iterations][3], d_found, d_found_sim3, d_best, d_ninliers [npairs], d_info [npairs][PGORB_S3_INFO];
+ *       d_first_iteration / d_best_inliers_in [npairs] or NULL = the params' values.  Three launches; the scratch arena holds 64 bytes
+ *       per pair and keypoint and per pair and iteration of the window. */
+typedef struct pgorb_sim3_params { float probability; int32_t min_inliers, max_iterations, fix_scale,
+                                   first_iteration, niterations, best_inliers_in; } pgorb_sim3_params;
+typedef struct pgorb_sim3_estimate { float R12[9], t12[3], s12; } pgorb_sim3_estimate;
+#define PGORB_S3_FEW      1   /* N < min_inliers: bNoMore, nothing evaluated */
+#define PGORB_S3_FOUND    2
+#define PGORB_S3_NO_MORE  4   /* mnIterations reached mRansacMaxIts */
+#define PGORB_S3_INFO     8   /* status, N, mRansacMaxIts, mnIterations after the call, nInliers, mnBestInliers, iteration of the best, reserved */
+#define PGORB_SIM3_MAX_ITERATIONS 1024
+int  pgorb_sim3_max_iterations(float probability, int min_inliers, int max_iterations, int N);
+int  pgorb_sim3_solver(pgorb_ctx* ctx,
+        const pgorb_keypoint* kps1, int n1, const pgorb_kf_pose* pose1, const int32_t* kf_point1,
+        const pgorb_keypoint* kps2, int n2, const pgorb_kf_pose* pose2, const int32_t* kf_point2,
+        const int32_t* matches12 /*[n1]: KF2 keypoint or -1*/,
+        int npoints, const pgorb_map_point* points, const uint8_t* point_bad /*[npoints] or NULL*/,
+        const pgorb_sim3_params* params, const uint32_t* draws /*[max_iterations][3]*/,
+        pgorb_sim3_estimate* found, pgorb_sim3* found_sim3, pgorb_sim3_estimate* best,
+        uint8_t* inlier /*[n1]*/, int32_t* matches12_out /*[n1]*/, uint8_t* already1 /*[n1] or NULL*/, uint8_t* already2 /*[n2] or NULL*/,
+        int32_t* info);
+int  pgorb_sim3_solver_batch_device(pgorb_ctx* ctx, const pgorb_keypoint* d_kps, const int32_t* d_n, int cap_per_frame,
+        const int32_t* d_pair_kf1, const int32_t* d_pair_kf2, int npairs, const pgorb_kf_pose* d_pose, const int32_t* d_kf_point,
+        const int32_t* d_matches12, int npoints, const pgorb_map_point* d_points, const uint8_t* d_point_bad,
+        const pgorb_sim3_params* params /*host, one for all*/,
+        const int32_t* d_first_iteration, const int32_t* d_best_inliers_in /*[npairs] or NULL = the params' values*/,
+        const uint32_t* d_draws /*[npairs][max_iterations][3]*/, pgorb_sim3_estimate* d_found, pgorb_sim3* d_found_sim3,
+        pgorb_sim3_estimate* d_best, uint8_t* d_inlier, int32_t* d_matches12_out, uint8_t* d_already1, uint8_t* d_already2,
+        int32_t* d_info, int32_t* d_ninliers, void* hip_stream);
+
 /* ---- Map-point refresh: the distinctive descriptor and the normal / depth range of many points --------------------------
  *   pgorb_refresh_map_points   for every selected point what MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:259-324)
  *       followed by MapPoint::UpdateNormalAndDepth (:347-388) would store, exactly.  The reference runs the pair once per point at

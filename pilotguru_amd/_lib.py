@@ -49,6 +49,7 @@ SYMBOLS = (
     "pgorb_search_by_projection_keyframe_pose", "pgorb_search_by_projection_keyframe_pose_batch_device",
     "pgorb_pose_optimization", "pgorb_pose_optimization_batch_device",
     "pgorb_slots_from_assignment", "pgorb_slots_from_assignment_batch_device",
+    "pgorb_sim3_solver", "pgorb_sim3_solver_batch_device", "pgorb_sim3_max_iterations",
     "pgorb_undistort_keypoints", "pgorb_undistort_keypoints_batch_device", "pgorb_image_bounds",
     "pgorb_host_alloc", "pgorb_host_free", "pgorb_host_register", "pgorb_host_unregister", "pgorb_stream_create", "pgorb_stream_create_ingest", "pgorb_stream_create_device", "pgorb_stream_submit_device", "pgorb_stream_wait_device", "pgorb_stream_lanes", "pgorb_stream_destroy", "pgorb_stream_input", "pgorb_stream_reset", "pgorb_stream_submit",
     "pgorb_stream_wait", "pgorb_stream_frontend", "pgorb_stream_frontend_results", "pgorb_set_option", "pgorb_get_option", "pgorb_matcher_is_popcount",
@@ -190,6 +191,13 @@ def lib():
     # (ctx, assigned, source, nsource | source_stride, kp_point, n | cap, [npairs, stream])
     L.pgorb_slots_from_assignment.argtypes = [vp, vp, vp, C.c_int, vp, C.c_int]
     L.pgorb_slots_from_assignment_batch_device.argtypes = [vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, vp]
+    # (ctx, kps1, n1, pose1, kf_point1, kps2, n2, pose2, kf_point2, matches12, npoints, points, point_bad, params, draws, found, found_sim3,
+    #  best, inlier, matches12_out, already1, already2, info)
+    L.pgorb_sim3_solver.argtypes = [vp, vp, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp, C.c_int] + [vp] * 12
+    # (ctx, kps, n, cap, pair_kf1, pair_kf2, npairs, pose, kf_point, matches12, npoints, points, point_bad, params, first_iteration,
+    #  best_inliers_in, draws, found, found_sim3, best, inlier, matches12_out, already1, already2, info, ninliers, stream)
+    L.pgorb_sim3_solver_batch_device.argtypes = [vp, vp, vp, C.c_int, vp, vp, C.c_int, vp, vp, vp, C.c_int] + [vp] * 16
+    L.pgorb_sim3_max_iterations.argtypes = [C.c_float, C.c_int, C.c_int, C.c_int]
     L.pgorb_log_f.argtypes = [C.c_float]
     L.pgorb_log_scale_factor.argtypes = [vp]
     L.pgorb_predict_scale.argtypes = [vp, C.c_float, C.c_float]

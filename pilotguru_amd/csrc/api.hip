@@ -119,6 +119,41 @@ int pg_ctx_pinned(pgorb_ctx* c, size_t bytes, void** p)
     *p = c->pinned;
     return 0;
 }
+// Sim3Solver::SetRansacParameters (Sim3Solver.cc:114-138) for N correspondences, in the reference's own expression: the host's log,
+// and pow of the float epsilon promoted to double.  N == 0 divides by zero there; iterate() returns before the value is used.
+int pg_sim3_cap(float probability, int min_inliers, int max_iterations, int N)
+{
+    const double mRansacProb = probability;
+    int nIterations;
+    if (min_inliers == N) nIterations = 1;
+    else if (N <= 0) nIterations = 1;
+    else {
+        const float epsilon = (float)min_inliers / N;
+        const double v = ceil(log(1 - mRansacProb) / log(1 - pow(epsilon, 3)));
+        nIterations = (v != v || v >= 2147483648.0 || v < -2147483648.0) ? (-2147483647 - 1) : (int)v;      // cvttsd2si
+    }
+    return std::max(1, std::min(nIterations, max_iterations));
+}
+// The table of those caps for N = 0 .. max_n, kept on the device and re-made when the parameters change or max_n grows.  Re-making
+// it waits for the device first: a call still queued on another stream may be reading the old table.
+int pg_ctx_sim3_caps(pgorb_ctx* c, float probability, int min_inliers, int max_iterations, int max_n, const int32_t** d_caps)
+{
+    const int entries = max_n + 1;
+    if (!(c->sim3Caps.p && c->sim3Prob == probability && c->sim3MinInliers == min_inliers && c->sim3MaxIts == max_iterations &&
+          c->sim3Entries >= entries)) {
+        PG_HIP(c, hipSetDevice(c->prm.device));
+        std::vector<int32_t> t((size_t)entries);
+        for (int N = 0; N < entries; N++) t[N] = pg_sim3_cap(probability, min_inliers, max_iterations, N);
+        PG_HIP(c, hipDeviceSynchronize());
+        c->sim3Entries = 0;
+        int rc = ensure(c, c->sim3Caps, (size_t)entries * 4);
+        if (rc) return rc;
+        PG_HIP(c, hipMemcpy(c->sim3Caps.p, t.data(), (size_t)entries * 4, hipMemcpyHostToDevice));
+        c->sim3Prob = probability; c->sim3MinInliers = min_inliers; c->sim3MaxIts = max_iterations; c->sim3Entries = entries;
+    }
+    *d_caps = (const int32_t*)c->sim3Caps.p;
+    return 0;
+}
 // the header of a vocabulary blob of `nbytes` bytes at `src` (bow.hip, blob layout) into `hdr`, checked: magic, version, and that the sections the
 // header implies fit; the structure itself is checked by pgorb_vocab_from_blob / the loader on the host path and by
 // k_vocab_validate on the device path
@@ -247,7 +282,7 @@ void pgorb_destroy(pgorb_ctx* c)
     (void)hipSetDevice(c->prm.device);
     while (!c->streams.empty()) pgorb_stream_destroy(c->streams.back());      // a stream holds a pointer to its context
     Arena* all[] = {&c->cellTab, &c->cellTabBal, &c->cellCand, &c->cellCount, &c->pyr, &c->cand, &c->sel, &c->nodes, &c->counters, &c->tables, &c->qtTab, &c->qtLeaf,
-                    &c->outBlk, &c->stageA, &c->stageOut, &c->stageSfi, &c->vocab, &c->xdesc};
+                    &c->outBlk, &c->stageA, &c->stageOut, &c->stageSfi, &c->vocab, &c->xdesc, &c->sim3Caps};
     for (Arena* a : all) if (a->p) (void)hipFree(a->p);
     destroy_side_streams(c);
     if (c->pinned) (void)hipHostFree(c->pinned);

@@ -1,6 +1,6 @@
 // kf_window.h -- what Fuse (fuse.hip) and loop closing's projection matchers (loop.hip) share: a map point projected into a key frame
 // and the scan of the key frame's search window.  Included by those two translation units and, for kf_to_camera and kf_depth_ok,
-// by the tracking thread's projection front (track.hip).
+// by the tracking thread's projection front (track.hip) and, for kf_row and kf_to_camera, by the Sim3Solver (sim3.hip).
 //
 // Restates (thirdparty/orb-slam2): the front part of ORBmatcher::Fuse (src/ORBmatcher.cc:856-897), repeated at :316-367, :1006-1058
 // and :1152-1199, and KeyFrame::GetFeaturesInArea / IsInImage (src/KeyFrame.cc:672-716).  Every float operation follows the

@@ -65,6 +65,9 @@ struct pgorb_ctx {
     std::vector<pgorb_stream*> streams;       // live pgorb_stream_* objects of this context (pgorb_destroy takes them along)
     // the matchers' shared scratch arena (stageSfi) may be used from different caller streams: the last use is an event
     hipEvent_t evSfi = nullptr; hipStream_t sfiStream = nullptr; bool sfiUsed = false;
+    // Sim3Solver's mRansacMaxIts as a function of N (pg_ctx_sim3_caps): the key it was made for and the device copy
+    Arena sim3Caps;
+    float sim3Prob = 0.0f; int sim3MinInliers = 0, sim3MaxIts = 0, sim3Entries = 0;
 };
 
 #pragma GCC visibility push(hidden)      // what follows is shared by the four host files, not exported

@@ -291,6 +291,9 @@ int pg_ctx_vocab_commit(pgorb_ctx* c, size_t nbytes, hipStream_t s);
 int pg_ctx_vocab_get(pgorb_ctx* c, const uint8_t** d_blob, int* k, int* L, int* nnodes);
 bool pg_ctx_vocab_kind(pgorb_ctx* c, int* scoring, int* weighting);             // false: no vocabulary uploaded
 void pg_ctx_vocab_drop(pgorb_ctx* c);
+// Sim3Solver::SetRansacParameters' iteration cap for N = 0 .. max_n on the device (sim3.hip); pg_sim3_cap is the host expression
+int pg_sim3_cap(float probability, int min_inliers, int max_iterations, int N);
+int pg_ctx_sim3_caps(pgorb_ctx* c, float probability, int min_inliers, int max_iterations, int max_n, const int32_t** d_caps);
 
 // One synchronous host call of a batched device form.  Its arrays are 64-byte aligned regions at the same offsets in the
 // context's stage arena (device) and page-locked buffer (host), declared in the order: uploads, in-out, downloads, device-only.

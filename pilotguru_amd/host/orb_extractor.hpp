@@ -392,6 +392,114 @@ class Optimizer {
     pgorb_ctx* ctx_;
 };
 
+// Sim3Solver (src/Sim3Solver.cc) on the GPU, with the reference's surface.  mnIterations and mnBestInliers live here and go to the
+// library as first_iteration / best_inliers_in, so iterate(5) can be called again on the same solver (LoopClosing.cc:274-342).
+// F1, F2: mvKeysUn (the octave is read); pose1, pose2: Tcw and each key frame's own camera; kfPoint1 / kfPoint2: the table index of
+// every slot's point or -1 (the caller owns GetIndexInKeyFrame); matches12[i1]: the KF2 keypoint SearchByBoW matched, or -1; points
+// (pos is read) and pointBad (empty = none) the table; draws: [>= maxIterations][3] raw rand() values in [0, 2^31), 3 per iteration.
+// Everything pgorb_sim3_solver refuses is a std::invalid_argument here, before the library is called.
+class Sim3Solver {
+ public:
+    Sim3Solver(pgorb_ctx* ctx, const Frame& F1, const Frame& F2, const pgorb_kf_pose& pose1, const pgorb_kf_pose& pose2,
+               const std::vector<int32_t>& kfPoint1, const std::vector<int32_t>& kfPoint2, const std::vector<int32_t>& matches12,
+               const std::vector<pgorb_map_point>& points, const std::vector<uint8_t>& pointBad, std::vector<uint32_t> draws,
+               bool bFixScale = false)
+        : ctx_(ctx), F1_(F1), F2_(F2), pose1_(pose1), pose2_(pose2), kfPoint1_(kfPoint1), kfPoint2_(kfPoint2), matches12_(matches12),
+          points_(points), pointBad_(pointBad), draws_(std::move(draws)), mbFixScale(bFixScale)
+    {
+        const int n1 = F1.N(), n2 = F2.N(), np = (int)points.size(), levels = pgorb_levels(ctx_);
+        if (kfPoint1.size() != (size_t)n1 || matches12.size() != (size_t)n1) fail("kfPoint1 or matches12 is not N1 entries long");
+        if (kfPoint2.size() != (size_t)n2) fail("kfPoint2 is not N2 entries long");
+        if (!pointBad.empty() && pointBad.size() != (size_t)np) fail("pointBad is neither empty nor one entry per point");
+        for (const pgorb_kf_pose* P : {&pose1, &pose2}) {
+            for (int k = 0; k < 12; k++)
+                if (!std::isfinite(P->Tcw[k])) fail("a pose is not finite");
+            if (!std::isfinite(P->fx) || !std::isfinite(P->fy) || !std::isfinite(P->cx) || !std::isfinite(P->cy)) fail("a camera is not finite");
+        }
+        for (int s : kfPoint1) if (s < -1 || s >= np) fail("a slot names a point outside the table");
+        for (int s : kfPoint2) if (s < -1 || s >= np) fail("a slot names a point outside the table");
+        for (int i = 0; i < n1; i++) {
+            const int j = matches12[i];
+            if (j < -1 || j >= n2) fail("matches12 is outside [-1, n2)");
+            if (j < 0 || kfPoint1[i] < 0 || kfPoint2[j] < 0) continue;
+            const int o1 = F1.mvKeysUndistorted[i].octave, o2 = F2.mvKeysUndistorted[j].octave;
+            if (levels > 0 && (o1 < 0 || o1 >= levels || o2 < 0 || o2 >= levels)) fail("an octave is outside the context's levels");
+            for (const float* p : {points[kfPoint1[i]].pos, points[kfPoint2[j]].pos})
+                if (!std::isfinite(p[0]) || !std::isfinite(p[1]) || !std::isfinite(p[2])) fail("a referenced point is not finite");
+        }
+        if (n1 > 16000 || n2 > 16000) fail("more than 16000 keypoints in a key frame");
+        SetRansacParameters();
+    }
+    // Sim3Solver.cc:114-138; resets mnIterations as the reference does (mnBestInliers stays)
+    void SetRansacParameters(double probability = 0.99, int minInliers = 6, int maxIterations = 300)
+    {
+        if (minInliers < 3) fail("minInliers is below 3");
+        if (!((float)probability > 0.0f && (float)probability < 1.0f)) fail("probability is outside (0, 1)");
+        if (maxIterations < 1) fail("maxIterations is below 1");
+        if (maxIterations > PGORB_SIM3_MAX_ITERATIONS) fail("maxIterations above PGORB_SIM3_MAX_ITERATIONS");
+        if (draws_.size() < (size_t)maxIterations * 3) fail("fewer than maxIterations x 3 draws");
+        for (size_t k = 0; k < (size_t)maxIterations * 3; k++)
+            if (draws_[k] >= 0x80000000u) fail("a draw is not below 2^31");
+        mRansacProb = probability; mRansacMinInliers = minInliers; mRansacMaxIts = maxIterations;
+        mnIterations = 0;
+    }
+    // Sim3Solver::iterate (:140-207): true = a hypothesis was returned; T12 = [s*R | t] row-major 4 x 4
+    bool iterate(int nIterations, bool& bNoMore, std::vector<bool>& vbInliers, int& nInliers, float T12[16] = nullptr)
+    {
+        if (nIterations < 1) fail("nIterations is below 1");
+        if (mnIterations < 0) fail("mnIterations is negative");
+        const int n1 = F1_.N(), n2 = F2_.N();
+        pgorb_sim3_params prm{(float)mRansacProb, mRansacMinInliers, mRansacMaxIts, mbFixScale ? 1 : 0, mnIterations, nIterations, mnBestInliers};
+        std::vector<uint8_t> fl(n1 > 0 ? n1 : 1, 0);
+        matches12Out.assign(n1 > 0 ? n1 : 1, -1); already1.assign(n1 > 0 ? n1 : 1, 0); already2.assign(n2 > 0 ? n2 : 1, 0);
+        pgorb_sim3_estimate b{};
+        const int rc = pgorb_sim3_solver(ctx_, F1_.mvKeysUndistorted.data(), n1, &pose1_, kfPoint1_.data(), F2_.mvKeysUndistorted.data(), n2,
+                                         &pose2_, kfPoint2_.data(), matches12_.data(), (int)points_.size(), points_.data(),
+                                         pointBad_.empty() ? nullptr : pointBad_.data(), &prm, draws_.data(), &found, &foundSim3, &b, fl.data(),
+                                         matches12Out.data(), already1.data(), already2.data(), info);
+        if (rc < 0) throw std::runtime_error(pgorb_last_error(ctx_));
+        matches12Out.resize(n1); already1.resize(n1); already2.resize(n2);
+        mnIterations = info[3]; mnBestInliers = info[5];
+        if (info[6] >= 0) best = b;
+        bNoMore = (info[0] & (PGORB_S3_FEW | PGORB_S3_NO_MORE)) != 0;
+        vbInliers.assign(n1, false);
+        for (int i = 0; i < n1; i++) vbInliers[i] = fl[i] != 0;
+        nInliers = rc;
+        const bool ok = (info[0] & PGORB_S3_FOUND) != 0;
+        if (ok && T12) {
+            for (int r = 0; r < 3; r++) { for (int c = 0; c < 3; c++) T12[4 * r + c] = foundSim3.sR12[3 * r + c]; T12[4 * r + 3] = foundSim3.t12[r]; }
+            T12[12] = T12[13] = T12[14] = 0.0f; T12[15] = 1.0f;
+        }
+        return ok;
+    }
+    bool find(std::vector<bool>& vbInliers12, int& nInliers, float T12[16] = nullptr)
+    {
+        bool bFlag;
+        return iterate(mRansacMaxIts, bFlag, vbInliers12, nInliers, T12);
+    }
+    const float* GetEstimatedRotation() const { return best.R12; }         // 3 x 3 row-major
+    const float* GetEstimatedTranslation() const { return best.t12; }
+    float GetEstimatedScale() const { return best.s12; }
+
+    int mnIterations = 0, mnBestInliers = 0;
+    pgorb_sim3_estimate found{}, best{};
+    pgorb_sim3 foundSim3{};                                                 // what pgorb_search_by_sim3 takes
+    std::vector<int32_t> matches12Out;                                      // LoopClosing.cc:313-318
+    std::vector<uint8_t> already1, already2;                                // ORBmatcher.cc:1133-1146
+    int32_t info[PGORB_S3_INFO] = {};
+ private:
+    static void fail(const char* m) { throw std::invalid_argument(std::string("Sim3Solver: ") + m); }
+    pgorb_ctx* ctx_;
+    const Frame& F1_; const Frame& F2_;
+    pgorb_kf_pose pose1_, pose2_;
+    std::vector<int32_t> kfPoint1_, kfPoint2_, matches12_;
+    std::vector<pgorb_map_point> points_;
+    std::vector<uint8_t> pointBad_;
+    std::vector<uint32_t> draws_;
+    bool mbFixScale;
+    double mRansacProb = 0.99; int mRansacMinInliers = 6, mRansacMaxIts = 300;
+};
+
 namespace detail {
 inline void checkRefresh(const std::vector<const KeyFrame*>& kfs, const std::vector<uint8_t>& kfBad, size_t npoints, size_t ndesc,
                          const std::vector<uint8_t>& pointBad, const MapPointObservations& O, const std::vector<int32_t>* select, int what)

@@ -801,6 +801,13 @@ def kf_pose(Tcw, Ow, fx, fy, cx, cy, invfx=None, invfy=None):
 SIM3_DTYPE = np.dtype([("sR12", "<f4", (9,)), ("t12", "<f4", (3,)), ("sR21", "<f4", (9,)), ("t21", "<f4", (3,))])
 
 
+# pgorb_sim3_params / pgorb_sim3_estimate: Sim3Solver's parameter block and one (R12, t12, s12) (include/pgorb.h)
+SIM3_PARAMS_DTYPE = np.dtype([("probability", "<f4"), ("min_inliers", "<i4"), ("max_iterations", "<i4"), ("fix_scale", "<i4"),
+                              ("first_iteration", "<i4"), ("niterations", "<i4"), ("best_inliers_in", "<i4")])
+SIM3_ESTIMATE_DTYPE = np.dtype([("R12", "<f4", (9,)), ("t12", "<f4", (3,)), ("s12", "<f4")])
+S3_FEW, S3_FOUND, S3_NO_MORE, S3_INFO, SIM3_MAX_ITERATIONS = 1, 2, 4, 8, 1024
+
+
 def sim3_record(sR12, t12, sR21, t21):
     """A SIM3_DTYPE record of sR12 = s12*R12, t12, sR21 = (1.0/s12)*R12.t() and t21 = -sR21*t12, each as the caller computed it."""
     r = np.zeros((), SIM3_DTYPE)
@@ -879,6 +886,192 @@ class Optimizer:
             _p(out), _p(fl), _p(ko), _p(nmap), _p(chi), _p(info)))
         return dict(ret=ret, pose=out, outlier=fl[:n].copy(), kp_point_out=ko[:n].copy(), nmatches_map=int(nmap[0]), chi2=chi[:n].copy(),
                     status=int(info[0]), rounds=int(info[1]), iterations=[int(x) for x in info[2:6]], trials=int(info[6]), edges=int(info[7]))
+
+
+class Sim3Solver:
+    """Sim3Solver (thirdparty/orb-slam2/src/Sim3Solver.cc) on the GPU, with the reference's surface: the constructor,
+    SetRansacParameters, iterate(n), find and the three getters.  mnIterations and mnBestInliers live here and go to the library
+    as first_iteration / best_inliers_in, so iterate(5) can be called again on the same solver as LoopClosing::ComputeSim3 does.
+
+    KF1, KF2: Frame-like objects (ext, N, mvKeysUndistorted: the octave is read); pose1, pose2: KF_POSE_DTYPE records (Tcw and each
+    key frame's own camera are read); kf_point1 / kf_point2: the table index of every slot's point or -1 (the caller owns
+    GetIndexInKeyFrame); matches12[i1]: the KF2 keypoint SearchByBoW matched, or -1; table: a MapPointTable (pos and bad are read).
+    draws: [>= maxIterations][3] raw rand() values in [0, 2^31); None draws them from numpy's RandomState(seed).  Every input
+    the library's checked call refuses is a ValueError here, before the library is called."""
+    MAX_N = 16000
+
+    def __init__(self, KF1, KF2, pose1, pose2, kf_point1, kf_point2, matches12, table, bFixScale=False, draws=None, seed=0):
+        if draws is not None:
+            self.check_params("Sim3Solver", 0.99, 6, 1, draws=draws)
+        self._a = self.check("Sim3Solver", KF1, KF2, pose1, pose2, kf_point1, kf_point2, matches12, table)
+        self.ext, self.table = KF1.ext, table
+        self.mbFixScale = bool(bFixScale)
+        self._draws_in, self._seed = draws, seed
+        self.mnIterations, self.mnBestInliers = 0, 0
+        self.best = np.zeros((), SIM3_ESTIMATE_DTYPE)
+        self.found_sim3 = np.zeros((), SIM3_DTYPE)
+        self.matches12_out = self.already1 = self.already2 = None
+        self.info = np.zeros(S3_INFO, np.int32)
+        self.SetRansacParameters()
+
+    @staticmethod
+    def check(name, KF1, KF2, pose1, pose2, kf_point1, kf_point2, matches12, table):
+        """The single call's checks of the key frames and the table, without a device; returns the arrays the library reads."""
+        n1, n2 = int(KF1.N), int(KF2.N)
+        if n1 < 0 or n2 < 0:
+            raise ValueError("%s: a negative keypoint count" % name)
+        k1 = _arr(KF1.mvKeysUndistorted, KEYPOINT_DTYPE, n1, name + " KF1 keypoints")
+        k2 = _arr(KF2.mvKeysUndistorted, KEYPOINT_DTYPE, n2, name + " KF2 keypoints")
+        s1, s2 = _arr(kf_point1, np.int32, n1, "kf_point1"), _arr(kf_point2, np.int32, n2, "kf_point2")
+        m = _arr(matches12, np.int32, n1, "matches12")
+        table.check_indices(s1, "kf_point1", name)
+        table.check_indices(s2, "kf_point2", name)
+        if n1 and (int(m.min()) < -1 or int(m.max()) >= n2):
+            raise ValueError("%s: matches12 is outside [-1, n2)" % name)
+        P1, P2 = (np.ascontiguousarray(P, KF_POSE_DTYPE).reshape(()) for P in (pose1, pose2))
+        for P in (P1, P2):
+            if not (np.isfinite(P["Tcw"]).all() and np.isfinite([float(P[k]) for k in ("fx", "fy", "cx", "cy")]).all()):
+                raise ValueError("%s: a pose or a camera is not finite" % name)
+        i1 = np.nonzero(m >= 0)[0]
+        i1 = i1[(s1[i1] >= 0) & (s2[m[i1]] >= 0)]
+        if len(i1):
+            if not (np.isfinite(table.points["pos"][s1[i1]]).all() and np.isfinite(table.points["pos"][s2[m[i1]]]).all()):
+                raise ValueError("%s: a referenced point is not finite" % name)
+            levels = KF1.ext.GetLevels()
+            o = np.concatenate([k1["octave"][i1], k2["octave"][m[i1]]])
+            if int(o.min()) < 0 or int(o.max()) >= levels:
+                raise ValueError("%s: an octave is outside the extractor's %d levels" % (name, levels))
+        if max(n1, n2) > Sim3Solver.MAX_N:
+            raise ValueError("%s: more than %d keypoints in a key frame" % (name, Sim3Solver.MAX_N))
+        return dict(n1=n1, n2=n2, k1=k1, k2=k2, s1=s1, s2=s2, m=m, P1=P1, P2=P2)
+
+    @staticmethod
+    def check_params(name, probability, minInliers, maxIterations, first_iteration=0, niterations=1, draws=None):
+        """The single call's checks of the parameter block and the draws."""
+        if int(minInliers) < 3:
+            raise ValueError("%s: minInliers is below 3" % name)
+        if not 0.0 < float(np.float32(probability)) < 1.0:
+            raise ValueError("%s: probability is outside (0, 1)" % name)
+        if int(maxIterations) < 1:
+            raise ValueError("%s: maxIterations is below 1" % name)
+        if int(first_iteration) < 0:
+            raise ValueError("%s: first_iteration is negative" % name)
+        if int(niterations) < 1:
+            raise ValueError("%s: niterations is below 1" % name)
+        if int(maxIterations) > SIM3_MAX_ITERATIONS:
+            raise ValueError("%s: maxIterations above %d" % (name, SIM3_MAX_ITERATIONS))
+        if draws is not None:
+            d = np.asarray(draws)
+            if d.ndim < 2 or d.shape[-1] != 3 or d.shape[-2] < int(maxIterations):
+                raise ValueError("%s: draws must be [maxIterations][3]" % name)
+            if d.size and (int(d.min()) < 0 or int(d.max()) >= 2 ** 31):
+                raise ValueError("%s: a draw is not in [0, 2^31)" % name)
+
+    def SetRansacParameters(self, probability=0.99, minInliers=6, maxIterations=300):
+        """Sim3Solver.cc:114-138; resets mnIterations as the reference does (mnBestInliers stays)."""
+        self.check_params("SetRansacParameters", probability, minInliers, maxIterations, draws=self._draws_in)
+        self.mRansacProb, self.mRansacMinInliers, self.mRansacMaxIts = float(probability), int(minInliers), int(maxIterations)
+        if self._draws_in is None:
+            self.draws = np.random.RandomState(self._seed).randint(0, 2 ** 31, (self.mRansacMaxIts, 3)).astype(np.uint32)
+        else:
+            self.draws = np.ascontiguousarray(np.asarray(self._draws_in)[:self.mRansacMaxIts], np.uint32)
+        self.mnIterations = 0
+
+    def iterate(self, nIterations):
+        """Sim3Solver::iterate (:140-207).  Returns (T12, bNoMore, vbInliers, nInliers): T12 the 4 x 4 float [s*R | t] of the
+        returned hypothesis or None."""
+        self.check_params("iterate", self.mRansacProb, self.mRansacMinInliers, self.mRansacMaxIts, self.mnIterations, nIterations)
+        a, ext, t = self._a, self.ext, self.table
+        prm = np.zeros(1, SIM3_PARAMS_DTYPE)
+        prm["probability"], prm["min_inliers"], prm["max_iterations"] = self.mRansacProb, self.mRansacMinInliers, self.mRansacMaxIts
+        prm["fix_scale"], prm["first_iteration"], prm["niterations"] = int(self.mbFixScale), self.mnIterations, min(int(nIterations), 2 ** 30)
+        prm["best_inliers_in"] = self.mnBestInliers
+        n1, n2 = a["n1"], a["n2"]
+        found, best, sim3 = np.zeros(1, SIM3_ESTIMATE_DTYPE), np.zeros(1, SIM3_ESTIMATE_DTYPE), np.zeros(1, SIM3_DTYPE)
+        fl, mo, a1, a2 = np.zeros(max(n1, 1), np.uint8), np.full(max(n1, 1), -1, np.int32), np.zeros(max(n1, 1), np.uint8), np.zeros(max(n2, 1), np.uint8)
+        info = np.zeros(S3_INFO, np.int32)
+        pad = lambda x, n, dt: x if n else np.zeros(1, dt)
+        ret = ext._check(ext._L.pgorb_sim3_solver(
+            ext._h, _p(pad(a["k1"], n1, KEYPOINT_DTYPE)), n1, _p(a["P1"]), _p(pad(a["s1"], n1, np.int32)), _p(pad(a["k2"], n2, KEYPOINT_DTYPE)), n2,
+            _p(a["P2"]), _p(pad(a["s2"], n2, np.int32)), _p(pad(a["m"], n1, np.int32)), t.n, _p(t.points), _p(t.bad), _p(prm), _p(self.draws),
+            _p(found), _p(sim3), _p(best), _p(fl), _p(mo), _p(a1), _p(a2), _p(info)))
+        self.info = info
+        self.mnIterations, self.mnBestInliers = int(info[3]), int(info[5])
+        if info[6] >= 0:
+            self.best = best[0].copy()
+        self.found, self.found_sim3 = found[0].copy(), sim3[0].copy()
+        self.matches12_out, self.already1, self.already2 = mo[:n1].copy(), a1[:n1].copy(), a2[:n2].copy()
+        no_more = bool(info[0] & (S3_FEW | S3_NO_MORE))
+        T12 = None
+        if info[0] & S3_FOUND:
+            T12 = np.eye(4, dtype=np.float32)
+            T12[:3, :3], T12[:3, 3] = sim3[0]["sR12"].reshape(3, 3), sim3[0]["t12"]
+        return T12, no_more, fl[:n1].astype(bool), int(ret)
+
+    def find(self):
+        """Sim3Solver::find (:209-213): iterate(mRansacMaxIts).  Returns (T12, vbInliers12, nInliers)."""
+        T12, _, inl, n = self.iterate(self.mRansacMaxIts)
+        return T12, inl, n
+
+    def GetEstimatedRotation(self):
+        return self.best["R12"].reshape(3, 3).copy()
+
+    def GetEstimatedTranslation(self):
+        return self.best["t12"].copy()
+
+    def GetEstimatedScale(self):
+        return float(self.best["s12"])
+
+    @staticmethod
+    def iterate_batch_device(ext, d_kps, d_n, cap_per_frame, d_pair_kf1, d_pair_kf2, d_pose, d_kf_point, d_matches12, npoints, d_points,
+                             d_point_bad, d_draws, probability=0.99, minInliers=20, maxIterations=300, nIterations=300, bFixScale=False,
+                             first_iteration=0, best_inliers_in=0, d_first_iteration=None, d_best_inliers_in=None, stream=None):
+        """pgorb_sim3_solver_batch_device over resident torch tensors: pair p aligns key frames d_pair_kf1[p] and d_pair_kf2[p];
+        d_draws is [npairs][maxIterations][3] uint32 (or int32 bits).  The parameters and the sizes are checked here as the single
+        call checks them, and the tensors' element types and sizes against npairs, cap and the number of frames (the pair count is
+        d_pair_kf1's element count, so the index tensors must be int32); the arrays' contents are not read: the batched form counts
+        a bad index as no correspondence and trusts the pair lists.  Returns a
+        dict of freshly allocated tensors: found, found_sim3, best (bytes of their dtypes per pair), inlier, matches12_out,
+        already1, already2 [npairs][cap], info [npairs][S3_INFO], ninliers [npairs]."""
+        import torch
+        name = "Sim3Solver.iterate_batch_device"
+        Sim3Solver.check_params(name, probability, minInliers, maxIterations, first_iteration, nIterations)
+        for nm, t_ in (("d_pair_kf1", d_pair_kf1), ("d_pair_kf2", d_pair_kf2), ("d_matches12", d_matches12), ("d_n", d_n), ("d_kf_point", d_kf_point),
+                       ("d_first_iteration", d_first_iteration), ("d_best_inliers_in", d_best_inliers_in)):
+            if t_ is not None and t_.dtype != torch.int32:
+                raise ValueError("%s: %s must be an int32 tensor (the pair count and the row lengths are taken from element counts)" % (name, nm))
+        if d_draws.element_size() != 4:
+            raise ValueError("%s: d_draws must have 4-byte elements" % name)
+        npairs, cap = int(d_pair_kf1.numel()), int(cap_per_frame)
+        if cap < 1 or cap > Sim3Solver.MAX_N:
+            raise ValueError("%s: cap_per_frame outside [1, %d]" % (name, Sim3Solver.MAX_N))
+        if int(d_pair_kf2.numel()) != npairs or int(npoints) < 0:
+            raise ValueError("%s: the pair lists differ in length or npoints is negative" % name)
+        if d_matches12.numel() != npairs * cap or d_draws.numel() != npairs * int(maxIterations) * 3:
+            raise ValueError("%s: d_matches12 must be [npairs][cap] and d_draws [npairs][maxIterations][3]" % name)
+        nframes = int(d_n.numel())
+        if d_kf_point.numel() != nframes * cap or d_kps.numel() * d_kps.element_size() != nframes * cap * KEYPOINT_DTYPE.itemsize or \
+                d_pose.numel() * d_pose.element_size() != nframes * KF_POSE_DTYPE.itemsize:
+            raise ValueError("%s: d_kps, d_kf_point and d_pose must hold one row per frame of d_n" % name)
+        if d_points.numel() * d_points.element_size() < int(npoints) * MAP_POINT_DTYPE.itemsize or \
+                (d_point_bad is not None and d_point_bad.numel() * d_point_bad.element_size() < int(npoints)):
+            raise ValueError("%s: the table is shorter than npoints" % name)
+        dev = d_matches12.device
+        prm = np.zeros(1, SIM3_PARAMS_DTYPE)
+        prm["probability"], prm["min_inliers"], prm["max_iterations"] = probability, minInliers, maxIterations
+        prm["fix_scale"], prm["first_iteration"], prm["niterations"], prm["best_inliers_in"] = int(bool(bFixScale)), first_iteration, nIterations, best_inliers_in
+        e = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
+        out = dict(found=e((npairs, SIM3_ESTIMATE_DTYPE.itemsize), torch.uint8), found_sim3=e((npairs, SIM3_DTYPE.itemsize), torch.uint8),
+                   best=e((npairs, SIM3_ESTIMATE_DTYPE.itemsize), torch.uint8), inlier=e((npairs, cap), torch.uint8),
+                   matches12_out=e((npairs, cap), torch.int32), already1=e((npairs, cap), torch.uint8), already2=e((npairs, cap), torch.uint8),
+                   info=e((npairs, S3_INFO), torch.int32), ninliers=e((npairs,), torch.int32))
+        q = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        s = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        ext._check(ext._L.pgorb_sim3_solver_batch_device(
+            ext._h, q(d_kps), q(d_n), cap, q(d_pair_kf1), q(d_pair_kf2), npairs, q(d_pose), q(d_kf_point), q(d_matches12), int(npoints), q(d_points),
+            q(d_point_bad), _p(prm), q(d_first_iteration), q(d_best_inliers_in), q(d_draws), q(out["found"]), q(out["found_sim3"]), q(out["best"]),
+            q(out["inlier"]), q(out["matches12_out"]), q(out["already1"]), q(out["already2"]), q(out["info"]), q(out["ninliers"]), C.c_void_p(s)))
+        return out
 
 
 # pgorb_refresh_map_points: what to refresh, the status word's bits, the limit (include/pgorb.h)

@@ -44,7 +44,15 @@ next to each, the oracle's CPU time for the same work (1 thread, a few frames, s
                of the tests (tests/pose_reference.py, OUR restatement on one core, NOT g2o) for ONE such problem.  There is no
                g2o build to hold these times against and no earlier path in this library.  --pose-only runs these rows alone
 
-usage: python tools/next_tier_bench.py [--batch 128] [--out profiles/r02_next_tier.txt] [--refresh-only | --place-only | --loop-only | --track-only | --pose-only]"""
+  sim3         Sim3Solver (Sim3Solver.cc:37-423) on the device (pgorb_sim3_solver, csrc/sim3.hip): one loop candidate through the
+               single call (wall clock, staging included) and 16 candidates in one batched resident call (HIP events), each 150
+               correspondences (30 % outliers) and a window of 300 iterations, all of which the device evaluates whenever the
+               stop rule would have returned; beside them the wall clock of the sequential Python reference of the tests
+               (tests/sim3_reference.py, OUR restatement on one core, NOT ORB-SLAM2: it needs OpenCV, which cannot be built here)
+               run to ITS end, which is the stop rule's.  No CPU figure exists to set a target against.  --sim3-only runs these
+               rows alone
+
+usage: python tools/next_tier_bench.py [--batch 128] [--out profiles/r02_next_tier.txt] [--refresh-only | --place-only | --loop-only | --track-only | --pose-only | --sim3-only]"""
 import argparse, ctypes as C, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -64,6 +72,7 @@ ap.add_argument("--place-only", action="store_true", help="the place-recognition
 ap.add_argument("--loop-only", action="store_true", help="loop closing's four matchers alone (no ride, no vocabulary)")
 ap.add_argument("--track-only", action="store_true", help="the tracking thread's SearchLocalPoints rows alone (no ride, no vocabulary)")
 ap.add_argument("--pose-only", action="store_true", help="the pose-optimisation rows alone (no ride, no vocabulary)")
+ap.add_argument("--sim3-only", action="store_true", help="the Sim3Solver rows alone (no ride, no vocabulary)")
 a = ap.parse_args()
 w, h, nf, B = 1920, 1080, a.features, a.batch
 
@@ -378,6 +387,62 @@ def pose_lines(npairs=128, cap=2000):
     return out
 
 
+def sim3_lines(npairs=16, ngood=105, nout=45):
+    """Sim3Solver: the single call and the batched resident call, beside the Python reference of the tests."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import sim3_cases as SC
+    ext = pg.ORBextractor(2000, 1.2, 8, 20, 7, max_width=640, max_height=480)
+    cs = [SC.scene("bench%d" % j, 3000 + j, ngood, nout, s=1.0 + 0.05 * j, noise=0.3) for j in range(npairs)]
+    N = ngood + nout
+    t0 = time.perf_counter(); ref = SC.run_reference(cs[0]); t_ref = (time.perf_counter() - t0) * 1e3
+    ts = []
+    for j in range(10):
+        t0 = time.perf_counter(); got = SC.run_gpu(cs[0], ext); ts.append((time.perf_counter() - t0) * 1e3)
+    assert got["ret"] == ref["ret"] and np.array_equal(got["inlier"], ref["inlier"]) and got["cap"] == 300
+    t1 = float(np.median(ts[1:]))
+    res = {}
+    run = lambda: res.__setitem__("r", SC.run_gpu_batch(cs, ext, N))
+    run()
+    # the batched call alone, on resident arrays: the runner's uploads are outside the events
+    G = lambda x: torch.from_numpy(np.ascontiguousarray(x)).cuda()
+    nfr = 2 * npairs
+    kp = np.zeros((nfr, N), pg.KEYPOINT_DTYPE); slots = np.full((nfr, N), -1, np.int32); m12 = np.full((npairs, N), -1, np.int32)
+    poses = np.zeros(nfr, pg.KF_POSE_DTYPE); draws = np.zeros((npairs, 300, 3), np.uint32)
+    base, tabs = 0, []
+    for j, c in enumerate(cs):
+        kp[2 * j, :c.n1] = SC.keypoints(c.octaves1)[:c.n1]; kp[2 * j + 1, :c.n2] = SC.keypoints(c.octaves2)[:c.n2]
+        slots[2 * j, :c.n1] = c.kf_point1 + base; slots[2 * j + 1, :c.n2] = c.kf_point2 + base
+        m12[j, :c.n1] = c.matches12; poses[2 * j], poses[2 * j + 1] = SC.pose_record(c.pose1), SC.pose_record(c.pose2)
+        draws[j] = c.draws; tabs.append(SC.table(c.points)[:len(c.points)]); base += len(c.points)
+    tab = np.concatenate(tabs)
+    dK, dN, dP, dS, dM = G(kp.view(np.uint8).reshape(nfr, N, 28)), G(np.full(nfr, N, np.int32)), G(poses.view(np.uint8).reshape(nfr, -1)), G(slots), G(m12)
+    dT, dD = G(tab.view(np.uint8).reshape(len(tab), 32)), G(draws.view(np.int32))
+    d1, d2 = G(np.arange(0, nfr, 2, dtype=np.int32)), G(np.arange(1, nfr, 2, dtype=np.int32))
+    out_t = None
+    def batched():
+        nonlocal out_t
+        out_t = pg.Sim3Solver.iterate_batch_device(ext, dK, dN, N, d1, d2, dP, dS, dM, len(tab), dT, None, dD, 0.99, 20, 300, 300)
+    t = timed(batched)
+    ninl = out_t["ninliers"].cpu().numpy()
+    assert [int(x) for x in ninl] == [r["ret"] for r in res["r"]] and int(ninl[0]) == ref["ret"]
+    its = out_t["info"].cpu().numpy()[:, 3]
+    return ["# Sim3Solver on the device; single call = wall clock with staging, median of 9; batched resident call = HIP events, median of 9 (its nine",
+            "# output arrays are allocated inside the timed call); every call evaluates its whole window of 300 iterations; reference = tests/sim3_reference.py",
+            "# for ONE candidate run to the stop rule's return, wall clock: OUR restatement in numpy on one core, NOT ORB-SLAM2's Sim3Solver, which needs",
+            "# OpenCV and cannot be built here.  No CPU figure exists to set a target against; none is set.",
+            "%-110s %10s %16s %16s" % ("call", "GPU ms", "GPU ms/candidate", "reference ms (1)"),
+            "%-110s %10.3f %16.4f %16.1f" % ("sim3_solver (single call): %d correspondences, 300 iterations evaluated, returned at iteration %d with %d inliers" % (
+                N, got["its_after"] - 1, got["ret"]), t1, t1, t_ref),
+            "%-110s %10.3f %16.4f %16.1f" % ("sim3_solver_batch_device: %d candidates x 300 iterations x %d correspondences (returned after %.1f iterations on average)" % (
+                npairs, N, its.mean()), t, t / npairs, t_ref)]
+
+
+if a.sim3_only:
+    lines = ["# python tools/next_tier_bench.py --sim3-only   (MI355X)"] + sim3_lines()
+    print("\n".join(lines))
+    if a.out:
+        open(a.out, "w").write("\n".join(lines) + "\n")
+    sys.exit(0)
 if a.pose_only:
     lines = ["# python tools/next_tier_bench.py --pose-only   (MI355X)"] + pose_lines()
     print("\n".join(lines))

@@ -889,6 +889,55 @@ int  pgorb_sim3_solver_batch_device(pgorb_ctx* ctx, const pgorb_keypoint* d_kps,
         pgorb_sim3_estimate* d_best, uint8_t* d_inlier, int32_t* d_matches12_out, uint8_t* d_already1, uint8_t* d_already2,
         int32_t* d_info, int32_t* d_ninliers, void* hip_stream);
 
+/*   pgorb_optimize_sim3   Optimizer::OptimizeSim3(pKF1, pKF2, vpMatches1, g2oS12, th2, bFixScale) (src/Optimizer.cc:1046-1241) with the
+ *       g2o path under it (VertexSim3Expmap, EdgeSim3ProjectXYZ, EdgeInverseSim3ProjectXYZ with their NUMERIC Jacobian, RobustKernelHuber,
+ *       OptimizationAlgorithmLevenberg, LinearSolverDense), in double: step 4 of LoopClosing::ComputeSim3, between pgorb_search_by_sim3
+ *       and pgorb_search_by_projection_sim3.  It is this project's READING of g2o and Eigen (DESIGN.md section 4 lists it), anchored
+ *       by the CPU tests of tests/test_optimize_sim3.py and not pinned to a g2o build.
+ * Inputs.  Both key frames and the table as for pgorb_sim3_solver (Tcw and each key frame's own fx, fy, cx, cy are read; pos and
+ * point_bad of the table).  matches12 [n1] = the KF2 keypoint or -1: the solver's matches12_out.  new_matches12 [n1] (may be NULL) =
+ * what pgorb_search_by_sim3 wrote: where it is >= 0 it replaces the entry, as the reference's in-place vpMatches12[idx1] = ... does.
+ * A correspondence is an entry i1 with a match i2, kf_point1[i1] >= 0, kf_point2[i2] >= 0 and neither point bad; it carries the edge
+ * pair e12 (obs1 - cam1(S12 * P2c)) and e21 (obs2 - cam2(S12^-1 * P1c)) with invSigma2 of each keypoint's octave.  estimate = the
+ * float R, t, s of LoopClosing.cc:320-325 (the solver's `found`); th2: the reference passes 10; fix_scale = mbFixScale.
+ * Outputs.  The return value is nIn.  estimate_out = R12, t12, s12 of the recovered g2o::Sim3 rounded to float.  matches12_out [n1] =
+ * the merged input with every removed correspondence set to -1.  chi2_12 / chi2_21 [n1] (may be NULL) = the float chi2 each edge held
+ * at its last classification, 0 where there is no edge.  scw_pose (may be NULL) = a complete pgorb_kf_pose for
+ * pgorb_search_by_projection_sim3: gScm * gSmw in double with gSmw from pose2 (LoopClosing.cc:333-335), Converter::toCvMat, then the
+ * decomposition described there; it carries KF1's camera.  info (may be NULL) = PGORB_OS3_INFO int32: status bits,
+ * nCorrespondences, nBad, iterations and Levenberg trials of the first optimize call, the same of the second, nMoreIterations.
+ * PGORB_OS3_FEW: nCorrespondences - nBad < 10 -- returns 0 before the vertex is recovered: estimate_out = estimate byte for byte,
+ * matches12_out keeps the -1s of the first classification, scw_pose is zeroed.
+ * PGORB_OS3_NONFINITE: the active chi2 a Levenberg iteration starts from, or an edge's chi2 at a classification, is not finite --
+ * returns 0, estimate_out = estimate byte for byte, matches12_out = the merged input, every chi2 0, scw_pose zeroed.
+ * Determinism: a pair's result depends on its inputs only; the single call equals the batched one byte for byte.
+ * PGORB_E_ARG (single call, on the host before anything else): a negative count, a NULL array that is read, a slot index outside
+ * [-1, npoints), matches12 or new_matches12 outside [-1, n2), the octave of a used keypoint outside the context's levels, a value
+ * of Tcw, fx, fy, cx, cy, the estimate or a referenced point that is not finite, th2 <= 0, s12 <= 0.  PGORB_E_LIMIT: more than 16000
+ * keypoints in a key frame (cap_per_frame).  The batched form checks th2 and the limits only: a bad index or octave counts as no
+ * correspondence.
+ *   Batched: pair p refines key frames d_pair_kf1[p] and d_pair_kf2[p]; d_pose and d_kf_point go by frame; d_matches12,
+ *       d_new_matches12 (or NULL), d_matches12_out, d_chi2_12 / 21 are [npairs][cap_per_frame] (every entry is written), d_estimate,
+ *       d_estimate_out, d_scw_pose, d_nin [npairs], d_info [npairs][PGORB_OS3_INFO].  One launch, one workgroup per pair; the scratch
+ *       arena holds 64 bytes per pair and keypoint. */
+#define PGORB_OS3_FEW        1
+#define PGORB_OS3_NONFINITE  2
+#define PGORB_OS3_INFO       8
+int  pgorb_optimize_sim3(pgorb_ctx* ctx,
+        const pgorb_keypoint* kps1, int n1, const pgorb_kf_pose* pose1, const int32_t* kf_point1,
+        const pgorb_keypoint* kps2, int n2, const pgorb_kf_pose* pose2, const int32_t* kf_point2,
+        const int32_t* matches12 /*[n1]*/, const int32_t* new_matches12 /*[n1] or NULL*/,
+        int npoints, const pgorb_map_point* points, const uint8_t* point_bad /*[npoints] or NULL*/,
+        const pgorb_sim3_estimate* estimate, float th2, int fix_scale,
+        pgorb_sim3_estimate* estimate_out, int32_t* matches12_out /*[n1]*/, float* chi2_12, float* chi2_21 /*[n1] or NULL*/,
+        pgorb_kf_pose* scw_pose, int32_t* info);
+int  pgorb_optimize_sim3_batch_device(pgorb_ctx* ctx, const pgorb_keypoint* d_kps, const int32_t* d_n, int cap_per_frame,
+        const int32_t* d_pair_kf1, const int32_t* d_pair_kf2, int npairs, const pgorb_kf_pose* d_pose, const int32_t* d_kf_point,
+        const int32_t* d_matches12, const int32_t* d_new_matches12, int npoints, const pgorb_map_point* d_points,
+        const uint8_t* d_point_bad, const pgorb_sim3_estimate* d_estimate, float th2, int fix_scale,
+        pgorb_sim3_estimate* d_estimate_out, int32_t* d_matches12_out, float* d_chi2_12, float* d_chi2_21,
+        pgorb_kf_pose* d_scw_pose, int32_t* d_info, int32_t* d_nin, void* hip_stream);
+
 /* ---- Map-point refresh: the distinctive descriptor and the normal / depth range of many points --------------------------
  *   pgorb_refresh_map_points   for every selected point what MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:259-324)
  *       followed by MapPoint::UpdateNormalAndDepth (:347-388) would store, exactly.  The reference runs the pair once per point at

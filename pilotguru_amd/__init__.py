@@ -9,5 +9,6 @@ from .orb import KF_POSE_DTYPE, NEW_MAP_POINT_DTYPE, LocalMapping, kf_pose  # no
 from .orb import MAP_POINT_DTYPE, MapPointTable, SIM3_DTYPE, sim3_pose, sim3_record  # noqa: F401
 from .orb import MP_BOTH, MP_DESCRIPTOR, MP_LIMIT, MP_MAX_OBS, MP_NORMAL_DEPTH  # noqa: F401
 from .orb import PO_FEW, PO_INFO, PO_NONFINITE, Optimizer  # noqa: F401
+from .orb import OS3_FEW, OS3_INFO, OS3_NONFINITE  # noqa: F401
 from .orb import S3_FEW, S3_FOUND, S3_INFO, S3_NO_MORE, SIM3_ESTIMATE_DTYPE, SIM3_MAX_ITERATIONS, SIM3_PARAMS_DTYPE, Sim3Solver  # noqa: F401
 from .place import KeyFrameDatabase  # noqa: F401

@@ -50,6 +50,7 @@ SYMBOLS = (
     "pgorb_pose_optimization", "pgorb_pose_optimization_batch_device",
     "pgorb_slots_from_assignment", "pgorb_slots_from_assignment_batch_device",
     "pgorb_sim3_solver", "pgorb_sim3_solver_batch_device", "pgorb_sim3_max_iterations",
+    "pgorb_optimize_sim3", "pgorb_optimize_sim3_batch_device",
     "pgorb_undistort_keypoints", "pgorb_undistort_keypoints_batch_device", "pgorb_image_bounds",
     "pgorb_host_alloc", "pgorb_host_free", "pgorb_host_register", "pgorb_host_unregister", "pgorb_stream_create", "pgorb_stream_create_ingest", "pgorb_stream_create_device", "pgorb_stream_submit_device", "pgorb_stream_wait_device", "pgorb_stream_lanes", "pgorb_stream_destroy", "pgorb_stream_input", "pgorb_stream_reset", "pgorb_stream_submit",
     "pgorb_stream_wait", "pgorb_stream_frontend", "pgorb_stream_frontend_results", "pgorb_set_option", "pgorb_get_option", "pgorb_matcher_is_popcount",
@@ -198,6 +199,13 @@ def lib():
     #  best_inliers_in, draws, found, found_sim3, best, inlier, matches12_out, already1, already2, info, ninliers, stream)
     L.pgorb_sim3_solver_batch_device.argtypes = [vp, vp, vp, C.c_int, vp, vp, C.c_int, vp, vp, vp, C.c_int] + [vp] * 16
     L.pgorb_sim3_max_iterations.argtypes = [C.c_float, C.c_int, C.c_int, C.c_int]
+    # (ctx, kps1, n1, pose1, kf_point1, kps2, n2, pose2, kf_point2, matches12, new_matches12, npoints, points, point_bad, estimate, th2,
+    #  fix_scale, estimate_out, matches12_out, chi2_12, chi2_21, scw_pose, info)
+    L.pgorb_optimize_sim3.argtypes = [vp, vp, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp, vp, C.c_int, vp, vp, vp, C.c_float, C.c_int] + [vp] * 6
+    # (ctx, kps, n, cap, pair_kf1, pair_kf2, npairs, pose, kf_point, matches12, new_matches12, npoints, points, point_bad, estimate, th2,
+    #  fix_scale, estimate_out, matches12_out, chi2_12, chi2_21, scw_pose, info, nin, stream)
+    L.pgorb_optimize_sim3_batch_device.argtypes = [vp, vp, vp, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp, C.c_int, vp, vp, vp, C.c_float, C.c_int] + \
+        [vp] * 8
     L.pgorb_log_f.argtypes = [C.c_float]
     L.pgorb_log_scale_factor.argtypes = [vp]
     L.pgorb_predict_scale.argtypes = [vp, C.c_float, C.c_float]

@@ -351,9 +351,69 @@ struct PoseOptimizationResult {
     int32_t info[PGORB_PO_INFO] = {};      // status, rounds, iterations of rounds 0..3, trials, edges
 };
 
+// What Optimizer::OptimizeSim3 returns beside nIn (include/pgorb.h).
+struct OptimizeSim3Result {
+    int inliers = 0;                       // nIn, the reference's return value
+    pgorb_sim3_estimate estimate{};        // R12, t12, s12 of the recovered g2o::Sim3 (the input with a status)
+    std::vector<int32_t> matches12;        // the merged input with every removed correspondence set to -1
+    std::vector<float> chi2_12, chi2_21;
+    pgorb_kf_pose scwPose{};               // gScm*gSmw decomposed, with KF1's camera: what SearchByProjection(pKF, Scw, ...) takes
+    int32_t info[PGORB_OS3_INFO] = {};     // status, nCorrespondences, nBad, iterations and trials of both optimize calls, nMoreIterations
+};
+
 class Optimizer {
  public:
     explicit Optimizer(pgorb_ctx* ctx) : ctx_(ctx) {}
+    // Optimizer::OptimizeSim3(pKF1, pKF2, vpMatches1, g2oS12, th2, bFixScale) (Optimizer.cc:1046-1241) on the GPU.  The key frames, the
+    // slots and the table as for Sim3Solver; matches12[i1]: the KF2 keypoint or -1 (the solver's matches12Out); newMatches12 (empty =
+    // none): what SearchBySim3 wrote, replacing an entry where it is >= 0; estimate: the solver's `found`.
+    // Everything pgorb_optimize_sim3 refuses is a std::invalid_argument here, before the library is called.
+    OptimizeSim3Result OptimizeSim3(const Frame& F1, const Frame& F2, const pgorb_kf_pose& pose1, const pgorb_kf_pose& pose2,
+                                    const std::vector<int32_t>& kfPoint1, const std::vector<int32_t>& kfPoint2,
+                                    const std::vector<int32_t>& matches12, const std::vector<int32_t>& newMatches12,
+                                    const std::vector<pgorb_map_point>& points, const std::vector<uint8_t>& pointBad,
+                                    const pgorb_sim3_estimate& estimate, float th2 = 10.0f, bool bFixScale = false)
+    {
+        const auto fail = [](const char* m) { throw std::invalid_argument(std::string("OptimizeSim3: ") + m); };
+        const int n1 = F1.N(), n2 = F2.N(), np = (int)points.size(), levels = pgorb_levels(ctx_);
+        if (kfPoint1.size() != (size_t)n1 || matches12.size() != (size_t)n1) fail("kfPoint1 or matches12 is not N1 entries long");
+        if (!newMatches12.empty() && newMatches12.size() != (size_t)n1) fail("newMatches12 is neither empty nor N1 entries long");
+        if (kfPoint2.size() != (size_t)n2) fail("kfPoint2 is not N2 entries long");
+        if (!pointBad.empty() && pointBad.size() != (size_t)np) fail("pointBad is neither empty nor one entry per point");
+        for (const pgorb_kf_pose* P : {&pose1, &pose2}) {
+            for (int k = 0; k < 12; k++)
+                if (!std::isfinite(P->Tcw[k])) fail("a pose is not finite");
+            if (!std::isfinite(P->fx) || !std::isfinite(P->fy) || !std::isfinite(P->cx) || !std::isfinite(P->cy)) fail("a camera is not finite");
+        }
+        for (int k = 0; k < 9; k++) if (!std::isfinite(estimate.R12[k])) fail("the estimate is not finite");
+        for (int k = 0; k < 3; k++) if (!std::isfinite(estimate.t12[k])) fail("the estimate is not finite");
+        if (!std::isfinite(estimate.s12)) fail("the estimate is not finite");
+        if (!(estimate.s12 > 0.0f)) fail("the estimate's scale is not positive");
+        if (!(th2 > 0.0f) || !std::isfinite(th2)) fail("th2 is not positive");
+        for (int s : kfPoint1) if (s < -1 || s >= np) fail("a slot names a point outside the table");
+        for (int s : kfPoint2) if (s < -1 || s >= np) fail("a slot names a point outside the table");
+        for (int i = 0; i < n1; i++) {
+            if (matches12[i] < -1 || matches12[i] >= n2) fail("matches12 is outside [-1, n2)");
+            if (!newMatches12.empty() && (newMatches12[i] < -1 || newMatches12[i] >= n2)) fail("newMatches12 is outside [-1, n2)");
+            const int j = (!newMatches12.empty() && newMatches12[i] >= 0) ? newMatches12[i] : matches12[i];
+            if (j < 0 || kfPoint1[i] < 0 || kfPoint2[j] < 0) continue;
+            const int o1 = F1.mvKeysUndistorted[i].octave, o2 = F2.mvKeysUndistorted[j].octave;
+            if (levels > 0 && (o1 < 0 || o1 >= levels || o2 < 0 || o2 >= levels)) fail("an octave is outside the context's levels");
+            for (const float* p : {points[kfPoint1[i]].pos, points[kfPoint2[j]].pos})
+                if (!std::isfinite(p[0]) || !std::isfinite(p[1]) || !std::isfinite(p[2])) fail("a referenced point is not finite");
+        }
+        if (n1 > 16000 || n2 > 16000) fail("more than 16000 keypoints in a key frame");
+        OptimizeSim3Result r;
+        r.matches12.assign(n1 > 0 ? n1 : 1, -1); r.chi2_12.assign(n1 > 0 ? n1 : 1, 0.0f); r.chi2_21.assign(n1 > 0 ? n1 : 1, 0.0f);
+        const int rc = pgorb_optimize_sim3(ctx_, F1.mvKeysUndistorted.data(), n1, &pose1, kfPoint1.data(), F2.mvKeysUndistorted.data(), n2, &pose2,
+                                           kfPoint2.data(), matches12.data(), newMatches12.empty() ? nullptr : newMatches12.data(), np, points.data(),
+                                           pointBad.empty() ? nullptr : pointBad.data(), &estimate, th2, bFixScale ? 1 : 0, &r.estimate,
+                                           r.matches12.data(), r.chi2_12.data(), r.chi2_21.data(), &r.scwPose, r.info);
+        if (rc < 0) throw std::runtime_error(pgorb_last_error(ctx_));
+        r.matches12.resize(n1); r.chi2_12.resize(n1); r.chi2_21.resize(n1);
+        r.inliers = rc;
+        return r;
+    }
     // Optimizer::PoseOptimization(pFrame) (Optimizer.cc:239-451), monocular, on the GPU.  F: mvKeysUn (pt and octave are read); pose:
     // the frame's pose and camera; kpPoint[i] = the table index of mvpMapPoints[i] or -1; points: the table (pos is read);
     // pointHasObs: Observations() > 0 per point (empty = all).  discardOutliers: the loop of Tracking.cc:768-787 runs too.

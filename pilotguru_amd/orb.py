@@ -840,10 +840,13 @@ def sim3_pose(Scw, fx, fy, cx, cy):
 
 # pgorb_pose_optimization: the status bits and the length of its info record (include/pgorb.h)
 PO_FEW, PO_NONFINITE, PO_INFO = 1, 2, 8
+# pgorb_optimize_sim3: the same
+OS3_FEW, OS3_NONFINITE, OS3_INFO = 1, 2, 8
 
 
 class Optimizer:
-    """Optimizer::PoseOptimization (thirdparty/orb-slam2/src/Optimizer.cc:239-451), monocular, on the GPU."""
+    """Optimizer::PoseOptimization (thirdparty/orb-slam2/src/Optimizer.cc:239-451, monocular) and Optimizer::OptimizeSim3
+    (:1046-1241) on the GPU."""
 
     @staticmethod
     def PoseOptimization(frame_keys, pose, kp_point, table, discard_outliers=False, point_has_obs=None):
@@ -886,6 +889,101 @@ class Optimizer:
             _p(out), _p(fl), _p(ko), _p(nmap), _p(chi), _p(info)))
         return dict(ret=ret, pose=out, outlier=fl[:n].copy(), kp_point_out=ko[:n].copy(), nmatches_map=int(nmap[0]), chi2=chi[:n].copy(),
                     status=int(info[0]), rounds=int(info[1]), iterations=[int(x) for x in info[2:6]], trials=int(info[6]), edges=int(info[7]))
+
+
+    @staticmethod
+    def check_sim3(name, KF1, KF2, pose1, pose2, kf_point1, kf_point2, matches12, new_matches12, table, estimate, th2):
+        """pgorb_optimize_sim3's checks, without a device; returns the arrays the library reads."""
+        n1, n2 = int(KF1.N), int(KF2.N)
+        if n1 < 0 or n2 < 0:
+            raise ValueError("%s: a negative keypoint count" % name)
+        m = _arr(matches12, np.int32, n1, "matches12")
+        nm = None if new_matches12 is None else _arr(new_matches12, np.int32, n1, "new_matches12")
+        for nme, a in (("matches12", m), ("new_matches12", nm)):
+            if a is not None and n1 and (int(a.min()) < -1 or int(a.max()) >= n2):
+                raise ValueError("%s: %s is outside [-1, n2)" % (name, nme))
+        e = np.ascontiguousarray(estimate, SIM3_ESTIMATE_DTYPE).reshape(())
+        if not (np.isfinite(e["R12"]).all() and np.isfinite(e["t12"]).all() and np.isfinite(e["s12"])):
+            raise ValueError("%s: the estimate is not finite" % name)
+        if not float(e["s12"]) > 0.0:
+            raise ValueError("%s: the estimate's scale is not positive" % name)
+        if not (float(np.float32(th2)) > 0.0 and np.isfinite(np.float32(th2))):
+            raise ValueError("%s: th2 is not positive" % name)
+        merged = m if nm is None else np.where(nm >= 0, nm, m).astype(np.int32)
+        a = Sim3Solver.check(name, KF1, KF2, pose1, pose2, kf_point1, kf_point2, merged, table)
+        a["m"], a["nm"], a["e"] = m, nm, e
+        return a
+
+    @staticmethod
+    def OptimizeSim3(KF1, KF2, pose1, pose2, kf_point1, kf_point2, matches12, table, estimate, th2=10.0, bFixScale=False, new_matches12=None):
+        """Optimizer::OptimizeSim3 (thirdparty/orb-slam2/src/Optimizer.cc:1046-1241) on the GPU: step 4 of LoopClosing::ComputeSim3.
+        The key frames, poses, slots and the table as for Sim3Solver; matches12[i1] = the KF2 keypoint or -1 (the solver's
+        matches12_out); new_matches12 (or None) = what SearchBySim3 wrote, replacing an entry where it is >= 0; estimate = a
+        SIM3_ESTIMATE_DTYPE record (R12, t12, s12: the solver's `found`).  Every input the library's checked call refuses is a
+        ValueError here, before the library is called.  Returns a dict: ret (nIn), estimate (SIM3_ESTIMATE_DTYPE), matches12_out,
+        chi2_12, chi2_21, scw_pose (a complete KF_POSE_DTYPE record for SearchByProjectionSim3; zeroed with a status), status
+        (OS3_FEW | OS3_NONFINITE bits), correspondences, nbad, iterations and trials (of the two optimize calls), more_iterations."""
+        a = Optimizer.check_sim3("OptimizeSim3", KF1, KF2, pose1, pose2, kf_point1, kf_point2, matches12, new_matches12, table, estimate, th2)
+        ext, t = KF1.ext, table
+        n1, n2 = a["n1"], a["n2"]
+        eo, sp = np.zeros((), SIM3_ESTIMATE_DTYPE), np.zeros((), KF_POSE_DTYPE)
+        mo, c12, c21 = np.full(max(n1, 1), -1, np.int32), np.zeros(max(n1, 1), np.float32), np.zeros(max(n1, 1), np.float32)
+        info = np.zeros(OS3_INFO, np.int32)
+        pad = lambda x, n, dt: x if n else np.zeros(1, dt)
+        ret = ext._check(ext._L.pgorb_optimize_sim3(
+            ext._h, _p(pad(a["k1"], n1, KEYPOINT_DTYPE)), n1, _p(a["P1"]), _p(pad(a["s1"], n1, np.int32)), _p(pad(a["k2"], n2, KEYPOINT_DTYPE)), n2,
+            _p(a["P2"]), _p(pad(a["s2"], n2, np.int32)), _p(pad(a["m"], n1, np.int32)), None if a["nm"] is None else _p(pad(a["nm"], n1, np.int32)),
+            t.n, _p(t.points), _p(t.bad), _p(a["e"]), float(np.float32(th2)), int(bool(bFixScale)), _p(eo), _p(mo), _p(c12), _p(c21), _p(sp), _p(info)))
+        return dict(ret=ret, estimate=eo, matches12_out=mo[:n1].copy(), chi2_12=c12[:n1].copy(), chi2_21=c21[:n1].copy(), scw_pose=sp,
+                    status=int(info[0]), correspondences=int(info[1]), nbad=int(info[2]), iterations=[int(info[3]), int(info[5])],
+                    trials=[int(info[4]), int(info[6])], more_iterations=int(info[7]))
+
+    @staticmethod
+    def OptimizeSim3_batch_device(ext, d_kps, d_n, cap_per_frame, d_pair_kf1, d_pair_kf2, d_pose, d_kf_point, d_matches12, npoints, d_points,
+                                  d_point_bad, d_estimate, th2=10.0, bFixScale=False, d_new_matches12=None, stream=None):
+        """pgorb_optimize_sim3_batch_device over resident torch tensors: pair p refines key frames d_pair_kf1[p] and d_pair_kf2[p]
+        from d_estimate[p] (the bytes of SIM3_ESTIMATE_DTYPE per pair: Sim3Solver.iterate_batch_device's `found`); d_matches12 and
+        d_new_matches12 (or None) are [npairs][cap].  th2, the sizes and the tensors' element types are checked here; the arrays'
+        contents are not read: the batched form counts a bad index as no correspondence.  Returns a dict of freshly allocated
+        tensors: estimate, scw_pose (bytes of their dtypes per pair), matches12_out, chi2_12, chi2_21 [npairs][cap],
+        info [npairs][OS3_INFO], nin [npairs]."""
+        import torch
+        name = "Optimizer.OptimizeSim3_batch_device"
+        if not (float(np.float32(th2)) > 0.0 and np.isfinite(np.float32(th2))):
+            raise ValueError("%s: th2 is not positive" % name)
+        for nm, t_ in (("d_pair_kf1", d_pair_kf1), ("d_pair_kf2", d_pair_kf2), ("d_matches12", d_matches12), ("d_n", d_n), ("d_kf_point", d_kf_point),
+                       ("d_new_matches12", d_new_matches12)):
+            if t_ is not None and t_.dtype != torch.int32:
+                raise ValueError("%s: %s must be an int32 tensor (the pair count and the row lengths are taken from element counts)" % (name, nm))
+        npairs, cap = int(d_pair_kf1.numel()), int(cap_per_frame)
+        if cap < 1 or cap > Sim3Solver.MAX_N:
+            raise ValueError("%s: cap_per_frame outside [1, %d]" % (name, Sim3Solver.MAX_N))
+        if int(d_pair_kf2.numel()) != npairs or int(npoints) < 0:
+            raise ValueError("%s: the pair lists differ in length or npoints is negative" % name)
+        if d_matches12.numel() != npairs * cap or (d_new_matches12 is not None and d_new_matches12.numel() != npairs * cap):
+            raise ValueError("%s: d_matches12 and d_new_matches12 must be [npairs][cap]" % name)
+        if d_estimate.numel() * d_estimate.element_size() != npairs * SIM3_ESTIMATE_DTYPE.itemsize:
+            raise ValueError("%s: d_estimate must hold one estimate per pair" % name)
+        nframes = int(d_n.numel())
+        if d_kf_point.numel() != nframes * cap or d_kps.numel() * d_kps.element_size() != nframes * cap * KEYPOINT_DTYPE.itemsize or \
+                d_pose.numel() * d_pose.element_size() != nframes * KF_POSE_DTYPE.itemsize:
+            raise ValueError("%s: d_kps, d_kf_point and d_pose must hold one row per frame of d_n" % name)
+        if d_points.numel() * d_points.element_size() < int(npoints) * MAP_POINT_DTYPE.itemsize or \
+                (d_point_bad is not None and d_point_bad.numel() * d_point_bad.element_size() < int(npoints)):
+            raise ValueError("%s: the table is shorter than npoints" % name)
+        L, h = ext._L, ext._h
+        dev = d_matches12.device
+        e = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
+        out = dict(estimate=e((npairs, SIM3_ESTIMATE_DTYPE.itemsize), torch.uint8), scw_pose=e((npairs, KF_POSE_DTYPE.itemsize), torch.uint8),
+                   matches12_out=e((npairs, cap), torch.int32), chi2_12=e((npairs, cap), torch.float32), chi2_21=e((npairs, cap), torch.float32),
+                   info=e((npairs, OS3_INFO), torch.int32), nin=e((npairs,), torch.int32))
+        q = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        s = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        ext._check(L.pgorb_optimize_sim3_batch_device(
+            h, q(d_kps), q(d_n), cap, q(d_pair_kf1), q(d_pair_kf2), npairs, q(d_pose), q(d_kf_point), q(d_matches12), q(d_new_matches12),
+            int(npoints), q(d_points), q(d_point_bad), q(d_estimate), float(np.float32(th2)), int(bool(bFixScale)), q(out["estimate"]),
+            q(out["matches12_out"]), q(out["chi2_12"]), q(out["chi2_21"]), q(out["scw_pose"]), q(out["info"]), q(out["nin"]), C.c_void_p(s)))
+        return out
 
 
 class Sim3Solver:

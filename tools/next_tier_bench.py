@@ -52,7 +52,13 @@ next to each, the oracle's CPU time for the same work (1 thread, a few frames, s
                run to ITS end, which is the stop rule's.  No CPU figure exists to set a target against.  --sim3-only runs these
                rows alone
 
-usage: python tools/next_tier_bench.py [--batch 128] [--out profiles/r02_next_tier.txt] [--refresh-only | --place-only | --loop-only | --track-only | --pose-only | --sim3-only]"""
+  optsim3      Optimizer::OptimizeSim3 (Optimizer.cc:1046-1241) on the device (pgorb_optimize_sim3, csrc/optimize_sim3.hip): one loop
+               candidate through the single call (wall clock, staging included) and 16 candidates in one batched resident call
+               (HIP events), each 150 correspondences (10 % gross outliers, 0.5 pixel noise); beside them the wall clock of the
+               sequential Python reference of the tests (tests/optsim3_reference.py, OUR restatement on one core, NOT g2o).  No
+               g2o build exists here, so no CPU counterpart exists and no target is set.  --optsim3-only runs these rows alone
+
+usage: python tools/next_tier_bench.py [--batch 128] [--out profiles/r02_next_tier.txt] [--refresh-only | --place-only | --loop-only | --track-only | --pose-only | --sim3-only | --optsim3-only]"""
 import argparse, ctypes as C, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -73,6 +79,7 @@ ap.add_argument("--loop-only", action="store_true", help="loop closing's four ma
 ap.add_argument("--track-only", action="store_true", help="the tracking thread's SearchLocalPoints rows alone (no ride, no vocabulary)")
 ap.add_argument("--pose-only", action="store_true", help="the pose-optimisation rows alone (no ride, no vocabulary)")
 ap.add_argument("--sim3-only", action="store_true", help="the Sim3Solver rows alone (no ride, no vocabulary)")
+ap.add_argument("--optsim3-only", action="store_true", help="the OptimizeSim3 rows alone (no ride, no vocabulary)")
 a = ap.parse_args()
 w, h, nf, B = 1920, 1080, a.features, a.batch
 
@@ -437,6 +444,59 @@ def sim3_lines(npairs=16, ngood=105, nout=45):
                 npairs, N, its.mean()), t, t / npairs, t_ref)]
 
 
+def optsim3_lines(npairs=16, ncorr=150, nout=15):
+    """OptimizeSim3: the single call and the batched resident call, beside the Python reference of the tests."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import optsim3_cases as OC
+    ext = pg.ORBextractor(2000, 1.2, 8, 20, 7, max_width=640, max_height=480)
+    cs = [OC.scene("bench%d" % j, 4000 + j, ncorr, nout, s=1.0 + 0.05 * j, noise=0.5, octaves="mixed") for j in range(npairs)]
+    t0 = time.perf_counter(); ref = OC.run_reference(cs[0]); t_ref = (time.perf_counter() - t0) * 1e3
+    ts = []
+    for j in range(10):
+        t0 = time.perf_counter(); got = OC.run_gpu(cs[0], ext); ts.append((time.perf_counter() - t0) * 1e3)
+    assert got["ret"] == ref["ret"] and np.array_equal(got["matches12_out"], ref["matches12_out"])
+    t1 = float(np.median(ts[1:]))
+    res = OC.run_gpu_batch(cs, ext)
+    # the batched call alone, on resident arrays
+    G = lambda x: torch.from_numpy(np.ascontiguousarray(x)).cuda()
+    nfr, cap = 2 * npairs, max(max(c.n1, c.n2) for c in cs)
+    kp = np.zeros((nfr, cap), pg.KEYPOINT_DTYPE); slots = np.full((nfr, cap), -1, np.int32); m12 = np.full((npairs, cap), -1, np.int32)
+    poses = np.zeros(nfr, pg.KF_POSE_DTYPE); ests = np.zeros(npairs, pg.SIM3_ESTIMATE_DTYPE); ns = np.zeros(nfr, np.int32)
+    base, tabs = 0, []
+    for j, c in enumerate(cs):
+        kp[2 * j, :c.n1] = OC.keypoints(c.keys1, c.octaves1); kp[2 * j + 1, :c.n2] = OC.keypoints(c.keys2, c.octaves2)
+        slots[2 * j, :c.n1] = np.where(c.kf_point1 >= 0, c.kf_point1 + base, -1); slots[2 * j + 1, :c.n2] = np.where(c.kf_point2 >= 0, c.kf_point2 + base, -1)
+        m12[j, :c.n1] = c.matches12; poses[2 * j], poses[2 * j + 1] = OC.pose_record(c.pose1), OC.pose_record(c.pose2)
+        ests[j] = OC.estimate_record(c.estimate)[0]; ns[2 * j], ns[2 * j + 1] = c.n1, c.n2
+        tabs.append(OC.table(c.points)[:len(c.points)]); base += len(c.points)
+    tab = np.concatenate(tabs)
+    dK, dN, dP, dS, dM = G(kp.view(np.uint8).reshape(nfr, cap, 28)), G(ns), G(poses.view(np.uint8).reshape(nfr, -1)), G(slots), G(m12)
+    dT, dE = G(tab.view(np.uint8).reshape(len(tab), 32)), G(ests.view(np.uint8).reshape(npairs, -1))
+    d1, d2 = G(np.arange(0, nfr, 2, dtype=np.int32)), G(np.arange(1, nfr, 2, dtype=np.int32))
+    out_t = None
+    def batched():
+        nonlocal out_t
+        out_t = pg.Optimizer.OptimizeSim3_batch_device(ext, dK, dN, cap, d1, d2, dP, dS, dM, len(tab), dT, None, dE, 10.0, False)
+    t = timed(batched)
+    nin = out_t["nin"].cpu().numpy()
+    assert [int(x) for x in nin] == [r["ret"] for r in res] and int(nin[0]) == ref["ret"]
+    info = out_t["info"].cpu().numpy()
+    return ["# Optimizer::OptimizeSim3 on the device; single call = wall clock with staging, median of 9; batched resident call = HIP events, median of 9 (its",
+            "# seven output arrays are allocated inside the timed call); reference = tests/optsim3_reference.py for ONE candidate, wall clock: OUR restatement",
+            "# in numpy on one core, NOT g2o.  No g2o build exists here to time, so no CPU counterpart exists; no target is set.",
+            "%-118s %10s %16s %16s" % ("call", "GPU ms", "GPU ms/candidate", "reference ms (1)"),
+            "%-118s %10.3f %16.4f %16.1f" % ("optimize_sim3 (single call): %d correspondences, %d removed, %d + %d iterations, %d + %d trials, %d inliers" % (
+                got["ncorr"], got["nbad"], got["iterations"][0], got["iterations"][1], got["trials"][0], got["trials"][1], got["ret"]), t1, t1, t_ref),
+            "%-118s %10.3f %16.4f %16.1f" % ("optimize_sim3_batch_device: %d candidates x %d correspondences (%.1f iterations, %.1f trials a candidate)" % (
+                npairs, ncorr, (info[:, 3] + info[:, 5]).mean(), (info[:, 4] + info[:, 6]).mean()), t, t / npairs, t_ref)]
+
+
+if a.optsim3_only:
+    lines = ["# python tools/next_tier_bench.py --optsim3-only   (MI355X)"] + optsim3_lines()
+    print("\n".join(lines))
+    if a.out:
+        open(a.out, "w").write("\n".join(lines) + "\n")
+    sys.exit(0)
 if a.sim3_only:
     lines = ["# python tools/next_tier_bench.py --sim3-only   (MI355X)"] + sim3_lines()
     print("\n".join(lines))

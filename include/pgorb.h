@@ -938,6 +938,86 @@ int  pgorb_optimize_sim3_batch_device(pgorb_ctx* ctx, const pgorb_keypoint* d_kp
         pgorb_sim3_estimate* d_estimate_out, int32_t* d_matches12_out, float* d_chi2_12, float* d_chi2_21,
         pgorb_kf_pose* d_scw_pose, int32_t* d_info, int32_t* d_nin, void* hip_stream);
 
+/*   pgorb_local_bundle_adjustment   Optimizer::LocalBundleAdjustment(pKF, pbStopFlag, pMap) (src/Optimizer.cc:453-778) with the g2o
+ *       path under it (VertexSE3Expmap, VertexSBAPointXYZ, EdgeSE3ProjectXYZ with its ANALYTIC Jacobian, RobustKernelHuber,
+ *       BlockSolver_6_3 with the Schur complement over the marginalised points, OptimizationAlgorithmLevenberg), monocular (mvuRight
+ *       < 0), in double: the step of LocalMapping::Run after SearchInNeighbors.  It is this project's READING of g2o and Eigen
+ *       (DESIGN.md sections 4 and 5 list the ten readings), anchored by the CPU tests of tests/test_local_bundle_adjustment.py and
+ *       not pinned to a g2o build.
+ * Inputs.  Key frames as for pgorb_refresh_map_points: nkf of them, each its undistorted keypoints (pt and octave are read), n[f], its
+ * pgorb_kf_pose (Tcw, fx, fy, cx, cy are read), kf_bad[f] = pKF->isBad() (NULL = none), its slots kf_point[f][i] = the table index of
+ * GetMapPoint(i) or -1, and kf_fixed_id0[f] != 0 for the key frame with mnId == 0 (setFixed(pKFi->mnId==0), :529; NULL = none).
+ * The window: local_kf[nlocal] = pKF and GetVectorCovisibleKeyFrames() by index, in any order; the covisibility graph stays with the
+ * caller.  Points: the resident table of pgorb_refresh_map_points -- pos (in and out), point_bad, and the observations as CSR of
+ * (obs_frame, obs_idx).  Nothing else is passed; the library derives, as flags and so without an order:
+ *   local key frames   the named key frames that are not bad.  (The reference keeps pKF itself in lLocalKeyFrames even when it is
+ *                  bad, :458; here every named bad key frame is dropped, pKF included: do not adjust around a bad key frame.)
+ *   local points   not bad and in a slot of a local key frame that is not bad (:470-486)              -> is_local [npoints]
+ *   fixed cameras  not bad, observing a local point, not named by the window (:488-504)               -> role [nkf]: PGORB_LBA_ROLE_*
+ *   edges          every CSR observation of a local point in a key frame that is not bad (:585-589)
+ * rounds: 2 is the normal path; 1 is bDoMore == false (:662-709): no classification between the rounds and no second optimize.
+ * The asynchronous pbStopFlag INSIDE g2o's loop is not reproducible and is not offered.
+ * Outputs.  The return value is the number of erased observations (vToErase.size()).  pose_out [nkf]: for every local key frame a
+ * complete pgorb_kf_pose (Converter::toCvMat(SE3Quat) to float, then SetPose's Ow = -Rcw.t()*tcw), the input's camera kept; the
+ * single call copies the input for the others, the batched form leaves them alone.  points[].pos of the local points are
+ * overwritten (Converter::toCvMat(Vector3d) to float); normal and distances keep their bytes -- pMP->UpdateNormalAndDepth() (:776)
+ * is pgorb_refresh_map_points(_batch_device) with what = PGORB_MP_NORMAL_DEPTH over the local points, on the same arrays.
+ * Per observation, aligned with the CSR: erase (membership of vToErase, :715-728), chi2 (float; what e->chi2() read at the last
+ * classification, stale where the reference's is: readings 6 and 7) and level (1 = set aside after the first optimize, :680-683);
+ * all 0 where the observation is no edge.  info (may be NULL) = PGORB_LBA_INFO int32: status bits, edges, local points, local key
+ * frames, fixed key frames, iterations and Levenberg trials of the first optimize, the same of the second, edges set to level 1.
+ * PGORB_LBA_NOTHING: no edge (no local point, or none observed in a live key frame) -- nothing is optimised, returns 0, pose_out of
+ * the local key frames = the input byte for byte, the points keep their bytes.
+ * PGORB_LBA_NONFINITE: the active chi2 a Levenberg iteration starts from, or an edge's chi2 at a classification, is not finite --
+ * returns 0, outputs as for PGORB_LBA_NOTHING, erase / chi2 / level 0, the counters of info 0.
+ * Determinism: no floating-point atomics; every sum runs in one documented order (csrc/local_ba.hip: a point's edges in CSR order,
+ * a camera's in table-then-CSR order, chi2 and computeScale in one fixed tree); a window's result depends on its inputs alone, not
+ * on its place in a batch, the stream or a repeat; the single call equals the batched one byte for byte.
+ * PGORB_E_ARG (single call, on the host before anything else): a negative count, a NULL array that is read or written, rounds
+ * outside 1..2, a local key frame, slot or observation out of range, obs_start not rising from 0, a key frame twice in one list, the
+ * octave of an observed keypoint outside the context's levels, a value of Tcw, fx, fy, cx, cy or a point that is not finite, fx or
+ * fy zero.  PGORB_E_LIMIT: more than 16000 keypoints in a key frame, or a window past a capacity below; the single call counts them
+ * on the host.  The reduced camera system ((6 * local)^2 doubles a window) and the records (320 bytes an observation, 244 a point)
+ * live in the context's scratch arena.  THE RECORDS ARE ADDRESSED BY CSR POSITION AND TABLE INDEX, so the arena, the clearing of
+ * the flags and the zeroing of erase / chi2 / level scale with the WHOLE table passed (320 * nobs + 244 * npoints bytes, plus
+ * 6 * nwin * nobs bytes of outputs), not with what the windows touch: pass the part of the map the windows can reach.
+ *   Batched: the key frames are nframes frames of one batch (d_kps [nframes][cap_per_frame], d_n, d_pose, d_kf_bad, d_kf_fixed_id0
+ *       [nframes], d_kf_point [nframes][cap_per_frame]); window w names d_win_kf[d_win_start[w] .. d_win_start[w + 1]), nwin_kf = the
+ *       length of d_win_kf.  d_erase, d_chi2, d_level are [nwin][nobs], d_is_local [nwin][npoints], d_role [nwin][nframes], d_info
+ *       [nwin][PGORB_LBA_INFO], d_nerased [nwin] (may be NULL); d_pose_out [nframes] is written for local key frames only and must
+ *       not be d_pose.  THE RULE: points are updated in place, so two windows of one call must not share a local point (a key frame
+ *       may be fixed in one and local in another: the input poses are read).  Nothing checks it; windows that break it stay inside
+ *       the arrays and return garbage.  This form checks pointers, rounds and cap_per_frame only: an index out of range is no slot,
+ *       no observation or no key frame, and a window past a capacity ends with PGORB_LBA_LIMIT in its status, nothing optimised,
+ *       its points untouched.  Two launches, one workgroup per window. */
+#define PGORB_LBA_NOTHING        1
+#define PGORB_LBA_NONFINITE      2
+#define PGORB_LBA_LIMIT          4
+#define PGORB_LBA_INFO           10
+#define PGORB_LBA_ROLE_NONE      0
+#define PGORB_LBA_ROLE_LOCAL     1
+#define PGORB_LBA_ROLE_FIXED     2
+#define PGORB_LBA_MAX_LOCAL_KF   64
+#define PGORB_LBA_MAX_FIXED_KF   256
+#define PGORB_LBA_MAX_POINTS     8192
+#define PGORB_LBA_MAX_EDGES      65536
+int  pgorb_local_bundle_adjustment(pgorb_ctx* ctx,
+        int nkf, const pgorb_keypoint* const* kps, const int32_t* n /*[nkf]*/, const pgorb_kf_pose* pose /*[nkf]*/,
+        const uint8_t* kf_bad /*[nkf] or NULL*/, const int32_t* const* kf_point /*[nkf][n[f]]*/, const uint8_t* kf_fixed_id0 /*[nkf] or NULL*/,
+        int nlocal, const int32_t* local_kf /*[nlocal]*/,
+        int npoints, pgorb_map_point* points /*in and out: pos*/, const uint8_t* point_bad /*[npoints] or NULL*/,
+        const int32_t* obs_start /*[npoints + 1]*/, const int32_t* obs_frame, const int32_t* obs_idx, int rounds,
+        pgorb_kf_pose* pose_out /*[nkf]*/, uint8_t* erase, float* chi2, uint8_t* level /*[nobs]*/, uint8_t* is_local /*[npoints]*/,
+        uint8_t* role /*[nkf]*/, int32_t* info);
+int  pgorb_local_bundle_adjustment_batch_device(pgorb_ctx* ctx,
+        const pgorb_keypoint* d_kps, const int32_t* d_n, int nframes, int cap_per_frame, const pgorb_kf_pose* d_pose,
+        const uint8_t* d_kf_bad, const int32_t* d_kf_point, const uint8_t* d_kf_fixed_id0,
+        const int32_t* d_win_start, const int32_t* d_win_kf, int nwin, int nwin_kf,
+        int npoints, pgorb_map_point* d_points, const uint8_t* d_point_bad, const int32_t* d_obs_start, const int32_t* d_obs_frame,
+        const int32_t* d_obs_idx, int nobs, int rounds,
+        pgorb_kf_pose* d_pose_out, uint8_t* d_erase, float* d_chi2, uint8_t* d_level, uint8_t* d_is_local, uint8_t* d_role,
+        int32_t* d_info, int32_t* d_nerased, void* hip_stream);
+
 /* ---- Map-point refresh: the distinctive descriptor and the normal / depth range of many points --------------------------
  *   pgorb_refresh_map_points   for every selected point what MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:259-324)
  *       followed by MapPoint::UpdateNormalAndDepth (:347-388) would store, exactly.  The reference runs the pair once per point at

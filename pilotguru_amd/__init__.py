@@ -10,5 +10,7 @@ from .orb import MAP_POINT_DTYPE, MapPointTable, SIM3_DTYPE, sim3_pose, sim3_rec
 from .orb import MP_BOTH, MP_DESCRIPTOR, MP_LIMIT, MP_MAX_OBS, MP_NORMAL_DEPTH  # noqa: F401
 from .orb import PO_FEW, PO_INFO, PO_NONFINITE, Optimizer  # noqa: F401
 from .orb import OS3_FEW, OS3_INFO, OS3_NONFINITE  # noqa: F401
+from .orb import (LBA_INFO, LBA_LIMIT, LBA_MAX_EDGES, LBA_MAX_FIXED_KF, LBA_MAX_LOCAL_KF, LBA_MAX_POINTS, LBA_NONFINITE,  # noqa: F401
+                  LBA_NOTHING, LBA_ROLE_FIXED, LBA_ROLE_LOCAL, LBA_ROLE_NONE)
 from .orb import S3_FEW, S3_FOUND, S3_INFO, S3_NO_MORE, SIM3_ESTIMATE_DTYPE, SIM3_MAX_ITERATIONS, SIM3_PARAMS_DTYPE, Sim3Solver  # noqa: F401
 from .place import KeyFrameDatabase  # noqa: F401

@@ -51,6 +51,7 @@ SYMBOLS = (
     "pgorb_slots_from_assignment", "pgorb_slots_from_assignment_batch_device",
     "pgorb_sim3_solver", "pgorb_sim3_solver_batch_device", "pgorb_sim3_max_iterations",
     "pgorb_optimize_sim3", "pgorb_optimize_sim3_batch_device",
+    "pgorb_local_bundle_adjustment", "pgorb_local_bundle_adjustment_batch_device",
     "pgorb_undistort_keypoints", "pgorb_undistort_keypoints_batch_device", "pgorb_image_bounds",
     "pgorb_host_alloc", "pgorb_host_free", "pgorb_host_register", "pgorb_host_unregister", "pgorb_stream_create", "pgorb_stream_create_ingest", "pgorb_stream_create_device", "pgorb_stream_submit_device", "pgorb_stream_wait_device", "pgorb_stream_lanes", "pgorb_stream_destroy", "pgorb_stream_input", "pgorb_stream_reset", "pgorb_stream_submit",
     "pgorb_stream_wait", "pgorb_stream_frontend", "pgorb_stream_frontend_results", "pgorb_set_option", "pgorb_get_option", "pgorb_matcher_is_popcount",
@@ -206,6 +207,13 @@ def lib():
     #  fix_scale, estimate_out, matches12_out, chi2_12, chi2_21, scw_pose, info, nin, stream)
     L.pgorb_optimize_sim3_batch_device.argtypes = [vp, vp, vp, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp, C.c_int, vp, vp, vp, C.c_float, C.c_int] + \
         [vp] * 8
+    # (ctx, nkf, kps[], n, pose, kf_bad, kf_point[], kf_fixed_id0, nlocal, local_kf, npoints, points, point_bad, obs_start, obs_frame,
+    #  obs_idx, rounds, pose_out, erase, chi2, level, is_local, role, info)
+    L.pgorb_local_bundle_adjustment.argtypes = [vp, C.c_int] + [vp] * 6 + [C.c_int, vp, C.c_int] + [vp] * 5 + [C.c_int] + [vp] * 7
+    # (ctx, kps, n, nframes, cap, pose, kf_bad, kf_point, kf_fixed_id0, win_start, win_kf, nwin, nwin_kf, npoints, points, point_bad,
+    #  obs_start, obs_frame, obs_idx, nobs, rounds, pose_out, erase, chi2, level, is_local, role, info, nerased, stream)
+    L.pgorb_local_bundle_adjustment_batch_device.argtypes = [vp, vp, vp, C.c_int, C.c_int] + [vp] * 6 + [C.c_int, C.c_int, C.c_int] + [vp] * 5 + \
+        [C.c_int, C.c_int] + [vp] * 9
     L.pgorb_log_f.argtypes = [C.c_float]
     L.pgorb_log_scale_factor.argtypes = [vp]
     L.pgorb_predict_scale.argtypes = [vp, C.c_float, C.c_float]

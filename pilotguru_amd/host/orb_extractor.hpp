@@ -361,9 +361,91 @@ struct OptimizeSim3Result {
     int32_t info[PGORB_OS3_INFO] = {};     // status, nCorrespondences, nBad, iterations and trials of both optimize calls, nMoreIterations
 };
 
+// What Optimizer::LocalBundleAdjustment returns beside the number of erased observations (include/pgorb.h).
+struct LocalBundleAdjustmentResult {
+    int erased = 0;                        // vToErase.size(), the library's return value
+    std::vector<pgorb_kf_pose> poses;      // per key frame: the local ones adjusted (complete records), the others as given
+    std::vector<uint8_t> erase, level;     // per observation, aligned with the lists
+    std::vector<float> chi2;
+    std::vector<std::pair<int32_t, int32_t>> toErase;   // vToErase as (key frame, point), in list order
+    std::vector<uint8_t> isLocal, role;    // per point; per key frame: PGORB_LBA_ROLE_*
+    int32_t info[PGORB_LBA_INFO] = {};     // status, edges, local points, local and fixed key frames, iterations and trials of both optimize calls, level-1 edges
+};
+
 class Optimizer {
  public:
     explicit Optimizer(pgorb_ctx* ctx) : ctx_(ctx) {}
+    // Optimizer::LocalBundleAdjustment(pKF, pbStopFlag, pMap) (Optimizer.cc:453-778), monocular, on the GPU.  keyFrames: frame
+    // (mvKeysUn: pt and octave) and pose are read; kfBad[f] = isBad(), kfFixedId0[f] = (mnId == 0) (empty = none); kfPoint[f][i] = the
+    // table index of GetMapPoint(i) or -1; localKf: pKF and its covisible key frames as positions in keyFrames.  points (pos is read
+    // and, for the local points, replaced in place), pointBad (empty = none) and obs (obsStart / obsFrame / obsIdx) are the table.
+    // rounds: 2, or 1 for bDoMore == false.  Everything pgorb_local_bundle_adjustment refuses as a bad argument is a
+    // std::invalid_argument here, before the library is called; a window past a capacity is the library's error (std::runtime_error).
+    LocalBundleAdjustmentResult LocalBundleAdjustment(const std::vector<const KeyFrame*>& keyFrames, const std::vector<uint8_t>& kfBad,
+                                                      const std::vector<uint8_t>& kfFixedId0, const std::vector<std::vector<int32_t>>& kfPoint,
+                                                      const std::vector<int32_t>& localKf, std::vector<pgorb_map_point>& points,
+                                                      const std::vector<uint8_t>& pointBad, const MapPointObservations& obs, int rounds = 2)
+    {
+        const auto fail = [](const char* m) { throw std::invalid_argument(std::string("LocalBundleAdjustment: ") + m); };
+        const size_t nkf = keyFrames.size(), np = points.size();
+        const int levels = pgorb_levels(ctx_);
+        if (rounds < 1 || rounds > 2) fail("rounds is neither 1 nor 2");
+        if (kfPoint.size() != nkf) fail("kfPoint is not one list per key frame");
+        if ((!kfBad.empty() && kfBad.size() != nkf) || (!kfFixedId0.empty() && kfFixedId0.size() != nkf)) fail("kfBad or kfFixedId0 is neither empty nor one entry per key frame");
+        if (!pointBad.empty() && pointBad.size() != np) fail("pointBad is neither empty nor one entry per point");
+        std::vector<const pgorb_keypoint*> kps(nkf + 1);
+        std::vector<const int32_t*> slots(nkf + 1);
+        std::vector<int32_t> n(nkf + 1);
+        std::vector<pgorb_kf_pose> pose(nkf + 1);
+        for (size_t f = 0; f < nkf; f++) {
+            if (!keyFrames[f]) fail("a key frame is NULL");
+            const Frame& F = keyFrames[f]->frame;
+            const pgorb_kf_pose& P = keyFrames[f]->pose;
+            if (kfPoint[f].size() != (size_t)F.N()) fail("a key frame's slots are not N entries long");
+            for (int k = 0; k < 12; k++)
+                if (!std::isfinite(P.Tcw[k])) fail("a pose is not finite");
+            if (!std::isfinite(P.fx) || !std::isfinite(P.fy) || !std::isfinite(P.cx) || !std::isfinite(P.cy)) fail("a camera is not finite");
+            if (P.fx == 0.0f || P.fy == 0.0f) fail("fx or fy is zero");
+            for (int s : kfPoint[f]) if (s < -1 || s >= (int)np) fail("a slot names a point outside the table");
+            if (F.N() > 16000) fail("more than 16000 keypoints in a key frame");
+            kps[f] = F.mvKeysUndistorted.data(); slots[f] = kfPoint[f].data(); n[f] = F.N(); pose[f] = P;
+        }
+        for (int f : localKf) if (f < 0 || f >= (int)nkf) fail("a local key frame is out of range");
+        for (const pgorb_map_point& p : points)
+            if (!std::isfinite(p.pos[0]) || !std::isfinite(p.pos[1]) || !std::isfinite(p.pos[2])) fail("a point is not finite");
+        if (obs.obsStart.size() != np + 1 || obs.obsStart[0] != 0) fail("obsStart is not npoints + 1 entries rising from 0");
+        for (size_t p = 0; p < np; p++) if (obs.obsStart[p + 1] < obs.obsStart[p]) fail("obsStart decreases");
+        const size_t nobs = (size_t)obs.obsStart[np];
+        if (obs.obsFrame.size() < nobs || obs.obsIdx.size() < nobs) fail("obsFrame or obsIdx is shorter than obsStart says");
+        std::vector<int32_t> seen(nkf + 1, -1);
+        for (size_t p = 0; p < np; p++)
+            for (int k = obs.obsStart[p]; k < obs.obsStart[p + 1]; k++) {
+                const int f = obs.obsFrame[k], i = obs.obsIdx[k];
+                if (f < 0 || f >= (int)nkf || i < 0 || i >= n[f]) fail("an observation names a key frame or keypoint out of range");
+                if (seen[f] == (int)p) fail("a list names a key frame twice");
+                seen[f] = (int)p;
+                const int o = kps[f][i].octave;
+                if (levels > 0 && (o < 0 || o >= levels)) fail("an octave is outside the context's levels");
+            }
+        LocalBundleAdjustmentResult r;
+        r.poses.resize(nkf + 1);
+        r.erase.assign(nobs + 1, 0); r.level.assign(nobs + 1, 0); r.chi2.assign(nobs + 1, 0.0f);
+        r.isLocal.assign(np + 1, 0); r.role.assign(nkf + 1, 0);
+        std::vector<pgorb_map_point> none(1);
+        const int rc = pgorb_local_bundle_adjustment(ctx_, (int)nkf, kps.data(), n.data(), pose.data(), kfBad.empty() ? nullptr : kfBad.data(),
+                                                     slots.data(), kfFixedId0.empty() ? nullptr : kfFixedId0.data(), (int)localKf.size(),
+                                                     localKf.data(), (int)np, np ? points.data() : none.data(),
+                                                     pointBad.empty() ? nullptr : pointBad.data(), obs.obsStart.data(), obs.obsFrame.data(),
+                                                     obs.obsIdx.data(), rounds, r.poses.data(), r.erase.data(), r.chi2.data(), r.level.data(),
+                                                     r.isLocal.data(), r.role.data(), r.info);
+        if (rc < 0) throw std::runtime_error(pgorb_last_error(ctx_));
+        r.poses.resize(nkf); r.erase.resize(nobs); r.level.resize(nobs); r.chi2.resize(nobs); r.isLocal.resize(np); r.role.resize(nkf);
+        for (size_t p = 0; p < np; p++)
+            for (int k = obs.obsStart[p]; k < obs.obsStart[p + 1]; k++)
+                if (r.erase[k]) r.toErase.emplace_back(obs.obsFrame[k], (int32_t)p);
+        r.erased = rc;
+        return r;
+    }
     // Optimizer::OptimizeSim3(pKF1, pKF2, vpMatches1, g2oS12, th2, bFixScale) (Optimizer.cc:1046-1241) on the GPU.  The key frames, the
     // slots and the table as for Sim3Solver; matches12[i1]: the KF2 keypoint or -1 (the solver's matches12Out); newMatches12 (empty =
     // none): what SearchBySim3 wrote, replacing an entry where it is >= 0; estimate: the solver's `found`.

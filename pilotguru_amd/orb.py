@@ -842,6 +842,10 @@ def sim3_pose(Scw, fx, fy, cx, cy):
 PO_FEW, PO_NONFINITE, PO_INFO = 1, 2, 8
 # pgorb_optimize_sim3: the same
 OS3_FEW, OS3_NONFINITE, OS3_INFO = 1, 2, 8
+# pgorb_local_bundle_adjustment: status bits, the info record, the roles and the capacities of one window
+LBA_NOTHING, LBA_NONFINITE, LBA_LIMIT, LBA_INFO = 1, 2, 4, 10
+LBA_ROLE_NONE, LBA_ROLE_LOCAL, LBA_ROLE_FIXED = 0, 1, 2
+LBA_MAX_LOCAL_KF, LBA_MAX_FIXED_KF, LBA_MAX_POINTS, LBA_MAX_EDGES = 64, 256, 8192, 65536
 
 
 class Optimizer:
@@ -983,6 +987,140 @@ class Optimizer:
             h, q(d_kps), q(d_n), cap, q(d_pair_kf1), q(d_pair_kf2), npairs, q(d_pose), q(d_kf_point), q(d_matches12), q(d_new_matches12),
             int(npoints), q(d_points), q(d_point_bad), q(d_estimate), float(np.float32(th2)), int(bool(bFixScale)), q(out["estimate"]),
             q(out["matches12_out"]), q(out["chi2_12"]), q(out["chi2_21"]), q(out["scw_pose"]), q(out["info"]), q(out["nin"]), C.c_void_p(s)))
+        return out
+
+    @staticmethod
+    def LocalBundleAdjustment(key_frames, poses, kf_point, local_kf, points, obs_start, obs_frame, obs_idx, point_bad=None, kf_bad=None,
+                              kf_fixed_id0=None, rounds=2, ext=None):
+        """Optimizer::LocalBundleAdjustment (thirdparty/orb-slam2/src/Optimizer.cc:453-778, monocular) on the GPU.  key_frames:
+        Frame-like objects (ext, N, mvKeysUndistorted: pt and octave are read); poses[f]: KF_POSE_DTYPE (Tcw and the camera are
+        read); kf_point[f][i] = the table index of GetMapPoint(i) or -1; kf_bad[f] = isBad(), kf_fixed_id0[f] = (mnId == 0) (None =
+        none); local_kf: pKF and its covisible key frames as positions in key_frames, in any order.  points (MAP_POINT_DTYPE; pos is
+        read), point_bad, and the observations as CSR of (obs_frame, obs_idx) as for RefreshMapPoints.  rounds: 2, or 1 for
+        bDoMore == false.  Every input pgorb_local_bundle_adjustment refuses is a ValueError here, before the library is called;
+        a window past a capacity (LBA_MAX_*) raises PgorbError.  Returns a dict: ret (the erased observations), poses (a copy with
+        the local key frames replaced), points (a copy with the local points' pos replaced), erase / chi2 / level per observation,
+        to_erase = vToErase as (frame, point) pairs in CSR order, is_local, role, status, edges, local_points, local_kfs, fixed_kfs,
+        iterations and trials (of the two optimize calls), level1."""
+        fn = "LocalBundleAdjustment"
+        nkf = len(key_frames)
+        if ext is None:
+            if not nkf:
+                raise ValueError(fn + ": no key frame and no ext")
+            ext = key_frames[0].ext
+        if rounds not in (1, 2):
+            raise ValueError(fn + ": rounds must be 1 or 2")
+        if len(poses) != nkf or len(kf_point) != nkf:
+            raise ValueError(fn + ": key_frames, poses and kf_point differ in length")
+        pts = np.array(np.ascontiguousarray(points, MAP_POINT_DTYPE).reshape(-1))       # a copy: moved in place
+        n = len(pts)
+        if not np.isfinite(pts["pos"]).all():
+            raise ValueError(fn + ": a point is not finite")
+        levels = ext.GetLevels()
+        P = np.zeros(max(nkf, 1), KF_POSE_DTYPE)
+        keep = []
+        kps, slots = [(C.c_void_p * max(nkf, 1))() for _ in range(2)]
+        nk = np.zeros(max(nkf, 1), np.int32)
+        octs = []
+        for f, K in enumerate(key_frames):
+            if int(K.N) < 0:
+                raise ValueError("%s: key frame %d has a negative keypoint count" % (fn, f))
+            kp = _arr(K.mvKeysUndistorted, KEYPOINT_DTYPE, K.N, "key frame %d keypoints" % f)
+            sl = _arr(kf_point[f], np.int32, K.N, "kf_point[%d]" % f)
+            if K.N and (int(sl.min()) < -1 or int(sl.max()) >= n):
+                raise ValueError("%s: a slot's point index is out of range" % fn)
+            kp_buf, sl_buf = (kp, sl) if K.N else (np.zeros(1, KEYPOINT_DTYPE), np.zeros(1, np.int32))
+            keep += [kp_buf, sl_buf]
+            kps[f], slots[f], nk[f] = kp_buf.ctypes.data, sl_buf.ctypes.data, K.N
+            octs.append(kp["octave"])
+            P[f] = np.asarray(poses[f], KF_POSE_DTYPE).reshape(())
+            cam = [float(P[f][k]) for k in ("fx", "fy", "cx", "cy")]
+            if not (np.isfinite(P[f]["Tcw"]).all() and np.isfinite(cam).all()):
+                raise ValueError(fn + ": a pose or a camera is not finite")
+            if cam[0] == 0.0 or cam[1] == 0.0:
+                raise ValueError(fn + ": fx or fy is zero")
+        kb, i0, pb = _mask(kf_bad, nkf, "kf_bad"), _mask(kf_fixed_id0, nkf, "kf_fixed_id0"), _mask(point_bad, n, "point_bad")
+        lk = np.ascontiguousarray(local_kf, np.int32).reshape(-1)
+        if len(lk) and (int(lk.min()) < 0 or int(lk.max()) >= nkf):
+            raise ValueError(fn + ": a local key frame is out of range")
+        st = _arr(obs_start, np.int32, n + 1, "obs_start")
+        of = np.ascontiguousarray(obs_frame, np.int32).reshape(-1)
+        oi = np.ascontiguousarray(obs_idx, np.int32).reshape(-1)
+        if st[0] != 0 or np.any(np.diff(st) < 0) or len(of) < int(st[-1]) or len(oi) < int(st[-1]):
+            raise ValueError(fn + ": obs_start must rise from 0 to at most len(obs_frame), len(obs_idx)")
+        m = int(st[-1])
+        if m and (of[:m].min() < 0 or of[:m].max() >= nkf or oi[:m].min() < 0 or np.any(oi[:m] >= nk[np.clip(of[:m], 0, max(nkf - 1, 0))])):
+            raise ValueError(fn + ": an observation names a key frame or keypoint out of range")
+        owner = np.repeat(np.arange(n, dtype=np.int64), np.diff(st))
+        if len(np.unique(owner * max(nkf, 1) + of[:m])) != m:
+            raise ValueError(fn + ": a list names a key frame twice")
+        for k in range(m):
+            o = int(octs[of[k]][oi[k]])
+            if o < 0 or o >= levels:
+                raise ValueError("%s: an octave is outside the extractor's %d levels" % (fn, levels))
+        if len(of) == 0:
+            of, oi = np.zeros(1, np.int32), np.zeros(1, np.int32)
+        po = np.zeros(max(nkf, 1), KF_POSE_DTYPE)
+        er, lv, chi = np.zeros(max(m, 1), np.uint8), np.zeros(max(m, 1), np.uint8), np.zeros(max(m, 1), np.float32)
+        il, ro, info = np.zeros(max(n, 1), np.uint8), np.zeros(max(nkf, 1), np.uint8), np.zeros(LBA_INFO, np.int32)
+        pts_buf = pts if n else np.zeros(1, MAP_POINT_DTYPE)
+        ret = ext._check(ext._L.pgorb_local_bundle_adjustment(
+            ext._h, nkf, kps, _p(nk), _p(P), _p(kb), slots, _p(i0), len(lk), _p(lk if len(lk) else np.zeros(1, np.int32)), n, _p(pts_buf), _p(pb),
+            _p(st), _p(of), _p(oi), int(rounds), _p(po), _p(er), _p(chi), _p(lv), _p(il), _p(ro), _p(info)))
+        er = er[:m].copy()
+        return dict(ret=ret, poses=po[:nkf].copy(), points=pts, erase=er, chi2=chi[:m].copy(), level=lv[:m].copy(),
+                    to_erase=[(int(of[k]), int(owner[k])) for k in np.flatnonzero(er)], is_local=il[:n].copy(), role=ro[:nkf].copy(),
+                    status=int(info[0]), edges=int(info[1]), local_points=int(info[2]), local_kfs=int(info[3]), fixed_kfs=int(info[4]),
+                    iterations=[int(info[5]), int(info[7])], trials=[int(info[6]), int(info[8])], level1=int(info[9]))
+
+    @staticmethod
+    def LocalBundleAdjustment_batch_device(ext, d_kps, d_n, cap_per_frame, d_pose, d_kf_point, d_win_start, d_win_kf, npoints, d_points,
+                                           d_obs_start, d_obs_frame, d_obs_idx, d_point_bad=None, d_kf_bad=None, d_kf_fixed_id0=None,
+                                           rounds=2, d_pose_out=None, stream=None):
+        """pgorb_local_bundle_adjustment_batch_device over resident torch tensors: window w adjusts the key frames
+        d_win_kf[d_win_start[w] : d_win_start[w + 1]] of one batch and the points they hold, IN PLACE in d_points.  Two windows of one
+        call must not share a local point (include/pgorb.h); nothing checks it.  The sizes and element types are checked here; the
+        contents are not read.  d_pose_out (bytes of KF_POSE_DTYPE per frame; default: a copy of d_pose) is written for the local key
+        frames only.  Returns a dict of tensors: pose_out, erase / chi2 / level [nwin][nobs], is_local [nwin][npoints], role
+        [nwin][nframes], info [nwin][LBA_INFO], nerased [nwin].  The chain into pMP->UpdateNormalAndDepth() is
+        pgorb_refresh_map_points_batch_device on the same d_points with d_pose = pose_out and select = the local points."""
+        import torch
+        name = "Optimizer.LocalBundleAdjustment_batch_device"
+        if rounds not in (1, 2):
+            raise ValueError(name + ": rounds must be 1 or 2")
+        for nm, t_ in (("d_n", d_n), ("d_kf_point", d_kf_point), ("d_win_start", d_win_start), ("d_win_kf", d_win_kf), ("d_obs_start", d_obs_start),
+                       ("d_obs_frame", d_obs_frame), ("d_obs_idx", d_obs_idx)):
+            if t_.dtype != torch.int32:
+                raise ValueError("%s: %s must be an int32 tensor (the counts are taken from element counts)" % (name, nm))
+        nframes, cap, npoints = int(d_n.numel()), int(cap_per_frame), int(npoints)
+        nwin, nwin_kf, nobs = int(d_win_start.numel()) - 1, int(d_win_kf.numel()), int(d_obs_frame.numel())
+        if cap < 1 or cap > Sim3Solver.MAX_N:
+            raise ValueError("%s: cap_per_frame outside [1, %d]" % (name, Sim3Solver.MAX_N))
+        if nwin < 0 or npoints < 0 or int(d_obs_start.numel()) != npoints + 1 or int(d_obs_idx.numel()) != nobs:
+            raise ValueError("%s: d_win_start needs nwin + 1 entries, d_obs_start npoints + 1, d_obs_frame and d_obs_idx the same length" % name)
+        if d_kf_point.numel() != nframes * cap or d_kps.numel() * d_kps.element_size() != nframes * cap * KEYPOINT_DTYPE.itemsize or \
+                d_pose.numel() * d_pose.element_size() != nframes * KF_POSE_DTYPE.itemsize:
+            raise ValueError("%s: d_kps, d_kf_point and d_pose must hold one row per frame of d_n" % name)
+        if d_points.numel() * d_points.element_size() < npoints * MAP_POINT_DTYPE.itemsize:
+            raise ValueError("%s: the table is shorter than npoints" % name)
+        for nm, t_, need in (("d_point_bad", d_point_bad, npoints), ("d_kf_bad", d_kf_bad, nframes), ("d_kf_fixed_id0", d_kf_fixed_id0, nframes)):
+            if t_ is not None and t_.numel() * t_.element_size() < need:
+                raise ValueError("%s: %s is too short" % (name, nm))
+        dev = d_n.device
+        if d_pose_out is None:
+            d_pose_out = d_pose.clone()
+        elif d_pose_out.data_ptr() == d_pose.data_ptr() or d_pose_out.numel() * d_pose_out.element_size() != nframes * KF_POSE_DTYPE.itemsize:
+            raise ValueError("%s: d_pose_out must be another tensor of d_pose's size" % name)
+        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)
+        out = dict(pose_out=d_pose_out, erase=z((max(nwin, 0), nobs), torch.uint8), chi2=z((max(nwin, 0), nobs), torch.float32),
+                   level=z((max(nwin, 0), nobs), torch.uint8), is_local=z((max(nwin, 0), npoints), torch.uint8),
+                   role=z((max(nwin, 0), nframes), torch.uint8), info=z((max(nwin, 0), LBA_INFO), torch.int32), nerased=z((max(nwin, 0),), torch.int32))
+        q = lambda t: None if t is None or t.numel() == 0 else C.c_void_p(t.data_ptr())
+        s = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        ext._check(ext._L.pgorb_local_bundle_adjustment_batch_device(
+            ext._h, q(d_kps), q(d_n), nframes, cap, q(d_pose), q(d_kf_bad), q(d_kf_point), q(d_kf_fixed_id0), q(d_win_start), q(d_win_kf), nwin,
+            nwin_kf, npoints, q(d_points), q(d_point_bad), q(d_obs_start), q(d_obs_frame), q(d_obs_idx), nobs, int(rounds), q(out["pose_out"]),
+            q(out["erase"]), q(out["chi2"]), q(out["level"]), q(out["is_local"]), q(out["role"]), q(out["info"]), q(out["nerased"]), C.c_void_p(s)))
         return out
 
 

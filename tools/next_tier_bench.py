@@ -58,7 +58,12 @@ next to each, the oracle's CPU time for the same work (1 thread, a few frames, s
                sequential Python reference of the tests (tests/optsim3_reference.py, OUR restatement on one core, NOT g2o).  No
                g2o build exists here, so no CPU counterpart exists and no target is set.  --optsim3-only runs these rows alone
 
-usage: python tools/next_tier_bench.py [--batch 128] [--out profiles/r02_next_tier.txt] [--refresh-only | --place-only | --loop-only | --track-only | --pose-only | --sim3-only | --optsim3-only]"""
+  local_ba     Optimizer::LocalBundleAdjustment (Optimizer.cc:453-778) on the device (pgorb_local_bundle_adjustment_batch_device,
+               csrc/local_ba.hip): one window of 20 local and 20 fixed key frames, 2000 points and 12000 edges (2 % gross outliers,
+               0.7 sigma noise), alone and 64 times in one call (HIP events); beside them the wall clock of the dense numpy reference of
+               the tests (tests/lba_reference.py, NOT g2o and not a tuned CPU baseline).  No target is set.  --lba-only runs these rows
+
+usage: python tools/next_tier_bench.py [--batch 128] [--out profiles/r02_next_tier.txt] [--refresh-only | --place-only | --loop-only | --track-only | --pose-only | --sim3-only | --optsim3-only | --lba-only]"""
 import argparse, ctypes as C, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -80,6 +85,7 @@ ap.add_argument("--track-only", action="store_true", help="the tracking thread's
 ap.add_argument("--pose-only", action="store_true", help="the pose-optimisation rows alone (no ride, no vocabulary)")
 ap.add_argument("--sim3-only", action="store_true", help="the Sim3Solver rows alone (no ride, no vocabulary)")
 ap.add_argument("--optsim3-only", action="store_true", help="the OptimizeSim3 rows alone (no ride, no vocabulary)")
+ap.add_argument("--lba-only", action="store_true", help="the LocalBundleAdjustment rows alone (no ride, no vocabulary)")
 a = ap.parse_args()
 w, h, nf, B = 1920, 1080, a.features, a.batch
 
@@ -491,6 +497,37 @@ def optsim3_lines(npairs=16, ncorr=150, nout=15):
                 npairs, ncorr, (info[:, 3] + info[:, 5]).mean(), (info[:, 4] + info[:, 6]).mean()), t, t / npairs, t_ref)]
 
 
+def lba_lines(nwin=64, nlocal=20, nfixed=20, npts=2000, nobs=6):
+    """LocalBundleAdjustment: one window and a batch of equal windows in the resident call, beside the Python reference of the tests."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import lba_cases as LC
+    import lba_reference as LR
+    ext = pg.ORBextractor(2000, 1.2, 8, 20, 7, max_width=640, max_height=480)
+    P = LC.window("bench", 7000, nlocal, nfixed, npts, nobs=nobs, noise=0.7, outliers=npts * nobs // 50, far=20)
+    LC._cache["bench"] = (P, 2)
+    t0 = time.perf_counter(); ref = LR.local_bundle_adjustment(P, 2); t_ref = (time.perf_counter() - t0) * 1e3
+    one, many = LC.Batch(["bench"]), LC.Batch(["bench"] * nwin)
+    r1 = LC.run_gpu_batch(one, ext, time_reps=5)[0]
+    rn = LC.run_gpu_batch(many, ext, time_reps=5)
+    assert list(r1["info"]) == list(ref["info"]) and r1["ret"] == ref["ret"] and np.array_equal(r1["erase"], ref["erase"])
+    assert all(r["table_bytes"] == r1["table_bytes"] and r["pose_bytes"] == r1["pose_bytes"] for r in rn)
+    i = r1["info"]
+    scene = "%d local + %d fixed key frames, %d points, %d edges, %d erased, %d + %d iterations, %d + %d trials" % (
+        i[3], i[4], i[2], i[1], r1["ret"], i[5], i[7], i[6], i[8])
+    return ["# Optimizer::LocalBundleAdjustment on the device, resident batched call, HIP events around the call alone (its eight output arrays are",
+            "# allocated inside it), median of 5; one workgroup per window.  reference = tests/lba_reference.py for ONE window, wall clock: OUR dense",
+            "# restatement in numpy on one core, NOT g2o and not a tuned CPU baseline.  No g2o build exists here to time; no target is set.",
+            "%-132s %10s %14s %16s" % ("call", "GPU ms", "GPU ms/window", "reference ms (1)"),
+            "%-132s %10.3f %14.4f %16.1f" % ("local_ba, 1 window: " + scene, one.ms, one.ms, t_ref),
+            "%-132s %10.3f %14.4f %16.1f" % ("local_ba, %d windows of that scene in one call" % nwin, many.ms, many.ms / nwin, t_ref)]
+
+
+if a.lba_only:
+    lines = ["# python tools/next_tier_bench.py --lba-only   (MI355X)"] + lba_lines()
+    print("\n".join(lines))
+    if a.out:
+        open(a.out, "w").write("\n".join(lines) + "\n")
+    sys.exit(0)
 if a.optsim3_only:
     lines = ["# python tools/next_tier_bench.py --optsim3-only   (MI355X)"] + optsim3_lines()
     print("\n".join(lines))

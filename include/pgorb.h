@@ -938,7 +938,76 @@ int  pgorb_optimize_sim3_batch_device(pgorb_ctx* ctx, const pgorb_keypoint* d_kp
         pgorb_sim3_estimate* d_estimate_out, int32_t* d_matches12_out, float* d_chi2_12, float* d_chi2_21,
         pgorb_kf_pose* d_scw_pose, int32_t* d_info, int32_t* d_nin, void* hip_stream);
 
-/*   pgorb_local_bundle_adjustment   Optimizer::LocalBundleAdjustment(pKF, pbStopFlag, pMap) (src/Optimizer.cc:453-778) with the g2o
+/*   pgorb_pnp_solver   PnPsolver (src/PnPsolver.cc:67-950, include/PnPsolver.h; Tracking::Relocalization, src/Tracking.cc:1341-1420): the
+ *       constructor, SetRansacParameters, one iterate(niterations) (find = iterate(mRansacMaxIts)), Refine, CheckInliers and the EPnP
+ *       under compute_pose, monocular.  Step 4 of relocalisation, between pgorb_search_by_bow and pgorb_pose_optimization: kp_point is
+ *       what pgorb_slots_from_assignment made of the former's assignment, pose_out / kp_point_out are what the latter reads as pose /
+ *       kp_point (Tracking.cc:1405-1420: the PnP pose, and no point where vbInliers is false).  It is this project's READING of
+ *       cvSVD (the PnPsolver rows) and is not pinned to OpenCV 2.4.9: a 4-point hypothesis depends on the
+ *       null-space basis the SVD happens to produce (section 5), so the device is pinned to tests/pnp_reference.py byte for byte.
+ * Inputs.  kps = mvKeysUn (pt and octave are read), camera = a pgorb_kf_pose of which fx, fy, cx, cy are read (invfx / invfy are
+ * copied to pose_out), kp_point[i] = the table index of vpMapPointMatches[i] or -1, the table as above (pos is read), point_bad
+ * [npoints] (NULL = none).  A correspondence is a keypoint whose slot is valid and not bad, in keypoint order (:78-101);
+ * mvMaxError = mvLevelSigma2[octave]*th2 in float.
+ *   params: SetRansacParameters' arguments (probability and epsilon are floats here; min_set must be 4) with th2, then the state a
+ *       solver carries between calls: first_iteration = mnIterations, best_inliers_in = mnBestInliers (with best_inlier_in =
+ *       mvbBestInliers by KEYPOINT and best_pose_in = mBestTcw; without both of them nothing is carried), and niterations.
+ *       pgorb_pnp_ransac returns the adjusted mRansacMinInliers and mRansacMaxIts of one N (:133-152), made on the host: no
+ *       device logarithm decides a ceil.
+ *   The window.  iterate's loop condition is `mnIterations < mRansacMaxIts || nCurrentIterations < nIterations`, an OR: a call runs
+ *       max(mRansacMaxIts - first_iteration, niterations) iterations unless Refine succeeds earlier.  draws [W][4] with W =
+ *       max(max_iterations, niterations) = raw rand() values (below 2^31), row k for the call's k-th iteration; RandomInt's formula
+ *       and the swap-with-back selection over mvAllIndices are applied here.  Every hypothesis of the window is evaluated; trace
+ *       (may be NULL) [W] receives them (R, t in double, mnInliersi, flags = 1; zeros past the window).
+ *   The stop rule (:209-238).  At an iteration with mnInliersi >= min: the best set is replaced only for mnInliersi >
+ *       mnBestInliers; Refine() then runs on the BEST set and the call returns its pose only for refined > min (strict).
+ * Outputs.  The return value is nInliers.  PGORB_PNP_FOUND | PGORB_PNP_REFINED: pose_out = Refine's R, t converted to float,
+ * inlier = mvbRefinedInliers by keypoint.  PGORB_PNP_FOUND | PGORB_PNP_NO_MORE: mnIterations reached mRansacMaxIts with
+ * mnBestInliers >= min: pose_out = mBestTcw, inlier = mvbBestInliers.  pose_out is a complete pgorb_kf_pose (Tcw, Ow = -Rcw.t()*tcw
+ * as Frame::SetPose, the camera copied); kp_point_out[i] = kp_point[i] where inlier[i], else -1.  Without PGORB_PNP_FOUND: returns
+ * 0, pose_out zeroed, inlier all 0, kp_point_out all -1.  PGORB_PNP_FEW (with NO_MORE): N < min, nothing evaluated, the carried
+ * state untouched.  best_inlier_out / best_pose_out (may be NULL) = the state after the call.  info (may be NULL) = PGORB_PNP_INFO
+ * int32: status bits, N, the adjusted min inliers, mRansacMaxIts, mnIterations after the call, nInliers, mnBestInliers, the
+ * iteration returned (-1: none, or mBestTcw).
+ * Determinism: a pair's result depends on its inputs only, not on its place in a batch, the batch size, the stream or a repeat; the
+ * single call is a one-pair batch.  Every sum runs from 0 in index order (Refine's too), so the device equals the reference's
+ * sequential form.
+ * PGORB_E_ARG (single call, checked on the host first): a negative count, a NULL array that is read, min_set != 4 or another
+ * parameter out of range, a slot outside [-1, npoints), the octave of a kept correspondence outside the context's levels, a value
+ * that is not finite, a draw >= 2^31.  The batched form checks the parameters and the limits only: a bad index or octave counts as
+ * no point.  PGORB_E_LIMIT: more than 16000 keypoints per frame; W above PGORB_PNP_MAX_WINDOW.
+ *   pgorb_pnp_solver_batch_device: pair p solves frame d_pair_frame[p] (NULL: frame p) with the camera of that frame; d_kp_point,
+ *       d_inlier, d_kp_point_out, d_best_inlier (in and out, NULL = nothing carried, nothing kept) [npairs][cap_per_frame]; d_best_pose
+ *       (in and out, may be NULL), d_pose_out, d_ninliers [npairs]; d_first_iteration / d_best_inliers_in [npairs] (NULL = the params'
+ *       values); d_draws [npairs][W][4], d_trace [npairs][W], d_info [npairs][PGORB_PNP_INFO].  Three launches; the records, the
+ *       hypotheses and Refine's arrays live in the context's scratch arena (138 bytes per pair and keypoint, 104 per pair and
+ *       iteration of W). */
+typedef struct pgorb_pnp_params { float probability; int32_t min_inliers, max_iterations, min_set; float epsilon, th2;
+                                  int32_t first_iteration, niterations, best_inliers_in; } pgorb_pnp_params;
+typedef struct pgorb_pnp_hypothesis { double R[9], t[3]; int32_t inliers, flags; } pgorb_pnp_hypothesis;
+#define PGORB_PNP_FEW      1   /* N < the adjusted min inliers: bNoMore, nothing evaluated */
+#define PGORB_PNP_FOUND    2   /* a pose is returned */
+#define PGORB_PNP_NO_MORE  4   /* bNoMore */
+#define PGORB_PNP_REFINED  8   /* the pose is Refine's */
+#define PGORB_PNP_INFO     8
+#define PGORB_PNP_MAX_WINDOW 1024
+int  pgorb_pnp_ransac(float probability, int min_inliers, int max_iterations, int min_set, float epsilon, int N,
+        int32_t* min_inliers_out, int32_t* max_iterations_out);
+int  pgorb_pnp_solver(pgorb_ctx* ctx, const pgorb_keypoint* kps, int n, const pgorb_kf_pose* camera, const int32_t* kp_point /*[n]*/,
+        int npoints, const pgorb_map_point* points, const uint8_t* point_bad /*[npoints] or NULL*/,
+        const pgorb_pnp_params* params, const uint32_t* draws /*[W][4]*/,
+        const uint8_t* best_inlier_in /*[n] or NULL*/, const pgorb_kf_pose* best_pose_in /*or NULL*/,
+        pgorb_kf_pose* pose_out, uint8_t* inlier /*[n]*/, int32_t* kp_point_out /*[n]*/,
+        uint8_t* best_inlier_out /*[n] or NULL*/, pgorb_kf_pose* best_pose_out /*or NULL*/,
+        pgorb_pnp_hypothesis* trace /*[W] or NULL*/, int32_t* info);
+int  pgorb_pnp_solver_batch_device(pgorb_ctx* ctx, const pgorb_keypoint* d_kps, const int32_t* d_n, int cap_per_frame,
+        const int32_t* d_pair_frame, int npairs, const pgorb_kf_pose* d_camera, const int32_t* d_kp_point,
+        int npoints, const pgorb_map_point* d_points, const uint8_t* d_point_bad, const pgorb_pnp_params* params /*host, one for all*/,
+        const int32_t* d_first_iteration, const int32_t* d_best_inliers_in, const uint32_t* d_draws,
+        uint8_t* d_best_inlier, pgorb_kf_pose* d_best_pose, pgorb_kf_pose* d_pose_out, uint8_t* d_inlier, int32_t* d_kp_point_out,
+        pgorb_pnp_hypothesis* d_trace, int32_t* d_info, int32_t* d_ninliers, void* hip_stream);
+
+/*   pgorb_local_bundle_adjustment  Optimizer::LocalBundleAdjustment(pKF, pbStopFlag, pMap) (src/Optimizer.cc:453-778) with the g2o
  *       path under it (VertexSE3Expmap, VertexSBAPointXYZ, EdgeSE3ProjectXYZ with its ANALYTIC Jacobian, RobustKernelHuber,
  *       BlockSolver_6_3 with the Schur complement over the marginalised points, OptimizationAlgorithmLevenberg), monocular (mvuRight
  *       < 0), in double: the step of LocalMapping::Run after SearchInNeighbors.  It is this project's READING of g2o and Eigen

@@ -51,6 +51,7 @@ SYMBOLS = (
     "pgorb_slots_from_assignment", "pgorb_slots_from_assignment_batch_device",
     "pgorb_sim3_solver", "pgorb_sim3_solver_batch_device", "pgorb_sim3_max_iterations",
     "pgorb_optimize_sim3", "pgorb_optimize_sim3_batch_device",
+    "pgorb_pnp_solver", "pgorb_pnp_solver_batch_device", "pgorb_pnp_ransac",
     "pgorb_local_bundle_adjustment", "pgorb_local_bundle_adjustment_batch_device",
     "pgorb_undistort_keypoints", "pgorb_undistort_keypoints_batch_device", "pgorb_image_bounds",
     "pgorb_host_alloc", "pgorb_host_free", "pgorb_host_register", "pgorb_host_unregister", "pgorb_stream_create", "pgorb_stream_create_ingest", "pgorb_stream_create_device", "pgorb_stream_submit_device", "pgorb_stream_wait_device", "pgorb_stream_lanes", "pgorb_stream_destroy", "pgorb_stream_input", "pgorb_stream_reset", "pgorb_stream_submit",
@@ -200,6 +201,13 @@ def lib():
     #  best_inliers_in, draws, found, found_sim3, best, inlier, matches12_out, already1, already2, info, ninliers, stream)
     L.pgorb_sim3_solver_batch_device.argtypes = [vp, vp, vp, C.c_int, vp, vp, C.c_int, vp, vp, vp, C.c_int] + [vp] * 16
     L.pgorb_sim3_max_iterations.argtypes = [C.c_float, C.c_int, C.c_int, C.c_int]
+    # (ctx, kps, n, camera, kp_point, npoints, points, point_bad, params, draws, best_inlier_in, best_pose_in, pose_out, inlier, kp_point_out,
+    #  best_inlier_out, best_pose_out, trace, info)
+    L.pgorb_pnp_solver.argtypes = [vp, vp, C.c_int, vp, vp, C.c_int] + [vp] * 13
+    # (ctx, kps, n, cap, pair_frame, npairs, camera, kp_point, npoints, points, point_bad, params, first_iteration, best_inliers_in, draws,
+    #  best_inlier, best_pose, pose_out, inlier, kp_point_out, trace, info, ninliers, stream)
+    L.pgorb_pnp_solver_batch_device.argtypes = [vp, vp, vp, C.c_int, vp, C.c_int, vp, vp, C.c_int] + [vp] * 15
+    L.pgorb_pnp_ransac.argtypes = [C.c_float, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, i32p, i32p]
     # (ctx, kps1, n1, pose1, kf_point1, kps2, n2, pose2, kf_point2, matches12, new_matches12, npoints, points, point_bad, estimate, th2,
     #  fix_scale, estimate_out, matches12_out, chi2_12, chi2_21, scw_pose, info)
     L.pgorb_optimize_sim3.argtypes = [vp, vp, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp, vp, C.c_int, vp, vp, vp, C.c_float, C.c_int] + [vp] * 6

@@ -154,6 +154,46 @@ int pg_ctx_sim3_caps(pgorb_ctx* c, float probability, int min_inliers, int max_i
     *d_caps = (const int32_t*)c->sim3Caps.p;
     return 0;
 }
+// PnPsolver::SetRansacParameters (src/PnPsolver.cc:121-157) for N correspondences: the adjusted mRansacMinInliers and mRansacMaxIts.
+// int(N*epsilon) is a float product truncated; epsilon is raised to (float)min/N; pow takes the float epsilon as a double; a value
+// no int holds converts as cvttsd2si does
+void pg_pnp_ransac(float probability, int min_inliers, int max_iterations, int min_set, float epsilon, int N, int32_t* min_out, int32_t* cap_out)
+{
+    const double mRansacProb = probability;
+    float mRansacEpsilon = epsilon;
+    int nMinInliers = (int)(N * mRansacEpsilon);
+    if (nMinInliers < min_inliers) nMinInliers = min_inliers;
+    if (nMinInliers < min_set) nMinInliers = min_set;
+    if (mRansacEpsilon < (float)nMinInliers / N) mRansacEpsilon = (float)nMinInliers / N;
+    int nIterations;
+    if (nMinInliers == N) nIterations = 1;
+    else {
+        const double v = ceil(log(1 - mRansacProb) / log(1 - pow((double)mRansacEpsilon, 3.0)));
+        nIterations = (v != v || v >= 2147483648.0 || v < -2147483648.0) ? (-2147483647 - 1) : (int)v;
+    }
+    *min_out = nMinInliers;
+    *cap_out = std::max(1, std::min(nIterations, max_iterations));
+}
+// The table of those pairs for N = 0 .. max_n on the device, kept and re-made as pg_ctx_sim3_caps keeps its own
+int pg_ctx_pnp_table(pgorb_ctx* c, float probability, int min_inliers, int max_iterations, int min_set, float epsilon, int max_n, const int32_t** d_table)
+{
+    const int entries = max_n + 1;
+    if (!(c->pnpTable.p && c->pnpProb == probability && c->pnpMinInliers == min_inliers && c->pnpMaxIts == max_iterations &&
+          c->pnpMinSet == min_set && c->pnpEpsilon == epsilon && c->pnpEntries >= entries)) {
+        PG_HIP(c, hipSetDevice(c->prm.device));
+        std::vector<int32_t> t((size_t)entries * 2);
+        for (int N = 0; N < entries; N++) pg_pnp_ransac(probability, min_inliers, max_iterations, min_set, epsilon, N, &t[2 * N], &t[2 * N + 1]);
+        PG_HIP(c, hipDeviceSynchronize());
+        c->pnpEntries = 0;
+        int rc = ensure(c, c->pnpTable, (size_t)entries * 8);
+        if (rc) return rc;
+        PG_HIP(c, hipMemcpy(c->pnpTable.p, t.data(), (size_t)entries * 8, hipMemcpyHostToDevice));
+        c->pnpProb = probability; c->pnpMinInliers = min_inliers; c->pnpMaxIts = max_iterations; c->pnpMinSet = min_set; c->pnpEpsilon = epsilon;
+        c->pnpEntries = entries;
+    }
+    *d_table = (const int32_t*)c->pnpTable.p;
+    return 0;
+}
 // the header of a vocabulary blob of `nbytes` bytes at `src` (bow.hip, blob layout) into `hdr`, checked: magic, version, and that the sections the
 // header implies fit; the structure itself is checked by pgorb_vocab_from_blob / the loader on the host path and by
 // k_vocab_validate on the device path
@@ -282,7 +322,7 @@ void pgorb_destroy(pgorb_ctx* c)
     (void)hipSetDevice(c->prm.device);
     while (!c->streams.empty()) pgorb_stream_destroy(c->streams.back());      // a stream holds a pointer to its context
     Arena* all[] = {&c->cellTab, &c->cellTabBal, &c->cellCand, &c->cellCount, &c->pyr, &c->cand, &c->sel, &c->nodes, &c->counters, &c->tables, &c->qtTab, &c->qtLeaf,
-                    &c->outBlk, &c->stageA, &c->stageOut, &c->stageSfi, &c->vocab, &c->xdesc, &c->sim3Caps};
+                    &c->outBlk, &c->stageA, &c->stageOut, &c->stageSfi, &c->vocab, &c->xdesc, &c->sim3Caps, &c->pnpTable};
     for (Arena* a : all) if (a->p) (void)hipFree(a->p);
     destroy_side_streams(c);
     if (c->pinned) (void)hipHostFree(c->pinned);

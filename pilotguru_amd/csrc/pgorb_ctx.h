@@ -68,6 +68,9 @@ struct pgorb_ctx {
     // Sim3Solver's mRansacMaxIts as a function of N (pg_ctx_sim3_caps): the key it was made for and the device copy
     Arena sim3Caps;
     float sim3Prob = 0.0f; int sim3MinInliers = 0, sim3MaxIts = 0, sim3Entries = 0;
+    // PnPsolver's adjusted mRansacMinInliers and mRansacMaxIts as a function of N (pg_ctx_pnp_table), kept the same way
+    Arena pnpTable;
+    float pnpProb = 0.0f, pnpEpsilon = 0.0f; int pnpMinInliers = 0, pnpMaxIts = 0, pnpMinSet = 0, pnpEntries = 0;
 };
 
 #pragma GCC visibility push(hidden)      // what follows is shared by the four host files, not exported

@@ -294,6 +294,9 @@ void pg_ctx_vocab_drop(pgorb_ctx* c);
 // Sim3Solver::SetRansacParameters' iteration cap for N = 0 .. max_n on the device (sim3.hip); pg_sim3_cap is the host expression
 int pg_sim3_cap(float probability, int min_inliers, int max_iterations, int N);
 int pg_ctx_sim3_caps(pgorb_ctx* c, float probability, int min_inliers, int max_iterations, int max_n, const int32_t** d_caps);
+// PnPsolver::SetRansacParameters for one N (the host expression) and its table {min inliers, cap} for N = 0 .. max_n on the device (pnp.hip)
+void pg_pnp_ransac(float probability, int min_inliers, int max_iterations, int min_set, float epsilon, int N, int32_t* min_out, int32_t* cap_out);
+int pg_ctx_pnp_table(pgorb_ctx* c, float probability, int min_inliers, int max_iterations, int min_set, float epsilon, int max_n, const int32_t** d_table);
 
 // One synchronous host call of a batched device form.  Its arrays are 64-byte aligned regions at the same offsets in the
 // context's stage arena (device) and page-locked buffer (host), declared in the order: uploads, in-out, downloads, device-only.

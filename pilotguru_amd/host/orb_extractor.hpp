@@ -642,6 +642,115 @@ class Sim3Solver {
     double mRansacProb = 0.99; int mRansacMinInliers = 6, mRansacMaxIts = 300;
 };
 
+// PnPsolver (thirdparty/orb-slam2/src/PnPsolver.cc) with the reference's surface: the constructor, SetRansacParameters, iterate(n)
+// and find.  mnIterations, mnBestInliers, mvbBestInliers (by keypoint) and mBestTcw live here and go to the library with every call, so
+// iterate(5) can be called again on the same solver as Tracking::Relocalization does.  F: the lost frame (mvKeysUndistorted: pt and
+// octave are read); camera: fx, fy, cx, cy are read; kpPoint: the table index of vpMapPointMatches[i] or -1; points (pos is read) and
+// pointBad (empty = none) the table; draws: [>= max(maxIterations, nIterations)][4] raw rand() values in [0, 2^31).
+// Everything pgorb_pnp_solver refuses is a std::invalid_argument here, before the library is called.
+class PnPsolver {
+ public:
+    PnPsolver(pgorb_ctx* ctx, const Frame& F, const pgorb_kf_pose& camera, const std::vector<int32_t>& kpPoint,
+              const std::vector<pgorb_map_point>& points, const std::vector<uint8_t>& pointBad, std::vector<uint32_t> draws)
+        : ctx_(ctx), n_(F.N()), keys_(F.mvKeysUndistorted), camera_(camera), kpPoint_(kpPoint), points_(points), pointBad_(pointBad), draws_(std::move(draws))
+    {
+        const int n = F.N(), np = (int)points.size(), levels = pgorb_levels(ctx_);
+        if (kpPoint.size() != (size_t)n) fail("kpPoint is not N entries long");
+        if (!pointBad.empty() && pointBad.size() != (size_t)np) fail("pointBad is neither empty nor one entry per point");
+        if (!std::isfinite(camera.fx) || !std::isfinite(camera.fy) || !std::isfinite(camera.cx) || !std::isfinite(camera.cy)) fail("the camera is not finite");
+        for (int i = 0; i < n; i++) {
+            const int s = kpPoint[i];
+            if (s < -1 || s >= np) fail("a slot names a point outside the table");
+            if (s < 0 || (!pointBad.empty() && pointBad[s])) continue;
+            const pgorb_keypoint& k = F.mvKeysUndistorted[i];
+            if (levels > 0 && (k.octave < 0 || k.octave >= levels)) fail("an octave is outside the context's levels");
+            const float* p = points[s].pos;
+            if (!std::isfinite(p[0]) || !std::isfinite(p[1]) || !std::isfinite(p[2]) || !std::isfinite(k.x) || !std::isfinite(k.y))
+                fail("a referenced point or keypoint is not finite");
+            N_++;
+        }
+        if (n > 16000) fail("more than 16000 keypoints in the frame");
+        mvbBestInliers.assign(n > 0 ? n : 1, 0);
+        SetRansacParameters();
+    }
+    // PnPsolver.cc:121-157 (the header's defaults); the adjusted minimum and the cap come from pgorb_pnp_ransac
+    void SetRansacParameters(double probability = 0.99, int minInliers = 8, int maxIterations = 300, int minSet = 4, float epsilon = 0.4f,
+                             float th2 = 5.991f)
+    {
+        prm_ = pgorb_pnp_params{(float)probability, minInliers, maxIterations, minSet, epsilon, th2, 0, 1, 0};
+        checkParams(prm_);
+        int32_t mi = 0, cap = 0;
+        pgorb_pnp_ransac(prm_.probability, minInliers, maxIterations, minSet, epsilon, N_, &mi, &cap);
+        mRansacMinInliers = mi; mRansacMaxIts = cap;
+    }
+    // PnPsolver::iterate (:165-258): true = a pose was returned; Tcw = the 4 x 4 float pose, row-major
+    bool iterate(int nIterations, bool& bNoMore, std::vector<bool>& vbInliers, int& nInliers, float Tcw[16] = nullptr)
+    {
+        pgorb_pnp_params prm = prm_;
+        prm.first_iteration = mnIterations; prm.niterations = nIterations; prm.best_inliers_in = mnBestInliers;
+        checkParams(prm);
+        const int n = n_;
+        const size_t W = (size_t)std::max(prm.max_iterations, prm.niterations);
+        if (draws_.size() < W * 4) fail("fewer than max(maxIterations, nIterations) x 4 draws");
+        for (size_t k = 0; k < W * 4; k++)
+            if (draws_[k] >= 0x80000000u) fail("a draw is not below 2^31");
+        std::vector<uint8_t> fl(n > 0 ? n : 1, 0), bi(n > 0 ? n : 1, 0);
+        kpPointOut.assign(n > 0 ? n : 1, -1);
+        pgorb_kf_pose bp{};
+        const int rc = pgorb_pnp_solver(ctx_, keys_.data(), n, &camera_, kpPoint_.data(), (int)points_.size(), points_.data(),
+                                        pointBad_.empty() ? nullptr : pointBad_.data(), &prm, draws_.data(), mvbBestInliers.data(), &mBestTcw,
+                                        &pose, fl.data(), kpPointOut.data(), bi.data(), &bp, nullptr, info);
+        if (rc < 0) throw std::runtime_error(pgorb_last_error(ctx_));
+        kpPointOut.resize(n);
+        mnIterations = info[4]; mnBestInliers = info[6];
+        mvbBestInliers = bi; mBestTcw = bp;
+        bNoMore = (info[0] & PGORB_PNP_NO_MORE) != 0;
+        vbInliers.assign(n, false);
+        for (int i = 0; i < n; i++) vbInliers[i] = fl[i] != 0;
+        nInliers = rc;
+        const bool ok = (info[0] & PGORB_PNP_FOUND) != 0;
+        if (ok && Tcw) {
+            for (int k = 0; k < 12; k++) Tcw[k] = pose.Tcw[k];
+            Tcw[12] = Tcw[13] = Tcw[14] = 0.0f; Tcw[15] = 1.0f;
+        }
+        return ok;
+    }
+    bool find(std::vector<bool>& vbInliers, int& nInliers, float Tcw[16] = nullptr)
+    {
+        bool bFlag;
+        return iterate(mRansacMaxIts, bFlag, vbInliers, nInliers, Tcw);
+    }
+
+    int mnIterations = 0, mnBestInliers = 0, mRansacMinInliers = 0, mRansacMaxIts = 0;
+    std::vector<uint8_t> mvbBestInliers;                                    // by keypoint
+    pgorb_kf_pose mBestTcw{};
+    pgorb_kf_pose pose{};                                                   // what pgorb_pose_optimization takes (Tracking.cc:1405)
+    std::vector<int32_t> kpPointOut;                                        // Tracking.cc:1411-1420: no point where vbInliers is false
+    int32_t info[PGORB_PNP_INFO] = {};
+ private:
+    static void fail(const char* m) { throw std::invalid_argument(std::string("PnPsolver: ") + m); }
+    static void checkParams(const pgorb_pnp_params& p)
+    {
+        if (p.min_set != 4) fail("minSet must be 4");
+        if (p.min_inliers < 1) fail("minInliers is below 1");
+        if (!(p.probability > 0.0f && p.probability < 1.0f)) fail("probability is outside (0, 1)");
+        if (!(p.epsilon > 0.0f && p.epsilon <= 1.0f)) fail("epsilon is outside (0, 1]");
+        if (!(p.th2 > 0.0f)) fail("th2 is not positive");
+        if (p.max_iterations < 1 || p.niterations < 1 || p.first_iteration < 0) fail("maxIterations or nIterations below 1, or a negative first iteration");
+        if (std::max(p.max_iterations, p.niterations) > PGORB_PNP_MAX_WINDOW) fail("a window above PGORB_PNP_MAX_WINDOW");
+    }
+    pgorb_ctx* ctx_;
+    int n_;
+    std::vector<pgorb_keypoint> keys_;                                      // a copy, as every other input: the solver may outlive its Frame
+    pgorb_kf_pose camera_;
+    std::vector<int32_t> kpPoint_;
+    std::vector<pgorb_map_point> points_;
+    std::vector<uint8_t> pointBad_;
+    std::vector<uint32_t> draws_;
+    pgorb_pnp_params prm_{};
+    int N_ = 0;
+};
+
 namespace detail {
 inline void checkRefresh(const std::vector<const KeyFrame*>& kfs, const std::vector<uint8_t>& kfBad, size_t npoints, size_t ndesc,
                          const std::vector<uint8_t>& pointBad, const MapPointObservations& O, const std::vector<int32_t>* select, int what)

@@ -1310,6 +1310,185 @@ class Sim3Solver:
         return out
 
 
+# pgorb_pnp_solver: the parameter block, a traced hypothesis, the status bits and the limits (include/pgorb.h)
+PNP_PARAMS_DTYPE = np.dtype([("probability", "<f4"), ("min_inliers", "<i4"), ("max_iterations", "<i4"), ("min_set", "<i4"), ("epsilon", "<f4"),
+                             ("th2", "<f4"), ("first_iteration", "<i4"), ("niterations", "<i4"), ("best_inliers_in", "<i4")])
+PNP_HYPOTHESIS_DTYPE = np.dtype([("R", "<f8", (9,)), ("t", "<f8", (3,)), ("inliers", "<i4"), ("flags", "<i4")])
+PNP_FEW, PNP_FOUND, PNP_NO_MORE, PNP_REFINED, PNP_INFO, PNP_MAX_WINDOW = 1, 2, 4, 8, 8, 1024
+
+
+class PnPsolver:
+    """PnPsolver (thirdparty/orb-slam2/src/PnPsolver.cc) on the GPU, with the reference's surface: the constructor,
+    SetRansacParameters, iterate(n) and find.  mnIterations, mnBestInliers, mvbBestInliers (by keypoint) and mBestTcw live here and
+    go to the library with every call, so iterate(5) can be called again on the same solver as Tracking::Relocalization does.
+
+    F: a Frame-like object (ext, N, mvKeysUndistorted: pt and octave are read); camera: a KF_POSE_DTYPE record (fx, fy, cx, cy are
+    read); kp_point: the table index of vpMapPointMatches[i] or -1; table: a MapPointTable (pos and bad are read).  draws:
+    [>= max(maxIterations, nIterations)][4] raw rand() values in [0, 2^31); None draws them from numpy's RandomState(seed).
+    Every input the library's checked call refuses is a ValueError here, before the library is called."""
+    MAX_N = 16000
+
+    def __init__(self, F, camera, kp_point, table, draws=None, seed=0):
+        self._a = self.check("PnPsolver", F, camera, kp_point, table)
+        self.ext, self.table = F.ext, table
+        self._draws_in, self._seed = draws, seed
+        self.mnIterations, self.mnBestInliers = 0, 0
+        self.mvbBestInliers = np.zeros(max(self._a["n"], 1), np.uint8)
+        self.mBestTcw = np.zeros(1, KF_POSE_DTYPE)
+        self.pose = np.zeros((), KF_POSE_DTYPE)
+        self.kp_point_out = None
+        self.info = np.zeros(PNP_INFO, np.int32)
+        self.SetRansacParameters()
+
+    @staticmethod
+    def check(name, F, camera, kp_point, table):
+        """The single call's checks of the frame and the table, without a device; returns the arrays the library reads."""
+        n = int(F.N)
+        if n < 0:
+            raise ValueError("%s: a negative keypoint count" % name)
+        k = _arr(F.mvKeysUndistorted, KEYPOINT_DTYPE, n, name + " keypoints")
+        s = _arr(kp_point, np.int32, n, "kp_point")
+        table.check_indices(s, "kp_point", name)
+        P = np.ascontiguousarray(camera, KF_POSE_DTYPE).reshape(())
+        if not np.isfinite([float(P[q]) for q in ("fx", "fy", "cx", "cy")]).all():
+            raise ValueError("%s: the camera is not finite" % name)
+        i = np.nonzero(s >= 0)[0]
+        if table.bad is not None and len(i):
+            i = i[np.asarray(table.bad)[s[i]] == 0]
+        if len(i):
+            if not (np.isfinite(table.points["pos"][s[i]]).all() and np.isfinite(k["x"][i]).all() and np.isfinite(k["y"][i]).all()):
+                raise ValueError("%s: a referenced point or keypoint is not finite" % name)
+            levels = F.ext.GetLevels()
+            if int(k["octave"][i].min()) < 0 or int(k["octave"][i].max()) >= levels:
+                raise ValueError("%s: an octave is outside the extractor's %d levels" % (name, levels))
+        if n > PnPsolver.MAX_N:
+            raise ValueError("%s: more than %d keypoints in the frame" % (name, PnPsolver.MAX_N))
+        return dict(n=n, k=k, s=s, P=P)
+
+    @staticmethod
+    def check_params(name, probability, minInliers, maxIterations, minSet, epsilon, th2, first_iteration=0, niterations=1, draws=None):
+        """The single call's checks of the parameter block and the draws."""
+        if int(minSet) != 4:
+            raise ValueError("%s: minSet must be 4" % name)
+        if int(minInliers) < 1:
+            raise ValueError("%s: minInliers is below 1" % name)
+        if not 0.0 < float(np.float32(probability)) < 1.0:
+            raise ValueError("%s: probability is outside (0, 1)" % name)
+        if not 0.0 < float(np.float32(epsilon)) <= 1.0:
+            raise ValueError("%s: epsilon is outside (0, 1]" % name)
+        if not float(np.float32(th2)) > 0.0:
+            raise ValueError("%s: th2 is not positive" % name)
+        if int(maxIterations) < 1 or int(niterations) < 1 or int(first_iteration) < 0:
+            raise ValueError("%s: maxIterations or nIterations below 1, or a negative first iteration" % name)
+        W = max(int(maxIterations), int(niterations))
+        if W > PNP_MAX_WINDOW:
+            raise ValueError("%s: a window above %d" % (name, PNP_MAX_WINDOW))
+        if draws is not None:
+            d = np.asarray(draws)
+            if d.ndim < 2 or d.shape[-1] != 4 or d.shape[-2] < W:
+                raise ValueError("%s: draws must be [max(maxIterations, nIterations)][4]" % name)
+            if d.size and (int(d.min()) < 0 or int(d.max()) >= 2 ** 31):
+                raise ValueError("%s: a draw is not in [0, 2^31)" % name)
+        return W
+
+    def SetRansacParameters(self, probability=0.99, minInliers=8, maxIterations=300, minSet=4, epsilon=0.4, th2=5.991):
+        """PnPsolver.cc:121-157 (the header's defaults).  The adjusted minimum and the cap come from pgorb_pnp_ransac."""
+        self.check_params("SetRansacParameters", probability, minInliers, maxIterations, minSet, epsilon, th2)
+        self._prm = (float(probability), int(minInliers), int(maxIterations), int(minSet), float(epsilon), float(th2))
+        mi, cap = C.c_int32(0), C.c_int32(0)
+        N = int(((self._a["s"] >= 0) & ((np.asarray(self.table.bad)[np.maximum(self._a["s"], 0)] == 0) if self.table.bad is not None else True)).sum())
+        self.ext._L.pgorb_pnp_ransac(C.c_float(probability), int(minInliers), int(maxIterations), int(minSet), C.c_float(epsilon), N,
+                                     C.byref(mi), C.byref(cap))
+        self.N, self.mRansacMinInliers, self.mRansacMaxIts = N, int(mi.value), int(cap.value)
+
+    def iterate(self, nIterations):
+        """PnPsolver::iterate (:165-258).  Returns (Tcw, bNoMore, vbInliers, nInliers): Tcw the 4 x 4 float pose or None."""
+        pr, mi, mx, ms, eps, th2 = self._prm
+        W = self.check_params("iterate", pr, mi, mx, ms, eps, th2, self.mnIterations, nIterations, self._draws_in)
+        if self._draws_in is None:
+            draws = np.random.RandomState(self._seed + self.mnIterations).randint(0, 2 ** 31, (W, 4)).astype(np.uint32)
+        else:
+            draws = np.ascontiguousarray(np.asarray(self._draws_in)[:W], np.uint32)
+        a, ext, t = self._a, self.ext, self.table
+        prm = np.zeros(1, PNP_PARAMS_DTYPE)
+        prm["probability"], prm["min_inliers"], prm["max_iterations"], prm["min_set"], prm["epsilon"], prm["th2"] = pr, mi, mx, ms, eps, th2
+        prm["first_iteration"], prm["niterations"], prm["best_inliers_in"] = self.mnIterations, int(nIterations), self.mnBestInliers
+        n = a["n"]
+        pose, bpose = np.zeros(1, KF_POSE_DTYPE), np.zeros(1, KF_POSE_DTYPE)
+        fl, kpo, bi = np.zeros(max(n, 1), np.uint8), np.full(max(n, 1), -1, np.int32), np.zeros(max(n, 1), np.uint8)
+        info = np.zeros(PNP_INFO, np.int32)
+        pad = lambda x, dt: x if n else np.zeros(1, dt)
+        ret = ext._check(ext._L.pgorb_pnp_solver(
+            ext._h, _p(pad(a["k"], KEYPOINT_DTYPE)), n, _p(a["P"]), _p(pad(a["s"], np.int32)), t.n, _p(t.points), _p(t.bad), _p(prm), _p(draws),
+            _p(self.mvbBestInliers), _p(self.mBestTcw), _p(pose), _p(fl), _p(kpo), _p(bi), _p(bpose), None, _p(info)))
+        self.info = info
+        self.mnIterations, self.mnBestInliers = int(info[4]), int(info[6])
+        self.mvbBestInliers, self.mBestTcw = bi, bpose
+        self.pose, self.kp_point_out = pose[0].copy(), kpo[:n].copy()
+        Tcw = None
+        if info[0] & PNP_FOUND:
+            Tcw = np.eye(4, dtype=np.float32)
+            Tcw[:3, :] = pose[0]["Tcw"].reshape(3, 4)
+        return Tcw, bool(info[0] & PNP_NO_MORE), fl[:n].astype(bool), int(ret)
+
+    def find(self):
+        """PnPsolver::find (:159-163): iterate(mRansacMaxIts).  Returns (Tcw, vbInliers, nInliers)."""
+        Tcw, _, inl, n = self.iterate(self.mRansacMaxIts)
+        return Tcw, inl, n
+
+    @staticmethod
+    def iterate_batch_device(ext, d_kps, d_n, cap_per_frame, d_pair_frame, npairs, d_camera, d_kp_point, npoints, d_points, d_point_bad, d_draws,
+                             probability=0.99, minInliers=10, maxIterations=300, minSet=4, epsilon=0.5, th2=5.991, nIterations=5,
+                             first_iteration=0, best_inliers_in=0, d_first_iteration=None, d_best_inliers_in=None, d_best_inlier=None,
+                             d_best_pose=None, trace=False, stream=None):
+        """pgorb_pnp_solver_batch_device over resident torch tensors (the defaults are Tracking::Relocalization's): pair p solves frame
+        d_pair_frame[p] (None: frame p); d_kp_point is [npairs][cap]; d_draws [npairs][W][4] with W = max(maxIterations, nIterations);
+        d_best_inlier [npairs][cap] uint8 and d_best_pose are read and rewritten in place where given.  The parameters, the element
+        types and the sizes are checked here; the arrays' contents are not read.  Returns a dict of freshly allocated tensors:
+        pose_out (bytes of KF_POSE_DTYPE per pair: what PoseOptimization reads as d_pose), inlier, kp_point_out [npairs][cap],
+        info [npairs][PNP_INFO], ninliers [npairs] and, with trace, trace (bytes of PNP_HYPOTHESIS_DTYPE, [npairs][W])."""
+        import torch
+        name = "PnPsolver.iterate_batch_device"
+        W = PnPsolver.check_params(name, probability, minInliers, maxIterations, minSet, epsilon, th2, first_iteration, nIterations)
+        for nm, t_ in (("d_pair_frame", d_pair_frame), ("d_n", d_n), ("d_kp_point", d_kp_point), ("d_first_iteration", d_first_iteration),
+                       ("d_best_inliers_in", d_best_inliers_in)):
+            if t_ is not None and t_.dtype != torch.int32:
+                raise ValueError("%s: %s must be an int32 tensor" % (name, nm))
+        npairs, cap = int(npairs), int(cap_per_frame)
+        if cap < 1 or cap > PnPsolver.MAX_N or npairs < 0 or int(npoints) < 0:
+            raise ValueError("%s: cap_per_frame outside [1, %d] or a negative count" % (name, PnPsolver.MAX_N))
+        if d_draws.element_size() != 4 or d_draws.numel() != npairs * W * 4 or d_kp_point.numel() != npairs * cap:
+            raise ValueError("%s: d_draws must be [npairs][%d][4] of 4-byte elements and d_kp_point [npairs][cap]" % (name, W))
+        nframes = int(d_n.numel())
+        if (d_pair_frame is None and nframes < npairs) or (d_pair_frame is not None and int(d_pair_frame.numel()) != npairs) or \
+                d_kps.numel() * d_kps.element_size() != nframes * cap * KEYPOINT_DTYPE.itemsize or \
+                d_camera.numel() * d_camera.element_size() != nframes * KF_POSE_DTYPE.itemsize:
+            raise ValueError("%s: d_kps and d_camera must hold one row per frame of d_n, d_pair_frame one entry per pair" % name)
+        if d_points.numel() * d_points.element_size() < int(npoints) * MAP_POINT_DTYPE.itemsize or \
+                (d_point_bad is not None and d_point_bad.numel() * d_point_bad.element_size() < int(npoints)):
+            raise ValueError("%s: the table is shorter than npoints" % name)
+        if (d_best_inlier is not None and (d_best_inlier.element_size() != 1 or d_best_inlier.numel() != npairs * cap)) or \
+                (d_best_pose is not None and d_best_pose.numel() * d_best_pose.element_size() != npairs * KF_POSE_DTYPE.itemsize):
+            raise ValueError("%s: d_best_inlier must be [npairs][cap] bytes and d_best_pose one pose per pair" % name)
+        dev = d_kp_point.device
+        prm = np.zeros(1, PNP_PARAMS_DTYPE)
+        prm["probability"], prm["min_inliers"], prm["max_iterations"], prm["min_set"], prm["epsilon"], prm["th2"] = \
+            probability, minInliers, maxIterations, minSet, epsilon, th2
+        prm["first_iteration"], prm["niterations"], prm["best_inliers_in"] = first_iteration, nIterations, best_inliers_in
+        e = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
+        out = dict(pose_out=e((npairs, KF_POSE_DTYPE.itemsize), torch.uint8), inlier=e((npairs, cap), torch.uint8),
+                   kp_point_out=e((npairs, cap), torch.int32), info=e((npairs, PNP_INFO), torch.int32), ninliers=e((npairs,), torch.int32))
+        if trace:
+            out["trace"] = e((npairs, W * PNP_HYPOTHESIS_DTYPE.itemsize), torch.uint8)
+        q = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        s = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        ext._check(ext._L.pgorb_pnp_solver_batch_device(
+            ext._h, q(d_kps), q(d_n), cap, q(d_pair_frame), npairs, q(d_camera), q(d_kp_point), int(npoints), q(d_points), q(d_point_bad), _p(prm),
+            q(d_first_iteration), q(d_best_inliers_in), q(d_draws), q(d_best_inlier), q(d_best_pose), q(out["pose_out"]), q(out["inlier"]),
+            q(out["kp_point_out"]), q(out.get("trace")), q(out["info"]), q(out["ninliers"]), C.c_void_p(s)))
+        return out
+
+
 # pgorb_refresh_map_points: what to refresh, the status word's bits, the limit (include/pgorb.h)
 MP_DESCRIPTOR, MP_NORMAL_DEPTH, MP_BOTH = 1, 2, 3
 MP_LIMIT, MP_BAD_INDEX, MP_MAX_OBS = -6, -1, 512

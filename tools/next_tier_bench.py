@@ -52,6 +52,14 @@ next to each, the oracle's CPU time for the same work (1 thread, a few frames, s
                run to ITS end, which is the stop rule's.  No CPU figure exists to set a target against.  --sim3-only runs these
                rows alone
 
+  pnp          PnPsolver (PnPsolver.cc:67-950) on the device (pgorb_pnp_solver, csrc/pnp.hip): one relocalisation candidate through the
+               single call (wall clock, staging included) and 16 candidates in one batched resident call (HIP events), each 150
+               correspondences (30 % outliers) with relocalisation's parameters, so a window of 35 iterations, all of which the
+               device evaluates whenever the stop rule would have returned; beside them the wall clock of the sequential Python
+               reference of the tests (tests/pnp_reference.py, OUR restatement on one core, NOT ORB-SLAM2: it needs OpenCV, which
+               cannot be built here) run to ITS end, which is the stop rule's.  No CPU figure exists to set a target against.
+               --pnp-only runs these rows alone
+
   optsim3      Optimizer::OptimizeSim3 (Optimizer.cc:1046-1241) on the device (pgorb_optimize_sim3, csrc/optimize_sim3.hip): one loop
                candidate through the single call (wall clock, staging included) and 16 candidates in one batched resident call
                (HIP events), each 150 correspondences (10 % gross outliers, 0.5 pixel noise); beside them the wall clock of the
@@ -63,7 +71,7 @@ next to each, the oracle's CPU time for the same work (1 thread, a few frames, s
                0.7 sigma noise), alone and 64 times in one call (HIP events); beside them the wall clock of the dense numpy reference of
                the tests (tests/lba_reference.py, NOT g2o and not a tuned CPU baseline).  No target is set.  --lba-only runs these rows
 
-usage: python tools/next_tier_bench.py [--batch 128] [--out profiles/r02_next_tier.txt] [--refresh-only | --place-only | --loop-only | --track-only | --pose-only | --sim3-only | --optsim3-only | --lba-only]"""
+usage: python tools/next_tier_bench.py [--batch 128] [--out profiles/r02_next_tier.txt] [--refresh-only | --place-only | --loop-only | --track-only | --pose-only | --sim3-only | --pnp-only | --optsim3-only | --lba-only]"""
 import argparse, ctypes as C, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -84,6 +92,7 @@ ap.add_argument("--loop-only", action="store_true", help="loop closing's four ma
 ap.add_argument("--track-only", action="store_true", help="the tracking thread's SearchLocalPoints rows alone (no ride, no vocabulary)")
 ap.add_argument("--pose-only", action="store_true", help="the pose-optimisation rows alone (no ride, no vocabulary)")
 ap.add_argument("--sim3-only", action="store_true", help="the Sim3Solver rows alone (no ride, no vocabulary)")
+ap.add_argument("--pnp-only", action="store_true", help="the PnPsolver rows alone (no ride, no vocabulary)")
 ap.add_argument("--optsim3-only", action="store_true", help="the OptimizeSim3 rows alone (no ride, no vocabulary)")
 ap.add_argument("--lba-only", action="store_true", help="the LocalBundleAdjustment rows alone (no ride, no vocabulary)")
 a = ap.parse_args()
@@ -450,6 +459,56 @@ def sim3_lines(npairs=16, ngood=105, nout=45):
                 npairs, N, its.mean()), t, t / npairs, t_ref)]
 
 
+def pnp_lines(npairs=16, ngood=105, nout=45):
+    """PnPsolver: the single call and the batched resident call, beside the Python reference of the tests."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import pnp_cases as PC
+    import pnp_reference as PR
+    ext = pg.ORBextractor(2000, 1.2, 8, 20, 7, max_width=640, max_height=480)
+    cs = [PC.scene("bench%d" % j, 4000 + j, ngood, nout, noise=0.3) for j in range(npairs)]
+    N = ngood + nout
+    rec = PC.records(cs[0])
+    t0 = time.perf_counter()
+    ref = PC.finish(cs[0], rec, PR.iterate_literal(rec, cs[0].cam, PC.ref_params(cs[0]), cs[0].draws, PC.state_of(cs[0], rec)))
+    t_ref = (time.perf_counter() - t0) * 1e3
+    ts = []
+    for j in range(10):
+        t0 = time.perf_counter(); got = PC.run_gpu(cs[0], ext); ts.append((time.perf_counter() - t0) * 1e3)
+    assert got["ret"] == ref["ninliers"] and np.array_equal(got["inlier"], ref["inlier"]) and got["cap"] == 35 and got["status"] == ref["status"]
+    t1 = float(np.median(ts[1:]))
+    res = PC.run_gpu_batch(cs, ext, N)
+    # the batched call alone, on resident arrays: the runner's uploads are outside the events
+    G = lambda x: torch.from_numpy(np.ascontiguousarray(x)).cuda()
+    W = PC.window_cap(cs[0].params)
+    kp = np.zeros((npairs, N), pg.KEYPOINT_DTYPE); slots = np.full((npairs, N), -1, np.int32)
+    cams = np.zeros(npairs, pg.KF_POSE_DTYPE); draws = np.zeros((npairs, W, 4), np.uint32)
+    base, tabs = 0, []
+    for j, c in enumerate(cs):
+        kp[j, :c.n] = PC.keypoints(c)[:c.n]; slots[j, :c.n] = c.kp_point + base
+        cams[j], draws[j] = PC.camera_record(c.cam), c.draws
+        tabs.append(PC.table(c.points)[:len(c.points)]); base += len(c.points)
+    tab = np.concatenate(tabs)
+    dK, dN, dC, dS = G(kp.view(np.uint8).reshape(npairs, N, 28)), G(np.full(npairs, N, np.int32)), G(cams.view(np.uint8).reshape(npairs, -1)), G(slots)
+    dT, dD = G(tab.view(np.uint8).reshape(len(tab), 32)), G(draws.view(np.int32))
+    out_t = None
+    def batched():
+        nonlocal out_t
+        out_t = pg.PnPsolver.iterate_batch_device(ext, dK, dN, N, None, npairs, dC, dS, len(tab), dT, None, dD)
+    t = timed(batched)
+    ninl = out_t["ninliers"].cpu().numpy()
+    assert [int(x) for x in ninl] == [r["ret"] for r in res] and int(ninl[0]) == ref["ninliers"]
+    its = out_t["info"].cpu().numpy()[:, 4]
+    return ["# PnPsolver on the device; single call = wall clock with staging, median of 9; batched resident call = HIP events, median of 9 (its five",
+            "# output arrays are allocated inside the timed call); every call evaluates its whole window of 35 iterations; reference = tests/pnp_reference.py",
+            "# for ONE candidate run to the stop rule's return, wall clock: OUR restatement in Python on one core, NOT ORB-SLAM2's PnPsolver, which needs",
+            "# OpenCV and cannot be built here.  No CPU figure exists to set a target against; none is set.",
+            "%-110s %10s %16s %16s" % ("call", "GPU ms", "GPU ms/candidate", "reference ms (1)"),
+            "%-110s %10.3f %16.4f %16.1f" % ("pnp_solver (single call): %d correspondences, 35 iterations evaluated, returned at iteration %d with %d inliers" % (
+                N, got["returned"], got["ret"]), t1, t1, t_ref),
+            "%-110s %10.3f %16.4f %16.1f" % ("pnp_solver_batch_device: %d candidates x 35 iterations x %d correspondences (returned after %.1f iterations on average)" % (
+                npairs, N, its.mean()), t, t / npairs, t_ref)]
+
+
 def optsim3_lines(npairs=16, ncorr=150, nout=15):
     """OptimizeSim3: the single call and the batched resident call, beside the Python reference of the tests."""
     sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -530,6 +589,12 @@ if a.lba_only:
     sys.exit(0)
 if a.optsim3_only:
     lines = ["# python tools/next_tier_bench.py --optsim3-only   (MI355X)"] + optsim3_lines()
+    print("\n".join(lines))
+    if a.out:
+        open(a.out, "w").write("\n".join(lines) + "\n")
+    sys.exit(0)
+if a.pnp_only:
+    lines = ["# python tools/next_tier_bench.py --pnp-only   (MI355X)"] + pnp_lines()
     print("\n".join(lines))
     if a.out:
         open(a.out, "w").write("\n".join(lines) + "\n")

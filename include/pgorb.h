@@ -1087,6 +1087,92 @@ int  pgorb_local_bundle_adjustment_batch_device(pgorb_ctx* ctx,
         pgorb_kf_pose* d_pose_out, uint8_t* d_erase, float* d_chi2, uint8_t* d_level, uint8_t* d_is_local, uint8_t* d_role,
         int32_t* d_info, int32_t* d_nerased, void* hip_stream);
 
+/*   pgorb_optimize_essential_graph  Optimizer::OptimizeEssentialGraph(pMap, pLoopKF, pCurKF, NonCorrectedSim3, CorrectedSim3,
+ *       LoopConnections, bFixScale) (src/Optimizer.cc:781-1044) with the g2o path under it (VertexSim3Expmap, EdgeSim3 with
+ *       BaseBinaryEdge's NUMERIC Jacobian, BlockSolver_7_3 without a Schur complement, OptimizationAlgorithmLevenberg with
+ *       setUserLambdaInit(1e-16)), in double: the call of LoopClosing::CorrectLoop (src/LoopClosing.cc:569) after SearchAndFuse.  One
+ *       graph per call, spread over many workgroups.  It is this project's READING of g2o and Eigen (DESIGN.md sections 4 and 5),
+ *       anchored by the CPU tests of tests/test_optimize_essential_graph.py and not pinned to a g2o build; LinearSolverEigen's
+ *       SimplicialLDLT is read as a Cholesky L L' in index order, stored as a block skyline.
+ * Inputs.  nkf key frames in strictly rising mnId order (kf_id; index order is then vertex-id order, g2o's order), pose (Tcw is read,
+ * the camera is copied through), kf_bad (NULL = none), loop_kf and cur_kf by index, fix_scale.  has_corrected / corrected =
+ * CorrectedSim3, has_non_corrected / non_corrected = NonCorrectedSim3 (pgorb_sim3d in double, as the reference's maps hold them; the
+ * flag arrays may be NULL = empty map).  Four candidate lists by index, holding what the containers hold, not what survives:
+ *   loop_conn [nloop_conn][3] = (i, j, pKF_i->GetWeight(pKF_j)) in LoopConnections' map-then-set iteration order;
+ *   parent [nkf] = GetParent() or -1;  loop_edge_start [nkf + 1] / loop_edge = GetLoopEdges() per key frame as CSR;
+ *   covis_start [nkf + 1] / covis / covis_weight = the covisibles per key frame as CSR, with weights.
+ * min_feat is the reference's 100, iterations its 20.  The point table of pgorb_refresh_map_points: pos (in and out), point_bad, and
+ * point_ref_kf [npoints] = the index of the key frame :1020-1029 selects (mnCorrectedByKF == cur ? mnCorrectedReference :
+ * GetReferenceKeyFrame()), -1 = none.
+ * Derived on the device.  The vertices (:809-844: the corrected estimate where present, else Sim3(Rcw, tcw, 1) of the float pose;
+ * loop_kf fixed).  The edges, kind 0..3: loop connections (:852-880: weight < min_feat skips unless (i, j) == (cur, loop); they make
+ * sInsertedEdges), then per key frame the spanning-tree edge to parent (1), the loop edges with a smaller mnId (2), and the
+ * covisibles (3) with weight >= min_feat that are not parent, not a child (parent[n] == i), not a loop edge of i, not bad, of a
+ * smaller mnId and not in sInsertedEdges.  Measurements: vScw on both sides for kind 0, NonCorrectedSim3 where present else vScw
+ * for the others.  The edge order -- kind 0 in list order, then per key frame 1, 2, 3 -- is the order every per-vertex sum runs in.
+ * ONE DEPARTURE: a bad key frame gets no vertex, no edge and no output (the reference would dereference a null vertex at :998;
+ * GetAllKeyFrames() never returns one).  A key frame with no surviving edge is not in the system and keeps its pose.
+ * Outputs.  The return value is the number of optimised (free, active) vertices.  sim3_out [nkf] = the recovered estimates (zeros for
+ * a bad key frame).  pose_out [nkf]: for a key frame with an edge [R | t/s] through Converter::toCvSE3 to float, then SetPose's Ow,
+ * the camera kept; the input's bytes for the others.  points[].pos is overwritten for every point that is not bad and whose
+ * point_ref_kf is valid and not bad with correctedSwr.map(Srw.map(pos)) in double, rounded to float; other points, normal and the
+ * distances keep their bytes -- pgorb_refresh_map_points_batch_device with PGORB_MP_NORMAL_DEPTH follows on the same arrays.
+ * edge_out (may be NULL; room for nloop_conn + nkf + loop edges + covisibles records) = the derived edges with e->chi2() at the
+ * final estimates.  info (may be NULL) = PGORB_EG_INFO int32: status bits, vertices, free vertices, edges of kind 0, 1, 2, 3,
+ * iterations, Levenberg trials, envelope blocks.
+ * PGORB_EG_NOTHING: no edge, or every active vertex fixed -- returns 0, pose_out = pose byte for byte, sim3_out = the input
+ * estimates, the points untouched.  PGORB_EG_NONFINITE: the chi2 a Levenberg iteration starts from is not finite -- the same
+ * outputs.  PGORB_EG_LIMIT: the envelope exceeds PGORB_EG_MAX_ENVELOPE_BLOCKS -- the same outputs; the single call then returns
+ * PGORB_E_LIMIT.
+ * Determinism: no floating-point atomics; a vertex's sums run in edge order, chi2 and computeScale in one fixed tree; the result
+ * depends on the inputs alone, not on the stream, a repeat or what the context ran before; the single call equals the device form
+ * byte for byte.
+ * PGORB_E_ARG (single call, on the host before anything else): a negative count, a NULL array that is read or written, kf_id not
+ * strictly rising, loop_kf, cur_kf, a list entry, a parent or point_ref_kf out of range, an edge from a key frame to itself, a start
+ * array not rising from 0, iterations < 0, a value of Tcw, a Sim3 that is read or a point that is not finite, a scale <= 0.
+ * PGORB_E_LIMIT: nkf > PGORB_EG_MAX_KF, or nloop_conn + nkf + loop edges + covisibles > PGORB_EG_MAX_EDGES (the candidates bound
+ * the edges).  The device form checks pointers and these two limits only: a list entry out of range is no candidate.  The scratch
+ * arena holds 336 bytes per key frame, 1456 per candidate and 788 per envelope block (the skyline and its factor).  THE ENVELOPE IS
+ * KNOWN ON THE DEVICE ONLY, so the arena is sized for min(PGORB_EG_MAX_ENVELOPE_BLOCKS, nkf (nkf + 1) / 2) blocks whatever the graph
+ * needs -- 103 MB from 512 key frames on, where a ride-shaped graph of 500 key frames uses 3225 blocks (2.5 MB) -- and for every
+ * candidate, and the context keeps it until it is destroyed.
+ *   pgorb_optimize_essential_graph_device: asynchronous on hip_stream; nloop_edges and ncovis are the lengths of the two CSR value
+ *       arrays; returns 0 and leaves the count in d_info[2], so d_info is required.  d_pose_out must not be d_pose.  Launches:
+ *       k_eg_prepare, iterations x (k_eg_linearize, k_eg_assemble, k_eg_step), k_eg_finish; no host round trip, no cooperative
+ *       launch; a kernel of a stopped graph returns at once. */
+typedef struct pgorb_sim3d { double r[4] /* x y z w, not renormalised */, t[3], s; } pgorb_sim3d;   /* g2o::Sim3 (pgorb_sim3 is the matchers' float record) */
+typedef struct pgorb_eg_edge { int32_t i, j, kind, pad; double chi2; } pgorb_eg_edge;         /* vertex 0, vertex 1 */
+#define PGORB_EG_NOTHING        1
+#define PGORB_EG_NONFINITE      2
+#define PGORB_EG_LIMIT          4
+#define PGORB_EG_INFO           10
+#define PGORB_EG_MAX_KF         2048
+#define PGORB_EG_MAX_EDGES      65536
+#define PGORB_EG_MAX_ENVELOPE_BLOCKS 131072
+int  pgorb_optimize_essential_graph(pgorb_ctx* ctx,
+        int nkf, const uint64_t* kf_id /*[nkf]*/, const pgorb_kf_pose* pose /*[nkf]*/, const uint8_t* kf_bad /*[nkf] or NULL*/,
+        int loop_kf, int cur_kf, int fix_scale,
+        const uint8_t* has_corrected /*[nkf] or NULL*/, const pgorb_sim3d* corrected /*[nkf]*/,
+        const uint8_t* has_non_corrected /*[nkf] or NULL*/, const pgorb_sim3d* non_corrected /*[nkf]*/,
+        int nloop_conn, const int32_t* loop_conn /*[nloop_conn][3]*/, const int32_t* parent /*[nkf]*/,
+        const int32_t* loop_edge_start /*[nkf + 1]*/, const int32_t* loop_edge,
+        const int32_t* covis_start /*[nkf + 1]*/, const int32_t* covis, const int32_t* covis_weight,
+        int min_feat, int iterations,
+        int npoints, pgorb_map_point* points /*in and out: pos*/, const uint8_t* point_bad /*[npoints] or NULL*/,
+        const int32_t* point_ref_kf /*[npoints]*/,
+        pgorb_sim3d* sim3_out /*[nkf]*/, pgorb_kf_pose* pose_out /*[nkf]*/, pgorb_eg_edge* edge_out /*or NULL*/, int32_t* info);
+int  pgorb_optimize_essential_graph_device(pgorb_ctx* ctx,
+        int nkf, const uint64_t* d_kf_id, const pgorb_kf_pose* d_pose, const uint8_t* d_kf_bad,
+        int loop_kf, int cur_kf, int fix_scale,
+        const uint8_t* d_has_corrected, const pgorb_sim3d* d_corrected,
+        const uint8_t* d_has_non_corrected, const pgorb_sim3d* d_non_corrected,
+        int nloop_conn, const int32_t* d_loop_conn, const int32_t* d_parent,
+        const int32_t* d_loop_edge_start, const int32_t* d_loop_edge, int nloop_edges,
+        const int32_t* d_covis_start, const int32_t* d_covis, const int32_t* d_covis_weight, int ncovis,
+        int min_feat, int iterations,
+        int npoints, pgorb_map_point* d_points, const uint8_t* d_point_bad, const int32_t* d_point_ref_kf,
+        pgorb_sim3d* d_sim3_out, pgorb_kf_pose* d_pose_out, pgorb_eg_edge* d_edge_out, int32_t* d_info, void* hip_stream);
+
 /* ---- Map-point refresh: the distinctive descriptor and the normal / depth range of many points --------------------------
  *   pgorb_refresh_map_points   for every selected point what MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:259-324)
  *       followed by MapPoint::UpdateNormalAndDepth (:347-388) would store, exactly.  The reference runs the pair once per point at

@@ -53,6 +53,7 @@ SYMBOLS = (
     "pgorb_optimize_sim3", "pgorb_optimize_sim3_batch_device",
     "pgorb_pnp_solver", "pgorb_pnp_solver_batch_device", "pgorb_pnp_ransac",
     "pgorb_local_bundle_adjustment", "pgorb_local_bundle_adjustment_batch_device",
+    "pgorb_optimize_essential_graph", "pgorb_optimize_essential_graph_device",
     "pgorb_undistort_keypoints", "pgorb_undistort_keypoints_batch_device", "pgorb_image_bounds",
     "pgorb_host_alloc", "pgorb_host_free", "pgorb_host_register", "pgorb_host_unregister", "pgorb_stream_create", "pgorb_stream_create_ingest", "pgorb_stream_create_device", "pgorb_stream_submit_device", "pgorb_stream_wait_device", "pgorb_stream_lanes", "pgorb_stream_destroy", "pgorb_stream_input", "pgorb_stream_reset", "pgorb_stream_submit",
     "pgorb_stream_wait", "pgorb_stream_frontend", "pgorb_stream_frontend_results", "pgorb_set_option", "pgorb_get_option", "pgorb_matcher_is_popcount",
@@ -222,6 +223,14 @@ def lib():
     #  obs_start, obs_frame, obs_idx, nobs, rounds, pose_out, erase, chi2, level, is_local, role, info, nerased, stream)
     L.pgorb_local_bundle_adjustment_batch_device.argtypes = [vp, vp, vp, C.c_int, C.c_int] + [vp] * 6 + [C.c_int, C.c_int, C.c_int] + [vp] * 5 + \
         [C.c_int, C.c_int] + [vp] * 9
+    # (ctx, nkf, kf_id, pose, kf_bad, loop_kf, cur_kf, fix_scale, has_corrected, corrected, has_non_corrected, non_corrected, nloop_conn,
+    #  loop_conn, parent, loop_edge_start, loop_edge, covis_start, covis, covis_weight, min_feat, iterations, npoints, points, point_bad,
+    #  point_ref_kf, sim3_out, pose_out, edge_out, info)
+    L.pgorb_optimize_essential_graph.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_int] + [vp] * 4 + [C.c_int] + [vp] * 7 + \
+        [C.c_int, C.c_int, C.c_int] + [vp] * 7
+    # (... loop_edge, nloop_edges, covis_start, covis, covis_weight, ncovis, ... info, stream)
+    L.pgorb_optimize_essential_graph_device.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_int] + [vp] * 4 + [C.c_int] + [vp] * 4 + \
+        [C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int] + [vp] * 8
     L.pgorb_log_f.argtypes = [C.c_float]
     L.pgorb_log_scale_factor.argtypes = [vp]
     L.pgorb_predict_scale.argtypes = [vp, C.c_float, C.c_float]

@@ -23,6 +23,7 @@
 //      inside each wave and then as (w0 + w1) + (w2 + w3) through LDS -- one fixed tree, so a pair's result depends on its inputs alone;
 //   4. the Levenberg state is carried identically by every lane.  Every loop is bounded by 2 calls x 10 iterations x 10 trials.
 #include "kf_window.h"
+#include "g2o_sim3.h"
 #include <math.h>
 #include <string>
 
@@ -44,139 +45,7 @@ struct OsBatch {
     pgorb_sim3_estimate* estOut; int32_t* matchesOut; float* chi12; float* chi21; pgorb_kf_pose* scwPose; int32_t* info; int32_t* nIn;
 };
 
-struct OsSim { double qx, qy, qz, qw, tx, ty, tz, s; };                 // g2o::Sim3: r (not renormalised), t, s
 struct OsCam { double fx, fy, cx, cy; };
-
-// Eigen's Quaterniond(Matrix3d); m row-major
-__device__ __forceinline__ void os_quat_from_matrix(const double (&m)[9], OsSim& P)
-{
-    double t = (m[0] + m[4]) + m[8];
-    if (t > 0.0) {
-        t = __dsqrt_rn(t + 1.0);
-        P.qw = 0.5 * t;
-        t = 0.5 / t;
-        P.qx = (m[7] - m[5]) * t; P.qy = (m[2] - m[6]) * t; P.qz = (m[3] - m[1]) * t;
-    } else {
-        int i = 0;
-        if (m[4] > m[0]) i = 1;
-        if (m[8] > (i ? m[4] : m[0])) i = 2;
-        if (i == 0) {
-            t = __dsqrt_rn(((m[0] - m[4]) - m[8]) + 1.0);
-            P.qx = 0.5 * t; t = 0.5 / t;
-            P.qw = (m[7] - m[5]) * t; P.qy = (m[3] + m[1]) * t; P.qz = (m[6] + m[2]) * t;
-        } else if (i == 1) {
-            t = __dsqrt_rn(((m[4] - m[8]) - m[0]) + 1.0);
-            P.qy = 0.5 * t; t = 0.5 / t;
-            P.qw = (m[2] - m[6]) * t; P.qz = (m[7] + m[5]) * t; P.qx = (m[1] + m[3]) * t;
-        } else {
-            t = __dsqrt_rn(((m[8] - m[0]) - m[4]) + 1.0);
-            P.qz = 0.5 * t; t = 0.5 / t;
-            P.qw = (m[3] - m[1]) * t; P.qx = (m[2] + m[6]) * t; P.qy = (m[5] + m[7]) * t;
-        }
-    }
-}
-
-// Eigen's Quaternion::toRotationMatrix, row-major
-__device__ __forceinline__ void os_matrix_from_quat(const OsSim& P, double (&m)[9])
-{
-    const double tx = 2.0 * P.qx, ty = 2.0 * P.qy, tz = 2.0 * P.qz;
-    const double twx = tx * P.qw, twy = ty * P.qw, twz = tz * P.qw, txx = tx * P.qx, txy = ty * P.qx, txz = tz * P.qx;
-    const double tyy = ty * P.qy, tyz = tz * P.qy, tzz = tz * P.qz;
-    m[0] = 1.0 - (tyy + tzz); m[1] = txy - twz; m[2] = txz + twy;
-    m[3] = txy + twz; m[4] = 1.0 - (txx + tzz); m[5] = tyz - twx;
-    m[6] = txz - twy; m[7] = tyz + twx; m[8] = 1.0 - (txx + tyy);
-}
-
-// Eigen's quaternion * vector: uv = vec x v; uv += uv; v + w * uv + vec x uv
-__device__ __forceinline__ void os_rotate(double qx, double qy, double qz, double qw, double X, double Y, double Z, double& rx, double& ry, double& rz)
-{
-    double ux = qy * Z - qz * Y, uy = qz * X - qx * Z, uz = qx * Y - qy * X;
-    ux += ux; uy += uy; uz += uz;
-    rx = (X + qw * ux) + (qy * uz - qz * uy);
-    ry = (Y + qw * uy) + (qz * ux - qx * uz);
-    rz = (Z + qw * uz) + (qx * uy - qy * ux);
-}
-
-// Sim3::operator*: r = a.r * b.r, t = a.s * (a.r * b.t) + a.t, s = a.s * b.s; no renormalisation
-__device__ __forceinline__ OsSim os_mul(const OsSim& a, const OsSim& b)
-{
-    OsSim O;
-    double rx, ry, rz;
-    O.qw = ((a.qw * b.qw - a.qx * b.qx) - a.qy * b.qy) - a.qz * b.qz;
-    O.qx = ((a.qw * b.qx + a.qx * b.qw) + a.qy * b.qz) - a.qz * b.qy;
-    O.qy = ((a.qw * b.qy + a.qy * b.qw) + a.qz * b.qx) - a.qx * b.qz;
-    O.qz = ((a.qw * b.qz + a.qz * b.qw) + a.qx * b.qy) - a.qy * b.qx;
-    os_rotate(a.qx, a.qy, a.qz, a.qw, b.tx, b.ty, b.tz, rx, ry, rz);
-    O.tx = a.s * rx + a.tx; O.ty = a.s * ry + a.ty; O.tz = a.s * rz + a.tz;
-    O.s = a.s * b.s;
-    return O;
-}
-
-// Sim3::inverse: Sim3(r.conjugate(), r.conjugate() * ((-1./s) * t), 1./s)
-__device__ __forceinline__ OsSim os_inverse(const OsSim& a)
-{
-    OsSim O;
-    const double k = -1.0 / a.s;
-    O.qx = -a.qx; O.qy = -a.qy; O.qz = -a.qz; O.qw = a.qw;
-    os_rotate(O.qx, O.qy, O.qz, O.qw, k * a.tx, k * a.ty, k * a.tz, O.tx, O.ty, O.tz);
-    O.s = 1.0 / a.s;
-    return O;
-}
-
-// Sim3(Vector7d) (sim3.h:70-142); update = (omega, upsilon, sigma)
-__device__ __forceinline__ OsSim os_exp(const double (&u)[7])
-{
-    const double o0 = u[0], o1 = u[1], o2 = u[2], sigma = u[6];
-    const double theta = __dsqrt_rn((o0 * o0 + o1 * o1) + o2 * o2);
-    const double Om[9] = {0.0, -o2, o1, o2, 0.0, -o0, -o1, o0, 0.0};
-    double Om2[9], R[9];
-#pragma unroll
-    for (int r = 0; r < 3; r++)
-#pragma unroll
-        for (int c = 0; c < 3; c++) Om2[r * 3 + c] = (Om[r * 3] * Om[c] + Om[r * 3 + 1] * Om[3 + c]) + Om[r * 3 + 2] * Om[6 + c];
-    OsSim E;
-    E.s = exp(sigma);
-    const double eps = 0.00001;
-    double A, Bc, Cc;
-    const bool smallTheta = theta < eps;
-    if (smallTheta) {
-#pragma unroll
-        for (int k = 0; k < 9; k++) R[k] = ((k % 4 == 0 ? 1.0 : 0.0) + Om[k]) + Om2[k];
-    } else {
-        const double a = sin(theta) / theta, b = (1.0 - cos(theta)) / (theta * theta);
-#pragma unroll
-        for (int k = 0; k < 9; k++) R[k] = ((k % 4 == 0 ? 1.0 : 0.0) + a * Om[k]) + b * Om2[k];
-    }
-    if (fabs(sigma) < eps) {
-        Cc = 1.0;
-        if (smallTheta) { A = 1.0 / 2.0; Bc = 1.0 / 6.0; }
-        else {
-            const double theta2 = theta * theta;
-            A = (1.0 - cos(theta)) / theta2;
-            Bc = (theta - sin(theta)) / (theta2 * theta);
-        }
-    } else {
-        Cc = (E.s - 1.0) / sigma;
-        const double sigma2 = sigma * sigma;
-        if (smallTheta) {
-            A = ((sigma - 1.0) * E.s + 1.0) / sigma2;
-            Bc = (((0.5 * sigma2 - sigma) + 1.0) * E.s) / (sigma2 * sigma);
-        } else {
-            const double a = E.s * sin(theta), b = E.s * cos(theta), theta2 = theta * theta;
-            const double c = theta2 + sigma2;
-            A = (a * sigma + (1.0 - b) * theta) / (theta * c);
-            Bc = (Cc - ((b - 1.0) * sigma + a * theta) / c) / theta2;
-        }
-    }
-    os_quat_from_matrix(R, E);
-    double W[9];
-#pragma unroll
-    for (int k = 0; k < 9; k++) W[k] = (A * Om[k] + Bc * Om2[k]) + Cc * (k % 4 == 0 ? 1.0 : 0.0);
-    E.tx = (W[0] * u[3] + W[1] * u[4]) + W[2] * u[5];
-    E.ty = (W[3] * u[3] + W[4] * u[4]) + W[5] * u[5];
-    E.tz = (W[6] * u[3] + W[7] * u[4]) + W[8] * u[5];
-    return E;
-}
 
 // computeError of either edge: obs - cam_map(project(S.map(X))); for EdgeInverseSim3ProjectXYZ S is the inverse
 __device__ __forceinline__ void os_error(const OsSim& S, const OsCam& C, double X, double Y, double Z, double ox, double oy, double& e0, double& e1)

@@ -372,9 +372,103 @@ struct LocalBundleAdjustmentResult {
     int32_t info[PGORB_LBA_INFO] = {};     // status, edges, local points, local and fixed key frames, iterations and trials of both optimize calls, level-1 edges
 };
 
+// The essential graph as the caller's containers hold it (include/pgorb.h, pgorb_optimize_essential_graph): key frames by index in
+// strictly rising mnId order; every list holds candidates, the library applies the filters.
+struct EssentialGraph {
+    std::vector<uint64_t> kfId;                       // mnId
+    std::vector<pgorb_kf_pose> pose;
+    std::vector<uint8_t> kfBad;                       // empty = none
+    int loopKf = 0, curKf = 0;
+    std::vector<uint8_t> hasCorrected, hasNonCorrected;      // empty = an empty map
+    std::vector<pgorb_sim3d> corrected, nonCorrected;        // CorrectedSim3, NonCorrectedSim3
+    std::vector<int32_t> loopConn;                    // (i, j, weight) triples in LoopConnections' iteration order
+    std::vector<int32_t> parent;                      // GetParent() or -1
+    std::vector<int32_t> loopEdgeStart, loopEdge;     // GetLoopEdges() per key frame, CSR
+    std::vector<int32_t> covisStart, covis, covisWeight;     // the covisibles per key frame with weights, CSR
+    std::vector<int32_t> pointRefKf;                  // per point: the key frame Optimizer.cc:1020-1029 selects, or -1
+};
+
+// What Optimizer::OptimizeEssentialGraph returns beside the number of optimised vertices.
+struct EssentialGraphResult {
+    int optimised = 0;
+    std::vector<pgorb_sim3d> sim3;         // the recovered estimates (zeros for a bad key frame)
+    std::vector<pgorb_kf_pose> poses;      // [R | t/s] with Ow for a key frame with an edge, the input for the others
+    std::vector<pgorb_eg_edge> edges;      // the derived edges (vertex 0, vertex 1, kind) with their final chi2
+    int32_t info[PGORB_EG_INFO] = {};      // status, vertices, free vertices, edges per kind, iterations, trials, envelope blocks
+};
+
 class Optimizer {
  public:
     explicit Optimizer(pgorb_ctx* ctx) : ctx_(ctx) {}
+    // Optimizer::OptimizeEssentialGraph(pMap, pLoopKF, pCurKF, NonCorrectedSim3, CorrectedSim3, LoopConnections, bFixScale)
+    // (Optimizer.cc:781-1044) on the GPU.  points (pos is read and corrected in place) and pointBad (empty = none) are the table;
+    // pMP->UpdateNormalAndDepth() is pgorb_refresh_map_points with PGORB_MP_NORMAL_DEPTH afterwards.  Everything
+    // pgorb_optimize_essential_graph refuses as a bad argument is a std::invalid_argument here, before the library is called, and so is
+    // an empty key-frame list (the library answers that one with PGORB_EG_NOTHING); a graph past a capacity is the library's error
+    // (std::runtime_error).
+    EssentialGraphResult OptimizeEssentialGraph(const EssentialGraph& g, std::vector<pgorb_map_point>& points, const std::vector<uint8_t>& pointBad,
+                                                bool bFixScale = false, int minFeat = 100, int iterations = 20)
+    {
+        const auto fail = [](const char* m) { throw std::invalid_argument(std::string("OptimizeEssentialGraph: ") + m); };
+        const size_t nkf = g.kfId.size(), np = points.size();
+        const auto simOk = [](const pgorb_sim3d& S) {
+            for (double v : S.r) if (!std::isfinite(v)) return false;
+            for (double v : S.t) if (!std::isfinite(v)) return false;
+            return std::isfinite(S.s) && S.s > 0.0;
+        };
+        if (iterations < 0) fail("iterations is negative");
+        if (!nkf) fail("no key frame");
+        if (g.pose.size() != nkf || g.parent.size() != nkf) fail("pose or parent is not one entry per key frame");
+        if (!g.kfBad.empty() && g.kfBad.size() != nkf) fail("kfBad is neither empty nor one entry per key frame");
+        if (!pointBad.empty() && pointBad.size() != np) fail("pointBad is neither empty nor one entry per point");
+        if (g.pointRefKf.size() != np) fail("pointRefKf is not one entry per point");
+        if (g.loopKf < 0 || g.loopKf >= (int)nkf || g.curKf < 0 || g.curKf >= (int)nkf) fail("loopKf or curKf is out of range");
+        if ((!g.hasCorrected.empty() && (g.hasCorrected.size() != nkf || g.corrected.size() != nkf)) ||
+            (!g.hasNonCorrected.empty() && (g.hasNonCorrected.size() != nkf || g.nonCorrected.size() != nkf))) fail("a Sim3 map is not one entry per key frame");
+        for (size_t i = 0; i < nkf; i++) {
+            if (i && !(g.kfId[i] > g.kfId[i - 1])) fail("kfId is not strictly rising");
+            if (g.parent[i] < -1 || g.parent[i] >= (int)nkf || g.parent[i] == (int)i) fail("a parent is out of range");
+            for (int k = 0; k < 12; k++) if (!std::isfinite(g.pose[i].Tcw[k])) fail("a pose is not finite");
+            if ((!g.hasCorrected.empty() && g.hasCorrected[i] && !simOk(g.corrected[i])) ||
+                (!g.hasNonCorrected.empty() && g.hasNonCorrected[i] && !simOk(g.nonCorrected[i]))) fail("a Sim3 is not finite or its scale is not positive");
+        }
+        if (g.loopConn.size() % 3) fail("loopConn is not a list of triples");
+        for (size_t k = 0; k + 2 < g.loopConn.size(); k += 3)
+            if (g.loopConn[k] < 0 || g.loopConn[k] >= (int)nkf || g.loopConn[k + 1] < 0 || g.loopConn[k + 1] >= (int)nkf || g.loopConn[k] == g.loopConn[k + 1])
+                fail("a loop connection is out of range or joins a key frame to itself");
+        const auto rows = [&](const std::vector<int32_t>& start, const std::vector<int32_t>& val, const char* what) {
+            if (start.size() != nkf + 1 || start[0] != 0) fail(what);
+            for (size_t i = 0; i < nkf; i++) {
+                if (start[i + 1] < start[i] || (size_t)start[i + 1] > val.size()) fail(what);
+                for (int k = start[i]; k < start[i + 1]; k++) if (val[k] < 0 || val[k] >= (int)nkf || val[k] == (int)i) fail(what);
+            }
+        };
+        rows(g.loopEdgeStart, g.loopEdge, "the loop edges are not a CSR of key frames");
+        rows(g.covisStart, g.covis, "the covisibles are not a CSR of key frames");
+        if (g.covisWeight.size() < g.covis.size()) fail("covisWeight is shorter than covis");
+        for (size_t p = 0; p < np; p++) {
+            if (g.pointRefKf[p] < -1 || g.pointRefKf[p] >= (int)nkf) fail("pointRefKf is out of range");
+            if (!std::isfinite(points[p].pos[0]) || !std::isfinite(points[p].pos[1]) || !std::isfinite(points[p].pos[2])) fail("a point is not finite");
+        }
+        const size_t ncand = g.loopConn.size() / 3 + nkf + (size_t)g.loopEdgeStart[nkf] + (size_t)g.covisStart[nkf];
+        EssentialGraphResult r;
+        r.sim3.resize(nkf); r.poses.resize(nkf); r.edges.resize(ncand + 1);
+        std::vector<pgorb_map_point> none(1);
+        std::vector<int32_t> one(1, 0);
+        const int rc = pgorb_optimize_essential_graph(ctx_, (int)nkf, g.kfId.data(), g.pose.data(), g.kfBad.empty() ? nullptr : g.kfBad.data(),
+                                                      g.loopKf, g.curKf, bFixScale ? 1 : 0, g.hasCorrected.empty() ? nullptr : g.hasCorrected.data(),
+                                                      g.corrected.data(), g.hasNonCorrected.empty() ? nullptr : g.hasNonCorrected.data(),
+                                                      g.nonCorrected.data(), (int)(g.loopConn.size() / 3), g.loopConn.empty() ? one.data() : g.loopConn.data(),
+                                                      g.parent.data(), g.loopEdgeStart.data(), g.loopEdge.empty() ? one.data() : g.loopEdge.data(),
+                                                      g.covisStart.data(), g.covis.empty() ? one.data() : g.covis.data(),
+                                                      g.covisWeight.empty() ? one.data() : g.covisWeight.data(), minFeat, iterations, (int)np,
+                                                      np ? points.data() : none.data(), pointBad.empty() ? nullptr : pointBad.data(),
+                                                      np ? g.pointRefKf.data() : one.data(), r.sim3.data(), r.poses.data(), r.edges.data(), r.info);
+        if (rc < 0) throw std::runtime_error(pgorb_last_error(ctx_));
+        r.edges.resize((size_t)(r.info[3] + r.info[4] + r.info[5] + r.info[6]));
+        r.optimised = rc;
+        return r;
+    }
     // Optimizer::LocalBundleAdjustment(pKF, pbStopFlag, pMap) (Optimizer.cc:453-778), monocular, on the GPU.  keyFrames: frame
     // (mvKeysUn: pt and octave) and pose are read; kfBad[f] = isBad(), kfFixedId0[f] = (mnId == 0) (empty = none); kfPoint[f][i] = the
     // table index of GetMapPoint(i) or -1; localKf: pKF and its covisible key frames as positions in keyFrames.  points (pos is read

@@ -846,11 +846,15 @@ OS3_FEW, OS3_NONFINITE, OS3_INFO = 1, 2, 8
 LBA_NOTHING, LBA_NONFINITE, LBA_LIMIT, LBA_INFO = 1, 2, 4, 10
 LBA_ROLE_NONE, LBA_ROLE_LOCAL, LBA_ROLE_FIXED = 0, 1, 2
 LBA_MAX_LOCAL_KF, LBA_MAX_FIXED_KF, LBA_MAX_POINTS, LBA_MAX_EDGES = 64, 256, 8192, 65536
+EG_NOTHING, EG_NONFINITE, EG_LIMIT, EG_INFO = 1, 2, 4, 10
+EG_MAX_KF, EG_MAX_EDGES, EG_MAX_ENVELOPE_BLOCKS = 2048, 65536, 131072
+SIM3D_DTYPE = np.dtype([("r", "<f8", (4,)), ("t", "<f8", (3,)), ("s", "<f8")])                    # pgorb_sim3d: g2o::Sim3
+EG_EDGE_DTYPE = np.dtype([("i", "<i4"), ("j", "<i4"), ("kind", "<i4"), ("pad", "<i4"), ("chi2", "<f8")])
 
 
 class Optimizer:
-    """Optimizer::PoseOptimization (thirdparty/orb-slam2/src/Optimizer.cc:239-451, monocular) and Optimizer::OptimizeSim3
-    (:1046-1241) on the GPU."""
+    """Optimizer::PoseOptimization (thirdparty/orb-slam2/src/Optimizer.cc:239-451, monocular), Optimizer::OptimizeSim3
+    (:1046-1241), Optimizer::LocalBundleAdjustment (:453-778) and Optimizer::OptimizeEssentialGraph (:781-1044) on the GPU."""
 
     @staticmethod
     def PoseOptimization(frame_keys, pose, kp_point, table, discard_outliers=False, point_has_obs=None):
@@ -1121,6 +1125,158 @@ class Optimizer:
             ext._h, q(d_kps), q(d_n), nframes, cap, q(d_pose), q(d_kf_bad), q(d_kf_point), q(d_kf_fixed_id0), q(d_win_start), q(d_win_kf), nwin,
             nwin_kf, npoints, q(d_points), q(d_point_bad), q(d_obs_start), q(d_obs_frame), q(d_obs_idx), nobs, int(rounds), q(out["pose_out"]),
             q(out["erase"]), q(out["chi2"]), q(out["level"]), q(out["is_local"]), q(out["role"]), q(out["info"]), q(out["nerased"]), C.c_void_p(s)))
+        return out
+
+    @staticmethod
+    def check_essential_graph(name, kf_id, poses, loop_kf, cur_kf, parent, loop_conn, loop_edge_start, loop_edge, covis_start, covis, covis_weight,
+                              points, point_ref_kf, kf_bad, point_bad, has_corrected, corrected, has_non_corrected, non_corrected, iterations):
+        """pgorb_optimize_essential_graph's checks, without a device; returns the arrays the library reads."""
+        ids = np.ascontiguousarray(kf_id, np.uint64).reshape(-1)
+        nkf = len(ids)
+        if nkf and np.any(np.diff(ids.astype(object)) <= 0):
+            raise ValueError("%s: kf_id is not strictly rising" % name)
+        if int(iterations) < 0:
+            raise ValueError("%s: iterations is negative" % name)
+        P = np.ascontiguousarray(poses, KF_POSE_DTYPE).reshape(-1)
+        par = np.ascontiguousarray(parent, np.int32).reshape(-1)
+        if len(P) != nkf or len(par) != nkf:
+            raise ValueError("%s: kf_id, poses and parent differ in length" % name)
+        if not np.isfinite(P["Tcw"]).all():
+            raise ValueError("%s: a pose is not finite" % name)
+        if nkf and not (0 <= int(loop_kf) < nkf and 0 <= int(cur_kf) < nkf):
+            raise ValueError("%s: loop_kf or cur_kf is out of range" % name)
+        if nkf and (int(par.min()) < -1 or int(par.max()) >= nkf or np.any(par == np.arange(nkf))):
+            raise ValueError("%s: a parent is out of range" % name)
+        maps = []
+        for nm, has, rec in (("corrected", has_corrected, corrected), ("non_corrected", has_non_corrected, non_corrected)):
+            if has is None:
+                maps += [None, None]
+                continue
+            h = _arr(has, np.uint8, nkf, "has_" + nm)
+            if rec is None:
+                raise ValueError("%s: has_%s without %s" % (name, nm, nm))
+            r = np.ascontiguousarray(rec, SIM3D_DTYPE).reshape(-1)
+            if len(r) != nkf:
+                raise ValueError("%s: %s needs one record per key frame" % (name, nm))
+            u = h != 0
+            if u.any() and not (np.isfinite(r["r"][u]).all() and np.isfinite(r["t"][u]).all() and np.isfinite(r["s"][u]).all() and (r["s"][u] > 0).all()):
+                raise ValueError("%s: a Sim3 of %s is not finite or its scale is not positive" % (name, nm))
+            maps += [h, r]
+        lc = np.ascontiguousarray(loop_conn, np.int32).reshape(-1, 3)
+        if len(lc) and (not nkf or int(lc[:, :2].min()) < 0 or int(lc[:, :2].max()) >= nkf or np.any(lc[:, 0] == lc[:, 1])):
+            raise ValueError("%s: a loop connection is out of range or joins a key frame to itself" % name)
+        rows = []
+        for nm, st, vals in (("loop_edge", loop_edge_start, [loop_edge]), ("covis", covis_start, [covis, covis_weight])):
+            s = _arr(st, np.int32, nkf + 1, nm + "_start")
+            if s[0] != 0 or np.any(np.diff(s) < 0):
+                raise ValueError("%s: %s_start must rise from 0" % (name, nm))
+            m = int(s[-1])
+            vs = [np.ascontiguousarray(v, np.int32).reshape(-1) for v in vals]
+            if any(len(v) < m for v in vs):
+                raise ValueError("%s: %s is shorter than its start array says" % (name, nm))
+            own = np.repeat(np.arange(nkf, dtype=np.int64), np.diff(s))
+            if m and (int(vs[0][:m].min()) < 0 or int(vs[0][:m].max()) >= nkf or np.any(vs[0][:m] == own)):
+                raise ValueError("%s: a %s entry is out of range or names its own key frame" % (name, nm))
+            rows += [s] + [v[:m] if m else np.zeros(1, np.int32) for v in vs]
+        pts = np.array(np.ascontiguousarray(points, MAP_POINT_DTYPE).reshape(-1))      # a copy: moved in place
+        ref = np.ascontiguousarray(point_ref_kf, np.int32).reshape(-1)
+        if len(ref) != len(pts):
+            raise ValueError("%s: point_ref_kf needs one entry per point" % name)
+        if len(pts) and (int(ref.min()) < -1 or int(ref.max()) >= nkf):
+            raise ValueError("%s: point_ref_kf is out of range" % name)
+        if not np.isfinite(pts["pos"]).all():
+            raise ValueError("%s: a point is not finite" % name)
+        return dict(nkf=nkf, ids=ids, P=P, par=par, maps=maps, lc=lc, rows=rows, pts=pts, ref=ref, kb=_mask(kf_bad, nkf, "kf_bad"),
+                    pb=_mask(point_bad, len(pts), "point_bad"))
+
+    @staticmethod
+    def OptimizeEssentialGraph(ext, kf_id, poses, loop_kf, cur_kf, parent, loop_conn, loop_edge_start, loop_edge, covis_start, covis, covis_weight,
+                               points, point_ref_kf, kf_bad=None, point_bad=None, has_corrected=None, corrected=None, has_non_corrected=None,
+                               non_corrected=None, bFixScale=False, min_feat=100, iterations=20):
+        """Optimizer::OptimizeEssentialGraph (thirdparty/orb-slam2/src/Optimizer.cc:781-1044) on the GPU: the call of
+        LoopClosing::CorrectLoop after SearchAndFuse.  Key frames by index in strictly rising kf_id (mnId) order with their
+        KF_POSE_DTYPE poses; loop_kf, cur_kf by index; corrected / non_corrected = CorrectedSim3 / NonCorrectedSim3 as SIM3D_DTYPE
+        records with their has_ flags (None = an empty map); loop_conn [m][3] = (i, j, weight) in LoopConnections' iteration order;
+        parent[i] or -1; GetLoopEdges() and the covisibles with weights as CSR per key frame; points (MAP_POINT_DTYPE; pos is read)
+        with point_ref_kf[p] = the key frame Optimizer.cc:1020-1029 selects, or -1.  The filters, the edge order and the
+        measurements are derived on the device (include/pgorb.h).  Every input pgorb_optimize_essential_graph refuses is a
+        ValueError here, before the library is called; a graph past a capacity (EG_MAX_*) raises PgorbError.  Returns a dict: ret
+        (the optimised vertices), poses, sim3 (SIM3D_DTYPE), points (a copy with pos corrected), edges (EG_EDGE_DTYPE: the
+        derived edges with their final chi2), status, vertices, free, kinds (edges per kind), iterations, trials, envelope."""
+        a = Optimizer.check_essential_graph("OptimizeEssentialGraph", kf_id, poses, loop_kf, cur_kf, parent, loop_conn, loop_edge_start, loop_edge,
+                                            covis_start, covis, covis_weight, points, point_ref_kf, kf_bad, point_bad, has_corrected, corrected,
+                                            has_non_corrected, non_corrected, iterations)
+        nkf, n = a["nkf"], len(a["pts"])
+        hc, cor, hn, non = a["maps"]
+        ls, le, cs, cv, cw = a["rows"]
+        ncand = len(a["lc"]) + nkf + int(ls[-1]) + int(cs[-1])
+        k1 = max(nkf, 1)
+        so, po, eo = np.zeros(k1, SIM3D_DTYPE), np.zeros(k1, KF_POSE_DTYPE), np.zeros(max(ncand, 1), EG_EDGE_DTYPE)
+        info = np.zeros(EG_INFO, np.int32)
+        pad = lambda x, dt: x if len(x) else np.zeros(1, dt)
+        q = lambda x: None if x is None else _p(x)
+        ret = ext._check(ext._L.pgorb_optimize_essential_graph(
+            ext._h, nkf, _p(pad(a["ids"], np.uint64)), _p(pad(a["P"], KF_POSE_DTYPE)), _p(a["kb"]), int(loop_kf), int(cur_kf), int(bool(bFixScale)),
+            q(hc), q(cor), q(hn), q(non), len(a["lc"]), _p(pad(a["lc"].reshape(-1), np.int32)), _p(pad(a["par"], np.int32)), _p(ls), _p(le), _p(cs),
+            _p(cv), _p(cw), int(min_feat), int(iterations), n, _p(pad(a["pts"], MAP_POINT_DTYPE)), _p(a["pb"]), _p(pad(a["ref"], np.int32)), _p(so),
+            _p(po), _p(eo), _p(info)))
+        ne = int(info[3:7].sum())
+        return dict(ret=ret, poses=po[:nkf].copy(), sim3=so[:nkf].copy(), points=a["pts"], edges=eo[:ne].copy(), status=int(info[0]),
+                    vertices=int(info[1]), free=int(info[2]), kinds=[int(x) for x in info[3:7]], iterations=int(info[7]), trials=int(info[8]),
+                    envelope=int(info[9]))
+
+    @staticmethod
+    def OptimizeEssentialGraph_device(ext, d_kf_id, d_pose, loop_kf, cur_kf, d_parent, d_loop_conn, d_loop_edge_start, d_loop_edge, d_covis_start,
+                                      d_covis, d_covis_weight, npoints, d_points, d_point_ref_kf, d_kf_bad=None, d_point_bad=None,
+                                      d_has_corrected=None, d_corrected=None, d_has_non_corrected=None, d_non_corrected=None, bFixScale=False,
+                                      min_feat=100, iterations=20, want_edges=True, stream=None):
+        """pgorb_optimize_essential_graph_device over resident torch tensors, asynchronous on `stream`: d_kf_id int64 (the bits of the
+        uint64 mnId), d_pose / d_corrected / d_non_corrected / d_points the bytes of their dtypes, the lists int32, the flags uint8.
+        The sizes and element types are checked here (an empty key-frame list is refused here, although the library answers it with
+        EG_NOTHING); the contents are not read: a list entry out of range is no candidate.  d_points
+        is corrected IN PLACE.  Returns a dict of freshly allocated tensors: pose_out, sim3_out (bytes of their dtypes per key
+        frame), edge_out (bytes of EG_EDGE_DTYPE per candidate; info[3:7] count the valid records; None without want_edges) and
+        info [EG_INFO].  The chain into pMP->UpdateNormalAndDepth() is pgorb_refresh_map_points_batch_device on the same d_points
+        with d_pose = pose_out."""
+        import torch
+        name = "Optimizer.OptimizeEssentialGraph_device"
+        if int(iterations) < 0:
+            raise ValueError(name + ": iterations is negative")
+        for nm, t_ in (("d_parent", d_parent), ("d_loop_conn", d_loop_conn), ("d_loop_edge_start", d_loop_edge_start), ("d_loop_edge", d_loop_edge),
+                       ("d_covis_start", d_covis_start), ("d_covis", d_covis), ("d_covis_weight", d_covis_weight), ("d_point_ref_kf", d_point_ref_kf)):
+            if t_.dtype != torch.int32:
+                raise ValueError("%s: %s must be an int32 tensor (the counts are taken from element counts)" % (name, nm))
+        if d_kf_id.dtype != torch.int64:
+            raise ValueError(name + ": d_kf_id must be an int64 tensor")
+        nkf, npoints = int(d_kf_id.numel()), int(npoints)
+        nlc, nle, ncv = int(d_loop_conn.numel()) // 3, int(d_loop_edge.numel()), int(d_covis.numel())
+        if not nkf or not (0 <= int(loop_kf) < nkf and 0 <= int(cur_kf) < nkf):
+            raise ValueError(name + ": no key frame, or loop_kf or cur_kf is out of range")
+        if int(d_parent.numel()) != nkf or int(d_loop_edge_start.numel()) != nkf + 1 or int(d_covis_start.numel()) != nkf + 1 or \
+                int(d_covis_weight.numel()) != ncv or int(d_loop_conn.numel()) != 3 * nlc or \
+                d_pose.numel() * d_pose.element_size() != nkf * KF_POSE_DTYPE.itemsize:
+            raise ValueError(name + ": d_pose and d_parent need one entry per key frame, the start arrays nkf + 1, d_covis_weight one per covisible")
+        if npoints < 0 or d_points.numel() * d_points.element_size() < npoints * MAP_POINT_DTYPE.itemsize or int(d_point_ref_kf.numel()) < npoints:
+            raise ValueError(name + ": the table or d_point_ref_kf is shorter than npoints")
+        for nm, has, rec in (("corrected", d_has_corrected, d_corrected), ("non_corrected", d_has_non_corrected, d_non_corrected)):
+            if has is not None and (rec is None or has.numel() * has.element_size() != nkf or rec.numel() * rec.element_size() != nkf * SIM3D_DTYPE.itemsize):
+                raise ValueError("%s: d_has_%s needs one byte and d_%s one record per key frame" % (name, nm, nm))
+        for nm, t_, need in (("d_kf_bad", d_kf_bad, nkf), ("d_point_bad", d_point_bad, npoints)):
+            if t_ is not None and t_.numel() * t_.element_size() < need:
+                raise ValueError("%s: %s is too short" % (name, nm))
+        dev = d_kf_id.device
+        ncand = nlc + nkf + nle + ncv
+        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)
+        out = dict(pose_out=z((nkf, KF_POSE_DTYPE.itemsize), torch.uint8), sim3_out=z((nkf, SIM3D_DTYPE.itemsize), torch.uint8),
+                   edge_out=z((ncand, EG_EDGE_DTYPE.itemsize), torch.uint8) if want_edges else None, info=z((EG_INFO,), torch.int32))
+        q = lambda t: None if t is None or t.numel() == 0 else C.c_void_p(t.data_ptr())
+        s = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        ext._check(ext._L.pgorb_optimize_essential_graph_device(
+            ext._h, nkf, q(d_kf_id), q(d_pose), q(d_kf_bad), int(loop_kf), int(cur_kf), int(bool(bFixScale)), q(d_has_corrected),
+            q(d_corrected) if d_has_corrected is not None else None, q(d_has_non_corrected), q(d_non_corrected) if d_has_non_corrected is not None else None,
+            nlc, q(d_loop_conn), q(d_parent), q(d_loop_edge_start), q(d_loop_edge), nle, q(d_covis_start), q(d_covis), q(d_covis_weight), ncv,
+            int(min_feat), int(iterations), npoints, q(d_points), q(d_point_bad), q(d_point_ref_kf), q(out["sim3_out"]), q(out["pose_out"]),
+            q(out["edge_out"]), q(out["info"]), C.c_void_p(s)))
         return out
 
 

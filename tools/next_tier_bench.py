@@ -71,7 +71,13 @@ next to each, the oracle's CPU time for the same work (1 thread, a few frames, s
                0.7 sigma noise), alone and 64 times in one call (HIP events); beside them the wall clock of the dense numpy reference of
                the tests (tests/lba_reference.py, NOT g2o and not a tuned CPU baseline).  No target is set.  --lba-only runs these rows
 
-usage: python tools/next_tier_bench.py [--batch 128] [--out profiles/r02_next_tier.txt] [--refresh-only | --place-only | --loop-only | --track-only | --pose-only | --sim3-only | --pnp-only | --optsim3-only | --lba-only]"""
+  essential_graph  Optimizer::OptimizeEssentialGraph (Optimizer.cc:781-1044) on the device (pgorb_optimize_essential_graph_device,
+               csrc/essential_graph.hip): ONE ride-shaped graph of 500 key frames -- the spanning tree, four covisibles back, a previous
+               loop edge and the new loop's three connections -- over its fixed sequence of launches (HIP events around the call alone);
+               beside it the wall clock of the dense numpy reference of the tests (tests/eg_reference.py) on the same shape with 100 key
+               frames (it is cubic in the key frames): NOT g2o and not a CPU baseline.  No target is set.  --eg-only runs this row
+
+usage: python tools/next_tier_bench.py [--batch 128] [--out profiles/r02_next_tier.txt] [--refresh-only | --place-only | --loop-only | --track-only | --pose-only | --sim3-only | --pnp-only | --optsim3-only | --lba-only | --eg-only]"""
 import argparse, ctypes as C, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -95,6 +101,7 @@ ap.add_argument("--sim3-only", action="store_true", help="the Sim3Solver rows al
 ap.add_argument("--pnp-only", action="store_true", help="the PnPsolver rows alone (no ride, no vocabulary)")
 ap.add_argument("--optsim3-only", action="store_true", help="the OptimizeSim3 rows alone (no ride, no vocabulary)")
 ap.add_argument("--lba-only", action="store_true", help="the LocalBundleAdjustment rows alone (no ride, no vocabulary)")
+ap.add_argument("--eg-only", action="store_true", help="the OptimizeEssentialGraph row alone (no ride, no vocabulary)")
 a = ap.parse_args()
 w, h, nf, B = 1920, 1080, a.features, a.batch
 
@@ -581,6 +588,59 @@ def lba_lines(nwin=64, nlocal=20, nfixed=20, npts=2000, nobs=6):
             "%-132s %10.3f %14.4f %16.1f" % ("local_ba, %d windows of that scene in one call" % nwin, many.ms, many.ms / nwin, t_ref)]
 
 
+def eg_lines(nkf=500, nref=100, back=4):
+    """OptimizeEssentialGraph: one graph in the resident call, beside the Python reference of the tests on a smaller graph of that shape."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import warnings
+    import eg_cases as EC
+    import eg_reference as ER
+    warnings.simplefilter("ignore")
+
+    def graph(n):
+        le = [[] for _ in range(n)]
+        le[3 * n // 5], le[n // 10] = [n // 10], [3 * n // 5]
+        return EC.build(n, 77, covis_back=back, loop_edges=le, loop_conn=[(n - 1, 0, 60), (n - 1, 1, 110), (n - 2, 0, 120)])
+    ext = pg.ORBextractor(2000, 1.2, 8, 20, 7, max_width=640, max_height=480)
+    small = graph(nref)
+    t0 = time.perf_counter(); ref = ER.optimize_essential_graph(small); t_ref = (time.perf_counter() - t0) * 1e3
+    c = graph(nkf)
+    dev = lambda x: torch.from_numpy(np.frombuffer(np.ascontiguousarray(x).tobytes(), np.uint8).copy()).cuda()
+    i32 = lambda x: torch.from_numpy(np.ascontiguousarray(x, np.int32).reshape(-1).copy()).cuda()
+    T = dict(id=torch.from_numpy(c["kf_id"].astype(np.int64)).cuda(), pose=dev(c["pose"]), par=i32(c["parent"]), lc=i32(c["loop_conn"]),
+             ls=i32(c["loop_edge_start"]), le=i32(c["loop_edge"]), cs=i32(c["covis_start"]), cv=i32(c["covis"]), cw=i32(c["covis_weight"]),
+             ref=i32(c["point_ref_kf"]), kb=dev(c["kf_bad"]), pb=dev(c["point_bad"]), hc=dev(c["has_corrected"]), co=dev(c["corrected"]),
+             hn=dev(c["has_non_corrected"]), no=dev(c["non_corrected"]))
+    pts0 = dev(c["points"])
+    ms, out = [], None
+    for _ in range(6):
+        pts = pts0.clone()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        out = pg.Optimizer.OptimizeEssentialGraph_device(ext, T["id"], T["pose"], c["loop_kf"], c["cur_kf"], T["par"], T["lc"], T["ls"], T["le"], T["cs"],
+                                                         T["cv"], T["cw"], len(c["points"]), pts, T["ref"], d_kf_bad=T["kb"], d_point_bad=T["pb"],
+                                                         d_has_corrected=T["hc"], d_corrected=T["co"], d_has_non_corrected=T["hn"],
+                                                         d_non_corrected=T["no"], bFixScale=False)
+        e1.record(); torch.cuda.synchronize()
+        ms.append(e0.elapsed_time(e1))
+    i = out["info"].cpu().numpy()
+    assert i[0] == 0 and i[2] == nkf - 1
+    t = float(np.median(ms[1:]))
+    scene = "%d key frames, %d + %d + %d + %d edges, %d envelope blocks, %d iterations, %d trials" % (i[1], i[3], i[4], i[5], i[6], i[9], i[7], i[8])
+    return ["# Optimizer::OptimizeEssentialGraph on the device, resident call, HIP events around the call alone (its four output arrays are allocated",
+            "# inside it), median of 5 after one warm-up: k_eg_prepare, 20 x (k_eg_linearize, k_eg_assemble, k_eg_step), k_eg_finish, of which the",
+            "# iterations after the stop flag return at once.  reference = tests/eg_reference.py on the same shape with %d key frames (%d iterations," % (nref, ref["iterations"]),
+            "# %d trials), wall clock: OUR dense restatement in numpy on one core, cubic in the key frames, NOT g2o and not a CPU baseline.  No g2o" % ref["trials"],
+            "# build exists here to time; no target is set.",
+            "%-128s %10s %22s" % ("call", "GPU ms", "reference ms (%d KFs)" % nref),
+            "%-128s %10.3f %22.1f" % ("essential_graph: " + scene, t, t_ref)]
+
+
+if a.eg_only:
+    lines = ["# python tools/next_tier_bench.py --eg-only   (MI355X)"] + eg_lines()
+    print("\n".join(lines))
+    if a.out:
+        open(a.out, "w").write("\n".join(lines) + "\n")
+    sys.exit(0)
 if a.lba_only:
     lines = ["# python tools/next_tier_bench.py --lba-only   (MI355X)"] + lba_lines()
     print("\n".join(lines))

@@ -1173,6 +1173,87 @@ int  pgorb_optimize_essential_graph_device(pgorb_ctx* ctx,
         int npoints, pgorb_map_point* d_points, const uint8_t* d_point_bad, const int32_t* d_point_ref_kf,
         pgorb_sim3d* d_sim3_out, pgorb_kf_pose* d_pose_out, pgorb_eg_edge* d_edge_out, int32_t* d_info, void* hip_stream);
 
+/*   pgorb_global_bundle_adjustment  Optimizer::GlobalBundleAdjustemnt(pMap, nIterations, pbStopFlag, nLoopKF, bRobust), that is
+ *       Optimizer::BundleAdjustment over every key frame and map point (src/Optimizer.cc:41-46, :49-237), with the g2o path under it
+ *       (VertexSE3Expmap, VertexSBAPointXYZ, EdgeSE3ProjectXYZ with its ANALYTIC Jacobian, optional RobustKernelHuber, BlockSolver_6_3
+ *       with the Schur complement over the marginalised points, OptimizationAlgorithmLevenberg), monocular (mvuRight < 0), in double:
+ *       the call of LoopClosing::RunGlobalBundleAdjustment (src/LoopClosing.cc:648-752) and of Tracking::CreateInitialMapMonocular
+ *       (src/Tracking.cc:682).  One problem per call, spread over many workgroups.  It is this project's READING of g2o and Eigen
+ *       (DESIGN.md sections 4 and 5: the local-bundle-adjustment readings hold, the global rows add to them), anchored by the CPU
+ *       tests of tests/test_global_bundle_adjustment.py and not pinned to a g2o build; LinearSolverEigen is read, as for the essential
+ *       graph, as a Cholesky L L' in index order on a block skyline.
+ * Inputs.  nkf key frames IN RISING mnId ORDER (index order is then vertex-id order, g2o's order), each its undistorted keypoints
+ * (pt and octave are read), n[f], its pgorb_kf_pose (Tcw, fx, fy, cx, cy are read), kf_bad[f] = isBad() (NULL = none),
+ * kf_fixed_id0[f] != 0 for the key frame with mnId == 0 (setFixed(pKF->mnId==0), :79; NULL = none: no gauge is fixed).  The point
+ * table of pgorb_refresh_map_points: points (pos), point_bad, and the observations as CSR of (obs_frame, obs_idx).  iterations:
+ * the reference's 10 from loop closing, 20 from initialisation.  robust: 0 from both callers; 1 = RobustKernelHuber with the
+ * reference's const float thHuber2D = sqrt(5.99) -- a float, and 5.99, NOT local bundle adjustment's sqrt(5.991).  No kf_point
+ * slots: the edges come from the observations alone.  Derived on the device, as flags and so without an order:
+ *   vertices   every key frame that is not bad (:71-83); the fixed one is kf_fixed_id0.  (ONE DEPARTURE: the reference adds bad
+ *              key frames' observations nowhere either (:105), but would hand a bad key frame in vpKFs no vertex and still read it
+ *              at :193; GetAllKeyFrames() never returns one.  Here a bad key frame gets no vertex and its input bytes.)
+ *   edges      every CSR observation of a point that is not bad, in a key frame that is not bad (:105-110)
+ *   points     included when they have at least one edge (vbNotIncludedMP, :175-183)
+ * One optimize(iterations): no classification, no second round, no erased observation.
+ * Outputs.  The return value is the number of free active vertices (optimised key frames).  pose_out [nkf]: for EVERY key frame that
+ * is not bad -- the fixed one and one without an edge included -- a complete pgorb_kf_pose: Converter::toCvMat(vSE3->estimate()) to
+ * float (:193-210; for a vertex that did not move that is the round trip of the input through the quaternion, not the input's
+ * bytes), then SetPose's Ow = -Rcw.t()*tcw, the camera kept; a bad key frame gets the input's bytes.  pos_out [npoints][3] (float):
+ * Converter::toCvMat(Vector3d) for included points, the input position for the others.  kf_done [nkf], point_done [npoints]
+ * (uint8): what mnBAGlobalForKF = nLoopKF marks (:196-209, :215-234): not bad, and for points also included.  in_place != 0 is the
+ * nLoopKF == 0 branch (:202, :226): points[].pos of the done points is overwritten too; normal and the distances keep their bytes and
+ * pgorb_refresh_map_points(_batch_device) with PGORB_MP_NORMAL_DEPTH follows on the same arrays, as after local bundle adjustment
+ * (SetPose is the caller's copy of pose_out).  With in_place == 0 the table is not written.  chi2 [nobs] (float, may be NULL): each
+ * edge's e->chi2() at the final estimates, 0 where the observation is no edge.  info (may be NULL) = PGORB_GBA_INFO int32: status
+ * bits, edges, included points, vertices, free active vertices, iterations, Levenberg trials, envelope blocks.
+ * PGORB_GBA_NOTHING: no edge, or no free active vertex (the reference would still move the points around fixed cameras; here
+ * nothing is optimised) -- returns 0, pose_out is still the round trip above, pos_out the input, the table untouched, chi2 0.
+ * PGORB_GBA_NONFINITE: the chi2 an iteration starts from is not finite -- the same outputs, the counters of info 0.
+ * PGORB_GBA_LIMIT: the envelope exceeds PGORB_GBA_MAX_ENVELOPE_BLOCKS -- the same outputs, nothing is factorised; the single call
+ * then returns PGORB_E_LIMIT.  The done flags do not depend on the status.
+ * Determinism: no floating-point atomics; a point's sums run in CSR order, a camera's over the points in table order and a point's
+ * edges in CSR order, chi2 and computeScale as per-workgroup trees whose partials are summed in one fixed tree; the result depends
+ * on the inputs alone, not on the stream, a repeat or what the context ran before; the single call equals the device form byte
+ * for byte.
+ * PGORB_E_ARG (single call, on the host before anything else): a negative count, a NULL array that is read or written,
+ * iterations < 0, an observation out of range, obs_start not rising from 0, a key frame twice in one list, the octave of an observed
+ * keypoint outside the context's levels, a value of Tcw, fx, fy, cx, cy or a point that is not finite, fx or fy zero.
+ * PGORB_E_LIMIT: nkf > PGORB_GBA_MAX_KF, npoints > PGORB_GBA_MAX_POINTS, observations > PGORB_GBA_MAX_EDGES (each from the counts
+ * alone), more than 16000 keypoints in a key frame.  The scratch arena holds 1636 bytes per key frame, 148 per point, 180 per
+ * observation and 292 per envelope block.  THE RECORDS ARE ADDRESSED BY TABLE INDEX AND CSR POSITION, so the arena scales with the
+ * table passed, and THE ENVELOPE IS KNOWN ON THE DEVICE ONLY, so it is sized for min(PGORB_GBA_MAX_ENVELOPE_BLOCKS, nkf (nkf + 1) / 2)
+ * blocks whatever the map needs (38 MB from 512 key frames on); the context keeps it until it is destroyed.
+ *   pgorb_global_bundle_adjustment_device: asynchronous on hip_stream; the key frames are nframes frames of one batch (d_kps
+ *       [nframes][cap_per_frame], d_n, d_pose, d_kf_bad, d_kf_fixed_id0 [nframes]); nobs = the length of d_obs_frame / d_obs_idx.
+ *       Returns 0 and leaves the count in d_info[4], so d_info is required.  d_pose_out must not be d_pose.  It checks pointers,
+ *       iterations, cap_per_frame and the three count limits only: an index out of range is no observation.  Launches: k_gba_prepare,
+ *       iterations x (k_gba_linearize, k_gba_begin, 10 x (k_gba_schur, k_gba_solve, k_gba_try, k_gba_decide)), k_gba_finish --
+ *       42 * iterations + 2, so 842 at 20 iterations; no host round trip, no cooperative launch, no workgroup waits on another; a
+ *       kernel behind the stop flag or the end of its iteration returns at once (about 4 us each: under 4 ms at 20 iterations). */
+#define PGORB_GBA_NOTHING        1
+#define PGORB_GBA_NONFINITE      2
+#define PGORB_GBA_LIMIT          4
+#define PGORB_GBA_INFO           8
+#define PGORB_GBA_MAX_KF         2048
+#define PGORB_GBA_MAX_POINTS     262144
+#define PGORB_GBA_MAX_EDGES      2097152
+#define PGORB_GBA_MAX_ENVELOPE_BLOCKS 131072
+int  pgorb_global_bundle_adjustment(pgorb_ctx* ctx,
+        int nkf, const pgorb_keypoint* const* kps, const int32_t* n /*[nkf]*/, const pgorb_kf_pose* pose /*[nkf]*/,
+        const uint8_t* kf_bad /*[nkf] or NULL*/, const uint8_t* kf_fixed_id0 /*[nkf] or NULL*/,
+        int npoints, pgorb_map_point* points /*pos; written when in_place*/, const uint8_t* point_bad /*[npoints] or NULL*/,
+        const int32_t* obs_start /*[npoints + 1]*/, const int32_t* obs_frame, const int32_t* obs_idx,
+        int iterations, int robust, int in_place,
+        pgorb_kf_pose* pose_out /*[nkf]*/, float* pos_out /*[npoints][3]*/, uint8_t* kf_done /*[nkf]*/, uint8_t* point_done /*[npoints]*/,
+        float* chi2 /*[nobs] or NULL*/, int32_t* info);
+int  pgorb_global_bundle_adjustment_device(pgorb_ctx* ctx,
+        const pgorb_keypoint* d_kps, const int32_t* d_n, int nframes, int cap_per_frame, const pgorb_kf_pose* d_pose,
+        const uint8_t* d_kf_bad, const uint8_t* d_kf_fixed_id0,
+        int npoints, pgorb_map_point* d_points, const uint8_t* d_point_bad, const int32_t* d_obs_start, const int32_t* d_obs_frame,
+        const int32_t* d_obs_idx, int nobs, int iterations, int robust, int in_place,
+        pgorb_kf_pose* d_pose_out, float* d_pos_out, uint8_t* d_kf_done, uint8_t* d_point_done, float* d_chi2, int32_t* d_info,
+        void* hip_stream);
+
 /* ---- Map-point refresh: the distinctive descriptor and the normal / depth range of many points --------------------------
  *   pgorb_refresh_map_points   for every selected point what MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:259-324)
  *       followed by MapPoint::UpdateNormalAndDepth (:347-388) would store, exactly.  The reference runs the pair once per point at

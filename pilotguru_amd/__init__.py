@@ -14,6 +14,8 @@ from .orb import (LBA_INFO, LBA_LIMIT, LBA_MAX_EDGES, LBA_MAX_FIXED_KF, LBA_MAX_
                   LBA_NOTHING, LBA_ROLE_FIXED, LBA_ROLE_LOCAL, LBA_ROLE_NONE)
 from .orb import (EG_EDGE_DTYPE, EG_INFO, EG_LIMIT, EG_MAX_EDGES, EG_MAX_ENVELOPE_BLOCKS, EG_MAX_KF, EG_NONFINITE, EG_NOTHING,  # noqa: F401
                   SIM3D_DTYPE)
+from .orb import (GBA_INFO, GBA_LIMIT, GBA_MAX_EDGES, GBA_MAX_ENVELOPE_BLOCKS, GBA_MAX_KF, GBA_MAX_POINTS, GBA_NONFINITE,  # noqa: F401
+                  GBA_NOTHING)
 from .orb import S3_FEW, S3_FOUND, S3_INFO, S3_NO_MORE, SIM3_ESTIMATE_DTYPE, SIM3_MAX_ITERATIONS, SIM3_PARAMS_DTYPE, Sim3Solver  # noqa: F401
 from .orb import (PNP_FEW, PNP_FOUND, PNP_HYPOTHESIS_DTYPE, PNP_INFO, PNP_MAX_WINDOW, PNP_NO_MORE, PNP_PARAMS_DTYPE, PNP_REFINED,  # noqa: F401
                   PnPsolver)

@@ -54,6 +54,7 @@ SYMBOLS = (
     "pgorb_pnp_solver", "pgorb_pnp_solver_batch_device", "pgorb_pnp_ransac",
     "pgorb_local_bundle_adjustment", "pgorb_local_bundle_adjustment_batch_device",
     "pgorb_optimize_essential_graph", "pgorb_optimize_essential_graph_device",
+    "pgorb_global_bundle_adjustment", "pgorb_global_bundle_adjustment_device",
     "pgorb_undistort_keypoints", "pgorb_undistort_keypoints_batch_device", "pgorb_image_bounds",
     "pgorb_host_alloc", "pgorb_host_free", "pgorb_host_register", "pgorb_host_unregister", "pgorb_stream_create", "pgorb_stream_create_ingest", "pgorb_stream_create_device", "pgorb_stream_submit_device", "pgorb_stream_wait_device", "pgorb_stream_lanes", "pgorb_stream_destroy", "pgorb_stream_input", "pgorb_stream_reset", "pgorb_stream_submit",
     "pgorb_stream_wait", "pgorb_stream_frontend", "pgorb_stream_frontend_results", "pgorb_set_option", "pgorb_get_option", "pgorb_matcher_is_popcount",
@@ -231,6 +232,13 @@ def lib():
     # (... loop_edge, nloop_edges, covis_start, covis, covis_weight, ncovis, ... info, stream)
     L.pgorb_optimize_essential_graph_device.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_int] + [vp] * 4 + [C.c_int] + [vp] * 4 + \
         [C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int] + [vp] * 8
+    # (ctx, nkf, kps[], n, pose, kf_bad, kf_fixed_id0, npoints, points, point_bad, obs_start, obs_frame, obs_idx, iterations, robust,
+    #  in_place, pose_out, pos_out, kf_done, point_done, chi2, info)
+    L.pgorb_global_bundle_adjustment.argtypes = [vp, C.c_int] + [vp] * 5 + [C.c_int] + [vp] * 5 + [C.c_int, C.c_int, C.c_int] + [vp] * 6
+    # (ctx, kps, n, nframes, cap, pose, kf_bad, kf_fixed_id0, npoints, points, point_bad, obs_start, obs_frame, obs_idx, nobs, iterations,
+    #  robust, in_place, pose_out, pos_out, kf_done, point_done, chi2, info, stream)
+    L.pgorb_global_bundle_adjustment_device.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, C.c_int] + [vp] * 5 + \
+        [C.c_int, C.c_int, C.c_int, C.c_int] + [vp] * 7
     L.pgorb_log_f.argtypes = [C.c_float]
     L.pgorb_log_scale_factor.argtypes = [vp]
     L.pgorb_predict_scale.argtypes = [vp, C.c_float, C.c_float]

@@ -397,9 +397,80 @@ struct EssentialGraphResult {
     int32_t info[PGORB_EG_INFO] = {};      // status, vertices, free vertices, edges per kind, iterations, trials, envelope blocks
 };
 
+// What Optimizer::GlobalBundleAdjustment returns beside the number of free active vertices (include/pgorb.h).
+struct GlobalBundleAdjustmentResult {
+    int optimised = 0;
+    std::vector<pgorb_kf_pose> poses;      // per key frame: every one that is not bad replaced (complete records), a bad one as given
+    std::vector<float> pos;                // [npoints][3]: the included points adjusted, the others as given
+    std::vector<uint8_t> kfDone, pointDone;      // what mnBAGlobalForKF = nLoopKF marks
+    std::vector<float> chi2;               // per observation, aligned with the lists
+    int32_t info[PGORB_GBA_INFO] = {};     // status, edges, included points, vertices, free active vertices, iterations, trials, envelope blocks
+};
+
 class Optimizer {
  public:
     explicit Optimizer(pgorb_ctx* ctx) : ctx_(ctx) {}
+    // Optimizer::GlobalBundleAdjustemnt(pMap, nIterations, pbStopFlag, nLoopKF, bRobust) (Optimizer.cc:41-237), monocular, on the GPU.
+    // keyFrames IN RISING mnId ORDER: frame (mvKeysUn: pt and octave) and pose are read; kfBad[f] = isBad(), kfFixedId0[f] = (mnId == 0)
+    // (empty = none).  points (pos is read; with inPlace, the nLoopKF == 0 branch, replaced for the done points), pointBad (empty =
+    // none) and obs are the table.  nIterations: 10 from loop closing, 20 from initialisation; bRobust: Huber with (float)sqrt(5.99).
+    // Everything pgorb_global_bundle_adjustment refuses as a bad argument is a std::invalid_argument here, before the library is
+    // called; a map past a capacity is the library's error (std::runtime_error).
+    GlobalBundleAdjustmentResult GlobalBundleAdjustment(const std::vector<const KeyFrame*>& keyFrames, const std::vector<uint8_t>& kfBad,
+                                                        const std::vector<uint8_t>& kfFixedId0, std::vector<pgorb_map_point>& points,
+                                                        const std::vector<uint8_t>& pointBad, const MapPointObservations& obs,
+                                                        int nIterations = 10, bool bRobust = false, bool inPlace = false)
+    {
+        const auto fail = [](const char* m) { throw std::invalid_argument(std::string("GlobalBundleAdjustment: ") + m); };
+        const size_t nkf = keyFrames.size(), np = points.size();
+        const int levels = pgorb_levels(ctx_);
+        if (nIterations < 0) fail("nIterations is negative");
+        if ((!kfBad.empty() && kfBad.size() != nkf) || (!kfFixedId0.empty() && kfFixedId0.size() != nkf)) fail("kfBad or kfFixedId0 is neither empty nor one entry per key frame");
+        if (!pointBad.empty() && pointBad.size() != np) fail("pointBad is neither empty nor one entry per point");
+        std::vector<const pgorb_keypoint*> kps(nkf + 1);
+        std::vector<int32_t> n(nkf + 1);
+        std::vector<pgorb_kf_pose> pose(nkf + 1);
+        for (size_t f = 0; f < nkf; f++) {
+            if (!keyFrames[f]) fail("a key frame is NULL");
+            const Frame& F = keyFrames[f]->frame;
+            const pgorb_kf_pose& P = keyFrames[f]->pose;
+            for (int k = 0; k < 12; k++)
+                if (!std::isfinite(P.Tcw[k])) fail("a pose is not finite");
+            if (!std::isfinite(P.fx) || !std::isfinite(P.fy) || !std::isfinite(P.cx) || !std::isfinite(P.cy)) fail("a camera is not finite");
+            if (P.fx == 0.0f || P.fy == 0.0f) fail("fx or fy is zero");
+            if (F.N() > 16000) fail("more than 16000 keypoints in a key frame");
+            kps[f] = F.mvKeysUndistorted.data(); n[f] = F.N(); pose[f] = P;
+        }
+        for (const pgorb_map_point& p : points)
+            if (!std::isfinite(p.pos[0]) || !std::isfinite(p.pos[1]) || !std::isfinite(p.pos[2])) fail("a point is not finite");
+        if (obs.obsStart.size() != np + 1 || obs.obsStart[0] != 0) fail("obsStart is not npoints + 1 entries rising from 0");
+        for (size_t p = 0; p < np; p++) if (obs.obsStart[p + 1] < obs.obsStart[p]) fail("obsStart decreases");
+        const size_t nobs = (size_t)obs.obsStart[np];
+        if (obs.obsFrame.size() < nobs || obs.obsIdx.size() < nobs) fail("obsFrame or obsIdx is shorter than obsStart says");
+        std::vector<int32_t> seen(nkf + 1, -1);
+        for (size_t p = 0; p < np; p++)
+            for (int k = obs.obsStart[p]; k < obs.obsStart[p + 1]; k++) {
+                const int f = obs.obsFrame[k], i = obs.obsIdx[k];
+                if (f < 0 || f >= (int)nkf || i < 0 || i >= n[f]) fail("an observation names a key frame or keypoint out of range");
+                if (seen[f] == (int)p) fail("a list names a key frame twice");
+                seen[f] = (int)p;
+                const int o = kps[f][i].octave;
+                if (levels > 0 && (o < 0 || o >= levels)) fail("an octave is outside the context's levels");
+            }
+        GlobalBundleAdjustmentResult r;
+        r.poses.resize(nkf + 1);
+        r.pos.assign(3 * (np + 1), 0.0f); r.kfDone.assign(nkf + 1, 0); r.pointDone.assign(np + 1, 0); r.chi2.assign(nobs + 1, 0.0f);
+        std::vector<pgorb_map_point> none(1);
+        const int rc = pgorb_global_bundle_adjustment(ctx_, (int)nkf, kps.data(), n.data(), pose.data(), kfBad.empty() ? nullptr : kfBad.data(),
+                                                      kfFixedId0.empty() ? nullptr : kfFixedId0.data(), (int)np, np ? points.data() : none.data(),
+                                                      pointBad.empty() ? nullptr : pointBad.data(), obs.obsStart.data(), obs.obsFrame.data(),
+                                                      obs.obsIdx.data(), nIterations, bRobust ? 1 : 0, inPlace ? 1 : 0, r.poses.data(), r.pos.data(),
+                                                      r.kfDone.data(), r.pointDone.data(), r.chi2.data(), r.info);
+        if (rc < 0) throw std::runtime_error(pgorb_last_error(ctx_));
+        r.poses.resize(nkf); r.pos.resize(3 * np); r.kfDone.resize(nkf); r.pointDone.resize(np); r.chi2.resize(nobs);
+        r.optimised = rc;
+        return r;
+    }
     // Optimizer::OptimizeEssentialGraph(pMap, pLoopKF, pCurKF, NonCorrectedSim3, CorrectedSim3, LoopConnections, bFixScale)
     // (Optimizer.cc:781-1044) on the GPU.  points (pos is read and corrected in place) and pointBad (empty = none) are the table;
     // pMP->UpdateNormalAndDepth() is pgorb_refresh_map_points with PGORB_MP_NORMAL_DEPTH afterwards.  Everything

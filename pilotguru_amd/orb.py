@@ -848,6 +848,8 @@ LBA_ROLE_NONE, LBA_ROLE_LOCAL, LBA_ROLE_FIXED = 0, 1, 2
 LBA_MAX_LOCAL_KF, LBA_MAX_FIXED_KF, LBA_MAX_POINTS, LBA_MAX_EDGES = 64, 256, 8192, 65536
 EG_NOTHING, EG_NONFINITE, EG_LIMIT, EG_INFO = 1, 2, 4, 10
 EG_MAX_KF, EG_MAX_EDGES, EG_MAX_ENVELOPE_BLOCKS = 2048, 65536, 131072
+GBA_NOTHING, GBA_NONFINITE, GBA_LIMIT, GBA_INFO = 1, 2, 4, 8
+GBA_MAX_KF, GBA_MAX_POINTS, GBA_MAX_EDGES, GBA_MAX_ENVELOPE_BLOCKS = 2048, 262144, 2097152, 131072
 SIM3D_DTYPE = np.dtype([("r", "<f8", (4,)), ("t", "<f8", (3,)), ("s", "<f8")])                    # pgorb_sim3d: g2o::Sim3
 EG_EDGE_DTYPE = np.dtype([("i", "<i4"), ("j", "<i4"), ("kind", "<i4"), ("pad", "<i4"), ("chi2", "<f8")])
 
@@ -1125,6 +1127,123 @@ class Optimizer:
             ext._h, q(d_kps), q(d_n), nframes, cap, q(d_pose), q(d_kf_bad), q(d_kf_point), q(d_kf_fixed_id0), q(d_win_start), q(d_win_kf), nwin,
             nwin_kf, npoints, q(d_points), q(d_point_bad), q(d_obs_start), q(d_obs_frame), q(d_obs_idx), nobs, int(rounds), q(out["pose_out"]),
             q(out["erase"]), q(out["chi2"]), q(out["level"]), q(out["is_local"]), q(out["role"]), q(out["info"]), q(out["nerased"]), C.c_void_p(s)))
+        return out
+
+    @staticmethod
+    def GlobalBundleAdjustment(key_frames, poses, points, obs_start, obs_frame, obs_idx, point_bad=None, kf_bad=None, kf_fixed_id0=None,
+                               iterations=10, robust=False, in_place=False, ext=None):
+        """Optimizer::GlobalBundleAdjustemnt (thirdparty/orb-slam2/src/Optimizer.cc:41-237, monocular) on the GPU.  key_frames:
+        Frame-like objects IN RISING mnId ORDER (ext, N, mvKeysUndistorted: pt and octave are read); poses[f]: KF_POSE_DTYPE (Tcw and
+        the camera are read); kf_bad[f] = isBad(), kf_fixed_id0[f] = (mnId == 0) (None = none).  points (MAP_POINT_DTYPE; pos is
+        read), point_bad, and the observations as CSR of (obs_frame, obs_idx) as for RefreshMapPoints.  iterations: 10 from loop
+        closing, 20 from initialisation; robust: RobustKernelHuber with (float)sqrt(5.99); in_place: the nLoopKF == 0 branch, the
+        returned table then holds the done points' new positions.  Every input pgorb_global_bundle_adjustment refuses is a ValueError
+        here, before the library is called; a map past a capacity (GBA_MAX_*) raises PgorbError.  Returns a dict: ret (the free
+        active vertices), poses (every live key frame replaced), pos [npoints][3], kf_done, point_done, chi2 per observation, points
+        (a copy of the table, written when in_place), status, edges, included_points, vertices, iterations, trials, envelope."""
+        fn = "GlobalBundleAdjustment"
+        nkf = len(key_frames)
+        if ext is None:
+            if not nkf:
+                raise ValueError(fn + ": no key frame and no ext")
+            ext = key_frames[0].ext
+        if int(iterations) < 0:
+            raise ValueError(fn + ": iterations is negative")
+        if len(poses) != nkf:
+            raise ValueError(fn + ": key_frames and poses differ in length")
+        pts = np.array(np.ascontiguousarray(points, MAP_POINT_DTYPE).reshape(-1))       # a copy: moved in place
+        n = len(pts)
+        if not np.isfinite(pts["pos"]).all():
+            raise ValueError(fn + ": a point is not finite")
+        levels = ext.GetLevels()
+        P = np.zeros(max(nkf, 1), KF_POSE_DTYPE)
+        keep = []
+        kps = (C.c_void_p * max(nkf, 1))()
+        nk = np.zeros(max(nkf, 1), np.int32)
+        octs = []
+        for f, K in enumerate(key_frames):
+            if int(K.N) < 0:
+                raise ValueError("%s: key frame %d has a negative keypoint count" % (fn, f))
+            kp = _arr(K.mvKeysUndistorted, KEYPOINT_DTYPE, K.N, "key frame %d keypoints" % f)
+            kp_buf = kp if K.N else np.zeros(1, KEYPOINT_DTYPE)
+            keep.append(kp_buf)
+            kps[f], nk[f] = kp_buf.ctypes.data, K.N
+            octs.append(kp["octave"])
+            P[f] = np.asarray(poses[f], KF_POSE_DTYPE).reshape(())
+            cam = [float(P[f][k]) for k in ("fx", "fy", "cx", "cy")]
+            if not (np.isfinite(P[f]["Tcw"]).all() and np.isfinite(cam).all()):
+                raise ValueError(fn + ": a pose or a camera is not finite")
+            if cam[0] == 0.0 or cam[1] == 0.0:
+                raise ValueError(fn + ": fx or fy is zero")
+        kb, i0, pb = _mask(kf_bad, nkf, "kf_bad"), _mask(kf_fixed_id0, nkf, "kf_fixed_id0"), _mask(point_bad, n, "point_bad")
+        st = _arr(obs_start, np.int32, n + 1, "obs_start")
+        of = np.ascontiguousarray(obs_frame, np.int32).reshape(-1)
+        oi = np.ascontiguousarray(obs_idx, np.int32).reshape(-1)
+        if st[0] != 0 or np.any(np.diff(st) < 0) or len(of) < int(st[-1]) or len(oi) < int(st[-1]):
+            raise ValueError(fn + ": obs_start must rise from 0 to at most len(obs_frame), len(obs_idx)")
+        m = int(st[-1])
+        if m and (of[:m].min() < 0 or of[:m].max() >= nkf or oi[:m].min() < 0 or np.any(oi[:m] >= nk[np.clip(of[:m], 0, max(nkf - 1, 0))])):
+            raise ValueError(fn + ": an observation names a key frame or keypoint out of range")
+        owner = np.repeat(np.arange(n, dtype=np.int64), np.diff(st))
+        if len(np.unique(owner * max(nkf, 1) + of[:m])) != m:
+            raise ValueError(fn + ": a list names a key frame twice")
+        for k in range(m):
+            o = int(octs[of[k]][oi[k]])
+            if o < 0 or o >= levels:
+                raise ValueError("%s: an octave is outside the extractor's %d levels" % (fn, levels))
+        if len(of) == 0:
+            of, oi = np.zeros(1, np.int32), np.zeros(1, np.int32)
+        po, pos = np.zeros(max(nkf, 1), KF_POSE_DTYPE), np.zeros((max(n, 1), 3), np.float32)
+        kd, pd, chi = np.zeros(max(nkf, 1), np.uint8), np.zeros(max(n, 1), np.uint8), np.zeros(max(m, 1), np.float32)
+        info = np.zeros(GBA_INFO, np.int32)
+        pts_buf = pts if n else np.zeros(1, MAP_POINT_DTYPE)
+        ret = ext._check(ext._L.pgorb_global_bundle_adjustment(
+            ext._h, nkf, kps, _p(nk), _p(P), _p(kb), _p(i0), n, _p(pts_buf), _p(pb), _p(st), _p(of), _p(oi), int(iterations), int(bool(robust)),
+            int(bool(in_place)), _p(po), _p(pos), _p(kd), _p(pd), _p(chi), _p(info)))
+        return dict(ret=ret, poses=po[:nkf].copy(), pos=pos[:n].copy(), kf_done=kd[:nkf].copy(), point_done=pd[:n].copy(), chi2=chi[:m].copy(),
+                    points=pts, status=int(info[0]), edges=int(info[1]), included_points=int(info[2]), vertices=int(info[3]),
+                    iterations=int(info[5]), trials=int(info[6]), envelope=int(info[7]))
+
+    @staticmethod
+    def GlobalBundleAdjustment_device(ext, d_kps, d_n, cap_per_frame, d_pose, npoints, d_points, d_obs_start, d_obs_frame, d_obs_idx,
+                                      d_point_bad=None, d_kf_bad=None, d_kf_fixed_id0=None, iterations=10, robust=False, in_place=False,
+                                      want_chi2=True, stream=None):
+        """pgorb_global_bundle_adjustment_device over resident torch tensors: the frames of one batch in rising mnId order and the
+        table.  The sizes and element types are checked here; the contents are not read.  Returns a dict of tensors: pose_out (bytes
+        of KF_POSE_DTYPE per frame), pos_out [npoints][3], kf_done, point_done, chi2 [nobs] (None without want_chi2), info [GBA_INFO]
+        (info[4] = the free active vertices).  With in_place d_points holds the done points' new positions and the chain into
+        pMP->UpdateNormalAndDepth() is pgorb_refresh_map_points_batch_device on the same d_points with d_pose = pose_out."""
+        import torch
+        name = "Optimizer.GlobalBundleAdjustment_device"
+        if int(iterations) < 0:
+            raise ValueError(name + ": iterations is negative")
+        for nm, t_ in (("d_n", d_n), ("d_obs_start", d_obs_start), ("d_obs_frame", d_obs_frame), ("d_obs_idx", d_obs_idx)):
+            if t_.dtype != torch.int32:
+                raise ValueError("%s: %s must be an int32 tensor (the counts are taken from element counts)" % (name, nm))
+        nframes, cap, npoints, nobs = int(d_n.numel()), int(cap_per_frame), int(npoints), int(d_obs_frame.numel())
+        if cap < 1 or cap > Sim3Solver.MAX_N:
+            raise ValueError("%s: cap_per_frame outside [1, %d]" % (name, Sim3Solver.MAX_N))
+        if npoints < 0 or int(d_obs_start.numel()) != npoints + 1 or int(d_obs_idx.numel()) != nobs:
+            raise ValueError("%s: d_obs_start needs npoints + 1 entries, d_obs_frame and d_obs_idx the same length" % name)
+        if d_kps.numel() * d_kps.element_size() != nframes * cap * KEYPOINT_DTYPE.itemsize or \
+                d_pose.numel() * d_pose.element_size() != nframes * KF_POSE_DTYPE.itemsize:
+            raise ValueError("%s: d_kps and d_pose must hold one row per frame of d_n" % name)
+        if d_points.numel() * d_points.element_size() < npoints * MAP_POINT_DTYPE.itemsize:
+            raise ValueError("%s: the table is shorter than npoints" % name)
+        for nm, t_, need in (("d_point_bad", d_point_bad, npoints), ("d_kf_bad", d_kf_bad, nframes), ("d_kf_fixed_id0", d_kf_fixed_id0, nframes)):
+            if t_ is not None and t_.numel() * t_.element_size() < need:
+                raise ValueError("%s: %s is too short" % (name, nm))
+        dev = d_n.device
+        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)
+        out = dict(pose_out=torch.zeros_like(d_pose), pos_out=z((npoints, 3), torch.float32), kf_done=z((nframes,), torch.uint8),
+                   point_done=z((npoints,), torch.uint8), chi2=z((nobs,), torch.float32) if want_chi2 else None, info=z((GBA_INFO,), torch.int32))
+        q = lambda t: None if t is None or t.numel() == 0 else C.c_void_p(t.data_ptr())
+        s = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        ext._check(ext._L.pgorb_global_bundle_adjustment_device(
+            ext._h, q(d_kps), q(d_n), nframes, cap, q(d_pose), q(d_kf_bad), q(d_kf_fixed_id0), npoints, q(d_points), q(d_point_bad),
+            C.c_void_p(d_obs_start.data_ptr()), q(d_obs_frame), q(d_obs_idx), nobs, int(iterations), int(bool(robust)), int(bool(in_place)),
+            q(out["pose_out"]), q(out["pos_out"]), q(out["kf_done"]), q(out["point_done"]), q(out["chi2"]), C.c_void_p(out["info"].data_ptr()),
+            C.c_void_p(s)))
         return out
 
     @staticmethod

@@ -76,8 +76,13 @@ next to each, the oracle's CPU time for the same work (1 thread, a few frames, s
                loop edge and the new loop's three connections -- over its fixed sequence of launches (HIP events around the call alone);
                beside it the wall clock of the dense numpy reference of the tests (tests/eg_reference.py) on the same shape with 100 key
                frames (it is cubic in the key frames): NOT g2o and not a CPU baseline.  No target is set.  --eg-only runs this row
+  global_ba        Optimizer::GlobalBundleAdjustemnt (Optimizer.cc:41-237) on the device (pgorb_global_bundle_adjustment_device,
+               csrc/global_ba.hip): ONE ride-shaped map of 500 key frames (about 40 points a key frame over 4 frames, one old loop and
+               the new one), and LocalBundleAdjustment's benchmark window (40 key frames, 2000 points, 12 000 edges) through both
+               optimisers in the same run, with the time per Levenberg trial.  No target is set.  --gba-only runs these rows
+               (profiles/next_tier_gba.txt).
 
-usage: python tools/next_tier_bench.py [--batch 128] [--out profiles/r02_next_tier.txt] [--refresh-only | --place-only | --loop-only | --track-only | --pose-only | --sim3-only | --pnp-only | --optsim3-only | --lba-only | --eg-only]"""
+usage: python tools/next_tier_bench.py [--batch 128] [--out profiles/r02_next_tier.txt] [--refresh-only | --place-only | --loop-only | --track-only | --pose-only | --sim3-only | --pnp-only | --optsim3-only | --lba-only | --eg-only | --gba-only]"""
 import argparse, ctypes as C, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -102,6 +107,7 @@ ap.add_argument("--pnp-only", action="store_true", help="the PnPsolver rows alon
 ap.add_argument("--optsim3-only", action="store_true", help="the OptimizeSim3 rows alone (no ride, no vocabulary)")
 ap.add_argument("--lba-only", action="store_true", help="the LocalBundleAdjustment rows alone (no ride, no vocabulary)")
 ap.add_argument("--eg-only", action="store_true", help="the OptimizeEssentialGraph row alone (no ride, no vocabulary)")
+ap.add_argument("--gba-only", action="store_true", help="the GlobalBundleAdjustment rows alone (no ride, no vocabulary)")
 a = ap.parse_args()
 w, h, nf, B = 1920, 1080, a.features, a.batch
 
@@ -635,6 +641,65 @@ def eg_lines(nkf=500, nref=100, back=4):
             "%-128s %10.3f %22.1f" % ("essential_graph: " + scene, t, t_ref)]
 
 
+def gba_lines(nkf=500, per_kf=40, span=4):
+    """GlobalBundleAdjustment: a ride-shaped map in the resident call, and LocalBundleAdjustment's benchmark window through both."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import warnings
+    import gba_cases as GC
+    import lba_cases as LC
+    warnings.simplefilter("ignore")
+    ext = pg.ORBextractor(2000, 1.2, 8, 20, 7, max_width=640, max_height=480)
+
+    def timed(name, reps=5):
+        D = GC.device_arrays(GC.case(name)[0])
+        ms, r = [], None
+        for _ in range(reps + 1):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            P, its, robust, in_place = GC.case(name)
+            T, cap = D[0], D[1]
+            e0.record()
+            out = pg.Optimizer.GlobalBundleAdjustment_device(ext, T["kps"], T["n"], cap, T["pose"], len(P.pos), T["pts"], T["os"], T["of"], T["oi"],
+                                                             T["pb"], T["kb"], T["id0"], its, robust, in_place)
+            e1.record(); torch.cuda.synchronize()
+            ms.append(e0.elapsed_time(e1))
+            r = out["info"].cpu().numpy()
+        return float(np.median(ms[1:])), r
+    # the ride: points over `span` consecutive key frames, one old loop and the new one
+    B, cams = GC._chain(7100, nkf, nkf * per_kf // span, nobs=span, far=20)
+    for k in range(40):
+        p = B.add_point([B.rng.uniform(-1, 1), B.rng.uniform(-1, 1), B.rng.uniform(25, 35)], 0.3)
+        for f in ((3 * nkf // 5, nkf // 10) if k < 20 else (nkf - 2, nkf - 1, 0, 1)):
+            B.observe(p, f)
+    GC._cache["bench_ride"] = (B.problem([], 0, "bench_ride", extra_keys=0), 10, 0, 0)
+    t_ride, i_ride = timed("bench_ride")
+    # LBA's benchmark window, through LBA (one workgroup) and through GBA (many) on the same machine in the same run
+    W = LC.window("bench", 7000, 20, 20, 2000, nobs=6, noise=0.7, outliers=2000 * 6 // 50, far=20)
+    LC._cache["bench"] = (W, 2)
+    one = LC.Batch(["bench"])
+    r1 = LC.run_gpu_batch(one, ext, time_reps=5)[0]
+    li = r1["info"]
+    GC._cache["bench_window"] = (W, 10, 0, 0)
+    t_win, i_win = timed("bench_window")
+    row = lambda i: "%d key frames (%d free), %d points, %d edges, %d envelope blocks, %d iterations, %d trials" % (i[3], i[4], i[2], i[1], i[7], i[5], i[6])
+    return ["# Optimizer::GlobalBundleAdjustemnt on the device, resident call, HIP events around the call alone (its six output arrays are allocated",
+            "# inside it), median of 5 after one warm-up: k_gba_prepare, 10 x (k_gba_linearize, k_gba_begin, 10 x (k_gba_schur, k_gba_solve, k_gba_try,",
+            "# k_gba_decide)), k_gba_finish = 422 launches, of which those behind the stop flag or the end of their iteration return at once.",
+            "# The window row is LocalBundleAdjustment's benchmark window; local_ba adjusts its 20 local key frames in one workgroup (two rounds, robust",
+            "# first), global_ba all 40 over many workgroups (one round, not robust): compare the time per Levenberg trial.  No g2o build exists",
+            "# here to time; no target is set.",
+            "%-132s %10s %14s" % ("call", "GPU ms", "GPU ms/trial"),
+            "%-132s %10.3f %14.4f" % ("global_ba, ride: " + row(i_ride), t_ride, t_ride / max(int(i_ride[6]), 1)),
+            "%-132s %10.3f %14.4f" % ("global_ba, window: " + row(i_win), t_win, t_win / max(int(i_win[6]), 1)),
+            "%-132s %10.3f %14.4f" % ("local_ba, window: %d local + %d fixed key frames, %d points, %d edges, %d + %d iterations, %d + %d trials" % (
+                li[3], li[4], li[2], li[1], li[5], li[7], li[6], li[8]), one.ms, one.ms / max(int(li[6] + li[8]), 1))]
+
+
+if a.gba_only:
+    lines = ["# python tools/next_tier_bench.py --gba-only   (MI355X)"] + gba_lines()
+    print("\n".join(lines))
+    if a.out:
+        open(a.out, "w").write("\n".join(lines) + "\n")
+    sys.exit(0)
 if a.eg_only:
     lines = ["# python tools/next_tier_bench.py --eg-only   (MI355X)"] + eg_lines()
     print("\n".join(lines))

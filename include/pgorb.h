@@ -1007,6 +1007,73 @@ int  pgorb_pnp_solver_batch_device(pgorb_ctx* ctx, const pgorb_keypoint* d_kps, 
         uint8_t* d_best_inlier, pgorb_kf_pose* d_best_pose, pgorb_kf_pose* d_pose_out, uint8_t* d_inlier, int32_t* d_kp_point_out,
         pgorb_pnp_hypothesis* d_trace, int32_t* d_info, int32_t* d_ninliers, void* hip_stream);
 
+/*   pgorb_initializer   Initializer::Initialize (src/Initializer.cc:33-929; Tracking::MonocularInitialization, src/Tracking.cc:564-631)
+ *       with the constructive part of Tracking::CreateInitialMapMonocular (:633-680): the step between
+ *       pgorb_search_for_initialization and the first pgorb_global_bundle_adjustment.  max_iterations sets of 8 matches, a homography
+ *       and a fundamental matrix from each (the SAME set for both), each scored over all N matches; RH = SH/(SH + SF) picks the model
+ *       (> 0.40: H); its 8 (H) or 4 (F) motion hypotheses are triangulated over the model's inliers and the reference's decision
+ *       is taken.  It is this project's READING of cv::Mat arithmetic and of OpenCV 2.4.9's JacobiSVDImpl_<float>, completion loop
+ *       included (DESIGN.md sections 4 and 5): an 8-point hypothesis depends on that routine to the last bit, so the device is
+ *       pinned to tests/init_reference.py byte for byte; only the parallax (an acos) is compared with a tolerance.
+ * Inputs.  kps1 / kps2: mvKeysUndistorted of the reference and the current frame (only pt is read; Normalize runs over ALL of
+ * them).  camera: fx, fy, cx, cy are read (the whole record is copied into pose_out).  matches12[i1] = i2 or -1 (vMatches12, what
+ * pgorb_search_for_initialization writes).  params: sigma and max_iterations (Tracking.cc:578 passes 1.0 and 200), min_parallax and
+ * min_triangulated (Initializer.cc:116-118 pass 1.0 and 50).  draws [max_iterations][8]: raw rand() values in [0, 2^31); the
+ * library applies RandomInt's formula and the swap-with-back selection over a fresh vAvailableIndices per iteration.
+ * Outputs.  The return value is the number of triangulated matches, 0 when Initialize would return false.  pose_out[0] = the
+ * identity pose of the reference frame, pose_out[1] = [R21 | t21], both complete records (Ow as Frame::SetPose, the camera
+ * copied).  P3D [n1][3] = vP3D and triangulated [n1] = vbTriangulated (entries CheckRT never writes are zeros); matches12_out[i] =
+ * matches12[i] where triangulated, else -1 (Tracking.cc:612-619).  On failure pose_out, P3D, triangulated are zeroed and
+ * matches12_out is all -1; trace, info and finfo are still written.
+ * The map (all seven NULL together, or none): one point per triangulated match in rising i1 order, points[k].pos = P3D[i1] with
+ * the normal and the distances zero (pgorb_refresh_map_points fills them); kf_point1 [n1] / kf_point2 [n2] = the slot or -1;
+ * obs_start [n1 + 1] (2*min(k, npoints)), obs_frame / obs_idx [2*n1] = (f1, i1) then (f2, i2) per point, -1 past the points (the
+ * single call's frames are 0 and 1); *npoints.  This is what pgorb_refresh_map_points and pgorb_global_bundle_adjustment_device
+ * read.  The median-depth rescale and its two acceptance tests (Tracking.cc:685-711) stay with the caller.
+ * trace (may be NULL) [max_iterations]: every hypothesis.  info [PGORB_INIT_INFO] int32: [0] status bits, [1] N, [2] best iteration
+ * of H or -1, [3] its inliers, [4] best iteration of F or -1, [5] its inliers, [6] the motion hypothesis the decision examined or
+ * -1, [7..14] nGood of the 8 (4) hypotheses, [15] the chosen model's inlier count, [16] the return value.  finfo
+ * [PGORB_INIT_FINFO] float: [0] SH, [1] SF, [2] RH, [3..10] the parallaxes.
+ * Errors, single call, checked on the host first: PGORB_E_ARG (a negative count, a NULL array that is read or written, matches12
+ * outside [-1, n2), a coordinate or camera value that is not finite, sigma <= 0, max_iterations < 1, a draw >= 2^31);
+ * PGORB_E_LIMIT (more than 16000 keypoints in a frame, max_iterations > PGORB_INIT_MAX_ITERATIONS).
+ *   pgorb_initializer_batch_device: pair p initialises from frames d_pair_f1[p] (reference) and d_pair_f2[p] (current) of one
+ *       batch in the layout of pgorb_extract_batch_device, with the camera of frame d_pair_f1[p]; d_matches12 [npairs][cap] is
+ *       what pgorb_search_for_initialization_batch_device writes; d_draws [npairs][max_iterations][8].  Outputs by pair:
+ *       d_pose_out [npairs][2], d_P3D [npairs][cap][3], d_triangulated, d_matches12_out [npairs][cap], the map (d_points,
+ *       d_kf_point1, d_kf_point2 [npairs][cap], d_obs_start [npairs][cap + 1], d_obs_frame, d_obs_idx [npairs][2*cap], d_npoints
+ *       [npairs]; frame indices are the batch's), d_trace [npairs][max_iterations], d_info [npairs][PGORB_INIT_INFO] (the count
+ *       is d_info[p][16]), d_finfo [npairs][PGORB_INIT_FINFO].  Checks the parameters and the limits only: a match index outside
+ *       [0, n[f2]) counts as no match.  Three launches (k_init_prepare, k_init_hypotheses, k_init_reconstruct), no atomics; the
+ *       scratch arena holds 40 + 136 bytes per (pair, keypoint slot) and 120 + cap/4 bytes per (pair, iteration). */
+typedef struct pgorb_init_params { float sigma; int32_t max_iterations; float min_parallax; int32_t min_triangulated; } pgorb_init_params;
+typedef struct pgorb_init_hypothesis { float H21[9], F21[9], scoreH, scoreF; int32_t inliersH, inliersF, set[8]; } pgorb_init_hypothesis;
+#define PGORB_INIT_FEW           1   /* N < 8: nothing is evaluated (the reference would index an empty vector) */
+#define PGORB_INIT_NO_MODEL      2   /* SH == 0 and SF == 0 */
+#define PGORB_INIT_MODEL_H       4   /* RH > 0.40 */
+#define PGORB_INIT_MODEL_F       8
+#define PGORB_INIT_OK            16  /* Initialize returned true */
+#define PGORB_INIT_DEGENERATE_H  32  /* d1/d2 < 1.00001 || d2/d3 < 1.00001 (:597) */
+#define PGORB_INIT_AMBIGUOUS     64  /* nsimilar > 1 (:517); secondBestGood < 0.75*bestGood false (:721) */
+#define PGORB_INIT_FEW_GOOD      128 /* maxGood < nMinGood (:517); either bestGood clause false (:721) */
+#define PGORB_INIT_LOW_PARALLAX  256 /* the parallax clause */
+#define PGORB_INIT_INFO          17
+#define PGORB_INIT_FINFO         11
+#define PGORB_INIT_MAX_ITERATIONS 1024
+int  pgorb_initializer(pgorb_ctx* ctx, const pgorb_keypoint* kps1, int n1, const pgorb_keypoint* kps2, int n2,
+        const pgorb_kf_pose* camera, const int32_t* matches12 /*[n1]*/, const pgorb_init_params* params,
+        const uint32_t* draws /*[max_iterations][8]*/, pgorb_kf_pose* pose_out /*[2]*/, float* P3D /*[n1][3]*/,
+        uint8_t* triangulated /*[n1]*/, int32_t* matches12_out /*[n1]*/,
+        pgorb_map_point* points /*[n1]*/, int32_t* kf_point1 /*[n1]*/, int32_t* kf_point2 /*[n2]*/, int32_t* obs_start /*[n1 + 1]*/,
+        int32_t* obs_frame /*[2*n1]*/, int32_t* obs_idx /*[2*n1]*/, int32_t* npoints,
+        pgorb_init_hypothesis* trace /*[max_iterations] or NULL*/, int32_t* info, float* finfo);
+int  pgorb_initializer_batch_device(pgorb_ctx* ctx, const pgorb_keypoint* d_kps, const int32_t* d_n, int cap_per_frame,
+        const int32_t* d_pair_f1, const int32_t* d_pair_f2, int npairs, const pgorb_kf_pose* d_camera /*by frame*/,
+        const int32_t* d_matches12, const pgorb_init_params* params /*host, one for all*/, const uint32_t* d_draws,
+        pgorb_kf_pose* d_pose_out, float* d_P3D, uint8_t* d_triangulated, int32_t* d_matches12_out,
+        pgorb_map_point* d_points, int32_t* d_kf_point1, int32_t* d_kf_point2, int32_t* d_obs_start, int32_t* d_obs_frame,
+        int32_t* d_obs_idx, int32_t* d_npoints, pgorb_init_hypothesis* d_trace, int32_t* d_info, float* d_finfo, void* hip_stream);
+
 /*   pgorb_local_bundle_adjustment  Optimizer::LocalBundleAdjustment(pKF, pbStopFlag, pMap) (src/Optimizer.cc:453-778) with the g2o
  *       path under it (VertexSE3Expmap, VertexSBAPointXYZ, EdgeSE3ProjectXYZ with its ANALYTIC Jacobian, RobustKernelHuber,
  *       BlockSolver_6_3 with the Schur complement over the marginalised points, OptimizationAlgorithmLevenberg), monocular (mvuRight

@@ -19,4 +19,6 @@ from .orb import (GBA_INFO, GBA_LIMIT, GBA_MAX_EDGES, GBA_MAX_ENVELOPE_BLOCKS, G
 from .orb import S3_FEW, S3_FOUND, S3_INFO, S3_NO_MORE, SIM3_ESTIMATE_DTYPE, SIM3_MAX_ITERATIONS, SIM3_PARAMS_DTYPE, Sim3Solver  # noqa: F401
 from .orb import (PNP_FEW, PNP_FOUND, PNP_HYPOTHESIS_DTYPE, PNP_INFO, PNP_MAX_WINDOW, PNP_NO_MORE, PNP_PARAMS_DTYPE, PNP_REFINED,  # noqa: F401
                   PnPsolver)
+from .orb import (INIT_AMBIGUOUS, INIT_DEGENERATE_H, INIT_FEW, INIT_FEW_GOOD, INIT_FINFO, INIT_HYPOTHESIS_DTYPE, INIT_INFO,  # noqa: F401
+                  INIT_LOW_PARALLAX, INIT_MAX_ITERATIONS, INIT_MODEL_F, INIT_MODEL_H, INIT_NO_MODEL, INIT_OK, INIT_PARAMS_DTYPE, Initializer)
 from .place import KeyFrameDatabase  # noqa: F401

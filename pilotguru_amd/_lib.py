@@ -52,6 +52,7 @@ SYMBOLS = (
     "pgorb_sim3_solver", "pgorb_sim3_solver_batch_device", "pgorb_sim3_max_iterations",
     "pgorb_optimize_sim3", "pgorb_optimize_sim3_batch_device",
     "pgorb_pnp_solver", "pgorb_pnp_solver_batch_device", "pgorb_pnp_ransac",
+    "pgorb_initializer", "pgorb_initializer_batch_device",
     "pgorb_local_bundle_adjustment", "pgorb_local_bundle_adjustment_batch_device",
     "pgorb_optimize_essential_graph", "pgorb_optimize_essential_graph_device",
     "pgorb_global_bundle_adjustment", "pgorb_global_bundle_adjustment_device",
@@ -210,6 +211,12 @@ def lib():
     #  best_inlier, best_pose, pose_out, inlier, kp_point_out, trace, info, ninliers, stream)
     L.pgorb_pnp_solver_batch_device.argtypes = [vp, vp, vp, C.c_int, vp, C.c_int, vp, vp, C.c_int] + [vp] * 15
     L.pgorb_pnp_ransac.argtypes = [C.c_float, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, i32p, i32p]
+    # (ctx, kps1, n1, kps2, n2, camera, matches12, params, draws, pose_out, P3D, triangulated, matches12_out, points, kf_point1, kf_point2,
+    #  obs_start, obs_frame, obs_idx, npoints, trace, info, finfo)
+    L.pgorb_initializer.argtypes = [vp, vp, C.c_int, vp, C.c_int] + [vp] * 18
+    # (ctx, kps, n, cap, pair_f1, pair_f2, npairs, camera, matches12, params, draws, pose_out, P3D, triangulated, matches12_out, points,
+    #  kf_point1, kf_point2, obs_start, obs_frame, obs_idx, npoints, trace, info, finfo, stream)
+    L.pgorb_initializer_batch_device.argtypes = [vp, vp, vp, C.c_int, vp, vp, C.c_int] + [vp] * 19
     # (ctx, kps1, n1, pose1, kf_point1, kps2, n2, pose2, kf_point2, matches12, new_matches12, npoints, points, point_bad, estimate, th2,
     #  fix_scale, estimate_out, matches12_out, chi2_12, chi2_21, scw_pose, info)
     L.pgorb_optimize_sim3.argtypes = [vp, vp, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp, vp, C.c_int, vp, vp, vp, C.c_float, C.c_int] + [vp] * 6

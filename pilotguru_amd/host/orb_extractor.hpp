@@ -8,6 +8,7 @@
 // pilotguru maintainer drops into Frame::ExtractORB.
 #pragma once
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <stdexcept>
 #include <string>
@@ -914,6 +915,82 @@ class PnPsolver {
     std::vector<uint32_t> draws_;
     pgorb_pnp_params prm_{};
     int N_ = 0;
+};
+
+// Initializer (src/Initializer.cc) over pgorb_initializer: the constructor and Initialize.  ReferenceFrame / CurrentFrame:
+// mvKeysUndistorted (pt is read); camera: fx, fy, cx, cy are read (mK); draws: [>= iterations][8] raw rand() values in [0, 2^31).
+// After Initialize: pose (Tracking.cc:622-626), matches12Out (Tracking.cc:612-619) and the map of CreateInitialMapMonocular
+// (points, kfPoint1, kfPoint2, obs) as pgorb_refresh_map_points and pgorb_global_bundle_adjustment read it.
+// Everything pgorb_initializer refuses is a std::invalid_argument here, before the library is called.
+class Initializer {
+ public:
+    Initializer(pgorb_ctx* ctx, const Frame& ReferenceFrame, const pgorb_kf_pose& camera, std::vector<uint32_t> draws, float sigma = 1.0f,
+                int iterations = 200, float minParallax = 1.0f, int minTriangulated = 50)
+        : ctx_(ctx), keys1_(ReferenceFrame.mvKeysUndistorted), camera_(camera), draws_(std::move(draws)),
+          prm_{sigma, iterations, minParallax, minTriangulated}
+    {
+        keys1_.resize(ReferenceFrame.N());
+        checkKeys(keys1_);
+        if (!std::isfinite(camera.fx) || !std::isfinite(camera.fy) || !std::isfinite(camera.cx) || !std::isfinite(camera.cy)) fail("the camera is not finite");
+        if (!(sigma > 0.0f) || !std::isfinite(sigma) || !std::isfinite(minParallax)) fail("sigma must be positive and finite, minParallax finite");
+        if (iterations < 1) fail("iterations is below 1");
+        if (iterations > PGORB_INIT_MAX_ITERATIONS) fail("iterations above PGORB_INIT_MAX_ITERATIONS");
+        if (draws_.size() < (size_t)iterations * 8) fail("fewer than iterations x 8 draws");
+        for (size_t k = 0; k < (size_t)iterations * 8; k++)
+            if (draws_[k] >= 0x80000000u) fail("a draw is not below 2^31");
+    }
+    // Initializer::Initialize (:44-121): R21 [9] and t21 [3] row-major (written when true), vP3D [n1][3], vbTriangulated [n1]
+    bool Initialize(const Frame& CurrentFrame, const std::vector<int32_t>& vMatches12, float R21[9], float t21[3],
+                    std::vector<std::array<float, 3>>& vP3D, std::vector<bool>& vbTriangulated)
+    {
+        std::vector<pgorb_keypoint> keys2(CurrentFrame.mvKeysUndistorted);
+        keys2.resize(CurrentFrame.N());
+        checkKeys(keys2);
+        const int n1 = (int)keys1_.size(), n2 = (int)keys2.size();
+        if (vMatches12.size() != (size_t)n1) fail("vMatches12 is not N entries long");
+        for (int i = 0; i < n1; i++)
+            if (vMatches12[i] < -1 || vMatches12[i] >= n2) fail("vMatches12 is outside [-1, n2)");
+        const size_t c1 = n1 > 0 ? n1 : 1, c2 = n2 > 0 ? n2 : 1;
+        std::vector<float> p3d(3 * c1, 0.0f);
+        std::vector<uint8_t> tri(c1, 0);
+        matches12Out.assign(c1, -1);
+        points.assign(c1, pgorb_map_point{});
+        kfPoint1.assign(c1, -1); kfPoint2.assign(c2, -1);
+        obsStart.assign(c1 + 1, 0); obsFrame.assign(2 * c1, -1); obsIdx.assign(2 * c1, -1);
+        int32_t np = 0;
+        const int rc = pgorb_initializer(ctx_, keys1_.data(), n1, keys2.data(), n2, &camera_, vMatches12.data(), &prm_, draws_.data(), pose,
+                                         p3d.data(), tri.data(), matches12Out.data(), points.data(), kfPoint1.data(), kfPoint2.data(),
+                                         obsStart.data(), obsFrame.data(), obsIdx.data(), &np, nullptr, info, finfo);
+        if (rc < 0) throw std::runtime_error(pgorb_last_error(ctx_));
+        matches12Out.resize(n1); kfPoint1.resize(n1); kfPoint2.resize(n2);
+        points.resize(np); obsStart.resize(np + 1); obsFrame.resize(2 * np); obsIdx.resize(2 * np);
+        vP3D.assign(n1, std::array<float, 3>{});
+        vbTriangulated.assign(n1, false);
+        for (int i = 0; i < n1; i++) { vP3D[i] = {p3d[3 * i], p3d[3 * i + 1], p3d[3 * i + 2]}; vbTriangulated[i] = tri[i] != 0; }
+        const bool ok = (info[0] & PGORB_INIT_OK) != 0;
+        if (ok)
+            for (int r = 0; r < 3; r++) { for (int c = 0; c < 3; c++) R21[3 * r + c] = pose[1].Tcw[4 * r + c]; t21[r] = pose[1].Tcw[4 * r + 3]; }
+        return ok;
+    }
+
+    pgorb_kf_pose pose[2] = {};                                             // the reference frame's identity pose, [R21 | t21]
+    std::vector<int32_t> matches12Out, kfPoint1, kfPoint2, obsStart, obsFrame, obsIdx;
+    std::vector<pgorb_map_point> points;
+    int32_t info[PGORB_INIT_INFO] = {};
+    float finfo[PGORB_INIT_FINFO] = {};
+ private:
+    static void fail(const char* m) { throw std::invalid_argument(std::string("Initializer: ") + m); }
+    static void checkKeys(const std::vector<pgorb_keypoint>& k)
+    {
+        if (k.size() > 16000) fail("more than 16000 keypoints in the frame");
+        for (const pgorb_keypoint& q : k)
+            if (!std::isfinite(q.x) || !std::isfinite(q.y)) fail("a keypoint coordinate is not finite");
+    }
+    pgorb_ctx* ctx_;
+    std::vector<pgorb_keypoint> keys1_;                                     // a copy: the initializer may outlive its Frame
+    pgorb_kf_pose camera_;
+    std::vector<uint32_t> draws_;
+    pgorb_init_params prm_;
 };
 
 namespace detail {

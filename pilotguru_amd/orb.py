@@ -1764,6 +1764,166 @@ class PnPsolver:
         return out
 
 
+# pgorb_initializer: the parameter block, a traced hypothesis, the status bits, the info tables and the limit (include/pgorb.h)
+INIT_PARAMS_DTYPE = np.dtype([("sigma", "<f4"), ("max_iterations", "<i4"), ("min_parallax", "<f4"), ("min_triangulated", "<i4")])
+INIT_HYPOTHESIS_DTYPE = np.dtype([("H21", "<f4", (9,)), ("F21", "<f4", (9,)), ("scoreH", "<f4"), ("scoreF", "<f4"), ("inliersH", "<i4"),
+                                  ("inliersF", "<i4"), ("set", "<i4", (8,))])
+INIT_FEW, INIT_NO_MODEL, INIT_MODEL_H, INIT_MODEL_F, INIT_OK, INIT_DEGENERATE_H, INIT_AMBIGUOUS, INIT_FEW_GOOD, INIT_LOW_PARALLAX = \
+    1, 2, 4, 8, 16, 32, 64, 128, 256
+INIT_INFO, INIT_FINFO, INIT_MAX_ITERATIONS = 17, 11, 1024
+
+
+def _camera_record(camera, name):
+    """a KF_POSE_DTYPE record from one, or from (fx, fy, cx, cy); the four values must be finite"""
+    if getattr(camera, "dtype", None) == KF_POSE_DTYPE:
+        P = np.array(camera, KF_POSE_DTYPE).reshape(1)
+    else:
+        fx, fy, cx, cy = (np.float32(x) for x in camera)
+        P = np.zeros(1, KF_POSE_DTYPE)
+        with np.errstate(all="ignore"):
+            P["fx"], P["fy"], P["cx"], P["cy"], P["invfx"], P["invfy"] = fx, fy, cx, cy, np.float32(1) / fx, np.float32(1) / fy
+    if not np.isfinite([float(P[q][0]) for q in ("fx", "fy", "cx", "cy")]).all():
+        raise ValueError("%s: the camera is not finite" % name)
+    return P
+
+
+class Initializer:
+    """Initializer (thirdparty/orb-slam2/src/Initializer.cc) on the GPU, with the reference's surface: the constructor and
+    Initialize.  ReferenceFrame / CurrentFrame: Frame-like objects (ext, N, mvKeysUndistorted: pt is read); camera: a KF_POSE_DTYPE
+    record or (fx, fy, cx, cy) (mK; default ReferenceFrame.camera).  draws: [>= iterations][8] raw rand() values in [0, 2^31);
+    None draws them from numpy's RandomState(seed).  After Initialize: status / info / finfo, pose (the two KF_POSE_DTYPE records of
+    Tracking.cc:622-626), matches12_out (Tracking.cc:612-619) and map (the arrays pgorb_refresh_map_points and global bundle
+    adjustment read: points, kf_point1, kf_point2, obs_start, obs_frame, obs_idx, npoints); trace where trace=True.
+    Every input the library's checked call refuses is a ValueError here, before the library is called."""
+    MAX_N = 16000
+
+    def __init__(self, ReferenceFrame, sigma=1.0, iterations=200, draws=None, camera=None, seed=0, minParallax=1.0, minTriangulated=50):
+        self.ext = ReferenceFrame.ext
+        self._k1 = self.check_frame("Initializer", ReferenceFrame)
+        self._cam = _camera_record(camera if camera is not None else ReferenceFrame.camera, "Initializer")
+        self.check_params("Initializer", sigma, iterations, minParallax, draws)
+        self.mSigma, self.mMaxIterations, self._draws_in, self._seed = float(sigma), int(iterations), draws, seed
+        self._min_parallax, self._min_tri = float(minParallax), int(minTriangulated)
+        self.info, self.finfo = np.zeros(INIT_INFO, np.int32), np.zeros(INIT_FINFO, np.float32)
+
+    @staticmethod
+    def check_frame(name, F):
+        n = int(F.N)
+        if n < 0:
+            raise ValueError("%s: a negative keypoint count" % name)
+        k = _arr(F.mvKeysUndistorted, KEYPOINT_DTYPE, n, name + " keypoints")
+        if n and not (np.isfinite(k["x"]).all() and np.isfinite(k["y"]).all()):
+            raise ValueError("%s: a keypoint coordinate is not finite" % name)
+        if n > Initializer.MAX_N:
+            raise ValueError("%s: more than %d keypoints in the frame" % (name, Initializer.MAX_N))
+        return k
+
+    @staticmethod
+    def check_params(name, sigma, iterations, minParallax=1.0, draws=None):
+        s = float(np.float32(sigma))
+        if not (s > 0.0 and np.isfinite(s)) or not np.isfinite(float(np.float32(minParallax))):
+            raise ValueError("%s: sigma must be positive and finite, minParallax finite" % name)
+        if int(iterations) < 1:
+            raise ValueError("%s: iterations is below 1" % name)
+        if int(iterations) > INIT_MAX_ITERATIONS:
+            raise ValueError("%s: iterations above %d" % (name, INIT_MAX_ITERATIONS))
+        if draws is not None:
+            d = np.asarray(draws)
+            if d.ndim < 2 or d.shape[-1] != 8 or d.shape[-2] < int(iterations):
+                raise ValueError("%s: draws must be [iterations][8]" % name)
+            if d.size and (int(d.min()) < 0 or int(d.max()) >= 2 ** 31):
+                raise ValueError("%s: a draw is not in [0, 2^31)" % name)
+
+    def Initialize(self, CurrentFrame, vMatches12, trace=False):
+        """Initializer::Initialize (:44-121).  Returns (ok, R21, t21, vP3D, vbTriangulated): R21 3 x 3 and t21 3 x 1 float32 (None
+        when ok is False), vP3D [n1][3] float32, vbTriangulated [n1] bool."""
+        k1, n1 = self._k1, len(self._k1)
+        k2 = self.check_frame("Initialize", CurrentFrame)
+        n2 = len(k2)
+        m = _arr(vMatches12, np.int32, n1, "vMatches12")
+        if n1 and (int(m.min()) < -1 or int(m.max()) >= n2):
+            raise ValueError("Initialize: vMatches12 is outside [-1, n2)")
+        it = self.mMaxIterations
+        if self._draws_in is None:
+            draws = np.random.RandomState(self._seed).randint(0, 2 ** 31, (it, 8)).astype(np.uint32)
+        else:
+            draws = np.ascontiguousarray(np.asarray(self._draws_in)[:it], np.uint32)
+        prm = np.zeros(1, INIT_PARAMS_DTYPE)
+        prm["sigma"], prm["max_iterations"], prm["min_parallax"], prm["min_triangulated"] = self.mSigma, it, self._min_parallax, self._min_tri
+        c1, c2 = max(n1, 1), max(n2, 1)
+        pad = lambda x, dt: x if len(x) else np.zeros(1, dt)
+        pose = np.zeros(2, KF_POSE_DTYPE)
+        P3D, tri, mo = np.zeros((c1, 3), np.float32), np.zeros(c1, np.uint8), np.full(c1, -1, np.int32)
+        pts, kp1, kp2 = np.zeros(c1, MAP_POINT_DTYPE), np.full(c1, -1, np.int32), np.full(c2, -1, np.int32)
+        os_, of, oi, npnt = np.zeros(c1 + 1, np.int32), np.full(2 * c1, -1, np.int32), np.full(2 * c1, -1, np.int32), np.zeros(1, np.int32)
+        tr = np.zeros(it, INIT_HYPOTHESIS_DTYPE) if trace else None
+        info, finfo = np.zeros(INIT_INFO, np.int32), np.zeros(INIT_FINFO, np.float32)
+        ext = self.ext
+        ret = ext._check(ext._L.pgorb_initializer(
+            ext._h, _p(pad(k1, KEYPOINT_DTYPE)), n1, _p(pad(k2, KEYPOINT_DTYPE)), n2, _p(self._cam), _p(pad(m, np.int32)), _p(prm), _p(draws),
+            _p(pose), _p(P3D), _p(tri), _p(mo), _p(pts), _p(kp1), _p(kp2), _p(os_), _p(of), _p(oi), _p(npnt),
+            None if tr is None else _p(tr), _p(info), _p(finfo)))
+        np_ = int(npnt[0])
+        self.info, self.finfo, self.status, self.trace = info, finfo, int(info[0]), tr
+        self.pose, self.matches12_out, self.ntriangulated = pose, mo[:n1].copy(), int(ret)
+        self.map = dict(points=pts[:np_].copy(), kf_point1=kp1[:n1].copy(), kf_point2=kp2[:n2].copy(), obs_start=os_[:np_ + 1].copy(),
+                        obs_frame=of[:2 * np_].copy(), obs_idx=oi[:2 * np_].copy(), npoints=np_)
+        ok = bool(info[0] & INIT_OK)
+        R21 = t21 = None
+        if ok:
+            T = pose[1]["Tcw"].reshape(3, 4)
+            R21, t21 = T[:, :3].copy(), T[:, 3:].copy()
+        return ok, R21, t21, P3D[:n1].copy(), tri[:n1].astype(bool)
+
+    @staticmethod
+    def initialize_batch_device(ext, d_kps, d_n, cap_per_frame, d_pair_f1, d_pair_f2, npairs, d_camera, d_matches12, d_draws, sigma=1.0,
+                                iterations=200, minParallax=1.0, minTriangulated=50, with_map=True, trace=False, stream=None):
+        """pgorb_initializer_batch_device over resident torch tensors: pair p initialises from frames d_pair_f1[p] and d_pair_f2[p]
+        (the layout ORBmatcher's SearchForInitialization batch writes: d_matches12 [npairs][cap]); d_camera holds one KF_POSE_DTYPE
+        record per frame; d_draws [npairs][iterations][8].  The parameters, the element types and the sizes are checked here; the
+        arrays' contents are not read.  Returns a dict of freshly allocated tensors: pose_out (bytes of two KF_POSE_DTYPE per pair),
+        P3D [npairs][cap][3], triangulated, matches12_out [npairs][cap], info [npairs][INIT_INFO], finfo [npairs][INIT_FINFO]; with
+        with_map points (bytes of MAP_POINT_DTYPE, [npairs][cap]), kf_point1, kf_point2 [npairs][cap], obs_start [npairs][cap + 1],
+        obs_frame, obs_idx [npairs][2*cap], npoints [npairs]; with trace, trace (bytes of INIT_HYPOTHESIS_DTYPE, [npairs][iterations])."""
+        import torch
+        name = "Initializer.initialize_batch_device"
+        Initializer.check_params(name, sigma, iterations, minParallax)
+        it, npairs, cap = int(iterations), int(npairs), int(cap_per_frame)
+        for nm, t_ in (("d_pair_f1", d_pair_f1), ("d_pair_f2", d_pair_f2), ("d_n", d_n), ("d_matches12", d_matches12)):
+            if t_.dtype != torch.int32:
+                raise ValueError("%s: %s must be an int32 tensor" % (name, nm))
+        if cap < 1 or cap > Initializer.MAX_N or npairs < 0:
+            raise ValueError("%s: cap_per_frame outside [1, %d] or a negative count" % (name, Initializer.MAX_N))
+        if d_draws.element_size() != 4 or d_draws.numel() != npairs * it * 8 or d_matches12.numel() != npairs * cap:
+            raise ValueError("%s: d_draws must be [npairs][%d][8] of 4-byte elements and d_matches12 [npairs][cap]" % (name, it))
+        nframes = int(d_n.numel())
+        if int(d_pair_f1.numel()) != npairs or int(d_pair_f2.numel()) != npairs or \
+                d_kps.numel() * d_kps.element_size() != nframes * cap * KEYPOINT_DTYPE.itemsize or \
+                d_camera.numel() * d_camera.element_size() != nframes * KF_POSE_DTYPE.itemsize:
+            raise ValueError("%s: d_kps and d_camera must hold one row per frame of d_n, d_pair_f1 / d_pair_f2 one entry per pair" % name)
+        dev = d_matches12.device
+        prm = np.zeros(1, INIT_PARAMS_DTYPE)
+        prm["sigma"], prm["max_iterations"], prm["min_parallax"], prm["min_triangulated"] = sigma, it, minParallax, minTriangulated
+        e = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
+        out = dict(pose_out=e((npairs, 2 * KF_POSE_DTYPE.itemsize), torch.uint8), P3D=e((npairs, cap, 3), torch.float32),
+                   triangulated=e((npairs, cap), torch.uint8), matches12_out=e((npairs, cap), torch.int32),
+                   info=e((npairs, INIT_INFO), torch.int32), finfo=e((npairs, INIT_FINFO), torch.float32))
+        if with_map:
+            out.update(points=e((npairs, cap * MAP_POINT_DTYPE.itemsize), torch.uint8), kf_point1=e((npairs, cap), torch.int32),
+                       kf_point2=e((npairs, cap), torch.int32), obs_start=e((npairs, cap + 1), torch.int32),
+                       obs_frame=e((npairs, 2 * cap), torch.int32), obs_idx=e((npairs, 2 * cap), torch.int32), npoints=e((npairs,), torch.int32))
+        if trace:
+            out["trace"] = e((npairs, it * INIT_HYPOTHESIS_DTYPE.itemsize), torch.uint8)
+        q = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        s = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        ext._check(ext._L.pgorb_initializer_batch_device(
+            ext._h, q(d_kps), q(d_n), cap, q(d_pair_f1), q(d_pair_f2), npairs, q(d_camera), q(d_matches12), _p(prm), q(d_draws),
+            q(out["pose_out"]), q(out["P3D"]), q(out["triangulated"]), q(out["matches12_out"]), q(out.get("points")), q(out.get("kf_point1")),
+            q(out.get("kf_point2")), q(out.get("obs_start")), q(out.get("obs_frame")), q(out.get("obs_idx")), q(out.get("npoints")),
+            q(out.get("trace")), q(out["info"]), q(out["finfo"]), C.c_void_p(s)))
+        return out
+
+
 # pgorb_refresh_map_points: what to refresh, the status word's bits, the limit (include/pgorb.h)
 MP_DESCRIPTOR, MP_NORMAL_DEPTH, MP_BOTH = 1, 2, 3
 MP_LIMIT, MP_BAD_INDEX, MP_MAX_OBS = -6, -1, 512

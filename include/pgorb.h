@@ -1381,6 +1381,123 @@ int  pgorb_refresh_map_points_batch_device(pgorb_ctx* ctx,
         const int32_t* d_ref_obs, int nsel, const int32_t* d_select, int what, int32_t* d_best_obs, int32_t* d_status,
         void* hip_stream);
 
+/* ---- The covisibility graph: UpdateConnections, its views, and Tracking::UpdateLocalMap (csrc/covisibility.hip) --------------
+ * The graph lives next to the map-point table, in the layouts the other entry points read.  Integers only; every result is exact.
+ * Shared conventions.  Key frames are the nframes frames of one resident batch; their slots are d_kf_point [nframes][cap_per_frame]
+ * (the table index of GetMapPointMatches()[s] or -1) with d_n.  The table is that of pgorb_refresh_map_points: d_point_bad (NULL =
+ * none) and the observations as CSR d_obs_start [npoints + 1] / d_obs_frame [nobs]; obs_idx is not read.  d_kf_order [nframes]
+ * (NULL = index order) is the RANK OF EACH KEY FRAME'S ADDRESS, a permutation of 0 .. nframes-1: the reference iterates
+ * std::map<KeyFrame*, ..> and std::set<KeyFrame*> and sorts pair<int, KeyFrame*>, so address order decides every tie, and the
+ * library cannot know it -- the same contract as the list order of pgorb_refresh_map_points.  An index out of range is no slot, no
+ * observation and no key frame; a key frame whose rank is out of range or named by a larger index too is no key frame.  The device
+ * forms never read or write out of bounds.
+ * The graph state, one row of capacity conn_cap per key frame, updated in place:
+ *   d_conn_kf / d_conn_w [nframes][conn_cap] + d_nconn   mConnectedKeyFrameWeights in address order: EVERY counter, also those below
+ *                                                        the threshold (mConnectedKeyFrameWeights = KFcounter, KeyFrame.cc:470)
+ *   d_ord_kf / d_ord_w + d_nord                          mvpOrderedConnectedKeyFrames / mvOrderedWeights
+ *   d_parent [nframes] (-1 = none), d_first_connection [nframes] (mbFirstConnection), d_kf_id0 [nframes] (NULL = none; mnId == 0)
+ *
+ *   pgorb_update_connections_batch_device   KeyFrame::UpdateConnections() (src/KeyFrame.cc:392-482, with AddConnection and
+ *       UpdateBestCovisibles, :226-260) of the key frames d_list [nlist] (distinct) ONE AFTER ANOTHER IN LIST ORDER, from the state
+ *       passed in.  th is the reference's 15.  Readings: a bad point is skipped; an observation by the key frame itself is skipped;
+ *       a key frame's own badness is not looked at; two slots holding one point count twice; pKFmax is the first strict maximum in
+ *       address order; both sorts end as descending (weight, address); an empty KFcounter returns before anything changes; the
+ *       parent is front() of the new list when first_connection and not id0.  The sequence decomposes exactly,
+ *       so a workgroup per list member counts (k_cov_count, LDS integer atomics) and a workgroup per row finishes (k_cov_finish).
+ *       d_row_status [nframes] bits: PGORB_COVIS_UPDATED (the row was rewritten from its own counters), RESORTED (an AddConnection
+ *       changed its map: the ordered list is the whole map, sub-threshold entries included), EMPTY (a list member with an empty
+ *       counter), FALLBACK (no counter reached th: pKFmax alone), PARENT_SET; PGORB_COVIS_LIMIT alone: the row would hold more than
+ *       conn_cap entries -- that key frame keeps ALL its input bytes (parent and first_connection too) and adds no loop connection;
+ *       what it sends to other rows is unaffected.  A row with status 0 was not written.
+ *       LoopConnections (src/LoopClosing.cc:548-566; d_loop_conn may be NULL with loop_conn_cap 0): per list member the keys of its
+ *       map right after its own update, minus its ordered list just before that update (which earlier members may already have
+ *       re-sorted), minus the list members, as d_loop_conn [loop_conn_cap][3] = (i, j, GetWeight) in map-then-set address order,
+ *       padded with (-1, -1, 0), which pgorb_optimize_essential_graph_device reads as no candidate: nloop_conn = loop_conn_cap
+ *       chains without a download.  d_info [PGORB_COVIS_INFO]: [0] PGORB_COVIS_LIMIT when there are more than loop_conn_cap (then
+ *       every record is padding; never with a NULL d_loop_conn), [1] their number (also when no record is asked for), [2] the number
+ *       of rows with PGORB_COVIS_LIMIT, [3] 0.  THE DEVICE FORM REQUIRES every input connection row in address order with no key
+ *       frame twice, as this call leaves them: only the single call checks it.  Another row cannot read or write out of bounds,
+ *       but a repeated key frame keeps either weight, and the loop records of a list member whose row is not rewritten (EMPTY,
+ *       nothing changed) are taken by position from the row as given, so they can name the wrong (j, weight).
+ *   pgorb_update_connections   the same from host buffers (kf_point[f] [n[f]]), checked: returns the number of rows with
+ *       PGORB_COVIS_UPDATED, or PGORB_E_ARG for a negative count, a NULL array that is read or written, th < 1, a slot, observation,
+ *       list entry, connection or parent out of range, obs_start not rising from 0, a key frame twice in one observation list or in
+ *       the list, kf_order not a permutation, a row count outside [0, conn_cap], a connection row not in address order, an ordered
+ *       entry that is not in its row's map.  It equals the device form byte for byte.
+ *   pgorb_covisibility_views_device   three views of the ordered rows (k_cov_views, a wave per key frame): d_best [nframes][nbest]
+ *       padded with -1 = GetBestCovisibilityKeyFrames(nbest) (:277-285), the d_neigh of place recognition at nbest = 10 (NULL =
+ *       skip); the CSR d_covis_start [nframes + 1] / d_covis / d_covis_weight that pgorb_optimize_essential_graph_device reads, rows
+ *       in ordered order (NULL d_covis_start = skip), more than ncovis_cap entries -> PGORB_COVIS_LIMIT in d_info[0] and every row
+ *       empty, d_info[1] = the entries; d_by_weight [nframes] (NULL = skip) = the length of GetCovisiblesByWeight(w) (:287-302):
+ *       upper_bound with weightComp finds the first weight BELOW w, so an equal weight is inside the prefix, and when no weight is
+ *       below w the reference returns an EMPTY vector: 0.
+ *   pgorb_update_local_map_batch_device   Tracking::UpdateLocalMap (src/Tracking.cc:1186-1321) of npairs frames: problem p is frame
+ *       d_pair_frame[p] (NULL: frame p) of the batch with the slots d_kp_point [npairs][cap_per_frame] (d_n of that frame in use).
+ *       It reads the table, d_kf_bad (NULL = none), the key frames' slots, d_ord_kf / d_nord, d_parent and d_kf_order, and follows
+ *       UpdateLocalKeyFrames literally: (1) a bad point's slot is cleared (d_kp_point_out, may be NULL, reports it), every other
+ *       point votes for every key frame of its list, bad key frames included, without a self-skip; (2) the voted key frames in
+ *       address order, the bad ones skipped, the strict maximum kept as the reference key frame; (3) the expansion over the
+ *       first-stage entries only, stopped when the list is longer than max_local (the reference's 80): per entry the first of its
+ *       best nbest (10) neighbours that is neither bad nor marked, the first such child in address order (parent[c] == i), and the
+ *       parent if unmarked -- NO bad test, and after pushing it the outer loop ENDS (the reference's break, :1310); (4)
+ *       UpdateLocalPoints (:1196-1210): key frames in list order, slots in slot order, a point kept if it is not NULL, not yet taken
+ *       for this frame and not bad.  With no vote the reference returns early (:1235) and walks its previous list: optional
+ *       d_prev_local_kf [npairs][lkf_cap] / d_nprev serve that; without them the lists come out empty; PGORB_LOCALMAP_NO_VOTES
+ *       either way, d_ref_kf -1.  If all voted key frames are bad the list is empty and d_ref_kf -1 (= keep).  Outputs: d_local_kf
+ *       [npairs][lkf_cap] + d_nlocal_kf, d_ref_kf, d_queries [npairs][qcap] + d_nq -- exactly what
+ *       pgorb_search_local_points_batch_device takes -- and d_status; PGORB_LOCALMAP_LIMIT: a list past its capacity, both counts 0.
+ *       k_cov_local, a workgroup per frame: the votes are LDS atomics, the first stage a scan in address order, the point union a
+ *       first-position key per (frame, table point) and a scan; only the expansion is a short sequential walk.
+ *   pgorb_update_local_map   one frame from host buffers, checked as above (nprev -1 = no previous list); returns nq.
+ * Limits (PGORB_E_LIMIT): nframes <= PGORB_COVIS_MAX_KF (the LDS counters are one int32 per key frame), conn_cap <=
+ * PGORB_COVIS_MAX_CONN (a row is sorted in LDS), lkf_cap <= PGORB_COVIS_MAX_KF, qcap <= 16000, cap_per_frame <= 16000.  Scratch
+ * arena: UpdateConnections nlist * nframes * 4 bytes (the dense counter rows) + nlist * conn_cap; UpdateLocalMap npairs * npoints * 4.
+ * Determinism: a result depends on its inputs alone, not on the batch position, the stream or a repeat. */
+#define PGORB_COVIS_MAX_KF     4096
+#define PGORB_COVIS_MAX_CONN   2048
+#define PGORB_COVIS_UPDATED    1
+#define PGORB_COVIS_RESORTED   2
+#define PGORB_COVIS_EMPTY      4
+#define PGORB_COVIS_FALLBACK   8
+#define PGORB_COVIS_PARENT_SET 16
+#define PGORB_COVIS_LIMIT      32
+#define PGORB_COVIS_INFO       4
+#define PGORB_LOCALMAP_NO_VOTES 1
+#define PGORB_LOCALMAP_LIMIT    2
+int  pgorb_update_connections(pgorb_ctx* ctx,
+        int nkf, const int32_t* const* kf_point, const int32_t* n /*[nkf]*/, int npoints, const uint8_t* point_bad /*[npoints] or NULL*/,
+        const int32_t* obs_start /*[npoints + 1]*/, const int32_t* obs_frame, const int32_t* kf_order /*[nkf] or NULL*/,
+        const uint8_t* kf_id0 /*[nkf] or NULL*/, int nlist, const int32_t* list, int th,
+        int conn_cap, int32_t* conn_kf, int32_t* conn_w /*[nkf][conn_cap]*/, int32_t* nconn, int32_t* ord_kf, int32_t* ord_w, int32_t* nord,
+        int32_t* parent /*[nkf]*/, uint8_t* first_connection /*[nkf]*/, int32_t* row_status /*[nkf]*/,
+        int loop_conn_cap, int32_t* loop_conn /*[loop_conn_cap][3] or NULL*/, int32_t* info /*[PGORB_COVIS_INFO]*/);
+int  pgorb_update_connections_batch_device(pgorb_ctx* ctx,
+        const int32_t* d_kf_point, const int32_t* d_n, int nframes, int cap_per_frame,
+        int npoints, const uint8_t* d_point_bad, const int32_t* d_obs_start, const int32_t* d_obs_frame, int nobs,
+        const int32_t* d_kf_order, const uint8_t* d_kf_id0, int nlist, const int32_t* d_list, int th,
+        int conn_cap, int32_t* d_conn_kf, int32_t* d_conn_w, int32_t* d_nconn, int32_t* d_ord_kf, int32_t* d_ord_w, int32_t* d_nord,
+        int32_t* d_parent, uint8_t* d_first_connection, int32_t* d_row_status,
+        int loop_conn_cap, int32_t* d_loop_conn, int32_t* d_info, void* hip_stream);
+int  pgorb_covisibility_views_device(pgorb_ctx* ctx,
+        int nframes, int conn_cap, const int32_t* d_ord_kf, const int32_t* d_ord_w, const int32_t* d_nord,
+        int nbest, int32_t* d_best, int ncovis_cap, int32_t* d_covis_start, int32_t* d_covis, int32_t* d_covis_weight,
+        int w, int32_t* d_by_weight, int32_t* d_info /*[2]*/, void* hip_stream);
+int  pgorb_update_local_map(pgorb_ctx* ctx,
+        int nkf, const int32_t* const* kf_point, const int32_t* n /*[nkf]*/, const uint8_t* kf_bad /*[nkf] or NULL*/,
+        const int32_t* kp_point /*[nkp]*/, int nkp, int npoints, const uint8_t* point_bad, const int32_t* obs_start, const int32_t* obs_frame,
+        int conn_cap, const int32_t* ord_kf /*[nkf][conn_cap]*/, const int32_t* nord, const int32_t* parent, const int32_t* kf_order,
+        int nbest, int max_local, int nprev, const int32_t* prev_local_kf,
+        int32_t* kp_point_out /*[nkp] or NULL*/, int lkf_cap, int32_t* local_kf, int32_t* nlocal_kf, int32_t* ref_kf,
+        int qcap, int32_t* queries, int32_t* nq, int32_t* status);
+int  pgorb_update_local_map_batch_device(pgorb_ctx* ctx,
+        const int32_t* d_kf_point, const int32_t* d_n, int nframes, int cap_per_frame, const uint8_t* d_kf_bad,
+        const int32_t* d_pair_frame, int npairs, const int32_t* d_kp_point,
+        int npoints, const uint8_t* d_point_bad, const int32_t* d_obs_start, const int32_t* d_obs_frame, int nobs,
+        int conn_cap, const int32_t* d_ord_kf, const int32_t* d_nord, const int32_t* d_parent, const int32_t* d_kf_order,
+        int nbest, int max_local, int lkf_cap, const int32_t* d_prev_local_kf, const int32_t* d_nprev,
+        int32_t* d_kp_point_out, int32_t* d_local_kf, int32_t* d_nlocal_kf, int32_t* d_ref_kf,
+        int qcap, int32_t* d_queries, int32_t* d_nq, int32_t* d_status, void* hip_stream);
+
 /* ---- ORB vocabulary (DBoW2 TemplatedVocabulary<FORB::TDescriptor, FORB>) -----------------
  *   pgorb_vocab_load_text     ORBVocabulary(text_file) -> TemplatedVocabulary::loadFromTextFile
  *                             thirdparty/orb-slam2/src/ORBVocabulary.cc:7-9,

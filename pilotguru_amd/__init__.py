@@ -21,4 +21,6 @@ from .orb import (PNP_FEW, PNP_FOUND, PNP_HYPOTHESIS_DTYPE, PNP_INFO, PNP_MAX_WI
                   PnPsolver)
 from .orb import (INIT_AMBIGUOUS, INIT_DEGENERATE_H, INIT_FEW, INIT_FEW_GOOD, INIT_FINFO, INIT_HYPOTHESIS_DTYPE, INIT_INFO,  # noqa: F401
                   INIT_LOW_PARALLAX, INIT_MAX_ITERATIONS, INIT_MODEL_F, INIT_MODEL_H, INIT_NO_MODEL, INIT_OK, INIT_PARAMS_DTYPE, Initializer)
+from .orb import (COVIS_EMPTY, COVIS_FALLBACK, COVIS_INFO, COVIS_LIMIT, COVIS_MAX_CONN, COVIS_MAX_KF, COVIS_PARENT_SET,  # noqa: F401
+                  COVIS_RESORTED, COVIS_UPDATED, LOCALMAP_LIMIT, LOCALMAP_NO_VOTES, CovisibilityGraph, Tracking)
 from .place import KeyFrameDatabase  # noqa: F401

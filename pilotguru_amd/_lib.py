@@ -39,6 +39,8 @@ SYMBOLS = (
     "pgorb_search_by_sim3", "pgorb_search_by_sim3_batch_device",
     "pgorb_search_by_bow_keyframes", "pgorb_search_by_bow_keyframes_batch_device",
     "pgorb_refresh_map_points", "pgorb_refresh_map_points_batch_device",
+    "pgorb_update_connections", "pgorb_update_connections_batch_device", "pgorb_covisibility_views_device",
+    "pgorb_update_local_map", "pgorb_update_local_map_batch_device",
     "pgorb_bow_vectors_batch_device", "pgorb_bow_score_l1_batch_device",
     "pgorb_detect_relocalization_candidates", "pgorb_detect_relocalization_candidates_batch_device",
     "pgorb_detect_loop_candidates", "pgorb_detect_loop_candidates_batch_device",
@@ -287,6 +289,24 @@ def lib():
     #  ref_obs, nsel, select, what, best_obs, status, stream)
     L.pgorb_refresh_map_points_batch_device.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, C.c_int] + [vp] * 6 + \
         [C.c_int, vp, C.c_int, vp, C.c_int, vp, vp, vp]
+    # (ctx, nkf, kf_point[], n, npoints, point_bad, obs_start, obs_frame, kf_order, kf_id0, nlist, list, th, conn_cap, conn_kf, conn_w, nconn,
+    #  ord_kf, ord_w, nord, parent, first_connection, row_status, loop_conn_cap, loop_conn, info)
+    L.pgorb_update_connections.argtypes = [vp, C.c_int, vp, vp, C.c_int] + [vp] * 5 + [C.c_int, vp, C.c_int, C.c_int] + [vp] * 9 + [C.c_int, vp, vp]
+    # (ctx, kf_point, n, nframes, cap, npoints, point_bad, obs_start, obs_frame, nobs, kf_order, kf_id0, nlist, list, th, conn_cap, 6 row arrays,
+    #  parent, first_connection, row_status, loop_conn_cap, loop_conn, info, stream)
+    L.pgorb_update_connections_batch_device.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, vp, C.c_int, vp, C.c_int,
+                                                        C.c_int] + [vp] * 9 + [C.c_int, vp, vp, vp]
+    # (ctx, nframes, conn_cap, ord_kf, ord_w, nord, nbest, best, ncovis_cap, covis_start, covis, covis_weight, w, by_weight, info, stream)
+    L.pgorb_covisibility_views_device.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp]
+    # (ctx, nkf, kf_point[], n, kf_bad, kp_point, nkp, npoints, point_bad, obs_start, obs_frame, conn_cap, ord_kf, nord, parent, kf_order, nbest,
+    #  max_local, nprev, prev_local_kf, kp_point_out, lkf_cap, local_kf, nlocal_kf, ref_kf, qcap, queries, nq, status)
+    L.pgorb_update_local_map.argtypes = [vp, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int,
+                                         C.c_int, vp, vp, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp]
+    # (ctx, kf_point, n, nframes, cap, kf_bad, pair_frame, npairs, kp_point, npoints, point_bad, obs_start, obs_frame, nobs, conn_cap, ord_kf,
+    #  nord, parent, kf_order, nbest, max_local, lkf_cap, prev_local_kf, nprev, kp_point_out, local_kf, nlocal_kf, ref_kf, qcap, queries, nq,
+    #  status, stream)
+    L.pgorb_update_local_map_batch_device.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, vp, C.c_int, vp, C.c_int, vp, vp, vp, C.c_int, C.c_int,
+                                                      vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp]
     # (ctx, word, weight, n, nframes, cap, bow_id, bow_val, nbow, stream)
     L.pgorb_bow_vectors_batch_device.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp]
     # (ctx, bow_id, bow_val, nbow, nframes, cap, pair_a, pair_b, npairs, score, stream)

@@ -1036,6 +1036,192 @@ inline void checkRefresh(const std::vector<const KeyFrame*>& kfs, const std::vec
             fail("refObs lies outside the point's list");
     }
 }
+
+// what pgorb_update_connections and pgorb_update_local_map both reject of the slots, the observation lists and the ranks
+inline void checkCovisTable(const char* fn, size_t nkf, const std::vector<std::vector<int32_t>>& kfPoint, size_t npoints,
+                            const std::vector<uint8_t>& pointBad, const MapPointObservations& O, const std::vector<int32_t>& kfOrder)
+{
+    auto fail = [&](const char* what) { throw std::invalid_argument(std::string(fn) + ": " + what); };
+    if (kfPoint.size() != nkf) fail("one slot array per key frame");
+    if (nkf > PGORB_COVIS_MAX_KF) fail("more than PGORB_COVIS_MAX_KF key frames");
+    for (const auto& s : kfPoint) {
+        if (s.size() > 16000) fail("more than 16000 keypoints");
+        for (int32_t p : s) if (p < -1 || p >= (int64_t)npoints) fail("a slot names a point out of range");
+    }
+    if (!pointBad.empty() && pointBad.size() != npoints) fail("pointBad needs one flag per point");
+    if (O.obsStart.size() != npoints + 1 || O.obsStart[0] != 0) fail("obsStart needs npoints + 1 entries rising from 0");
+    for (size_t i = 0; i < npoints; i++) if (O.obsStart[i + 1] < O.obsStart[i]) fail("obsStart decreases");
+    if ((int64_t)O.obsFrame.size() < O.obsStart[npoints]) fail("obsFrame is shorter than obsStart says");
+    std::vector<int32_t> seen(nkf + 1, -1);
+    for (size_t i = 0; i < npoints; i++)
+        for (int k = O.obsStart[i]; k < O.obsStart[i + 1]; k++) {
+            const int f = O.obsFrame[k];
+            if (f < 0 || f >= (int64_t)nkf) fail("an observation names a key frame out of range");
+            if (seen[f] == (int32_t)i) fail("a list names a key frame twice");
+            seen[f] = (int32_t)i;
+        }
+    if (!kfOrder.empty()) {
+        if (kfOrder.size() != nkf) fail("kfOrder needs one rank per key frame");
+        std::vector<uint8_t> used(nkf + 1, 0);
+        for (int32_t r : kfOrder) {
+            if (r < 0 || r >= (int64_t)nkf || used[r]) fail("kfOrder is not a permutation");
+            used[r] = 1;
+        }
+    }
+}
 }  // namespace detail
+
+// The covisibility graph of nkf key frames as the arrays the library keeps (include/pgorb.h): connKf / connW / nconn =
+// mConnectedKeyFrameWeights in address order, ordKf / ordW / nord = mvpOrderedConnectedKeyFrames / mvOrderedWeights, parent
+// (-1 = none) and firstConnection.  kfOrder[f] = the rank of key frame f's address (empty = index order); kfId0[f] = mnId == 0.
+class CovisibilityGraph {
+ public:
+    CovisibilityGraph(pgorb_ctx* ctx, int nkf, int connCap, std::vector<int32_t> kfOrder = {}, std::vector<uint8_t> kfId0 = {})
+        : ctx_(ctx), nkf_(nkf), connCap_(connCap), kfOrder(std::move(kfOrder)), kfId0(std::move(kfId0))
+    {
+        if (nkf < 0 || nkf > PGORB_COVIS_MAX_KF) throw std::invalid_argument("CovisibilityGraph: nkf outside 0..PGORB_COVIS_MAX_KF");
+        if (connCap < 1 || connCap > PGORB_COVIS_MAX_CONN) throw std::invalid_argument("CovisibilityGraph: connCap outside 1..PGORB_COVIS_MAX_CONN");
+        const size_t k1 = (size_t)std::max(nkf, 1);
+        connKf.assign(k1 * connCap, -1); connW.assign(k1 * connCap, 0); ordKf.assign(k1 * connCap, -1); ordW.assign(k1 * connCap, 0);
+        nconn.assign(k1, 0); nord.assign(k1, 0); parent.assign(k1, -1); firstConnection.assign(k1, 1);
+    }
+    int nkf() const { return nkf_; }
+    int connCap() const { return connCap_; }
+    // KeyFrame::UpdateConnections() (KeyFrame.cc:392-482) of `keyFrames` one after another, in place.  kfPoint[f] = the table
+    // indices of key frame f's slots (-1 = none).  rowStatus [nkf] (PGORB_COVIS_* bits); loopConn (when loopConnCap > 0) =
+    // LoopConnections (LoopClosing.cc:548-566) as (i, j, weight) records.  Returns the number of rows rewritten from their counters.
+    int UpdateConnections(const std::vector<std::vector<int32_t>>& kfPoint, size_t npoints, const std::vector<uint8_t>& pointBad,
+                          const MapPointObservations& obs, const std::vector<int32_t>& keyFrames, int th, std::vector<int32_t>& rowStatus,
+                          int loopConnCap = 0, std::vector<std::array<int32_t, 3>>* loopConn = nullptr, std::array<int32_t, PGORB_COVIS_INFO>* info = nullptr)
+    {
+        const char* fn = "CovisibilityGraph::UpdateConnections";
+        auto fail = [&](const char* what) { throw std::invalid_argument(std::string(fn) + ": " + what); };
+        detail::checkCovisTable(fn, (size_t)nkf_, kfPoint, npoints, pointBad, obs, kfOrder);
+        if (th < 1 || loopConnCap < 0) fail("th < 1 or loopConnCap < 0");
+        if (!kfId0.empty() && kfId0.size() != (size_t)nkf_) fail("kfId0 needs one flag per key frame");
+        std::vector<uint8_t> listed((size_t)nkf_ + 1, 0);
+        for (int32_t f : keyFrames) {
+            if (f < 0 || f >= nkf_) fail("a list entry is out of range");
+            if (listed[f]) fail("the list names a key frame twice");
+            listed[f] = 1;
+        }
+        std::vector<int32_t> mark((size_t)nkf_ + 1, -1);
+        for (int f = 0; f < nkf_; f++) {
+            if (nconn[f] < 0 || nconn[f] > connCap_ || nord[f] < 0 || nord[f] > connCap_) fail("a row count is outside [0, connCap]");
+            if (parent[f] < -1 || parent[f] >= nkf_) fail("a parent is out of range");
+            int last = -1;
+            for (int t = 0; t < nconn[f]; t++) {
+                const int j = connKf[(size_t)f * connCap_ + t];
+                if (j < 0 || j >= nkf_ || j == f) fail("a connection is out of range");
+                const int r = kfOrder.empty() ? j : kfOrder[j];
+                if (r <= last) fail("a connection row is not in address order");
+                last = r; mark[j] = f;
+            }
+            for (int t = 0; t < nord[f]; t++) {
+                const int j = ordKf[(size_t)f * connCap_ + t];
+                if (j < 0 || j >= nkf_ || mark[j] != f) fail("an ordered entry is not in the row's map");
+            }
+        }
+        std::vector<const int32_t*> slots((size_t)nkf_ + 1, nullptr);
+        std::vector<int32_t> n((size_t)nkf_ + 1, 0);
+        for (int f = 0; f < nkf_; f++) { slots[f] = kfPoint[f].data(); n[f] = (int32_t)kfPoint[f].size(); }
+        rowStatus.assign((size_t)std::max(nkf_, 1), 0);
+        std::vector<int32_t> loop((size_t)std::max(loopConnCap, 1) * 3, 0);
+        std::array<int32_t, PGORB_COVIS_INFO> inf{};
+        const int rc = pgorb_update_connections(ctx_, nkf_, slots.data(), n.data(), (int)npoints, pointBad.empty() ? nullptr : pointBad.data(),
+                                                obs.obsStart.data(), obs.obsFrame.data(), kfOrder.empty() ? nullptr : kfOrder.data(),
+                                                kfId0.empty() ? nullptr : kfId0.data(), (int)keyFrames.size(), keyFrames.empty() ? n.data() : keyFrames.data(),
+                                                th, connCap_, connKf.data(), connW.data(), nconn.data(), ordKf.data(), ordW.data(), nord.data(),
+                                                parent.data(), firstConnection.data(), rowStatus.data(), loopConnCap, loopConnCap ? loop.data() : nullptr,
+                                                inf.data());
+        if (rc < 0) throw std::runtime_error(pgorb_last_error(ctx_));
+        rowStatus.resize((size_t)nkf_);
+        if (info) *info = inf;
+        if (loopConn) {
+            loopConn->clear();
+            const int m = (inf[0] & PGORB_COVIS_LIMIT) ? 0 : std::min(inf[1], loopConnCap);
+            for (int e = 0; e < m; e++) loopConn->push_back({loop[3 * e], loop[3 * e + 1], loop[3 * e + 2]});
+        }
+        return rc;
+    }
+    // GetBestCovisibilityKeyFrames(N) (KeyFrame.cc:277-285)
+    std::vector<int32_t> GetBestCovisibilityKeyFrames(int f, int N) const
+    {
+        const int32_t* row = &ordKf[(size_t)f * connCap_];
+        return std::vector<int32_t>(row, row + std::min((int)nord[f], std::max(N, 0)));
+    }
+    // GetCovisiblesByWeight(w) (:287-302): upper_bound with weightComp; when no weight is below w the reference returns an empty vector
+    std::vector<int32_t> GetCovisiblesByWeight(int f, int w) const
+    {
+        const int32_t* row = &ordKf[(size_t)f * connCap_];
+        int len = 0;
+        for (int t = 0; t < nord[f]; t++) len += ordW[(size_t)f * connCap_ + t] >= w;
+        return std::vector<int32_t>(row, row + (len == nord[f] ? 0 : len));
+    }
+    std::vector<int32_t> connKf, connW, nconn, ordKf, ordW, nord, parent;
+    std::vector<uint8_t> firstConnection;
+ private:
+    pgorb_ctx* ctx_;
+    int nkf_, connCap_;
+ public:
+    std::vector<int32_t> kfOrder;
+    std::vector<uint8_t> kfId0;
+};
+
+struct LocalMapResult {
+    std::vector<int32_t> kpPoint, localKf, queries;   // the frame's slots after the first loop, mvpLocalKeyFrames, mvpLocalMapPoints
+    int refKf = -1, status = 0;                        // -1: mpReferenceKF is kept; PGORB_LOCALMAP_* bits
+};
+
+class Tracking {
+ public:
+    explicit Tracking(pgorb_ctx* ctx) : ctx_(ctx) {}
+    // Tracking::UpdateLocalMap (Tracking.cc:1186-1321) for a frame whose mvpMapPoints are the table indices kpPoint (-1 = none), over
+    // `graph` and the key frames' slots; prevLocalKf = mvpLocalKeyFrames before the call (NULL = none), walked again when no point votes.
+    LocalMapResult UpdateLocalMap(const CovisibilityGraph& graph, const std::vector<int32_t>& kpPoint, const std::vector<std::vector<int32_t>>& kfPoint,
+                                  size_t npoints, const std::vector<uint8_t>& pointBad, const MapPointObservations& obs, const std::vector<uint8_t>& kfBad,
+                                  const std::vector<int32_t>* prevLocalKf = nullptr, int nbest = 10, int maxLocal = 80, int lkfCap = 256, int qcap = 16000)
+    {
+        const char* fn = "Tracking::UpdateLocalMap";
+        auto fail = [&](const char* what) { throw std::invalid_argument(std::string(fn) + ": " + what); };
+        const int nkf = graph.nkf(), cc = graph.connCap();
+        if (nkf + 1 > PGORB_COVIS_MAX_KF) fail("more than PGORB_COVIS_MAX_KF - 1 key frames");
+        detail::checkCovisTable(fn, (size_t)nkf, kfPoint, npoints, pointBad, obs, graph.kfOrder);
+        if (kpPoint.size() > 16000) fail("more than 16000 slots");
+        for (int32_t p : kpPoint) if (p < -1 || p >= (int64_t)npoints) fail("a slot names a point out of range");
+        if (lkfCap < 1 || lkfCap > PGORB_COVIS_MAX_KF || qcap < 1 || qcap > 16000 || nbest < 0 || maxLocal < 0)
+            fail("lkfCap outside 1..PGORB_COVIS_MAX_KF, qcap outside 1..16000, or a negative nbest / maxLocal");
+        if (!kfBad.empty() && kfBad.size() != (size_t)nkf) fail("kfBad needs one flag per key frame");
+        if (prevLocalKf) {
+            if ((int64_t)prevLocalKf->size() > lkfCap) fail("the previous list is longer than lkfCap");
+            for (int32_t f : *prevLocalKf) if (f < 0 || f >= nkf) fail("a previous key frame is out of range");
+        }
+        for (int f = 0; f < nkf; f++) {
+            if (graph.nord[f] < 0 || graph.nord[f] > cc || graph.parent[f] < -1 || graph.parent[f] >= nkf) fail("an ordered row or a parent is out of range");
+            for (int t = 0; t < graph.nord[f]; t++)
+                if (graph.ordKf[(size_t)f * cc + t] < 0 || graph.ordKf[(size_t)f * cc + t] >= nkf) fail("an ordered entry is out of range");
+        }
+        std::vector<const int32_t*> slots((size_t)nkf + 1, nullptr);
+        std::vector<int32_t> n((size_t)nkf + 1, 0);
+        for (int f = 0; f < nkf; f++) { slots[f] = kfPoint[f].data(); n[f] = (int32_t)kfPoint[f].size(); }
+        LocalMapResult r;
+        r.kpPoint.assign(kpPoint.size() + 1, -1);
+        r.localKf.assign((size_t)lkfCap, 0);
+        r.queries.assign((size_t)qcap, 0);
+        int32_t nlocal = 0, nq = 0, ref = -1, status = 0;
+        const int rc = pgorb_update_local_map(ctx_, nkf, slots.data(), n.data(), kfBad.empty() ? nullptr : kfBad.data(), kpPoint.data(), (int)kpPoint.size(),
+                                              (int)npoints, pointBad.empty() ? nullptr : pointBad.data(), obs.obsStart.data(), obs.obsFrame.data(), cc,
+                                              graph.ordKf.data(), graph.nord.data(), graph.parent.data(), graph.kfOrder.empty() ? nullptr : graph.kfOrder.data(),
+                                              nbest, maxLocal, prevLocalKf ? (int)prevLocalKf->size() : -1,
+                                              prevLocalKf && !prevLocalKf->empty() ? prevLocalKf->data() : nullptr, r.kpPoint.data(), lkfCap,
+                                              r.localKf.data(), &nlocal, &ref, qcap, r.queries.data(), &nq, &status);
+        if (rc < 0) throw std::runtime_error(pgorb_last_error(ctx_));
+        r.kpPoint.resize(kpPoint.size()); r.localKf.resize((size_t)nlocal); r.queries.resize((size_t)nq);
+        r.refKf = ref; r.status = status;
+        return r;
+    }
+ private:
+    pgorb_ctx* ctx_;
+};
 
 }  // namespace pgorb

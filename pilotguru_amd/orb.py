@@ -2058,6 +2058,160 @@ class LocalMapping:
         return pts, pd, best[:nsel].copy(), status[:nsel].copy()
 
 
+# the covisibility graph (include/pgorb.h): row status bits, limits, the local map's status bits
+COVIS_UPDATED, COVIS_RESORTED, COVIS_EMPTY, COVIS_FALLBACK, COVIS_PARENT_SET, COVIS_LIMIT = 1, 2, 4, 8, 16, 32
+COVIS_MAX_KF, COVIS_MAX_CONN, COVIS_INFO = 4096, 2048, 4
+LOCALMAP_NO_VOTES, LOCALMAP_LIMIT = 1, 2
+
+
+def _covis_table(fn, nkf, kf_point, npoints, obs_start, obs_frame, point_bad, kf_order):
+    """The slots, the observation lists and the address ranks, checked as the single calls check them."""
+    if len(kf_point) != nkf:
+        raise ValueError(fn + ": one slot array per key frame")
+    if nkf > COVIS_MAX_KF:
+        raise ValueError(fn + ": more than COVIS_MAX_KF key frames")
+    slots = [np.ascontiguousarray(s, np.int32).reshape(-1) for s in kf_point]
+    for s in slots:
+        if len(s) > 16000:
+            raise ValueError(fn + ": more than 16000 keypoints")
+        if len(s) and (s.min() < -1 or s.max() >= npoints):
+            raise ValueError(fn + ": a slot names a point out of range")
+    st = _arr(obs_start, np.int32, npoints + 1, "obs_start")
+    of = np.ascontiguousarray(obs_frame, np.int32).reshape(-1)
+    if st[0] != 0 or np.any(np.diff(st) < 0) or len(of) < int(st[-1]):
+        raise ValueError(fn + ": obs_start must rise from 0 to at most len(obs_frame)")
+    m = int(st[-1])
+    if m and (of[:m].min() < 0 or of[:m].max() >= nkf):
+        raise ValueError(fn + ": an observation names a key frame out of range")
+    owner = np.repeat(np.arange(npoints, dtype=np.int64), np.diff(st))
+    if len(np.unique(owner * max(nkf, 1) + of[:m])) != m:
+        raise ValueError(fn + ": a list names a key frame twice")
+    pb = _mask(point_bad, npoints, "point_bad")
+    ko = None
+    if kf_order is not None:
+        ko = _arr(kf_order, np.int32, nkf, "kf_order")
+        if not np.array_equal(np.sort(ko), np.arange(nkf)):
+            raise ValueError(fn + ": kf_order is not a permutation")
+    if len(of) == 0:
+        of = np.zeros(1, np.int32)
+    ptrs = (C.c_void_p * max(nkf, 1))()
+    for f, s in enumerate(slots):
+        ptrs[f] = s.ctypes.data if len(s) else None
+    nk = np.array([len(s) for s in slots] + ([0] if not nkf else []), np.int32)
+    return slots, ptrs, nk, st, of, pb, ko
+
+
+class CovisibilityGraph:
+    """The covisibility graph of nkf key frames as the arrays the library keeps (include/pgorb.h): conn_kf / conn_w / nconn =
+    mConnectedKeyFrameWeights in address order, ord_kf / ord_w / nord = mvpOrderedConnectedKeyFrames / mvOrderedWeights, parent
+    (-1 = none) and first_connection.  kf_order[f] = the rank of key frame f's address (None = index order)."""
+
+    def __init__(self, ext, nkf, conn_cap, kf_order=None, kf_id0=None):
+        if conn_cap < 1 or conn_cap > COVIS_MAX_CONN:
+            raise ValueError("CovisibilityGraph: conn_cap outside 1..COVIS_MAX_CONN")
+        if nkf < 0 or nkf > COVIS_MAX_KF:
+            raise ValueError("CovisibilityGraph: nkf outside 0..COVIS_MAX_KF")
+        self.ext, self.nkf, self.conn_cap = ext, int(nkf), int(conn_cap)
+        self.kf_order = None if kf_order is None else _arr(kf_order, np.int32, nkf, "kf_order")
+        self.kf_id0 = _mask(kf_id0, nkf, "kf_id0")
+        k1 = max(nkf, 1)
+        self.conn_kf, self.conn_w = np.full((k1, conn_cap), -1, np.int32), np.zeros((k1, conn_cap), np.int32)
+        self.ord_kf, self.ord_w = np.full((k1, conn_cap), -1, np.int32), np.zeros((k1, conn_cap), np.int32)
+        self.nconn, self.nord = np.zeros(k1, np.int32), np.zeros(k1, np.int32)
+        self.parent, self.first_connection = np.full(k1, -1, np.int32), np.ones(k1, np.uint8)
+
+    def UpdateConnections(self, kf_point, npoints, obs_start, obs_frame, key_frames, point_bad=None, th=15, loop_conn_cap=0):
+        """KeyFrame::UpdateConnections() (src/KeyFrame.cc:392-482) of `key_frames` one after another, in place.  kf_point[f] = the
+        table indices of key frame f's slots (-1 = none); the table's observation lists as CSR.  Returns (row_status [nkf],
+        loop_conn [m][3], info): loop_conn = LoopConnections (LoopClosing.cc:548-566) when loop_conn_cap > 0.  Raises ValueError for
+        everything pgorb_update_connections refuses."""
+        fn = "CovisibilityGraph.UpdateConnections"
+        nkf = self.nkf
+        slots, ptrs, nk, st, of, pb, ko = _covis_table(fn, nkf, kf_point, int(npoints), obs_start, obs_frame, point_bad, self.kf_order)
+        lst = np.ascontiguousarray(key_frames, np.int32).reshape(-1)
+        if int(th) < 1 or int(loop_conn_cap) < 0:
+            raise ValueError(fn + ": th < 1 or loop_conn_cap < 0")
+        if len(lst) and (lst.min() < 0 or lst.max() >= nkf):
+            raise ValueError(fn + ": a list entry is out of range")
+        if len(np.unique(lst)) != len(lst):
+            raise ValueError(fn + ": the list names a key frame twice")
+        rank = ko if ko is not None else np.arange(nkf, dtype=np.int32)
+        for f in range(nkf):
+            nc, no = int(self.nconn[f]), int(self.nord[f])
+            if not (0 <= nc <= self.conn_cap and 0 <= no <= self.conn_cap):
+                raise ValueError(fn + ": a row count is outside [0, conn_cap]")
+            row = self.conn_kf[f, :nc]
+            if nc and (row.min() < 0 or row.max() >= nkf or np.any(row == f) or np.any(np.diff(rank[row]) <= 0)):
+                raise ValueError(fn + ": a connection row is out of range or not in address order")
+            if no and not np.all(np.isin(self.ord_kf[f, :no], row)):
+                raise ValueError(fn + ": an ordered entry is not in the row's map")
+            if not -1 <= int(self.parent[f]) < nkf:
+                raise ValueError(fn + ": a parent is out of range")
+        status = np.zeros(max(nkf, 1), np.int32)
+        loop = np.zeros((max(int(loop_conn_cap), 1), 3), np.int32)
+        info = np.zeros(COVIS_INFO, np.int32)
+        ext = self.ext
+        ext._check(ext._L.pgorb_update_connections(
+            ext._h, nkf, ptrs, _p(nk), int(npoints), _p(pb), _p(st), _p(of), None if ko is None else _p(ko), _p(self.kf_id0), len(lst),
+            _p(lst if len(lst) else np.zeros(1, np.int32)), int(th), self.conn_cap, _p(self.conn_kf), _p(self.conn_w), _p(self.nconn),
+            _p(self.ord_kf), _p(self.ord_w), _p(self.nord), _p(self.parent), _p(self.first_connection), _p(status), int(loop_conn_cap),
+            _p(loop) if loop_conn_cap else None, _p(info)))
+        m = 0 if info[0] & COVIS_LIMIT else min(int(info[1]), int(loop_conn_cap))
+        return status[:nkf].copy(), loop[:m].copy(), info
+
+    def GetBestCovisibilityKeyFrames(self, f, N):
+        return self.ord_kf[f, :min(int(self.nord[f]), N)].copy()
+
+    def GetCovisiblesByWeight(self, f, w):
+        """KeyFrame.cc:287-302: upper_bound with weightComp; no weight below w -> an empty vector."""
+        ws = self.ord_w[f, :int(self.nord[f])]
+        n = int((ws >= w).sum())
+        return self.ord_kf[f, :0 if n == len(ws) else n].copy()
+
+
+class Tracking:
+    """Tracking::UpdateLocalMap (thirdparty/orb-slam2/src/Tracking.cc:1186-1321) on the GPU."""
+
+    @staticmethod
+    def UpdateLocalMap(graph, kp_point, kf_point, npoints, obs_start, obs_frame, point_bad=None, kf_bad=None, prev_local_kf=None,
+                       nbest=10, max_local=80, lkf_cap=256, qcap=16000):
+        """UpdateLocalKeyFrames + UpdateLocalPoints for a frame whose mvpMapPoints are the table indices kp_point (-1 = none), over
+        `graph` (a CovisibilityGraph) and the key frames' slots kf_point.  prev_local_kf = mvpLocalKeyFrames before the call (None =
+        none), walked again when no point votes.  Returns a dict: kp_point (a bad point's slot cleared), local_kf, ref_kf (-1 =
+        keep), queries (mvpLocalMapPoints as table indices, what SearchLocalPoints takes), status (LOCALMAP_NO_VOTES |
+        LOCALMAP_LIMIT).  Raises ValueError for everything pgorb_update_local_map refuses."""
+        fn = "Tracking.UpdateLocalMap"
+        nkf = graph.nkf
+        if nkf + 1 > COVIS_MAX_KF:
+            raise ValueError(fn + ": more than COVIS_MAX_KF - 1 key frames")
+        slots, ptrs, nk, st, of, pb, ko = _covis_table(fn, nkf, kf_point, int(npoints), obs_start, obs_frame, point_bad, graph.kf_order)
+        kp = np.ascontiguousarray(kp_point, np.int32).reshape(-1)
+        if len(kp) > 16000 or (len(kp) and (kp.min() < -1 or kp.max() >= npoints)):
+            raise ValueError(fn + ": more than 16000 slots, or a slot names a point out of range")
+        if not (1 <= int(lkf_cap) <= COVIS_MAX_KF and 1 <= int(qcap) <= 16000) or nbest < 0 or max_local < 0:
+            raise ValueError(fn + ": lkf_cap outside 1..COVIS_MAX_KF, qcap outside 1..16000, or a negative nbest / max_local")
+        prev = None if prev_local_kf is None else np.ascontiguousarray(prev_local_kf, np.int32).reshape(-1)
+        if prev is not None and (len(prev) > lkf_cap or (len(prev) and (prev.min() < 0 or prev.max() >= nkf))):
+            raise ValueError(fn + ": the previous list is longer than lkf_cap or names a key frame out of range")
+        for f in range(nkf):
+            no = int(graph.nord[f])
+            if not 0 <= no <= graph.conn_cap or (no and (graph.ord_kf[f, :no].min() < 0 or graph.ord_kf[f, :no].max() >= nkf)) or \
+                    not -1 <= int(graph.parent[f]) < nkf:
+                raise ValueError(fn + ": an ordered row or a parent is out of range")
+        kb = _mask(kf_bad, nkf, "kf_bad")
+        kpo = np.zeros(max(len(kp), 1), np.int32)
+        lk, q = np.zeros(int(lkf_cap), np.int32), np.zeros(int(qcap), np.int32)
+        outs = [np.zeros(1, np.int32) for _ in range(4)]                  # nlocal_kf, ref_kf, nq, status
+        ext = graph.ext
+        ext._check(ext._L.pgorb_update_local_map(
+            ext._h, nkf, ptrs, _p(nk), _p(kb), _p(kp if len(kp) else kpo), len(kp), int(npoints), _p(pb), _p(st), _p(of), graph.conn_cap,
+            _p(graph.ord_kf), _p(graph.nord), _p(graph.parent), None if ko is None else _p(ko), int(nbest), int(max_local),
+            -1 if prev is None else len(prev), None if prev is None or not len(prev) else _p(prev), _p(kpo), int(lkf_cap), _p(lk), _p(outs[0]),
+            _p(outs[1]), int(qcap), _p(q), _p(outs[2]), _p(outs[3])))
+        return dict(kp_point=kpo[:len(kp)].copy(), local_kf=lk[:int(outs[0][0])].copy(), ref_kf=int(outs[1][0]), queries=q[:int(outs[2][0])].copy(),
+                    status=int(outs[3][0]))
+
+
 
 class FrameStream:
     """Streamed ingest (include/pgorb.h, pgorb_stream_*): the frame loop around the extractor for frames that

@@ -81,8 +81,15 @@ next to each, the oracle's CPU time for the same work (1 thread, a few frames, s
                the new one), and LocalBundleAdjustment's benchmark window (40 key frames, 2000 points, 12 000 edges) through both
                optimisers in the same run, with the time per Levenberg trial.  No target is set.  --gba-only runs these rows
                (profiles/next_tier_gba.txt).
+  covisibility     the covisibility graph on the device (csrc/covisibility.hip), HIP events: a whole-map KeyFrame::UpdateConnections
+               (KeyFrame.cc:392-482) of ONE ride-shaped map -- 500 key frames x 2000 slots, tracks of 2 to 10 consecutive key frames, every
+               key frame in the list, th 15 (pgorb_update_connections_batch_device); its views (pgorb_covisibility_views_device); and
+               Tracking::UpdateLocalMap (Tracking.cc:1186-1321) of 128 frames of that map, each tracking a third of one key frame's
+               points (pgorb_update_local_map_batch_device).  One row's counters are checked against numpy.  Nobody has measured this
+               before and there is no CPU baseline (the Python reference of the tests is not one): no target is set, the rows record what
+               was measured.  --covis-only runs these rows alone (profiles/next_tier_covis.txt).
 
-usage: python tools/next_tier_bench.py [--batch 128] [--out profiles/r02_next_tier.txt] [--refresh-only | --place-only | --loop-only | --track-only | --pose-only | --sim3-only | --pnp-only | --optsim3-only | --lba-only | --eg-only | --gba-only]"""
+usage: python tools/next_tier_bench.py [--batch 128] [--out profiles/r02_next_tier.txt] [--refresh-only | --place-only | --loop-only | --track-only | --pose-only | --sim3-only | --pnp-only | --optsim3-only | --lba-only | --eg-only | --gba-only | --covis-only]"""
 import argparse, ctypes as C, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -108,6 +115,7 @@ ap.add_argument("--optsim3-only", action="store_true", help="the OptimizeSim3 ro
 ap.add_argument("--lba-only", action="store_true", help="the LocalBundleAdjustment rows alone (no ride, no vocabulary)")
 ap.add_argument("--eg-only", action="store_true", help="the OptimizeEssentialGraph row alone (no ride, no vocabulary)")
 ap.add_argument("--gba-only", action="store_true", help="the GlobalBundleAdjustment rows alone (no ride, no vocabulary)")
+ap.add_argument("--covis-only", action="store_true", help="the covisibility-graph rows alone (no ride, no vocabulary)")
 a = ap.parse_args()
 w, h, nf, B = 1920, 1080, a.features, a.batch
 
@@ -641,6 +649,81 @@ def eg_lines(nkf=500, nref=100, back=4):
             "%-128s %10.3f %22.1f" % ("essential_graph: " + scene, t, t_ref)]
 
 
+def covis_lines(nkf=500, cap=2000, held=1400, npairs=128, conn_cap=256, lkf_cap=256, qcap=16000):
+    """The covisibility graph: a whole-map UpdateConnections of a ride-shaped map, its views, and UpdateLocalMap of a batch of frames."""
+    rng = np.random.RandomState(11)
+    npts = nkf * held // 6
+    start = rng.randint(0, nkf, npts)
+    length = np.minimum(rng.randint(2, 11, npts), nkf - start)                  # a track: 2..10 consecutive key frames
+    obs_start = np.zeros(npts + 1, np.int32)
+    obs_start[1:] = np.cumsum(length)
+    owner = np.repeat(np.arange(npts), length)
+    obs_frame = (np.repeat(start, length) + np.arange(obs_start[-1]) - np.repeat(obs_start[:-1], length)).astype(np.int32)
+    kf_point = np.full((nkf + npairs, cap), -1, np.int32)
+    n = np.zeros(nkf + npairs, np.int32)
+    order = np.argsort(obs_frame, kind="stable")
+    for f, lo, hi in zip(range(nkf), np.searchsorted(obs_frame[order], np.arange(nkf)), np.searchsorted(obs_frame[order], np.arange(nkf), "right")):
+        pts = owner[order[lo:hi]][:cap]
+        kf_point[f, :len(pts)], n[f] = pts, len(pts)
+    kp_point = np.full((npairs, cap), -1, np.int32)
+    for p_ in range(npairs):                                                    # a frame tracks a share of the points of one key frame
+        f = int(rng.randint(0, nkf))
+        kp_point[p_, :n[f]:3] = kf_point[f, :n[f]:3]
+        n[nkf + p_] = n[f]
+    bad = (rng.randint(0, 50, npts) == 0).astype(np.uint8)
+    rank = rng.permutation(nkf + npairs).astype(np.int32)
+    ext = pg.ORBextractor(2000, 1.2, 8, 20, 7, max_width=640, max_height=480)
+    dev = lambda x: torch.from_numpy(np.ascontiguousarray(x)).cuda()
+    nfr = nkf + npairs
+    T = dict(kf_point=dev(kf_point), n=dev(n), bad=dev(bad), os=dev(obs_start), of=dev(obs_frame), rank=dev(rank), lst=dev(np.arange(nkf, dtype=np.int32)),
+             kp=dev(kp_point), pf=dev(np.arange(nkf, nfr, dtype=np.int32)))
+    z = lambda *shape: torch.zeros(shape, dtype=torch.int32, device="cuda")
+    G = dict(ck=z(nfr, conn_cap), cw=z(nfr, conn_cap), nc=z(nfr), ok=z(nfr, conn_cap), ow=z(nfr, conn_cap), no=z(nfr), par=z(nfr) - 1,
+             first=torch.ones(nfr, dtype=torch.uint8, device="cuda"), st=z(nfr), loop=z(64, 3), info=z(4))
+    O = dict(best=z(nfr, 10), cs=z(nfr + 1), cv=z(nfr * 64), cvw=z(nfr * 64), bw=z(nfr), vinfo=z(2), kpo=z(npairs, cap), lk=z(npairs, lkf_cap), nl=z(npairs),
+             ref=z(npairs), q=z(npairs, qcap), nq=z(npairs), lst=z(npairs))
+    p = lambda t: C.c_void_p(t.data_ptr())
+    s = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    L, h = ext._L, ext._h
+
+    def update():
+        G["nc"].zero_(); G["no"].zero_(); G["par"].fill_(-1); G["first"].fill_(1)
+        ext._check(L.pgorb_update_connections_batch_device(h, p(T["kf_point"]), p(T["n"]), nfr, cap, npts, p(T["bad"]), p(T["os"]), p(T["of"]),
+                                                           int(obs_start[-1]), p(T["rank"]), None, nkf, p(T["lst"]), 15, conn_cap, p(G["ck"]), p(G["cw"]), p(G["nc"]),
+                                                           p(G["ok"]), p(G["ow"]), p(G["no"]), p(G["par"]), p(G["first"]), p(G["st"]), 64, p(G["loop"]), p(G["info"]), s))
+
+    def views():
+        ext._check(L.pgorb_covisibility_views_device(h, nfr, conn_cap, p(G["ok"]), p(G["ow"]), p(G["no"]), 10, p(O["best"]), nfr * 64, p(O["cs"]), p(O["cv"]),
+                                                     p(O["cvw"]), 30, p(O["bw"]), p(O["vinfo"]), s))
+
+    def local_map():
+        ext._check(L.pgorb_update_local_map_batch_device(h, p(T["kf_point"]), p(T["n"]), nfr, cap, None, p(T["pf"]), npairs, p(T["kp"]), npts, p(T["bad"]),
+                                                         p(T["os"]), p(T["of"]), int(obs_start[-1]), conn_cap, p(G["ok"]), p(G["no"]), p(G["par"]), p(T["rank"]),
+                                                         10, 80, lkf_cap, None, None, p(O["kpo"]), p(O["lk"]), p(O["nl"]), p(O["ref"]), qcap, p(O["q"]), p(O["nq"]),
+                                                         p(O["lst"]), s))
+    t_up, t_vw, t_lm = timed(update), timed(views), timed(local_map)
+    st, nc, no = G["st"].cpu().numpy()[:nkf], G["nc"].cpu().numpy()[:nkf], G["no"].cpu().numpy()[:nkf]
+    assert np.all(st & 1) and not np.any(st & 32) and int(O["vinfo"][0]) == 0 and int(G["info"][1]) == 0
+    f = nkf // 2                                                               # one row against numpy: the counters of key frame f
+    pts = kf_point[f, :n[f]]
+    pts = pts[bad[pts] == 0]
+    seen = np.concatenate([obs_frame[obs_start[q]:obs_start[q + 1]] for q in pts])
+    cnt = np.bincount(seen[seen != f], minlength=nkf)
+    row = dict(zip(G["ck"][f, :nc[f]].cpu().numpy().tolist(), G["cw"][f, :nc[f]].cpu().numpy().tolist()))
+    assert row == {int(j): int(c) for j, c in enumerate(cnt) if c}, "row %d differs from numpy" % f
+    nl, nq, ls = O["nl"].cpu().numpy(), O["nq"].cpu().numpy(), O["lst"].cpu().numpy()
+    assert np.all(ls == 0) and nl.min() > 0 and nq.min() > 0
+    scene = "%d key frames x %d slots, %d points, %d observations" % (nkf, cap, npts, obs_start[-1])
+    return ["# The covisibility graph on the device, resident calls, HIP events, median of 9 after one warm-up.  No CPU baseline exists (the Python",
+            "# reference of the tests is not one) and no target is set: this records what was measured.",
+            "%-150s %10s" % ("call", "GPU ms"),
+            "%-150s %10.3f" % ("update_connections, whole map in list order, th 15: %s; rows hold %.0f counters, %.0f ordered, on average (k_cov_prep, k_cov_count, "
+                               "k_cov_finish, k_cov_loop; 4 small resets included)" % (scene, nc.mean(), no.mean()), t_up),
+            "%-150s %10.3f" % ("covisibility_views: best 10, the essential graph's CSR (%d entries), GetCovisiblesByWeight(30) lengths" % int(O["vinfo"][1]), t_vw),
+            "%-150s %10.3f" % ("update_local_map: %d frames of that map, a third of a key frame's points each: %.0f local key frames, %.0f local points on average"
+                               % (npairs, nl.mean(), nq.mean()), t_lm)]
+
+
 def gba_lines(nkf=500, per_kf=40, span=4):
     """GlobalBundleAdjustment: a ride-shaped map in the resident call, and LocalBundleAdjustment's benchmark window through both."""
     sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -732,6 +815,12 @@ if a.sim3_only:
     sys.exit(0)
 if a.pose_only:
     lines = ["# python tools/next_tier_bench.py --pose-only   (MI355X)"] + pose_lines()
+    print("\n".join(lines))
+    if a.out:
+        open(a.out, "w").write("\n".join(lines) + "\n")
+    sys.exit(0)
+if a.covis_only:
+    lines = ["# python tools/next_tier_bench.py --covis-only   (MI355X)"] + covis_lines()
     print("\n".join(lines))
     if a.out:
         open(a.out, "w").write("\n".join(lines) + "\n")

@@ -1498,6 +1498,120 @@ int  pgorb_update_local_map_batch_device(pgorb_ctx* ctx,
         int32_t* d_kp_point_out, int32_t* d_local_kf, int32_t* d_nlocal_kf, int32_t* d_ref_kf,
         int qcap, int32_t* d_queries, int32_t* d_nq, int32_t* d_status, void* hip_stream);
 
+/* ---- The cullings: LocalMapping::MapPointCulling and KeyFrameCulling with the map surgery they trigger (csrc/culling.hip) ------
+ * The conventions of the covisibility block hold: key frames are the nframes frames of one resident batch with their slots
+ * d_kf_point [nframes][cap_per_frame] + d_n, the table is that of pgorb_refresh_map_points (d_point_bad, the CSR d_obs_start /
+ * d_obs_frame / d_obs_idx), d_kf_order is the address rank, an index out of range is no slot, no observation and no key frame, and
+ * the device forms never read or write out of bounds.  Integers only; every result is exact.  Here d_kf_point and d_point_bad are
+ * in/out and must not be NULL.
+ * Erased observations.  The CSR keeps its shape during a culling: d_obs_live [nobs] (uint8, in/out) masks it, and a dead
+ * observation does not exist for any count or walk.  Observations() is the number of live entries of the list (the monocular
+ * reading).  d_ref_obs [npoints] (in/out) is the position of mpRefKF in the point's own list, as pgorb_refresh_map_points reads it.
+ *
+ *   pgorb_compact_observations_device   a fresh CSR from the old one, the mask and d_ref_obs: d_obs_start_out [npoints + 1],
+ *       d_obs_frame_out / d_obs_idx_out [room for nobs], the order inside each list kept; d_ref_obs_out = ref_obs re-based to the
+ *       compacted list, -1 when it names no live entry (an empty list always); d_info[0] = the new length.  THE OUTPUTS MUST NOT
+ *       ALIAS THE INPUTS; the device form cannot see an alias.  The other entry points read these outputs as they are, with the old
+ *       nobs as the bound.  k_cull_compact_scan (one workgroup) + k_cull_compact_copy (a thread per point).
+ *   pgorb_map_point_culling_device   LocalMapping::MapPointCulling (src/LocalMapping.cc:170-207) over d_recent [nrecent] = table
+ *       indices in mlpRecentAddedMapPoints order (distinct).  Per point d_first_kf_id (mnFirstKFid), d_visible, d_found (int32);
+ *       cur_kf_id = mpCurrentKeyFrame->mnId; th_obs is the reference's 2.  The four tests in the reference's order, d_action [nrecent]:
+ *       PGORB_CULL_MP_WAS_BAD (already bad), FOUND_RATIO ((float)found / (float)visible, one correctly rounded division, < 0.25f; a
+ *       zero `visible` follows IEEE: inf or NaN is not below), FEW_OBS ((int)cur_kf_id - (int)first_kf_id >= 2 and Observations() <=
+ *       th_obs), AGED (that difference >= 3: it only leaves the list), else KEEP; an entry out of range is dropped with
+ *       PGORB_CULL_MP_NONE.  FOUND_RATIO and FEW_OBS run MapPoint::SetBadFlag (src/MapPoint.cc:172-187): the bad flag is set, the slot
+ *       kf_point[f][i] of every live observer becomes -1, all its observations die.  d_recent_out + d_nrecent_out = the surviving
+ *       list (KEEP), order kept, entries past the count keep their bytes.  d_info [PGORB_CULL_INFO] = (0, survivors, points culled,
+ *       0).  Map::EraseMapPoint stays with the caller, who reads d_action.  k_cull_points, a thread per entry.
+ *   pgorb_keyframe_culling_device   LocalMapping::KeyFrameCulling (:634-698) with KeyFrame::SetBadFlag (src/KeyFrame.cc:556-648) and
+ *       MapPoint::EraseObservation (src/MapPoint.cc:132-158); one problem per call.  Reads d_kps (only `octave`), d_kf_id0 (NULL =
+ *       none), d_kf_not_erase (NULL = none; mbNotErase), cur_kf; in/out the slots, the table with d_point_bad / d_obs_live /
+ *       d_ref_obs, d_kf_bad, d_kf_to_be_erased (NULL = not reported) and the graph state of the covisibility block.
+ *       The list is cur_kf's ordered row AS IT STANDS WHEN THE CALL STARTS (:640 copies it); more than list_cap members ->
+ *       PGORB_CULL_LIMIT in d_info[0], the length in d_info[1], and nothing else is written.  The members are evaluated one after
+ *       another in list order, each against the state the earlier SetBadFlags left; d_record [list_cap][4] = (key frame, nMPs,
+ *       nRedundantObservations, action), records past the list keep their bytes:
+ *         PGORB_CULL_KF_NONE   a member out of range, counts -1;  PGORB_CULL_KF_ID0   mnId == 0, counts -1;
+ *         otherwise the slots in order: an empty slot or a bad point is skipped, every other point adds one to nMPs, and it is
+ *         redundant when Observations() > 3 and at least three live observers other than the member have a keypoint octave <= the
+ *         slot's octave + 1.  The decision is (double)nRedundant > 0.9 * (double)nMPs.
+ *         PGORB_CULL_KF_WAS_BAD   kf_bad was set: counted and recorded, nothing written (a second SetBadFlag finds nothing left);
+ *         PGORB_CULL_KF_KEEP;  PGORB_CULL_KF_TO_BE_ERASED   redundant with not_erase: mbToBeErased and nothing else;
+ *         PGORB_CULL_KF_CULLED   SetBadFlag runs to its end before the next member is looked at.
+ *       SetBadFlag of A: (1) for every key of A's map in address order, EraseConnection(A) on that row if it holds A: the entry
+ *       leaves the row's map and the ordered list becomes the WHOLE map, sub-threshold entries included, descending (weight, address)
+ *       -- the reading of PGORB_COVIS_RESORTED; (2) for every non-empty slot of A, with no bad test, EraseObservation(A) if the list
+ *       holds a live (A, .): it dies; if ref_obs named it, ref_obs becomes the first live entry in list order or -1; with two or
+ *       fewer live observations left the point goes bad (the slots of its remaining observers -1, all observations dead, ref_obs
+ *       kept); A's own slots keep their values; (3) A's two rows are emptied; (4) the spanning tree: the children are the c with
+ *       parent[c] == A and kf_bad[c] == 0 in address order, the candidates start as {parent[A]}; repeatedly, over the children in
+ *       address order and each child's current ordered list in list order, the entry that is a candidate with the first strictly
+ *       largest GetWeight (the weight in the child's map, 0 when absent) gives that child its parent, and the child joins the
+ *       candidates; every child left gets parent[A] (-1 = none); parent[A] itself keeps its value, for mTcp; (5) kf_bad[A] = 1.
+ *       Row bytes: a rewritten row holds -1 / 0 from its new count up to its old count, entries beyond the old count keep their bytes.
+ *       d_row_status [nframes] bits: PGORB_CULL_ROW_ERASED (lost an entry, re-sorted), ROW_CLEARED (the culled key frame),
+ *       ROW_REPARENTED; a row with status 0 keeps every byte.  d_info = (0, list length, key frames culled, points that went bad).
+ *       mTcp, Map::EraseKeyFrame and KeyFrameDatabase::erase stay with the caller, who reads d_record.  k_cull_eval counts every
+ *       member from the input state, a workgroup each; k_cull_walk, ONE workgroup, walks the list, counts a member again only when a
+ *       cull cleared one of its slots or claimed a point one of its slots holds (nothing else can change its counts), and does the
+ *       surgery of a culled member with the row sorts in LDS; a point held in several slots of A is handled once.  THE DEVICE FORM REQUIRES connection rows in address
+ *       order with no key frame twice and no key frame twice in one observation list; only the single call checks it.
+ *   pgorb_map_point_culling / pgorb_keyframe_culling   the same from host buffers (kf_point[f] [n[f]], kps[f]), checked: return
+ *       the number of points / key frames culled, or PGORB_E_ARG for a negative count, a NULL array that is read or written, a slot,
+ *       observation (key frame or keypoint), recent entry, connection, parent or cur_kf out of range, obs_start not rising from 0, a
+ *       key frame twice in one list, a recent point twice, kf_order not a permutation, a row count outside [0, conn_cap], a connection
+ *       row not in address order, an ordered entry that is not in its row's map, ref_obs outside [-1, length) of a non-empty list,
+ *       list_cap < 1.  They equal the device forms byte for byte.
+ * Limits (PGORB_E_LIMIT): nframes <= PGORB_COVIS_MAX_KF, conn_cap <= PGORB_COVIS_MAX_CONN, cap_per_frame <= 16000.  Scratch arena
+ * (KeyFrameCulling): (nframes + npoints + 2 * conn_cap) * 4 bytes.  Determinism: a result depends on its inputs alone. */
+#define PGORB_CULL_MP_KEEP         0
+#define PGORB_CULL_MP_WAS_BAD      1
+#define PGORB_CULL_MP_FOUND_RATIO  2
+#define PGORB_CULL_MP_FEW_OBS      3
+#define PGORB_CULL_MP_AGED         4
+#define PGORB_CULL_MP_NONE         5
+#define PGORB_CULL_KF_KEEP         0
+#define PGORB_CULL_KF_CULLED       1
+#define PGORB_CULL_KF_TO_BE_ERASED 2
+#define PGORB_CULL_KF_ID0          3
+#define PGORB_CULL_KF_WAS_BAD      4
+#define PGORB_CULL_KF_NONE         5
+#define PGORB_CULL_ROW_ERASED      1
+#define PGORB_CULL_ROW_CLEARED     2
+#define PGORB_CULL_ROW_REPARENTED  4
+#define PGORB_CULL_LIMIT           32
+#define PGORB_CULL_INFO            4
+int  pgorb_compact_observations_device(pgorb_ctx* ctx,
+        int npoints, const int32_t* d_obs_start, const int32_t* d_obs_frame, const int32_t* d_obs_idx, int nobs,
+        const uint8_t* d_obs_live, const int32_t* d_ref_obs, int32_t* d_obs_start_out, int32_t* d_obs_frame_out, int32_t* d_obs_idx_out,
+        int32_t* d_ref_obs_out, int32_t* d_info /*[1]*/, void* hip_stream);
+int  pgorb_map_point_culling(pgorb_ctx* ctx,
+        int nkf, int32_t* const* kf_point, const int32_t* n /*[nkf]*/, int npoints, uint8_t* point_bad /*[npoints]*/,
+        const int32_t* obs_start /*[npoints + 1]*/, const int32_t* obs_frame, const int32_t* obs_idx, uint8_t* obs_live,
+        const int32_t* first_kf_id, const int32_t* visible, const int32_t* found /*[npoints]*/, int nrecent, const int32_t* recent,
+        int cur_kf_id, int th_obs, int32_t* action /*[nrecent]*/, int32_t* recent_out /*[nrecent]*/, int32_t* nrecent_out,
+        int32_t* info /*[PGORB_CULL_INFO]*/);
+int  pgorb_map_point_culling_device(pgorb_ctx* ctx,
+        int32_t* d_kf_point, const int32_t* d_n, int nframes, int cap_per_frame, int npoints, uint8_t* d_point_bad,
+        const int32_t* d_obs_start, const int32_t* d_obs_frame, const int32_t* d_obs_idx, int nobs, uint8_t* d_obs_live,
+        const int32_t* d_first_kf_id, const int32_t* d_visible, const int32_t* d_found, int nrecent, const int32_t* d_recent,
+        int cur_kf_id, int th_obs, int32_t* d_action, int32_t* d_recent_out, int32_t* d_nrecent_out, int32_t* d_info, void* hip_stream);
+int  pgorb_keyframe_culling(pgorb_ctx* ctx,
+        int nkf, const pgorb_keypoint* const* kps, int32_t* const* kf_point, const int32_t* n /*[nkf]*/,
+        int npoints, uint8_t* point_bad, const int32_t* obs_start, const int32_t* obs_frame, const int32_t* obs_idx, uint8_t* obs_live,
+        int32_t* ref_obs /*[npoints]*/, const int32_t* kf_order /*[nkf] or NULL*/, const uint8_t* kf_id0 /*[nkf] or NULL*/,
+        const uint8_t* kf_not_erase /*[nkf] or NULL*/, uint8_t* kf_bad /*[nkf]*/, uint8_t* kf_to_be_erased /*[nkf] or NULL*/, int cur_kf,
+        int conn_cap, int32_t* conn_kf, int32_t* conn_w /*[nkf][conn_cap]*/, int32_t* nconn, int32_t* ord_kf, int32_t* ord_w, int32_t* nord,
+        int32_t* parent /*[nkf]*/, int list_cap, int32_t* record /*[list_cap][4]*/, int32_t* row_status /*[nkf]*/,
+        int32_t* info /*[PGORB_CULL_INFO]*/);
+int  pgorb_keyframe_culling_device(pgorb_ctx* ctx,
+        const pgorb_keypoint* d_kps, int32_t* d_kf_point, const int32_t* d_n, int nframes, int cap_per_frame,
+        int npoints, uint8_t* d_point_bad, const int32_t* d_obs_start, const int32_t* d_obs_frame, const int32_t* d_obs_idx, int nobs,
+        uint8_t* d_obs_live, int32_t* d_ref_obs, const int32_t* d_kf_order, const uint8_t* d_kf_id0, const uint8_t* d_kf_not_erase,
+        uint8_t* d_kf_bad, uint8_t* d_kf_to_be_erased, int cur_kf,
+        int conn_cap, int32_t* d_conn_kf, int32_t* d_conn_w, int32_t* d_nconn, int32_t* d_ord_kf, int32_t* d_ord_w, int32_t* d_nord,
+        int32_t* d_parent, int list_cap, int32_t* d_record, int32_t* d_row_status, int32_t* d_info, void* hip_stream);
+
 /* ---- ORB vocabulary (DBoW2 TemplatedVocabulary<FORB::TDescriptor, FORB>) -----------------
  *   pgorb_vocab_load_text     ORBVocabulary(text_file) -> TemplatedVocabulary::loadFromTextFile
  *                             thirdparty/orb-slam2/src/ORBVocabulary.cc:7-9,

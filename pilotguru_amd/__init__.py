@@ -23,4 +23,7 @@ from .orb import (INIT_AMBIGUOUS, INIT_DEGENERATE_H, INIT_FEW, INIT_FEW_GOOD, IN
                   INIT_LOW_PARALLAX, INIT_MAX_ITERATIONS, INIT_MODEL_F, INIT_MODEL_H, INIT_NO_MODEL, INIT_OK, INIT_PARAMS_DTYPE, Initializer)
 from .orb import (COVIS_EMPTY, COVIS_FALLBACK, COVIS_INFO, COVIS_LIMIT, COVIS_MAX_CONN, COVIS_MAX_KF, COVIS_PARENT_SET,  # noqa: F401
                   COVIS_RESORTED, COVIS_UPDATED, LOCALMAP_LIMIT, LOCALMAP_NO_VOTES, CovisibilityGraph, Tracking)
+from .orb import (CULL_INFO, CULL_KF_CULLED, CULL_KF_ID0, CULL_KF_KEEP, CULL_KF_NONE, CULL_KF_TO_BE_ERASED, CULL_KF_WAS_BAD, CULL_LIMIT,  # noqa: F401
+                  CULL_MP_AGED, CULL_MP_FEW_OBS, CULL_MP_FOUND_RATIO, CULL_MP_KEEP, CULL_MP_NONE, CULL_MP_WAS_BAD, CULL_ROW_CLEARED,
+                  CULL_ROW_ERASED, CULL_ROW_REPARENTED, compact_observations)
 from .place import KeyFrameDatabase  # noqa: F401

@@ -41,6 +41,8 @@ SYMBOLS = (
     "pgorb_refresh_map_points", "pgorb_refresh_map_points_batch_device",
     "pgorb_update_connections", "pgorb_update_connections_batch_device", "pgorb_covisibility_views_device",
     "pgorb_update_local_map", "pgorb_update_local_map_batch_device",
+    "pgorb_compact_observations_device", "pgorb_map_point_culling", "pgorb_map_point_culling_device",
+    "pgorb_keyframe_culling", "pgorb_keyframe_culling_device",
     "pgorb_bow_vectors_batch_device", "pgorb_bow_score_l1_batch_device",
     "pgorb_detect_relocalization_candidates", "pgorb_detect_relocalization_candidates_batch_device",
     "pgorb_detect_loop_candidates", "pgorb_detect_loop_candidates_batch_device",
@@ -307,6 +309,22 @@ def lib():
     #  status, stream)
     L.pgorb_update_local_map_batch_device.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, vp, C.c_int, vp, C.c_int, vp, vp, vp, C.c_int, C.c_int,
                                                       vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp]
+    # (ctx, npoints, obs_start, obs_frame, obs_idx, nobs, obs_live, ref_obs, obs_start_out, obs_frame_out, obs_idx_out, ref_obs_out, info, stream)
+    L.pgorb_compact_observations_device.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int] + [vp] * 8
+    # (ctx, nkf, kf_point[], n, npoints, point_bad, obs_start, obs_frame, obs_idx, obs_live, first_kf_id, visible, found, nrecent, recent,
+    #  cur_kf_id, th_obs, action, recent_out, nrecent_out, info)
+    L.pgorb_map_point_culling.argtypes = [vp, C.c_int, vp, vp, C.c_int] + [vp] * 8 + [C.c_int, vp, C.c_int, C.c_int] + [vp] * 4
+    # (ctx, kf_point, n, nframes, cap, npoints, point_bad, obs_start, obs_frame, obs_idx, nobs, obs_live, first_kf_id, visible, found, nrecent,
+    #  recent, cur_kf_id, th_obs, action, recent_out, nrecent_out, info, stream)
+    L.pgorb_map_point_culling_device.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, C.c_int, vp,
+                                                 C.c_int, C.c_int] + [vp] * 5
+    # (ctx, nkf, kps[], kf_point[], n, npoints, point_bad, obs_start, obs_frame, obs_idx, obs_live, ref_obs, kf_order, kf_id0, kf_not_erase,
+    #  kf_bad, kf_to_be_erased, cur_kf, conn_cap, 6 row arrays, parent, list_cap, record, row_status, info)
+    L.pgorb_keyframe_culling.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int] + [vp] * 11 + [C.c_int, C.c_int] + [vp] * 7 + [C.c_int, vp, vp, vp]
+    # (ctx, kps, kf_point, n, nframes, cap, npoints, point_bad, obs_start, obs_frame, obs_idx, nobs, obs_live, ref_obs, kf_order, kf_id0,
+    #  kf_not_erase, kf_bad, kf_to_be_erased, cur_kf, conn_cap, 6 row arrays, parent, list_cap, record, row_status, info, stream)
+    L.pgorb_keyframe_culling_device.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int] + [vp] * 7 + \
+        [C.c_int, C.c_int] + [vp] * 7 + [C.c_int, vp, vp, vp, vp]
     # (ctx, word, weight, n, nframes, cap, bow_id, bow_val, nbow, stream)
     L.pgorb_bow_vectors_batch_device.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp]
     # (ctx, bow_id, bow_val, nbow, nframes, cap, pair_a, pair_b, npairs, score, stream)

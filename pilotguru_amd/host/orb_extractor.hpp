@@ -259,9 +259,28 @@ inline void checkRefresh(const std::vector<const KeyFrame*>& kfs, const std::vec
                          const std::vector<uint8_t>& pointBad, const MapPointObservations& O, const std::vector<int32_t>* select, int what);
 }  // namespace detail
 
+class CovisibilityGraph;
+
 class LocalMapping {
  public:
     explicit LocalMapping(pgorb_ctx* ctx) : ctx_(ctx) {}
+    // LocalMapping::MapPointCulling (LocalMapping.cc:170-207) over recent = mlpRecentAddedMapPoints as table indices; obsLive masks the
+    // observation lists (include/pgorb.h).  kfPoint, pointBad (one flag per point) and obsLive are updated in place; action[t] =
+    // PGORB_CULL_MP_*; survivors = the list afterwards.  Returns the number of points culled.  Defined below CovisibilityGraph.
+    int MapPointCulling(std::vector<std::vector<int32_t>>& kfPoint, std::vector<uint8_t>& pointBad, const MapPointObservations& obs,
+                        std::vector<uint8_t>& obsLive, const std::vector<int32_t>& firstKfId, const std::vector<int32_t>& visible,
+                        const std::vector<int32_t>& found, const std::vector<int32_t>& recent, int curKfId, int thObs,
+                        std::vector<int32_t>& action, std::vector<int32_t>& survivors, std::array<int32_t, PGORB_CULL_INFO>* info = nullptr);
+    // LocalMapping::KeyFrameCulling (:634-698) with KeyFrame::SetBadFlag and MapPoint::EraseObservation over `graph` with
+    // mpCurrentKeyFrame = curKf.  octaves[f][i] = mvKeysUn[i].octave; kfPoint, pointBad, obsLive, refObs, kfBad, kfToBeErased (one flag
+    // per key frame) and the graph are updated in place; kfNotErase empty = none.  record = (key frame, nMPs, nRedundantObservations,
+    // PGORB_CULL_KF_*) per list member; rowStatus [nkf] (PGORB_CULL_ROW_* bits).  Returns the number of key frames culled; info[0] ==
+    // PGORB_CULL_LIMIT: the list is longer than listCap and nothing was done.
+    int KeyFrameCulling(CovisibilityGraph& graph, int curKf, const std::vector<std::vector<int32_t>>& octaves,
+                        std::vector<std::vector<int32_t>>& kfPoint, std::vector<uint8_t>& pointBad, const MapPointObservations& obs,
+                        std::vector<uint8_t>& obsLive, std::vector<int32_t>& refObs, const std::vector<uint8_t>& kfNotErase,
+                        std::vector<uint8_t>& kfBad, std::vector<uint8_t>& kfToBeErased, int listCap, std::vector<int32_t>& record,
+                        std::vector<int32_t>& rowStatus, std::array<int32_t, PGORB_CULL_INFO>* info = nullptr);
     // MapPoint::ComputeDistinctiveDescriptors (MapPoint.cc:259-324) and MapPoint::UpdateNormalAndDepth (:347-388) of many points in
     // one call, as LocalMapping.cc:444-446 and :519-532 run them.  keyFrames: frame (mvKeysUn, mDescriptors) and pose are read;
     // kfBad[f] = isBad() (empty = none); points / descriptors (32 bytes each) / pointBad (empty = none) are the table, refreshed
@@ -1105,23 +1124,7 @@ class CovisibilityGraph {
             if (listed[f]) fail("the list names a key frame twice");
             listed[f] = 1;
         }
-        std::vector<int32_t> mark((size_t)nkf_ + 1, -1);
-        for (int f = 0; f < nkf_; f++) {
-            if (nconn[f] < 0 || nconn[f] > connCap_ || nord[f] < 0 || nord[f] > connCap_) fail("a row count is outside [0, connCap]");
-            if (parent[f] < -1 || parent[f] >= nkf_) fail("a parent is out of range");
-            int last = -1;
-            for (int t = 0; t < nconn[f]; t++) {
-                const int j = connKf[(size_t)f * connCap_ + t];
-                if (j < 0 || j >= nkf_ || j == f) fail("a connection is out of range");
-                const int r = kfOrder.empty() ? j : kfOrder[j];
-                if (r <= last) fail("a connection row is not in address order");
-                last = r; mark[j] = f;
-            }
-            for (int t = 0; t < nord[f]; t++) {
-                const int j = ordKf[(size_t)f * connCap_ + t];
-                if (j < 0 || j >= nkf_ || mark[j] != f) fail("an ordered entry is not in the row's map");
-            }
-        }
+        checkRows(fn);
         std::vector<const int32_t*> slots((size_t)nkf_ + 1, nullptr);
         std::vector<int32_t> n((size_t)nkf_ + 1, 0);
         for (int f = 0; f < nkf_; f++) { slots[f] = kfPoint[f].data(); n[f] = (int32_t)kfPoint[f].size(); }
@@ -1143,6 +1146,29 @@ class CovisibilityGraph {
             for (int e = 0; e < m; e++) loopConn->push_back({loop[3 * e], loop[3 * e + 1], loop[3 * e + 2]});
         }
         return rc;
+    }
+    // what pgorb_update_connections and pgorb_keyframe_culling reject of the rows: the counts, the address order of the map, the
+    // ordered entries inside it, the parents
+    void checkRows(const char* fn) const
+    {
+        auto fail = [&](const char* what) { throw std::invalid_argument(std::string(fn) + ": " + what); };
+        std::vector<int32_t> mark((size_t)nkf_ + 1, -1);
+        for (int f = 0; f < nkf_; f++) {
+            if (nconn[f] < 0 || nconn[f] > connCap_ || nord[f] < 0 || nord[f] > connCap_) fail("a row count is outside [0, connCap]");
+            if (parent[f] < -1 || parent[f] >= nkf_) fail("a parent is out of range");
+            int last = -1;
+            for (int t = 0; t < nconn[f]; t++) {
+                const int j = connKf[(size_t)f * connCap_ + t];
+                if (j < 0 || j >= nkf_ || j == f) fail("a connection is out of range");
+                const int r = kfOrder.empty() ? j : kfOrder[j];
+                if (r <= last) fail("a connection row is not in address order");
+                last = r; mark[j] = f;
+            }
+            for (int t = 0; t < nord[f]; t++) {
+                const int j = ordKf[(size_t)f * connCap_ + t];
+                if (j < 0 || j >= nkf_ || mark[j] != f) fail("an ordered entry is not in the row's map");
+            }
+        }
     }
     // GetBestCovisibilityKeyFrames(N) (KeyFrame.cc:277-285)
     std::vector<int32_t> GetBestCovisibilityKeyFrames(int f, int N) const
@@ -1223,5 +1249,104 @@ class Tracking {
  private:
     pgorb_ctx* ctx_;
 };
+
+namespace detail {
+// what both cullings reject of the masked observation lists beyond checkCovisTable
+inline void checkCullTable(const char* fn, const std::vector<std::vector<int32_t>>& kfPoint, size_t npoints, const std::vector<uint8_t>& pointBad,
+                           const MapPointObservations& O, const std::vector<uint8_t>& obsLive, const std::vector<int32_t>& kfOrder)
+{
+    auto fail = [&](const char* what) { throw std::invalid_argument(std::string(fn) + ": " + what); };
+    if (pointBad.size() != npoints) fail("pointBad needs one flag per point");
+    checkCovisTable(fn, kfPoint.size(), kfPoint, npoints, pointBad, O, kfOrder);
+    const size_t m = (size_t)O.obsStart[npoints];
+    if (O.obsIdx.size() < m || obsLive.size() < m) fail("obsIdx and obsLive need one entry per observation");
+    for (size_t k = 0; k < m; k++)
+        if (O.obsIdx[k] < 0 || O.obsIdx[k] >= (int64_t)kfPoint[O.obsFrame[k]].size()) fail("an observation names a keypoint out of range");
+}
+}  // namespace detail
+
+inline int LocalMapping::MapPointCulling(std::vector<std::vector<int32_t>>& kfPoint, std::vector<uint8_t>& pointBad, const MapPointObservations& obs,
+                                         std::vector<uint8_t>& obsLive, const std::vector<int32_t>& firstKfId, const std::vector<int32_t>& visible,
+                                         const std::vector<int32_t>& found, const std::vector<int32_t>& recent, int curKfId, int thObs,
+                                         std::vector<int32_t>& action, std::vector<int32_t>& survivors, std::array<int32_t, PGORB_CULL_INFO>* info)
+{
+    const char* fn = "LocalMapping::MapPointCulling";
+    auto fail = [&](const char* what) { throw std::invalid_argument(std::string(fn) + ": " + what); };
+    const size_t np = pointBad.size(), nkf = kfPoint.size();
+    detail::checkCullTable(fn, kfPoint, np, pointBad, obs, obsLive, {});
+    if (firstKfId.size() != np || visible.size() != np || found.size() != np) fail("firstKfId, visible and found need one entry per point");
+    std::vector<uint8_t> listed(np + 1, 0);
+    for (int32_t p : recent) {
+        if (p < 0 || p >= (int64_t)np) fail("a recent entry is out of range");
+        if (listed[p]) fail("the recent list names a point twice");
+        listed[p] = 1;
+    }
+    std::vector<int32_t*> slots(nkf + 1, nullptr);
+    std::vector<int32_t> n(nkf + 1, 0);
+    for (size_t f = 0; f < nkf; f++) { slots[f] = kfPoint[f].data(); n[f] = (int32_t)kfPoint[f].size(); }
+    const size_t nr = recent.size();
+    action.assign(nr + 1, 0);
+    survivors.assign(nr + 1, 0);
+    int32_t nout = 0;
+    std::array<int32_t, PGORB_CULL_INFO> inf{};
+    const int rc = pgorb_map_point_culling(ctx_, (int)nkf, slots.data(), n.data(), (int)np, pointBad.data(), obs.obsStart.data(), obs.obsFrame.data(),
+                                           obs.obsIdx.data(), obsLive.data(), firstKfId.data(), visible.data(), found.data(), (int)nr,
+                                           nr ? recent.data() : n.data(), curKfId, thObs, action.data(), survivors.data(), &nout, inf.data());
+    if (rc < 0) throw std::runtime_error(pgorb_last_error(ctx_));
+    action.resize(nr);
+    survivors.resize((size_t)nout);
+    if (info) *info = inf;
+    return rc;
+}
+
+inline int LocalMapping::KeyFrameCulling(CovisibilityGraph& graph, int curKf, const std::vector<std::vector<int32_t>>& octaves,
+                                         std::vector<std::vector<int32_t>>& kfPoint, std::vector<uint8_t>& pointBad, const MapPointObservations& obs,
+                                         std::vector<uint8_t>& obsLive, std::vector<int32_t>& refObs, const std::vector<uint8_t>& kfNotErase,
+                                         std::vector<uint8_t>& kfBad, std::vector<uint8_t>& kfToBeErased, int listCap, std::vector<int32_t>& record,
+                                         std::vector<int32_t>& rowStatus, std::array<int32_t, PGORB_CULL_INFO>* info)
+{
+    const char* fn = "LocalMapping::KeyFrameCulling";
+    auto fail = [&](const char* what) { throw std::invalid_argument(std::string(fn) + ": " + what); };
+    const int nkf = graph.nkf(), cc = graph.connCap();
+    const size_t np = pointBad.size();
+    if (kfPoint.size() != (size_t)nkf) fail("one slot array per key frame");
+    detail::checkCullTable(fn, kfPoint, np, pointBad, obs, obsLive, graph.kfOrder);
+    if (curKf < 0 || curKf >= nkf) fail("curKf is out of range");
+    if (listCap < 1) fail("listCap < 1");
+    if (octaves.size() != (size_t)nkf) fail("one octave array per key frame");
+    for (int f = 0; f < nkf; f++) if (octaves[f].size() != kfPoint[f].size()) fail("one octave per slot");
+    if (refObs.size() != np) fail("refObs needs one entry per point");
+    for (size_t p = 0; p < np; p++) {
+        const int len = obs.obsStart[p + 1] - obs.obsStart[p];
+        if (len && (refObs[p] < -1 || refObs[p] >= len)) fail("refObs lies outside the point's list");
+    }
+    if (kfBad.size() != (size_t)nkf || kfToBeErased.size() != (size_t)nkf || (!kfNotErase.empty() && kfNotErase.size() != (size_t)nkf) ||
+        (!graph.kfId0.empty() && graph.kfId0.size() != (size_t)nkf))
+        fail("kfBad, kfToBeErased, kfNotErase and kfId0 need one flag per key frame");
+    graph.checkRows(fn);
+    std::vector<std::vector<pgorb_keypoint>> keys((size_t)nkf);
+    std::vector<const pgorb_keypoint*> kps((size_t)nkf + 1, nullptr);
+    std::vector<int32_t*> slots((size_t)nkf + 1, nullptr);
+    std::vector<int32_t> n((size_t)nkf + 1, 0);
+    for (int f = 0; f < nkf; f++) {
+        keys[f].assign(octaves[f].size() + 1, pgorb_keypoint{});
+        for (size_t i = 0; i < octaves[f].size(); i++) keys[f][i].octave = octaves[f][i];
+        kps[f] = keys[f].data(); slots[f] = kfPoint[f].data(); n[f] = (int32_t)kfPoint[f].size();
+    }
+    record.assign((size_t)listCap * 4, 0);
+    rowStatus.assign((size_t)std::max(nkf, 1), 0);
+    std::array<int32_t, PGORB_CULL_INFO> inf{};
+    const int rc = pgorb_keyframe_culling(ctx_, nkf, kps.data(), slots.data(), n.data(), (int)np, pointBad.data(), obs.obsStart.data(), obs.obsFrame.data(),
+                                          obs.obsIdx.data(), obsLive.data(), refObs.data(), graph.kfOrder.empty() ? nullptr : graph.kfOrder.data(),
+                                          graph.kfId0.empty() ? nullptr : graph.kfId0.data(), kfNotErase.empty() ? nullptr : kfNotErase.data(),
+                                          kfBad.data(), kfToBeErased.data(), curKf, cc, graph.connKf.data(), graph.connW.data(), graph.nconn.data(),
+                                          graph.ordKf.data(), graph.ordW.data(), graph.nord.data(), graph.parent.data(), listCap, record.data(),
+                                          rowStatus.data(), inf.data());
+    if (rc < 0) throw std::runtime_error(pgorb_last_error(ctx_));
+    record.resize((inf[0] & PGORB_CULL_LIMIT) ? 0 : (size_t)inf[1] * 4);
+    rowStatus.resize((size_t)nkf);
+    if (info) *info = inf;
+    return rc;
+}
 
 }  // namespace pgorb

@@ -2057,6 +2057,145 @@ class LocalMapping:
                                                    int(what), _p(best), _p(status)))
         return pts, pd, best[:nsel].copy(), status[:nsel].copy()
 
+    @staticmethod
+    def MapPointCulling(ext, kf_point, npoints, point_bad, obs_start, obs_frame, obs_idx, obs_live, first_kf_id, visible, found, recent,
+                        cur_kf_id, th_obs=2):
+        """LocalMapping::MapPointCulling (src/LocalMapping.cc:170-207) over recent = mlpRecentAddedMapPoints as table indices.
+        kf_point[f] = key frame f's slots; the table's lists as CSR with the mask obs_live; first_kf_id / visible / found per
+        point.  Nothing passed in is changed.  Returns a dict: kf_point (a list of arrays), point_bad, obs_live afterwards, action
+        [nrecent] (CULL_MP_*), recent (the surviving list) and info.  Raises ValueError for everything pgorb_map_point_culling refuses."""
+        fn = "LocalMapping.MapPointCulling"
+        n, nkf = int(npoints), len(kf_point)
+        slots, ptrs, nk, st, of, oi, live, pb = _cull_table(fn, nkf, kf_point, n, point_bad, obs_start, obs_frame, obs_idx, obs_live, None)[:8]
+        fk, vi, fo = (_arr(x, np.int32, n, nm) for x, nm in ((first_kf_id, "first_kf_id"), (visible, "visible"), (found, "found")))
+        rec = np.ascontiguousarray(recent, np.int32).reshape(-1)
+        if len(rec) and (rec.min() < 0 or rec.max() >= n):
+            raise ValueError(fn + ": a recent entry is out of range")
+        if len(np.unique(rec)) != len(rec):
+            raise ValueError(fn + ": the recent list names a point twice")
+        nr = max(len(rec), 1)
+        action, out, nout, info = np.zeros(nr, np.int32), np.zeros(nr, np.int32), np.zeros(1, np.int32), np.zeros(CULL_INFO, np.int32)
+        one = np.zeros(1, np.int32)
+        ext._check(ext._L.pgorb_map_point_culling(
+            ext._h, nkf, ptrs, _p(nk), n, _p(pb), _p(st), _p(of), _p(oi), _p(live), _p(fk if n else one), _p(vi if n else one), _p(fo if n else one),
+            len(rec), _p(rec if len(rec) else one), int(cur_kf_id), int(th_obs), _p(action), _p(out), _p(nout), _p(info)))
+        return dict(kf_point=slots, point_bad=pb[:n], obs_live=live[:int(st[-1])], action=action[:len(rec)], recent=out[:int(nout[0])].copy(), info=info)
+
+    @staticmethod
+    def KeyFrameCulling(graph, cur_kf, octaves, kf_point, npoints, point_bad, obs_start, obs_frame, obs_idx, obs_live, ref_obs, kf_bad=None,
+                        kf_not_erase=None, kf_to_be_erased=None, list_cap=None):
+        """LocalMapping::KeyFrameCulling (src/LocalMapping.cc:634-698) with KeyFrame::SetBadFlag and MapPoint::EraseObservation over
+        `graph` (a CovisibilityGraph, updated IN PLACE) with mpCurrentKeyFrame = cur_kf.  octaves[f] = mvKeysUn[i].octave of key
+        frame f, kf_point[f] its slots; the table's lists as CSR with the mask obs_live and ref_obs.  Apart from the graph nothing
+        passed in is changed.  Returns a dict: kf_point, point_bad, obs_live, ref_obs, kf_bad, kf_to_be_erased afterwards, record
+        [list length][4] = (key frame, nMPs, nRedundantObservations, CULL_KF_*), row_status (CULL_ROW_*) and info; info[0] ==
+        CULL_LIMIT: the list is longer than list_cap (default: conn_cap) and nothing was done.  Raises ValueError for everything
+        pgorb_keyframe_culling refuses."""
+        fn = "LocalMapping.KeyFrameCulling"
+        n, nkf = int(npoints), graph.nkf
+        slots, ptrs, nk, st, of, oi, live, pb, ko = _cull_table(fn, nkf, kf_point, n, point_bad, obs_start, obs_frame, obs_idx, obs_live, graph.kf_order)
+        if not 0 <= int(cur_kf) < nkf:
+            raise ValueError(fn + ": cur_kf is out of range")
+        list_cap = graph.conn_cap if list_cap is None else int(list_cap)
+        if list_cap < 1:
+            raise ValueError(fn + ": list_cap < 1")
+        if len(octaves) != nkf or any(len(o) != len(s) for o, s in zip(octaves, slots)):
+            raise ValueError(fn + ": one octave per slot of every key frame")
+        ro = np.array(_arr(ref_obs, np.int32, n, "ref_obs"))
+        ln = np.diff(st)
+        if np.any((ln > 0) & ((ro[:n] < -1) | (ro[:n] >= ln))):
+            raise ValueError(fn + ": ref_obs lies outside the point's list")
+        _covis_rows(fn, graph, nkf, ko)
+        keep = []
+        kps = (C.c_void_p * max(nkf, 1))()
+        for f, o in enumerate(octaves):
+            k = np.zeros(max(len(o), 1), KEYPOINT_DTYPE)
+            k["octave"][:len(o)] = o
+            keep.append(k)
+            kps[f] = k.ctypes.data
+        kb, ne, tbe = (np.array(_mask(m, nkf, nm)) for m, nm in ((kf_bad, "kf_bad"), (kf_not_erase, "kf_not_erase"), (kf_to_be_erased, "kf_to_be_erased")))
+        record, status, info = np.zeros((list_cap, 4), np.int32), np.zeros(max(nkf, 1), np.int32), np.zeros(CULL_INFO, np.int32)
+        ext = graph.ext
+        ext._check(ext._L.pgorb_keyframe_culling(
+            ext._h, nkf, kps, ptrs, _p(nk), n, _p(pb), _p(st), _p(of), _p(oi), _p(live), _p(ro if n else np.zeros(1, np.int32)),
+            None if ko is None else _p(ko), _p(graph.kf_id0), _p(ne), _p(kb), _p(tbe), int(cur_kf), graph.conn_cap, _p(graph.conn_kf), _p(graph.conn_w),
+            _p(graph.nconn), _p(graph.ord_kf), _p(graph.ord_w), _p(graph.nord), _p(graph.parent), list_cap, _p(record), _p(status), _p(info)))
+        nl = 0 if info[0] & CULL_LIMIT else int(info[1])
+        return dict(kf_point=slots, point_bad=pb[:n], obs_live=live[:int(st[-1])], ref_obs=ro[:n], kf_bad=kb[:nkf], kf_to_be_erased=tbe[:nkf],
+                    record=record[:nl].copy(), row_status=status[:nkf].copy(), info=info)
+
+
+# the cullings (include/pgorb.h): MapPointCulling's and KeyFrameCulling's action codes, the row status bits
+CULL_MP_KEEP, CULL_MP_WAS_BAD, CULL_MP_FOUND_RATIO, CULL_MP_FEW_OBS, CULL_MP_AGED, CULL_MP_NONE = 0, 1, 2, 3, 4, 5
+CULL_KF_KEEP, CULL_KF_CULLED, CULL_KF_TO_BE_ERASED, CULL_KF_ID0, CULL_KF_WAS_BAD, CULL_KF_NONE = 0, 1, 2, 3, 4, 5
+CULL_ROW_ERASED, CULL_ROW_CLEARED, CULL_ROW_REPARENTED = 1, 2, 4
+CULL_LIMIT, CULL_INFO = 32, 4
+
+
+def _cull_table(fn, nkf, kf_point, npoints, point_bad, obs_start, obs_frame, obs_idx, obs_live, kf_order):
+    """The slots and the masked observation lists as the cullings take them, checked as the single calls check them; the arrays
+    that the call writes are copies."""
+    slots, ptrs, nk, st, of, pb, ko = _covis_table(fn, nkf, kf_point, npoints, obs_start, obs_frame, point_bad, kf_order)
+    slots = [np.array(s) for s in slots]
+    for f, s in enumerate(slots):
+        ptrs[f] = s.ctypes.data if len(s) else None
+    m = int(st[-1])
+    oi = np.ascontiguousarray(obs_idx, np.int32).reshape(-1)
+    live = np.array(np.ascontiguousarray(obs_live, np.uint8).reshape(-1))
+    if len(oi) < m or len(live) < m:
+        raise ValueError(fn + ": obs_idx and obs_live need one entry per observation")
+    if m and (oi[:m].min() < 0 or np.any(oi[:m] >= nk[of[:m]])):
+        raise ValueError(fn + ": an observation names a keypoint out of range")
+    if len(oi) == 0:
+        oi, live = np.zeros(1, np.int32), np.zeros(1, np.uint8)
+    return slots, ptrs, nk, st, of, oi, live, np.array(pb), ko
+
+
+def _covis_rows(fn, graph, nkf, ko):
+    """The graph rows as pgorb_update_connections and pgorb_keyframe_culling require them."""
+    rank = ko if ko is not None else np.arange(nkf, dtype=np.int32)
+    for f in range(nkf):
+        nc, no = int(graph.nconn[f]), int(graph.nord[f])
+        if not (0 <= nc <= graph.conn_cap and 0 <= no <= graph.conn_cap):
+            raise ValueError(fn + ": a row count is outside [0, conn_cap]")
+        row = graph.conn_kf[f, :nc]
+        if nc and (row.min() < 0 or row.max() >= nkf or np.any(row == f) or np.any(np.diff(rank[row]) <= 0)):
+            raise ValueError(fn + ": a connection row is out of range or not in address order")
+        if no and not np.all(np.isin(graph.ord_kf[f, :no], row)):
+            raise ValueError(fn + ": an ordered entry is not in the row's map")
+        if not -1 <= int(graph.parent[f]) < nkf:
+            raise ValueError(fn + ": a parent is out of range")
+
+
+def compact_observations(obs_start, obs_frame, obs_idx, obs_live, ref_obs, out=None):
+    """What pgorb_compact_observations_device writes, in numpy: (obs_start, obs_frame, obs_idx, ref_obs) of the live entries, the
+    order inside each list kept, ref_obs re-based (-1 when it names no live entry).  out = four arrays to fill instead (obs_frame /
+    obs_idx with room for the old length); they must not share memory with an input."""
+    st = np.ascontiguousarray(obs_start, np.int32).reshape(-1)
+    n = len(st) - 1
+    if n < 0 or st[0] != 0 or np.any(np.diff(st) < 0):
+        raise ValueError("compact_observations: obs_start must rise from 0")
+    m = int(st[-1])
+    of, oi, lv = (np.asarray(x).reshape(-1) for x in (obs_frame, obs_idx, obs_live))
+    ro = _arr(ref_obs, np.int32, n, "ref_obs")
+    if min(len(of), len(oi), len(lv)) < m:
+        raise ValueError("compact_observations: obs_frame, obs_idx and obs_live need one entry per observation")
+    if out is not None and any(np.shares_memory(o, i) for o in out for i in (obs_start, obs_frame, obs_idx, obs_live, ref_obs) if isinstance(i, np.ndarray)):
+        raise ValueError("compact_observations: an output aliases an input")
+    keep = lv[:m] != 0
+    before = np.concatenate([[0], np.cumsum(keep)]).astype(np.int32)           # live entries in front of each position
+    start = before[st]
+    pos = st[:-1].astype(np.int64) + ro
+    named = (ro >= 0) & (ro < np.diff(st))
+    named[named] = keep[pos[named]]
+    ref = np.where(named, before[np.where(named, pos, 0)] - start[:-1], -1).astype(np.int32)
+    res = (start, of[:m][keep].astype(np.int32), oi[:m][keep].astype(np.int32), ref)
+    if out is None:
+        return res
+    for o, r in zip(out, res):
+        o[:len(r)] = r
+    return tuple(out)
+
 
 # the covisibility graph (include/pgorb.h): row status bits, limits, the local map's status bits
 COVIS_UPDATED, COVIS_RESORTED, COVIS_EMPTY, COVIS_FALLBACK, COVIS_PARENT_SET, COVIS_LIMIT = 1, 2, 4, 8, 16, 32

@@ -88,8 +88,14 @@ next to each, the oracle's CPU time for the same work (1 thread, a few frames, s
                points (pgorb_update_local_map_batch_device).  One row's counters are checked against numpy.  Nobody has measured this
                before and there is no CPU baseline (the Python reference of the tests is not one): no target is set, the rows record what
                was measured.  --covis-only runs these rows alone (profiles/next_tier_covis.txt).
+  cullings         local mapping's cullings on the device (csrc/culling.hip), HIP events: LocalMapping::KeyFrameCulling (LocalMapping.cc:634-698,
+               with KeyFrame::SetBadFlag) of ONE ride-shaped map -- 200 key frames x 2000 slots, tracks of 2 to 40 consecutive key frames, the
+               graph from a whole-map UpdateConnections at th 15, the list of the middle key frame -- against the literal Python reference of the
+               tests on one core (NOT ORB-SLAM2, not a tuned baseline), whose records the GPU's must equal; MapPointCulling of 3000 recent
+               points; the compaction of the observation lists.  No target is set.  --cull-only runs these rows alone
+               (profiles/next_tier_cull.txt).
 
-usage: python tools/next_tier_bench.py [--batch 128] [--out profiles/r02_next_tier.txt] [--refresh-only | --place-only | --loop-only | --track-only | --pose-only | --sim3-only | --pnp-only | --optsim3-only | --lba-only | --eg-only | --gba-only | --covis-only]"""
+usage: python tools/next_tier_bench.py [--batch 128] [--out profiles/r02_next_tier.txt] [--refresh-only | --place-only | --loop-only | --track-only | --pose-only | --sim3-only | --pnp-only | --optsim3-only | --lba-only | --eg-only | --gba-only | --covis-only | --cull-only]"""
 import argparse, ctypes as C, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -116,6 +122,7 @@ ap.add_argument("--lba-only", action="store_true", help="the LocalBundleAdjustme
 ap.add_argument("--eg-only", action="store_true", help="the OptimizeEssentialGraph row alone (no ride, no vocabulary)")
 ap.add_argument("--gba-only", action="store_true", help="the GlobalBundleAdjustment rows alone (no ride, no vocabulary)")
 ap.add_argument("--covis-only", action="store_true", help="the covisibility-graph rows alone (no ride, no vocabulary)")
+ap.add_argument("--cull-only", action="store_true", help="the culling rows alone (no ride, no vocabulary)")
 a = ap.parse_args()
 w, h, nf, B = 1920, 1080, a.features, a.batch
 
@@ -724,6 +731,112 @@ def covis_lines(nkf=500, cap=2000, held=1400, npairs=128, conn_cap=256, lkf_cap=
                                % (npairs, nl.mean(), nq.mean()), t_lm)]
 
 
+def cull_lines():
+    """The cullings: KeyFrameCulling of a ride-shaped map against the Python reference of the tests on one core -- a map with much to cull
+    and one with nothing to cull --, MapPointCulling and the compaction of the observation lists."""
+    head = ["# The cullings on the device, resident calls, HIP events, median of 9 after one warm-up, the in/out state restored before every call.  The CPU",
+            "# column is the literal Python reference of the tests (tests/cull_reference.py) on one core, NOT ORB-SLAM2 and not a tuned baseline.  No target",
+            "# is set: this records what was measured.",
+            "%-150s %10s %12s" % ("call", "GPU ms", "Python ms")]
+    return head + cull_rows(0.5)[:1] + cull_rows(0.55)
+
+
+def cull_rows(short, nkf=200, cap=2000, conn_cap=256, list_cap=256, nrecent=3000):
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import cull_cases as K
+    import cull_reference as CU
+    rng = np.random.RandomState(17)
+    w = K.World(nkf, None, [f == 0 for f in range(nkf)])
+    for it in range(4 * nkf * cap // 5):                                        # tracks of 2..3 (a share `short` of them) or 4..40 consecutive key frames
+        f0 = int(rng.randint(0, nkf))
+        ln = int(rng.randint(2, 4)) if rng.rand() < short else int(rng.randint(4, 41))
+        fs = [f for f in range(f0, min(f0 + ln, nkf)) if len(w.slots[f]) < cap]
+        if len(fs) >= 2:
+            w.point(fs, octave={f: int(rng.randint(0, 3)) for f in fs}, ref_kf=fs[int(rng.randint(0, len(fs)))])
+        if it % 256 == 0 and min(len(s) for s in w.slots[20:nkf - 20]) >= cap:
+            break
+    npts, cur = len(w.obs), nkf // 2
+    a = K.arrays(w, conn_cap)
+    a["conn_kf"][:], a["conn_w"][:], a["ord_kf"][:], a["ord_w"][:] = -1, 0, -1, 0
+    ext = pg.ORBextractor(2000, 1.2, 8, 20, 7, max_width=640, max_height=480)
+    d = K.upload(a)
+    p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+    s = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    L, h = ext._L, ext._h
+    z = lambda *shape: torch.zeros(shape, dtype=torch.int32, device="cuda")
+    first, st, info = torch.ones(nkf, dtype=torch.uint8, device="cuda"), z(nkf), z(4)
+    ext._check(L.pgorb_update_connections_batch_device(h, p(d["kf_point"]), p(d["n"]), nkf, a["cap"], npts, p(d["point_bad"]), p(d["obs_start"]), p(d["obs_frame"]),
+                                                       a["nobs"], None, p(d["id0"]), nkf, p(torch.arange(nkf, dtype=torch.int32, device="cuda")), 15, conn_cap,
+                                                       p(d["conn_kf"]), p(d["conn_w"]), p(d["nconn"]), p(d["ord_kf"]), p(d["ord_w"]), p(d["nord"]), p(d["parent"]),
+                                                       p(first), p(st), 0, None, p(info), s))
+    torch.cuda.synchronize()
+    assert not np.any(st.cpu().numpy() & 32)
+    inout = ("kf_point", "point_bad", "obs_live", "ref_obs", "kf_bad", "to_be_erased", "conn_kf", "conn_w", "nconn", "ord_kf", "ord_w", "nord", "parent")
+    keep = {k: d[k].clone() for k in inout}
+    record, status = z(list_cap, 4), z(nkf)
+
+    def restore():
+        for k in inout:
+            d[k].copy_(keep[k])
+
+    def cull():
+        ext._check(L.pgorb_keyframe_culling_device(h, p(d["kps"]), p(d["kf_point"]), p(d["n"]), nkf, a["cap"], npts, p(d["point_bad"]), p(d["obs_start"]),
+                                                   p(d["obs_frame"]), p(d["obs_idx"]), a["nobs"], p(d["obs_live"]), p(d["ref_obs"]), None, p(d["id0"]), None,
+                                                   p(d["kf_bad"]), p(d["to_be_erased"]), cur, conn_cap, p(d["conn_kf"]), p(d["conn_w"]), p(d["nconn"]),
+                                                   p(d["ord_kf"]), p(d["ord_w"]), p(d["nord"]), p(d["parent"]), list_cap, p(record), p(status), p(info), s))
+
+    def timed_fresh(fn, reps=9):
+        ms = []
+        for r in range(reps + 1):
+            restore()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(); fn(); e1.record(); torch.cuda.synchronize()
+            ms.append(e0.elapsed_time(e1))
+        return float(np.median(ms[1:]))
+    t_kf = timed_fresh(cull)
+    inf = info.cpu().numpy().copy()
+    rec = record.cpu().numpy()[:inf[1]]
+    assert inf[0] == 0
+    # the same map through the Python reference of the tests, one core
+    g = {k: keep[k].cpu().numpy() for k in ("conn_kf", "conn_w", "nconn", "ord_kf", "ord_w", "nord", "parent")}
+    for f in range(nkf):
+        w.conn[f] = {int(j): int(x) for j, x in zip(g["conn_kf"][f, :g["nconn"][f]], g["conn_w"][f, :g["nconn"][f]])}
+        w.ordl[f] = [(int(j), int(x)) for j, x in zip(g["ord_kf"][f, :g["nord"][f]], g["ord_w"][f, :g["nord"][f]])]
+        w.parent[f] = int(g["parent"][f])
+    kfs, pts = K.objects(w)
+    t0 = time.perf_counter()
+    want = CU.keyframe_culling(kfs[cur], kfs)
+    t_ref = (time.perf_counter() - t0) * 1e3
+    assert [tuple(int(x) for x in r) for r in rec] == [tuple(r) for r in want], "the device's records differ from the reference's"
+    assert np.array_equal(d["kf_bad"].cpu().numpy()[:nkf], np.array([k.bad for k in kfs], np.uint8))
+    # MapPointCulling of nrecent points and the compaction, on the state the cull left
+    recent = torch.from_numpy(rng.permutation(npts)[:nrecent].astype(np.int32)).cuda()
+    nr = int(recent.numel())
+    fk, vi, fo = (torch.from_numpy(rng.randint(lo, hi, npts).astype(np.int32)).cuda() for lo, hi in ((96, 101), (1, 40), (0, 12)))
+    action, rout, nout, minfo = z(nr), z(nr), z(1), z(4)
+    keep2 = {k: d[k].clone() for k in inout}
+
+    def points():
+        ext._check(L.pgorb_map_point_culling_device(h, p(d["kf_point"]), p(d["n"]), nkf, a["cap"], npts, p(d["point_bad"]), p(d["obs_start"]), p(d["obs_frame"]),
+                                                    p(d["obs_idx"]), a["nobs"], p(d["obs_live"]), p(fk), p(vi), p(fo), nr, p(recent), 100, 2, p(action), p(rout),
+                                                    p(nout), p(minfo), s))
+    keep = keep2
+    t_mp = timed_fresh(points)
+    cst, cof, coi, cref, cinfo = z(npts + 1), z(a["nobs"] + 1), z(a["nobs"] + 1), z(npts + 1), z(1)
+
+    def compact():
+        ext._check(L.pgorb_compact_observations_device(h, npts, p(d["obs_start"]), p(d["obs_frame"]), p(d["obs_idx"]), a["nobs"], p(d["obs_live"]), p(d["ref_obs"]),
+                                                       p(cst), p(cof), p(coi), p(cref), p(cinfo), s))
+    t_co = timed(compact)
+    assert int(cinfo[0]) == int(d["obs_live"][:a["nobs"]].sum())
+    mi = minfo.cpu().numpy()
+    scene = "%d key frames x %d slots (%d filled on average), %d points, %d observations" % (nkf, cap, a["n"][:nkf].mean(), npts, a["nobs"])
+    return ["%-150s %10.3f %12.1f" % ("keyframe_culling, %.0f%% short tracks: %s; the list of key frame %d has %d members, %d culled, %d points went bad (k_cull_eval, k_cull_walk; "
+                                      "2 small resets included)" % (100 * short, scene, cur, inf[1], inf[2], inf[3]), t_kf, t_ref),
+            "%-150s %10.3f %12s" % ("map_point_culling: %d recent points of that map, %d survive, %d culled (k_cull_points, one workgroup)" % (nr, mi[1], mi[2]), t_mp, "-"),
+            "%-150s %10.3f %12s" % ("compact_observations: %d observations, %d live (k_cull_compact_scan, k_cull_compact_copy)" % (a["nobs"], int(cinfo[0])), t_co, "-")]
+
+
 def gba_lines(nkf=500, per_kf=40, span=4):
     """GlobalBundleAdjustment: a ride-shaped map in the resident call, and LocalBundleAdjustment's benchmark window through both."""
     sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -777,6 +890,12 @@ def gba_lines(nkf=500, per_kf=40, span=4):
                 li[3], li[4], li[2], li[1], li[5], li[7], li[6], li[8]), one.ms, one.ms / max(int(li[6] + li[8]), 1))]
 
 
+if a.cull_only:
+    lines = ["# python tools/next_tier_bench.py --cull-only   (MI355X)"] + cull_lines()
+    print("\n".join(lines))
+    if a.out:
+        open(a.out, "w").write("\n".join(lines) + "\n")
+    sys.exit(0)
 if a.gba_only:
     lines = ["# python tools/next_tier_bench.py --gba-only   (MI355X)"] + gba_lines()
     print("\n".join(lines))

@@ -1612,6 +1612,106 @@ int  pgorb_keyframe_culling_device(pgorb_ctx* ctx,
         int conn_cap, int32_t* d_conn_kf, int32_t* d_conn_w, int32_t* d_nconn, int32_t* d_ord_kf, int32_t* d_ord_w, int32_t* d_nord,
         int32_t* d_parent, int list_cap, int32_t* d_record, int32_t* d_row_status, int32_t* d_info, void* hip_stream);
 
+/* ---- Loop correction: CorrectLoop's propagation and the map update after global bundle adjustment (csrc/loop_correct.hip) ------
+ * The two map rewrites between loop closing's numerical steps, on the arrays those steps read and write, so that ComputeSim3 ->
+ * correction -> Fuse(Sim3) -> UpdateConnections -> OptimizeEssentialGraph -> GlobalBundleAdjustment -> map update -> refresh is one
+ * stream of launches.  The conventions of the covisibility block hold: key frames are the nframes frames of one resident batch with
+ * their slots d_kf_point [nframes][cap_per_frame] + d_n, the table is that of pgorb_refresh_map_points (d_points, d_point_bad (NULL
+ * = none), the CSR d_obs_start / d_obs_frame / d_obs_idx, d_ref_obs), d_kf_order is the address rank (NULL = index order), an index
+ * out of range is no slot, no observation and no key frame, and the device forms never read or write out of bounds.  The library is
+ * built with -ffp-contract=off and these paths use + - x / and correctly rounded square roots only: every result is exact.
+ *
+ *   pgorb_correct_loop_poses_device   LoopClosing::CorrectLoop, :438-516, without the per-member UpdateConnections() of :515 (that
+ *       is pgorb_update_connections_batch_device with the members in address order) and without the Replace bookkeeping of :520-537.
+ *       Inputs: d_kps (only `octave` is read), d_pose (Tcw and Ow are read AS GIVEN; the camera is copied through), cur_kf, d_scw =
+ *       mg2oScw (one pgorb_sim3d on the device, e.g. where OptimizeSim3 left it), d_list [nlist] = mvpCurrentConnectedKFs: an entry
+ *       that is negative, out of range or cur_kf is skipped, one named twice counts once, and the library adds cur_kf itself.  A
+ *       row of d_ord_kf may therefore be passed with its whole capacity (d_list = d_ord_kf + cur_kf * conn_cap, nlist = conn_cap),
+ *       BUT WITH ITS COUNT: past a row's count the padding is not reliably -1.  The cullings write -1 into the entries a row
+ *       loses, but pgorb_update_connections_batch_device writes entries [0, nord) only, so a row that it made shorter keeps stale
+ *       key-frame indices behind its count (and a row it never wrote holds whatever the caller put there; pilotguru_amd's
+ *       CovisibilityGraph starts with -1).  d_list_count (NULL = nlist) is that count on the device, d_nord + cur_kf: entries at
+ *       or past min(nlist, *d_list_count) are not read as members.  d_ref_kf [npoints] = GetReferenceKeyFrame() by index, -1 = none.
+ *       Members = the list + cur_kf.  NonCorrectedSim3[i] = Sim3(Quaterniond(Riw), tiw, 1); CorrectedSim3[cur] = scw byte for byte;
+ *       for the others Sim3(Ric, tic, 1) * scw with Tic = Tiw * Twc, a 4 x 4 float product, Twc = [Rcw' | Ow]
+ *       of cur_kf.  The point loop runs over CorrectedSim3, a std::map<KeyFrame*, ..>: a live point is corrected ONCE, by the member
+ *       of smallest address rank that holds it in a slot (mnCorrectedByKF): pos = correctedSwi.map(Siw.map(pos)) in double, rounded
+ *       to float.  Then UpdateNormalAndDepth in the state the reference is in at that moment: with i the correcting member, an
+ *       observing key frame j contributes its CORRECTED camera centre if and only if j is a member and rank(j) < rank(i) strictly
+ *       (i's own SetPose follows its point loop, :512), every other observer the centre passed in; the reference key frame (the
+ *       observation d_ref_obs names) by the same rule.  In a consistent map (every observing member holds the point in a slot) all
+ *       centres are the ones passed in.  A list longer than PGORB_MP_MAX_OBS: the position is corrected, normal and distances keep
+ *       their bytes, PGORB_LC_OVER_OBS.  An empty list: the same, silently (MapPoint.cc:362-363).  In the device form a list outside
+ *       [0, nobs], an observation outside the batch or a d_ref_obs outside its list does the same with PGORB_LC_BAD_INDEX.
+ *       Outputs, exactly what pgorb_optimize_essential_graph_device reads: d_has_corrected / d_corrected / d_has_non_corrected /
+ *       d_non_corrected [nframes] (flag 0 and a zero record for a key frame that is no member); d_pose_out [nframes] (must not be
+ *       d_pose): for members [R | t/s] through Converter::toCvSE3 to float, then SetPose's Ow, the camera kept; the input's bytes
+ *       for the others; the table in place (pos, normal, min_distance, max_distance of the corrected points); d_corrected_by
+ *       [npoints] = the correcting key frame or -1 (mnCorrectedReference); d_point_ref_kf [npoints] = d_corrected_by where it is
+ *       set, else d_ref_kf -- the array the essential graph takes; d_info [PGORB_LC_INFO] = status bits, members, points corrected,
+ *       points over the observation limit.  Launches: k_lc_init, k_lc_rank (with a d_kf_order), k_lc_members (a thread per member),
+ *       k_lc_claim (a thread per (member, slot): an integer atomicMin of the address rank per point -- a minimum has no order),
+ *       k_lc_points (a thread per point); no floating-point atomic, no host round trip.  Scratch arena: (2 nframes + npoints) * 4.
+ *   pgorb_global_ba_map_update_device   LoopClosing::RunGlobalBundleAdjustment, :679-742.  d_pose = the poses as local mapping left
+ *       them (what becomes mTcwBefGBA); d_pose_gba / d_kf_done / d_pos_gba / d_point_done as pgorb_global_bundle_adjustment_device
+ *       writes them; d_parent the covisibility graph's; d_kf_origin [nframes] (uint8) = is in mvpKeyFrameOrigins; d_kf_bad (NULL =
+ *       none); d_ref_kf as above.  A key frame is VISITED when it is not bad and its parent chain reaches an origin without passing
+ *       a bad key frame or a cycle (the chain ends at the first origin; an origin's own parent is not followed).  A visited key
+ *       frame that is done takes d_pose_gba's record.  A visited one that is not done takes (Tcw_child * Twc_parent) *
+ *       TcwGBA_parent: two 4 x 4 float products, Twc_parent = [Rcw' | Ow] of the parent's pose BEFORE the update, TcwGBA_parent the
+ *       parent's result; then SetPose's Ow, the camera kept.  Both operands of the first product are pre-update poses, so the result
+ *       depends on the chain down from the nearest done ancestor alone and is multiplied in exactly that order -- float rounding
+ *       forbids regrouping.  ONE DEPARTURE: a key frame that is not visited, or whose chain holds no done key frame up to its origin
+ *       (the reference would read a stale mTcwGBA there), keeps its input bytes and gets d_kf_updated = 0.  Cost: a thread per key
+ *       frame walks up its chain (depth d) and multiplies down it, finding each ancestor by walking again: d products and d^2 / 2
+ *       parent reads per key frame, so a tree of depth d costs at most nframes * d^2 / 2 reads (13.5 M for a chain of 300); no cap
+ *       on the depth other than nframes, and two launches (k_mu_kf, k_mu_points) whatever the tree's depth.
+ *       Points: a bad point keeps its bytes; a done point takes d_pos_gba; otherwise, when d_ref_kf is valid and that key frame
+ *       was updated, pos = Rwc_new * (Rcw_bef * pos + tcw_bef) + Ow_new on gemm's small-matrix path with the translation folded
+ *       into C (kf_row); any other point keeps its bytes.  No UpdateNormalAndDepth follows in the reference;
+ *       pgorb_refresh_map_points_batch_device with PGORB_MP_NORMAL_DEPTH may be chained.  Outputs:
+ *       d_pose_out (must not be d_pose), d_kf_updated [nframes], d_points[].pos in place, d_point_updated [npoints], d_info
+ *       [PGORB_MU_INFO] = 0, key frames updated, of those recomputed, points updated.
+ *   pgorb_correct_loop_poses / pgorb_global_ba_map_update   the same from host buffers (kps[f], kf_point[f] [n[f]]; scw on the
+ *       host), checked on the host before anything else: PGORB_E_ARG for a negative count, a NULL array that is read or written,
+ *       cur_kf, a slot, an observation (key frame or keypoint), ref_kf or a parent out of range, kf_order not a permutation, a pose
+ *       (Tcw, Ow), scw, a point or a done result that is not finite, a scale <= 0, obs_start not rising from 0, ref_obs outside the
+ *       list of a live point with 1 .. PGORB_MP_MAX_OBS observations, a key frame twice in one list, a parent cycle.  They return the number of points corrected /
+ *       key frames updated and equal the device forms byte for byte.  The device forms check pointers and limits only.
+ * Limits (PGORB_E_LIMIT): nframes and nlist <= PGORB_COVIS_MAX_KF, cap_per_frame <= 16000.  Determinism: a result depends on its
+ * inputs alone, not on the stream, a repeat or what the context ran before. */
+#define PGORB_LC_OVER_OBS  1
+#define PGORB_LC_BAD_INDEX 2
+#define PGORB_LC_INFO      4
+#define PGORB_MU_INFO      4
+int  pgorb_correct_loop_poses(pgorb_ctx* ctx,
+        int nkf, const pgorb_keypoint* const* kps, const int32_t* n /*[nkf]*/, const pgorb_kf_pose* pose /*[nkf]*/, int cur_kf,
+        const pgorb_sim3d* scw, int nlist, const int32_t* list, const int32_t* kf_order /*[nkf] or NULL*/,
+        const int32_t* const* kf_point /*[nkf][n[f]]*/, int npoints, pgorb_map_point* points /*in and out*/,
+        const uint8_t* point_bad /*[npoints] or NULL*/, const int32_t* obs_start /*[npoints + 1]*/, const int32_t* obs_frame,
+        const int32_t* obs_idx, const int32_t* ref_obs /*[npoints]*/, const int32_t* ref_kf /*[npoints]*/,
+        uint8_t* has_corrected, pgorb_sim3d* corrected, uint8_t* has_non_corrected, pgorb_sim3d* non_corrected /*[nkf]*/,
+        pgorb_kf_pose* pose_out /*[nkf]*/, int32_t* corrected_by, int32_t* point_ref_kf /*[npoints]*/, int32_t* info /*[PGORB_LC_INFO]*/);
+int  pgorb_correct_loop_poses_device(pgorb_ctx* ctx,
+        const pgorb_keypoint* d_kps, const int32_t* d_n, int nframes, int cap_per_frame, const pgorb_kf_pose* d_pose, int cur_kf,
+        const pgorb_sim3d* d_scw, int nlist, const int32_t* d_list, const int32_t* d_list_count /*[1] or NULL*/,
+        const int32_t* d_kf_order, const int32_t* d_kf_point, int npoints, pgorb_map_point* d_points, const uint8_t* d_point_bad, const int32_t* d_obs_start, const int32_t* d_obs_frame,
+        const int32_t* d_obs_idx, int nobs, const int32_t* d_ref_obs, const int32_t* d_ref_kf,
+        uint8_t* d_has_corrected, pgorb_sim3d* d_corrected, uint8_t* d_has_non_corrected, pgorb_sim3d* d_non_corrected,
+        pgorb_kf_pose* d_pose_out, int32_t* d_corrected_by, int32_t* d_point_ref_kf, int32_t* d_info, void* hip_stream);
+int  pgorb_global_ba_map_update(pgorb_ctx* ctx,
+        int nkf, const pgorb_kf_pose* pose, const pgorb_kf_pose* pose_gba /*[nkf]*/, const uint8_t* kf_done /*[nkf]*/,
+        const int32_t* parent /*[nkf]*/, const uint8_t* kf_origin /*[nkf]*/, const uint8_t* kf_bad /*[nkf] or NULL*/,
+        int npoints, pgorb_map_point* points /*in and out: pos*/, const float* pos_gba /*[npoints][3]*/, const uint8_t* point_done,
+        const uint8_t* point_bad /*[npoints] or NULL*/, const int32_t* ref_kf /*[npoints]*/,
+        pgorb_kf_pose* pose_out /*[nkf]*/, uint8_t* kf_updated /*[nkf]*/, uint8_t* point_updated /*[npoints]*/, int32_t* info /*[PGORB_MU_INFO]*/);
+int  pgorb_global_ba_map_update_device(pgorb_ctx* ctx,
+        int nframes, const pgorb_kf_pose* d_pose, const pgorb_kf_pose* d_pose_gba, const uint8_t* d_kf_done, const int32_t* d_parent,
+        const uint8_t* d_kf_origin, const uint8_t* d_kf_bad,
+        int npoints, pgorb_map_point* d_points, const float* d_pos_gba, const uint8_t* d_point_done, const uint8_t* d_point_bad,
+        const int32_t* d_ref_kf, pgorb_kf_pose* d_pose_out, uint8_t* d_kf_updated, uint8_t* d_point_updated, int32_t* d_info,
+        void* hip_stream);
+
 /* ---- ORB vocabulary (DBoW2 TemplatedVocabulary<FORB::TDescriptor, FORB>) -----------------
  *   pgorb_vocab_load_text     ORBVocabulary(text_file) -> TemplatedVocabulary::loadFromTextFile
  *                             thirdparty/orb-slam2/src/ORBVocabulary.cc:7-9,

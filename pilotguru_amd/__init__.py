@@ -26,4 +26,5 @@ from .orb import (COVIS_EMPTY, COVIS_FALLBACK, COVIS_INFO, COVIS_LIMIT, COVIS_MA
 from .orb import (CULL_INFO, CULL_KF_CULLED, CULL_KF_ID0, CULL_KF_KEEP, CULL_KF_NONE, CULL_KF_TO_BE_ERASED, CULL_KF_WAS_BAD, CULL_LIMIT,  # noqa: F401
                   CULL_MP_AGED, CULL_MP_FEW_OBS, CULL_MP_FOUND_RATIO, CULL_MP_KEEP, CULL_MP_NONE, CULL_MP_WAS_BAD, CULL_ROW_CLEARED,
                   CULL_ROW_ERASED, CULL_ROW_REPARENTED, compact_observations)
+from .orb import LC_BAD_INDEX, LC_INFO, LC_OVER_OBS, MU_INFO, LoopClosing  # noqa: F401
 from .place import KeyFrameDatabase  # noqa: F401

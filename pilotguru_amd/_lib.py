@@ -43,6 +43,7 @@ SYMBOLS = (
     "pgorb_update_local_map", "pgorb_update_local_map_batch_device",
     "pgorb_compact_observations_device", "pgorb_map_point_culling", "pgorb_map_point_culling_device",
     "pgorb_keyframe_culling", "pgorb_keyframe_culling_device",
+    "pgorb_correct_loop_poses", "pgorb_correct_loop_poses_device", "pgorb_global_ba_map_update", "pgorb_global_ba_map_update_device",
     "pgorb_bow_vectors_batch_device", "pgorb_bow_score_l1_batch_device",
     "pgorb_detect_relocalization_candidates", "pgorb_detect_relocalization_candidates_batch_device",
     "pgorb_detect_loop_candidates", "pgorb_detect_loop_candidates_batch_device",
@@ -325,6 +326,18 @@ def lib():
     #  kf_not_erase, kf_bad, kf_to_be_erased, cur_kf, conn_cap, 6 row arrays, parent, list_cap, record, row_status, info, stream)
     L.pgorb_keyframe_culling_device.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int] + [vp] * 7 + \
         [C.c_int, C.c_int] + [vp] * 7 + [C.c_int, vp, vp, vp, vp]
+    # (ctx, nkf, kps[], n, pose, cur_kf, scw, nlist, list, kf_order, kf_point[], npoints, points, point_bad, obs_start, obs_frame, obs_idx,
+    #  ref_obs, ref_kf, has_corrected, corrected, has_non_corrected, non_corrected, pose_out, corrected_by, point_ref_kf, info)
+    L.pgorb_correct_loop_poses.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int, vp, C.c_int, vp, vp, vp, C.c_int] + [vp] * 15
+    # (ctx, kps, n, nframes, cap, pose, cur_kf, scw, nlist, list, list_count, kf_order, kf_point, npoints, points, point_bad, obs_start,
+    #  obs_frame, obs_idx, nobs, ref_obs, ref_kf, has_corrected, corrected, has_non_corrected, non_corrected, pose_out, corrected_by,
+    #  point_ref_kf, info, stream)
+    L.pgorb_correct_loop_poses_device.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp, vp, vp, C.c_int] + [vp] * 5 + \
+        [C.c_int] + [vp] * 11
+    # (ctx, nkf, pose, pose_gba, kf_done, parent, kf_origin, kf_bad, npoints, points, pos_gba, point_done, point_bad, ref_kf, pose_out,
+    #  kf_updated, point_updated, info[, stream])
+    L.pgorb_global_ba_map_update.argtypes = [vp, C.c_int] + [vp] * 6 + [C.c_int] + [vp] * 9
+    L.pgorb_global_ba_map_update_device.argtypes = [vp, C.c_int] + [vp] * 6 + [C.c_int] + [vp] * 10
     # (ctx, word, weight, n, nframes, cap, bow_id, bow_val, nbow, stream)
     L.pgorb_bow_vectors_batch_device.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp]
     # (ctx, bow_id, bow_val, nbow, nframes, cap, pair_a, pair_b, npairs, score, stream)

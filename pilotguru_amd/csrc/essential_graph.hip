@@ -27,7 +27,7 @@
 //   k_eg_finish     all CUs: pose_out, sim3_out, edge_out, the point correction, info.
 // The three kernels of an iteration return at once when the state's stop flag is set.
 #include "kf_window.h"
-#include "g2o_sim3.h"
+#include "loop_pose.h"                     // lp_map, lp_pose_from_sim3: shared with loop_correct.hip
 #include <math.h>
 #include <string>
 
@@ -71,14 +71,6 @@ struct EgArgs {
 __device__ __forceinline__ bool eg_finite(double v) { return fabs(v) <= EG_DBL_MAX; }
 __device__ __forceinline__ bool eg_bad(const EgArgs& G, int i) { return G.bad && G.bad[i]; }
 __device__ __forceinline__ bool eg_kf(const EgArgs& G, int i) { return i >= 0 && i < G.nkf && !eg_bad(G, i); }
-
-// Sim3::map: s*(r*xyz) + t
-__device__ __forceinline__ void eg_map(const OsSim& S, double X, double Y, double Z, double& x, double& y, double& z)
-{
-    double rx, ry, rz;
-    os_rotate(S.qx, S.qy, S.qz, S.qw, X, Y, Z, rx, ry, rz);
-    x = S.s * rx + S.tx; y = S.s * ry + S.ty; z = S.s * rz + S.tz;
-}
 
 // EdgeSim3::computeError: (C * v1 * v2^-1).log()
 __device__ __forceinline__ void eg_error(const OsSim& C, const OsSim& Si, const OsSim& Sj, double (&e)[7])
@@ -593,19 +585,7 @@ __global__ __launch_bounds__(256) void k_eg_finish(EgArgs G)
             S = est[i];
             if (!keepIn && G.deg[i] > 0) {
                 // [R | t/s] (:1001-1007), Converter::toCvSE3 to float, SetPose's Ow = -Rcw.t()*tcw
-                double R[9];
-                os_matrix_from_quat(S, R);
-                const double k = 1.0 / S.s;
-                const double t[3] = {S.tx * k, S.ty * k, S.tz * k};
-#pragma unroll
-                for (int r = 0; r < 3; r++) {
-#pragma unroll
-                    for (int c = 0; c < 3; c++) o.Tcw[r * 4 + c] = __double2float_rn(R[r * 3 + c]);
-                    o.Tcw[r * 4 + 3] = __double2float_rn(t[r]);
-                }
-#pragma unroll
-                for (int c = 0; c < 3; c++)
-                    o.Ow[c] = cnm_f(__dmul_rn((double)cnm_dot3f(o.Tcw[c], o.Tcw[4 + c], o.Tcw[8 + c], o.Tcw[3], o.Tcw[7], o.Tcw[11]), -1.0));
+                lp_pose_from_sim3(S, o);
             }
         }
         G.poseOut[i] = o;
@@ -624,8 +604,8 @@ __global__ __launch_bounds__(256) void k_eg_finish(EgArgs G)
         if (eg_kf(G, r)) {
             float* pos = G.pts[g].pos;
             double x, y, z, X, Y, Z;
-            eg_map(G.scw[r], (double)pos[0], (double)pos[1], (double)pos[2], x, y, z);
-            eg_map(os_inverse(G.est[r]), x, y, z, X, Y, Z);
+            lp_map(G.scw[r], (double)pos[0], (double)pos[1], (double)pos[2], x, y, z);
+            lp_map(os_inverse(G.est[r]), x, y, z, X, Y, Z);
             pos[0] = __double2float_rn(X); pos[1] = __double2float_rn(Y); pos[2] = __double2float_rn(Z);
         }
     }

@@ -15,7 +15,7 @@
 //   k_mp_big        64 < n <= PGORB_MP_MAX_OBS: a workgroup per point, the descriptors in LDS, a thread per row
 // The normal's terms are formed one per lane and added serially in list order; every float operation follows the reference's
 // cv::Mat arithmetic under the readings of DESIGN.md section 4 (cnm_normd / cnm_f of match_common.h).
-#include "match_common.h"
+#include "loop_pose.h"                     // mp_term, mp_depth: shared with loop_correct.hip
 
 #define MP_CLASSES 5                       // n <= 2, 8, 32, 64, PGORB_MP_MAX_OBS
 #define MP_BIG_T 256
@@ -64,22 +64,6 @@ __global__ __launch_bounds__(256) void k_mp_bin(PgMpBatch B, int32_t* __restrict
 __device__ __forceinline__ bool mp_obs_ok(const PgMpBatch& B, int f, int i)
 {
     return f >= 0 && f < B.nframes && i >= 0 && i < min(B.n[f], B.cap);
-}
-
-// one term of the normal: normali*(float)(1/cv::norm(normali)), normali = mWorldPos - Ow (:370-372); nd = cv::norm(normali)
-__device__ __forceinline__ void mp_term(const float* pos, const float* Ow, float t[3], double& nd)
-{
-    const float x = __fsub_rn(pos[0], Ow[0]), y = __fsub_rn(pos[1], Ow[1]), z = __fsub_rn(pos[2], Ow[2]);
-    nd = cnm_normd(x, y, z);
-    const float sc = cnm_f(__ddiv_rn(1.0, nd));
-    t[0] = __fmul_rn(x, sc); t[1] = __fmul_rn(y, sc); t[2] = __fmul_rn(z, sc);
-}
-// mfMaxDistance, mfMinDistance from dist = cv::norm(Pos - Ow_ref) and the reference keypoint's octave (:376-385)
-__device__ __forceinline__ void mp_depth(const PgMpBatch& B, double nd, int octave, float& minD, float& maxD)
-{
-    const int level = min((unsigned)octave, (unsigned)PG_MAXL);
-    maxD = __fmul_rn(cnm_f(nd), B.sf[level]);
-    minD = __fdiv_rn(maxD, B.sf[max(B.nlevels - 1, 0)]);
 }
 
 // minimum over the SEG lanes of a segment, in every lane: quad permutes and row mirrors on DPP, the halves above 16 by shuffles
@@ -162,7 +146,7 @@ template <int SEG> __global__ __launch_bounds__(256) void k_mp_seg(PgMpBatch B, 
             mp_term(pos, B.pose[f].Ow, t, nd);
             if (l == r) {
                 float mn, mx;
-                mp_depth(B, nd, B.K[(int64_t)f * B.cap + i].octave, mn, mx);
+                mp_depth(B.sf, B.nlevels, nd, B.K[(int64_t)f * B.cap + i].octave, mn, mx);
                 B.pts[p].min_distance = mn; B.pts[p].max_distance = mx;
             }
         }
@@ -211,7 +195,7 @@ __global__ __launch_bounds__(MP_BIG_T) void k_mp_big(PgMpBatch B, const int32_t*
             if (B.what & PGORB_MP_NORMAL_DEPTH) {
                 double nd;
                 mp_term(B.pts[p].pos, B.pose[f].Ow, t, nd);
-                if (l == r) { float mn, mx; mp_depth(B, nd, B.K[(int64_t)f * B.cap + i].octave, mn, mx); sMin = mn; sMax = mx; }
+                if (l == r) { float mn, mx; mp_depth(B.sf, B.nlevels, nd, B.K[(int64_t)f * B.cap + i].octave, mn, mx); sMin = mn; sMax = mx; }
             }
         }
         sD[2 * l] = q0; sD[2 * l + 1] = q1;

@@ -1,7 +1,8 @@
 // match_common.h -- what the Frame side, the guided matchers, CreateNewMapPoints, Fuse, loop closing's matchers and the map-point refresh
 // share: included by frame.hip, init_match.hip (through cand_lists.h), window_match.hip (through proj_match.h, which includes
 // cand_lists.h), node_match.hip, mapping.hip, fuse.hip, loop.hip (the last two through kf_window.h), track.hip (through kf_window.h
-// and proj_match.h), sim3.hip (through kf_window.h), pose_opt.hip, map_point.hip and initializer.hip, and by no other translation unit.
+// and proj_match.h), sim3.hip (through kf_window.h), pose_opt.hip, initializer.hip, and map_point.hip, essential_graph.hip and
+// loop_correct.hip (through loop_pose.h), and by no other translation unit.
 #pragma once
 #include "pgorb_internal.h"
 #include <algorithm>

@@ -1349,4 +1349,131 @@ inline int LocalMapping::KeyFrameCulling(CovisibilityGraph& graph, int curKf, co
     return rc;
 }
 
+struct LoopCorrection {
+    std::vector<uint8_t> hasCorrected, hasNonCorrected;       // CorrectedSim3 / NonCorrectedSim3 as pgorb_optimize_essential_graph takes them
+    std::vector<pgorb_sim3d> corrected, nonCorrected;
+    std::vector<pgorb_kf_pose> poses;
+    std::vector<int32_t> correctedBy, pointRefKf;             // mnCorrectedReference (-1 = not corrected); the essential graph's point_ref_kf
+    std::array<int32_t, PGORB_LC_INFO> info{};
+};
+struct MapUpdate {
+    std::vector<pgorb_kf_pose> poses;
+    std::vector<uint8_t> kfUpdated, pointUpdated;
+    std::array<int32_t, PGORB_MU_INFO> info{};
+};
+
+// The two map rewrites of loop closing (LoopClosing.cc:438-516 and :679-742); include/pgorb.h states both contracts.  Every input
+// the single calls refuse is a std::invalid_argument here, before the library is called.
+class LoopClosing {
+ public:
+    explicit LoopClosing(pgorb_ctx* ctx) : ctx_(ctx) {}
+    // CorrectLoop's propagation.  octaves[f] = mvKeysUn[i].octave, poses, curKf, scw = mg2oScw, connected = mvpCurrentConnectedKFs
+    // (an entry that is negative, out of range or curKf is skipped), kfPoint[f] the slots, the table (points corrected IN PLACE),
+    // obs with refObs, refKf[p] = GetReferenceKeyFrame() or -1, kfOrder the address ranks (empty = index order).  Returns the
+    // number of points corrected.
+    int CorrectLoopPoses(const std::vector<std::vector<int32_t>>& octaves, const std::vector<pgorb_kf_pose>& poses, int curKf, const pgorb_sim3d& scw,
+                         const std::vector<int32_t>& connected, const std::vector<std::vector<int32_t>>& kfPoint, std::vector<pgorb_map_point>& points,
+                         const std::vector<uint8_t>& pointBad, const MapPointObservations& obs, const std::vector<int32_t>& refKf,
+                         const std::vector<int32_t>& kfOrder, LoopCorrection& out)
+    {
+        const char* fn = "LoopClosing::CorrectLoopPoses";
+        auto fail = [&](const char* what) { throw std::invalid_argument(std::string(fn) + ": " + what); };
+        const size_t nkf = kfPoint.size(), np = points.size();
+        detail::checkCovisTable(fn, nkf, kfPoint, np, pointBad, obs, kfOrder);
+        if (curKf < 0 || curKf >= (int64_t)nkf) fail("curKf is out of range");
+        if (poses.size() != nkf || octaves.size() != nkf) fail("poses and octaves need one entry per key frame");
+        for (size_t f = 0; f < nkf; f++) {
+            if (octaves[f].size() != kfPoint[f].size()) fail("one octave per slot");
+            if (!poseFinite(poses[f])) fail("a pose is not finite");
+        }
+        for (int k = 0; k < 4; k++) if (!std::isfinite(scw.r[k])) fail("scw is not finite");
+        for (int k = 0; k < 3; k++) if (!std::isfinite(scw.t[k])) fail("scw is not finite");
+        if (!std::isfinite(scw.s)) fail("scw is not finite");
+        if (!(scw.s > 0.0)) fail("the scale of scw is not positive");
+        if (connected.size() > PGORB_COVIS_MAX_KF) fail("more than PGORB_COVIS_MAX_KF list entries");
+        const size_t m = (size_t)obs.obsStart[np];
+        if (obs.obsIdx.size() < m) fail("obsIdx is shorter than obsStart says");
+        for (size_t k = 0; k < m; k++)
+            if (obs.obsIdx[k] < 0 || obs.obsIdx[k] >= (int64_t)kfPoint[obs.obsFrame[k]].size()) fail("an observation names a keypoint out of range");
+        if (obs.refObs.size() != np || refKf.size() != np) fail("refObs and refKf need one entry per point");
+        for (size_t p = 0; p < np; p++) {
+            const int len = obs.obsStart[p + 1] - obs.obsStart[p];
+            if (!posFinite(points[p].pos)) fail("a point is not finite");
+            if (refKf[p] < -1 || refKf[p] >= (int64_t)nkf) fail("refKf is out of range");
+            if (!(!pointBad.empty() && pointBad[p]) && len > 0 && len <= PGORB_MP_MAX_OBS && (obs.refObs[p] < 0 || obs.refObs[p] >= len))
+                fail("refObs lies outside the point's list");
+        }
+        std::vector<std::vector<pgorb_keypoint>> keys(nkf);
+        std::vector<const pgorb_keypoint*> kps(nkf + 1, nullptr);
+        std::vector<const int32_t*> slots(nkf + 1, nullptr);
+        std::vector<int32_t> n(nkf + 1, 0);
+        for (size_t f = 0; f < nkf; f++) {
+            keys[f].assign(octaves[f].size() + 1, pgorb_keypoint{});
+            for (size_t i = 0; i < octaves[f].size(); i++) keys[f][i].octave = octaves[f][i];
+            kps[f] = keys[f].data(); slots[f] = kfPoint[f].data(); n[f] = (int32_t)kfPoint[f].size();
+        }
+        out.hasCorrected.assign(nkf, 0); out.hasNonCorrected.assign(nkf, 0);
+        out.corrected.assign(nkf, pgorb_sim3d{}); out.nonCorrected.assign(nkf, pgorb_sim3d{});
+        out.poses.assign(nkf, pgorb_kf_pose{});
+        out.correctedBy.assign(np + 1, -1); out.pointRefKf.assign(np + 1, -1);
+        std::vector<pgorb_map_point> one(1);
+        const int rc = pgorb_correct_loop_poses(ctx_, (int)nkf, kps.data(), n.data(), poses.data(), curKf, &scw, (int)connected.size(),
+                                                connected.empty() ? n.data() : connected.data(), kfOrder.empty() ? nullptr : kfOrder.data(), slots.data(),
+                                                (int)np, np ? points.data() : one.data(), pointBad.empty() ? nullptr : pointBad.data(), obs.obsStart.data(),
+                                                obs.obsFrame.data(), obs.obsIdx.data(), np ? obs.refObs.data() : n.data(), np ? refKf.data() : n.data(),
+                                                out.hasCorrected.data(), out.corrected.data(), out.hasNonCorrected.data(), out.nonCorrected.data(),
+                                                out.poses.data(), out.correctedBy.data(), out.pointRefKf.data(), out.info.data());
+        if (rc < 0) throw std::runtime_error(pgorb_last_error(ctx_));
+        out.correctedBy.resize(np); out.pointRefKf.resize(np);
+        return rc;
+    }
+    // The map update after global bundle adjustment.  poses = the poses as they stand (mTcwBefGBA), posesGba / kfDone / posGba
+    // [np][3] / pointDone as GlobalBundleAdjustment leaves them, parent[f] or -1, kfOrigin[f] = is in mvpKeyFrameOrigins, kfBad and
+    // pointBad may be empty, refKf[p] or -1; points[].pos is updated IN PLACE.  Returns the number of key frames updated.
+    int UpdateMapAfterGBA(const std::vector<pgorb_kf_pose>& poses, const std::vector<pgorb_kf_pose>& posesGba, const std::vector<uint8_t>& kfDone,
+                          const std::vector<int32_t>& parent, const std::vector<uint8_t>& kfOrigin, const std::vector<uint8_t>& kfBad,
+                          std::vector<pgorb_map_point>& points, const std::vector<float>& posGba, const std::vector<uint8_t>& pointDone,
+                          const std::vector<uint8_t>& pointBad, const std::vector<int32_t>& refKf, MapUpdate& out)
+    {
+        const char* fn = "LoopClosing::UpdateMapAfterGBA";
+        auto fail = [&](const char* what) { throw std::invalid_argument(std::string(fn) + ": " + what); };
+        const size_t nkf = parent.size(), np = points.size();
+        if (nkf > PGORB_COVIS_MAX_KF) fail("more than PGORB_COVIS_MAX_KF key frames");
+        if (poses.size() != nkf || posesGba.size() != nkf || kfDone.size() != nkf || kfOrigin.size() != nkf || (!kfBad.empty() && kfBad.size() != nkf))
+            fail("poses, posesGba, kfDone, kfOrigin and kfBad need one entry per key frame");
+        if (posGba.size() != 3 * np || pointDone.size() != np || refKf.size() != np || (!pointBad.empty() && pointBad.size() != np))
+            fail("posGba, pointDone, refKf and pointBad need one entry per point");
+        for (size_t k = 0; k < nkf; k++) {
+            if (parent[k] < -1 || parent[k] >= (int64_t)nkf) fail("a parent is out of range");
+            if (!poseFinite(poses[k]) || (kfDone[k] && !poseFinite(posesGba[k]))) fail("a pose is not finite");
+        }
+        std::vector<int32_t> mark(nkf + 1, -1);
+        for (size_t k = 0; k < nkf; k++) {
+            int cur = (int)k;
+            while (cur >= 0 && mark[cur] < 0) { mark[cur] = (int32_t)k; cur = parent[cur]; }
+            if (cur >= 0 && mark[cur] == (int32_t)k) fail("the parents form a cycle");
+        }
+        for (size_t p = 0; p < np; p++) {
+            if (refKf[p] < -1 || refKf[p] >= (int64_t)nkf) fail("refKf is out of range");
+            if (!posFinite(points[p].pos) || (pointDone[p] && !posFinite(&posGba[3 * p]))) fail("a point is not finite");
+        }
+        out.poses.assign(nkf + 1, pgorb_kf_pose{}); out.kfUpdated.assign(nkf + 1, 0); out.pointUpdated.assign(np + 1, 0);
+        const int rc = pgorb_global_ba_map_update(ctx_, (int)nkf, poses.data(), posesGba.data(), kfDone.data(), parent.data(), kfOrigin.data(),
+                                                  kfBad.empty() ? nullptr : kfBad.data(), (int)np, points.data(), posGba.data(), pointDone.data(),
+                                                  pointBad.empty() ? nullptr : pointBad.data(), refKf.data(), out.poses.data(), out.kfUpdated.data(),
+                                                  out.pointUpdated.data(), out.info.data());
+        if (rc < 0) throw std::runtime_error(pgorb_last_error(ctx_));
+        out.poses.resize(nkf); out.kfUpdated.resize(nkf); out.pointUpdated.resize(np);
+        return rc;
+    }
+ private:
+    static bool poseFinite(const pgorb_kf_pose& P)
+    {
+        for (float v : P.Tcw) if (!std::isfinite(v)) return false;
+        return std::isfinite(P.Ow[0]) && std::isfinite(P.Ow[1]) && std::isfinite(P.Ow[2]);
+    }
+    static bool posFinite(const float* p) { return std::isfinite(p[0]) && std::isfinite(p[1]) && std::isfinite(p[2]); }
+    pgorb_ctx* ctx_;
+};
+
 }  // namespace pgorb

@@ -2351,6 +2351,214 @@ class Tracking:
                     status=int(outs[3][0]))
 
 
+# loop correction (include/pgorb.h): the status bits and the info lengths
+LC_OVER_OBS, LC_BAD_INDEX, LC_INFO, MU_INFO = 1, 2, 4, 4
+
+
+class LoopClosing:
+    """The two map rewrites of loop closing (thirdparty/orb-slam2/src/LoopClosing.cc) on the GPU: CorrectLoop's propagation
+    (:438-516) and the map update after global bundle adjustment (:679-742).  include/pgorb.h states both contracts."""
+
+    @staticmethod
+    def check_sim3(name, scw):
+        S = np.ascontiguousarray(scw, SIM3D_DTYPE).reshape(1)
+        if not (np.isfinite(S["r"]).all() and np.isfinite(S["t"]).all() and np.isfinite(S["s"]).all()):
+            raise ValueError(name + ": scw is not finite")
+        if not float(S["s"][0]) > 0.0:
+            raise ValueError(name + ": the scale of scw is not positive")
+        return S
+
+    @staticmethod
+    def check_poses(name, poses, nkf, what="poses"):
+        P = np.ascontiguousarray(poses, KF_POSE_DTYPE).reshape(-1)
+        if len(P) != nkf:
+            raise ValueError("%s: %s needs one record per key frame" % (name, what))
+        return P
+
+    @staticmethod
+    def CorrectLoopPoses(ext, octaves, poses, cur_kf, scw, connected, kf_point, points, obs_start, obs_frame, obs_idx, ref_obs, ref_kf,
+                         point_bad=None, kf_order=None):
+        """LoopClosing::CorrectLoop, :438-516 (without :515's UpdateConnections): the Sim3 correction of cur_kf's neighbourhood and
+        of every map point it holds.  octaves[f] = mvKeysUn[i].octave of key frame f, poses KF_POSE_DTYPE, scw = mg2oScw
+        (SIM3D_DTYPE), connected = mvpCurrentConnectedKFs by index (an entry that is negative, out of range or cur_kf is skipped;
+        cur_kf is added), kf_point[f] the slots, the table as LocalMapping.RefreshMapPoints takes it, ref_kf[p] =
+        GetReferenceKeyFrame() or -1, kf_order the address ranks (None = index order).  Nothing passed in is changed.  Returns a
+        dict: has_corrected, corrected, has_non_corrected, non_corrected (what Optimizer.OptimizeEssentialGraph takes), poses,
+        points, corrected_by, point_ref_kf, info [LC_INFO], status, members, corrected_points.  Raises ValueError for
+        everything pgorb_correct_loop_poses refuses."""
+        fn = "LoopClosing.CorrectLoopPoses"
+        nkf = len(kf_point)
+        pts = np.array(np.ascontiguousarray(points, MAP_POINT_DTYPE).reshape(-1))       # a copy: corrected in place
+        n = len(pts)
+        slots, ptrs, nk, st, of, pb, ko = _covis_table(fn, nkf, kf_point, n, obs_start, obs_frame, point_bad, kf_order)
+        if not 0 <= int(cur_kf) < nkf:
+            raise ValueError(fn + ": cur_kf is out of range")
+        P = LoopClosing.check_poses(fn, poses, nkf)
+        if not (np.isfinite(P["Tcw"]).all() and np.isfinite(P["Ow"]).all()):
+            raise ValueError(fn + ": a pose is not finite")
+        S = LoopClosing.check_sim3(fn, scw)
+        if len(octaves) != nkf or any(len(o) != len(s) for o, s in zip(octaves, slots)):
+            raise ValueError(fn + ": one octave per slot of every key frame")
+        m = int(st[-1])
+        oi = np.ascontiguousarray(obs_idx, np.int32).reshape(-1)
+        if len(oi) < m or (m and (oi[:m].min() < 0 or np.any(oi[:m] >= nk[of[:m]]))):
+            raise ValueError(fn + ": an observation names a keypoint out of range")
+        if not np.isfinite(pts["pos"]).all():
+            raise ValueError(fn + ": a point is not finite")
+        ro, rk = _arr(ref_obs, np.int32, n, "ref_obs"), _arr(ref_kf, np.int32, n, "ref_kf")
+        if n and (int(rk.min()) < -1 or int(rk.max()) >= nkf):
+            raise ValueError(fn + ": ref_kf is out of range")
+        ln = np.diff(st)
+        if np.any((pb[:n] == 0) & (ln > 0) & (ln <= MP_MAX_OBS) & ((ro < 0) | (ro >= ln))):
+            raise ValueError(fn + ": ref_obs lies outside the point's list")
+        lst = np.ascontiguousarray(connected, np.int32).reshape(-1)
+        if len(lst) > COVIS_MAX_KF:
+            raise ValueError(fn + ": more than COVIS_MAX_KF list entries")
+        keep = []
+        kps = (C.c_void_p * max(nkf, 1))()
+        for f, o in enumerate(octaves):
+            k = np.zeros(max(len(o), 1), KEYPOINT_DTYPE)
+            k["octave"][:len(o)] = o
+            keep.append(k)
+            kps[f] = k.ctypes.data
+        one = np.zeros(1, np.int32)
+        hc, hn = np.zeros(nkf, np.uint8), np.zeros(nkf, np.uint8)
+        cor, non, po = np.zeros(nkf, SIM3D_DTYPE), np.zeros(nkf, SIM3D_DTYPE), np.zeros(nkf, KF_POSE_DTYPE)
+        by, pr, info = np.full(max(n, 1), -1, np.int32), np.full(max(n, 1), -1, np.int32), np.zeros(LC_INFO, np.int32)
+        ret = ext._check(ext._L.pgorb_correct_loop_poses(
+            ext._h, nkf, kps, _p(nk), _p(P), int(cur_kf), _p(S), len(lst), _p(lst if len(lst) else one), None if ko is None else _p(ko), ptrs, n,
+            _p(pts if n else np.zeros(1, MAP_POINT_DTYPE)), _p(pb), _p(st), _p(of), _p(oi if len(oi) else one), _p(ro if n else one),
+            _p(rk if n else one), _p(hc), _p(cor), _p(hn), _p(non), _p(po), _p(by), _p(pr), _p(info)))
+        return dict(has_corrected=hc, corrected=cor, has_non_corrected=hn, non_corrected=non, poses=po, points=pts, corrected_by=by[:n].copy(),
+                    point_ref_kf=pr[:n].copy(), info=info, status=int(info[0]), members=int(info[1]), corrected_points=int(ret))
+
+    @staticmethod
+    def CorrectLoopPoses_device(ext, d_kps, d_n, cap_per_frame, d_pose, cur_kf, d_scw, d_list, d_kf_point, npoints, d_points, d_obs_start,
+                                d_obs_frame, d_obs_idx, d_ref_obs, d_ref_kf, d_point_bad=None, d_kf_order=None, d_list_count=None, stream=None):
+        """pgorb_correct_loop_poses_device over resident torch tensors, asynchronous on `stream`: d_kps / d_pose / d_scw / d_points
+        the bytes of their dtypes, the lists int32, the flags uint8; d_list may be a whole row of the covisibility graph's ord_kf
+        with d_list_count = the one-element slice of nord (include/pgorb.h says why the count is needed).  The sizes and element
+        types are checked here; the contents are not read.  d_points is corrected IN PLACE.  Returns a dict of freshly allocated
+        tensors: has_corrected, corrected, has_non_corrected, non_corrected, pose_out (what Optimizer.OptimizeEssentialGraph_device
+        takes), corrected_by, point_ref_kf and info [LC_INFO]."""
+        import torch
+        name = "LoopClosing.CorrectLoopPoses_device"
+        for nm, t_ in (("d_n", d_n), ("d_list", d_list), ("d_kf_point", d_kf_point), ("d_obs_start", d_obs_start), ("d_obs_frame", d_obs_frame),
+                       ("d_obs_idx", d_obs_idx), ("d_ref_obs", d_ref_obs), ("d_ref_kf", d_ref_kf), ("d_kf_order", d_kf_order),
+                       ("d_list_count", d_list_count)):
+            if t_ is not None and t_.dtype != torch.int32:
+                raise ValueError("%s: %s must be an int32 tensor (the counts are taken from element counts)" % (name, nm))
+        nkf, cap, npoints, nlist, nobs = int(d_n.numel()), int(cap_per_frame), int(npoints), int(d_list.numel()), int(d_obs_frame.numel())
+        if not nkf or not 0 <= int(cur_kf) < nkf:
+            raise ValueError(name + ": no key frame, or cur_kf is out of range")
+        if cap < 1 or cap > 16000 or nkf > COVIS_MAX_KF or nlist > COVIS_MAX_KF or npoints < 0:
+            raise ValueError(name + ": cap_per_frame outside [1, 16000], more than COVIS_MAX_KF key frames or list entries, or a negative count")
+        if d_kps.numel() * d_kps.element_size() != nkf * cap * KEYPOINT_DTYPE.itemsize or int(d_kf_point.numel()) != nkf * cap or \
+                d_pose.numel() * d_pose.element_size() != nkf * KF_POSE_DTYPE.itemsize or d_scw.numel() * d_scw.element_size() != SIM3D_DTYPE.itemsize:
+            raise ValueError(name + ": d_kps and d_kf_point must be [nframes][cap], d_pose one record per frame, d_scw one record")
+        if d_points.numel() * d_points.element_size() < npoints * MAP_POINT_DTYPE.itemsize or int(d_obs_start.numel()) != npoints + 1 or \
+                int(d_obs_idx.numel()) != nobs or int(d_ref_obs.numel()) < npoints or int(d_ref_kf.numel()) < npoints:
+            raise ValueError(name + ": the table, d_ref_obs or d_ref_kf is shorter than npoints, or d_obs_start is not npoints + 1")
+        for nm, t_, need in (("d_point_bad", d_point_bad, npoints), ("d_kf_order", d_kf_order, nkf), ("d_list_count", d_list_count, 1)):
+            if t_ is not None and t_.numel() < need:
+                raise ValueError("%s: %s is too short" % (name, nm))
+        dev = d_n.device
+        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)
+        out = dict(has_corrected=z((nkf,), torch.uint8), corrected=z((nkf, SIM3D_DTYPE.itemsize), torch.uint8),
+                   has_non_corrected=z((nkf,), torch.uint8), non_corrected=z((nkf, SIM3D_DTYPE.itemsize), torch.uint8),
+                   pose_out=z((nkf, KF_POSE_DTYPE.itemsize), torch.uint8), corrected_by=z((max(npoints, 1),), torch.int32),
+                   point_ref_kf=z((max(npoints, 1),), torch.int32), info=z((LC_INFO,), torch.int32))
+        q = lambda t: None if t is None or t.numel() == 0 else C.c_void_p(t.data_ptr())
+        s = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        ext._check(ext._L.pgorb_correct_loop_poses_device(
+            ext._h, q(d_kps), q(d_n), nkf, cap, q(d_pose), int(cur_kf), q(d_scw), nlist, q(d_list), q(d_list_count), q(d_kf_order), q(d_kf_point),
+            npoints, q(d_points), q(d_point_bad), q(d_obs_start), q(d_obs_frame), q(d_obs_idx), nobs, q(d_ref_obs), q(d_ref_kf),
+            q(out["has_corrected"]), q(out["corrected"]), q(out["has_non_corrected"]), q(out["non_corrected"]), q(out["pose_out"]),
+            q(out["corrected_by"]), q(out["point_ref_kf"]), q(out["info"]), C.c_void_p(s)))
+        return out
+
+    @staticmethod
+    def UpdateMapAfterGBA(ext, poses, poses_gba, kf_done, parent, kf_origin, points, pos_gba, point_done, ref_kf, kf_bad=None, point_bad=None):
+        """LoopClosing::RunGlobalBundleAdjustment, :679-742: the spanning-tree propagation of the adjusted poses and the map points'
+        update.  poses = the poses as they stand (mTcwBefGBA), poses_gba / kf_done / pos_gba / point_done as
+        Optimizer.GlobalBundleAdjustment returns them, parent[f] or -1, kf_origin[f] = is in mvpKeyFrameOrigins, ref_kf[p] =
+        GetReferenceKeyFrame() or -1.  Nothing passed in is changed.  Returns a dict: poses, kf_updated, points, point_updated, info
+        [MU_INFO], updated (key frames), recomputed, updated_points.  Raises ValueError for everything pgorb_global_ba_map_update
+        refuses."""
+        fn = "LoopClosing.UpdateMapAfterGBA"
+        par = np.ascontiguousarray(parent, np.int32).reshape(-1)
+        nkf = len(par)
+        if nkf > COVIS_MAX_KF:
+            raise ValueError(fn + ": more than COVIS_MAX_KF key frames")
+        P, G = LoopClosing.check_poses(fn, poses, nkf), LoopClosing.check_poses(fn, poses_gba, nkf, "poses_gba")
+        kd, ko, kb = _arr(kf_done, np.uint8, nkf, "kf_done"), _arr(kf_origin, np.uint8, nkf, "kf_origin"), _mask(kf_bad, nkf, "kf_bad")
+        if nkf and (int(par.min()) < -1 or int(par.max()) >= nkf):
+            raise ValueError(fn + ": a parent is out of range")
+        u = kd != 0
+        if not (np.isfinite(P["Tcw"]).all() and np.isfinite(P["Ow"]).all() and np.isfinite(G["Tcw"][u]).all() and np.isfinite(G["Ow"][u]).all()):
+            raise ValueError(fn + ": a pose is not finite")
+        mark = np.full(nkf, -1, np.int64)
+        for k in range(nkf):
+            cur = k
+            while cur >= 0 and mark[cur] < 0:
+                mark[cur] = k
+                cur = int(par[cur])
+            if cur >= 0 and mark[cur] == k:
+                raise ValueError(fn + ": the parents form a cycle")
+        pts = np.array(np.ascontiguousarray(points, MAP_POINT_DTYPE).reshape(-1))       # a copy: moved in place
+        n = len(pts)
+        pg, pd, pb = _arr(pos_gba, np.float32, n, "pos_gba", 3), _arr(point_done, np.uint8, n, "point_done"), _mask(point_bad, n, "point_bad")
+        rk = _arr(ref_kf, np.int32, n, "ref_kf")
+        if n and (int(rk.min()) < -1 or int(rk.max()) >= nkf):
+            raise ValueError(fn + ": ref_kf is out of range")
+        if not (np.isfinite(pts["pos"]).all() and np.isfinite(pg[pd != 0]).all()):
+            raise ValueError(fn + ": a point is not finite")
+        k1, n1 = max(nkf, 1), max(n, 1)
+        po, ku, pu, info = np.zeros(k1, KF_POSE_DTYPE), np.zeros(k1, np.uint8), np.zeros(n1, np.uint8), np.zeros(MU_INFO, np.int32)
+        pad = lambda x, dt, w=None: x if len(x) else np.zeros(1 if w is None else (1, w), dt)
+        ret = ext._check(ext._L.pgorb_global_ba_map_update(
+            ext._h, nkf, _p(pad(P, KF_POSE_DTYPE)), _p(pad(G, KF_POSE_DTYPE)), _p(pad(kd, np.uint8)), _p(pad(par, np.int32)), _p(pad(ko, np.uint8)),
+            _p(kb), n, _p(pad(pts, MAP_POINT_DTYPE)), _p(pad(pg, np.float32, 3)), _p(pad(pd, np.uint8)), _p(pb), _p(pad(rk, np.int32)), _p(po), _p(ku),
+            _p(pu), _p(info)))
+        return dict(poses=po[:nkf].copy(), kf_updated=ku[:nkf].copy(), points=pts, point_updated=pu[:n].copy(), info=info, updated=int(ret),
+                    recomputed=int(info[2]), updated_points=int(info[3]))
+
+    @staticmethod
+    def UpdateMapAfterGBA_device(ext, d_pose, d_pose_gba, d_kf_done, d_parent, d_kf_origin, npoints, d_points, d_pos_gba, d_point_done, d_ref_kf,
+                                 d_kf_bad=None, d_point_bad=None, stream=None):
+        """pgorb_global_ba_map_update_device over resident torch tensors, asynchronous on `stream`: d_pose / d_pose_gba / d_points the
+        bytes of their dtypes, d_parent / d_ref_kf int32, d_pos_gba float32 [npoints][3], the flags uint8.  The sizes and element
+        types are checked here; the contents are not read.  d_points[].pos is updated IN PLACE.  Returns a dict of freshly
+        allocated tensors: pose_out, kf_updated, point_updated, info [MU_INFO]."""
+        import torch
+        name = "LoopClosing.UpdateMapAfterGBA_device"
+        if d_parent.dtype != torch.int32 or d_ref_kf.dtype != torch.int32 or d_pos_gba.dtype != torch.float32:
+            raise ValueError(name + ": d_parent and d_ref_kf must be int32 tensors, d_pos_gba float32")
+        nkf, npoints = int(d_parent.numel()), int(npoints)
+        if not nkf or nkf > COVIS_MAX_KF or npoints < 0:
+            raise ValueError(name + ": no key frame, more than COVIS_MAX_KF, or a negative count")
+        if d_pose.numel() * d_pose.element_size() != nkf * KF_POSE_DTYPE.itemsize or \
+                d_pose_gba.numel() * d_pose_gba.element_size() != nkf * KF_POSE_DTYPE.itemsize or \
+                d_kf_done.numel() * d_kf_done.element_size() != nkf or d_kf_origin.numel() * d_kf_origin.element_size() != nkf:
+            raise ValueError(name + ": d_pose and d_pose_gba need one record, d_kf_done and d_kf_origin one byte per key frame")
+        if d_points.numel() * d_points.element_size() < npoints * MAP_POINT_DTYPE.itemsize or int(d_pos_gba.numel()) < 3 * npoints or \
+                d_point_done.numel() * d_point_done.element_size() < npoints or int(d_ref_kf.numel()) < npoints:
+            raise ValueError(name + ": the table, d_pos_gba, d_point_done or d_ref_kf is shorter than npoints")
+        for nm, t_, need in (("d_kf_bad", d_kf_bad, nkf), ("d_point_bad", d_point_bad, npoints)):
+            if t_ is not None and t_.numel() * t_.element_size() < need:
+                raise ValueError("%s: %s is too short" % (name, nm))
+        dev = d_parent.device
+        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)
+        out = dict(pose_out=z((nkf, KF_POSE_DTYPE.itemsize), torch.uint8), kf_updated=z((nkf,), torch.uint8),
+                   point_updated=z((max(npoints, 1),), torch.uint8), info=z((MU_INFO,), torch.int32))
+        q = lambda t: None if t is None or t.numel() == 0 else C.c_void_p(t.data_ptr())
+        s = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        ext._check(ext._L.pgorb_global_ba_map_update_device(
+            ext._h, nkf, q(d_pose), q(d_pose_gba), q(d_kf_done), q(d_parent), q(d_kf_origin), q(d_kf_bad), npoints, q(d_points), q(d_pos_gba),
+            q(d_point_done), q(d_point_bad), q(d_ref_kf), q(out["pose_out"]), q(out["kf_updated"]), q(out["point_updated"]), q(out["info"]),
+            C.c_void_p(s)))
+        return out
+
 
 class FrameStream:
     """Streamed ingest (include/pgorb.h, pgorb_stream_*): the frame loop around the extractor for frames that

@@ -94,8 +94,13 @@ next to each, the oracle's CPU time for the same work (1 thread, a few frames, s
                tests on one core (NOT ORB-SLAM2, not a tuned baseline), whose records the GPU's must equal; MapPointCulling of 3000 recent
                points; the compaction of the observation lists.  No target is set.  --cull-only runs these rows alone
                (profiles/next_tier_cull.txt).
+  loop correction  loop closing's two map rewrites on the device (csrc/loop_correct.hip), HIP events: CorrectLoop's propagation
+               (LoopClosing.cc:438-516) over the last key frame of a ride-shaped map and its 30 predecessors, and the map update after
+               GlobalBundleAdjustment (:679-742) of the same map with the last 50 key frames made while the adjustment ran.  The parent commit
+               has no such path and ORB-SLAM2 cannot be built here, so there is nothing measured to compare against: no target is set, the rows
+               record what was measured.  --loop-correct-only runs these rows alone (profiles/next_tier_loop_correct.txt).
 
-usage: python tools/next_tier_bench.py [--batch 128] [--out profiles/r02_next_tier.txt] [--refresh-only | --place-only | --loop-only | --track-only | --pose-only | --sim3-only | --pnp-only | --optsim3-only | --lba-only | --eg-only | --gba-only | --covis-only | --cull-only]"""
+usage: python tools/next_tier_bench.py [--batch 128] [--out profiles/r02_next_tier.txt] [--refresh-only | --place-only | --loop-only | --track-only | --pose-only | --sim3-only | --pnp-only | --optsim3-only | --lba-only | --eg-only | --gba-only | --covis-only | --cull-only | --loop-correct-only]"""
 import argparse, ctypes as C, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -123,6 +128,8 @@ ap.add_argument("--eg-only", action="store_true", help="the OptimizeEssentialGra
 ap.add_argument("--gba-only", action="store_true", help="the GlobalBundleAdjustment rows alone (no ride, no vocabulary)")
 ap.add_argument("--covis-only", action="store_true", help="the covisibility-graph rows alone (no ride, no vocabulary)")
 ap.add_argument("--cull-only", action="store_true", help="the culling rows alone (no ride, no vocabulary)")
+ap.add_argument("--loop-correct-only", action="store_true", help="the loop-correction rows alone (no ride, no vocabulary); writes "
+                "profiles/next_tier_loop_correct.txt unless --out names another file")
 a = ap.parse_args()
 w, h, nf, B = 1920, 1080, a.features, a.batch
 
@@ -890,6 +897,72 @@ def gba_lines(nkf=500, per_kf=40, span=4):
                 li[3], li[4], li[2], li[1], li[5], li[7], li[6], li[8]), one.ms, one.ms / max(int(li[6] + li[8]), 1))]
 
 
+def loop_correct_lines(nkf=200, cap=2000, nlist=30, fresh=50):
+    """Loop correction: both device forms on one ride-shaped map; a sample of the results is held against the Python reference."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import loop_correct_cases as K
+    import loop_correct_reference as LR
+    rng = np.random.RandomState(29)
+    poses = [K.pose(K.rot((0.05, 1, 0.02), 0.9 * f), (0.05 * np.sin(0.3 * f), 0.02 * np.cos(0.2 * f), 4.0 + 0.03 * f)) for f in range(nkf)]
+    fill, pts = [0] * nkf, []
+    for it in range(4 * nkf * cap // 5):                                        # tracks of 2..40 consecutive key frames
+        f0, ln = int(rng.randint(0, nkf)), int(rng.randint(2, 41))
+        fs = [f for f in range(f0, min(f0 + ln, nkf)) if fill[f] < cap]
+        if len(fs) >= 2:
+            for f in fs:
+                fill[f] += 1
+            pts.append(dict(pos=rng.normal(size=3) * 2.0, holders=fs, ref=fs[int(rng.randint(len(fs)))], octave=int(rng.randint(8))))
+        if it % 256 == 0 and min(fill[20:nkf - 20]) >= cap:
+            break
+    cur = nkf - 1
+    lc = K.loop_case("ride", poses, cur, K.sim3_near(poses[cur], 1.1, rng), list(range(cur - nlist, cur)), pts, [int(x) for x in rng.permutation(nkf)])
+    ext = pg.ORBextractor(2000, 1.2, 8, 20, 7, max_width=640, max_height=480)
+    n, nobs = lc["npoints"], len(lc["obs_frame"])
+
+    def timed_fresh(run, D, reps=9):
+        keep, ms = D["pts"].clone(), []
+        for r in range(reps + 1):
+            D["pts"].copy_(keep)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(); run(D, False); e1.record(); torch.cuda.synchronize()
+            ms.append(e0.elapsed_time(e1))
+        D["pts"].copy_(keep)
+        return float(np.median(ms[1:])), run(D, True)
+    D = K.loop_device_arrays(lc)
+    t_lc, (got, _) = timed_fresh(lambda D, dl: K.run_device_loop(lc, ext, D=D, download=dl), D)
+    t0 = time.perf_counter()
+    want = LR.correct_loop(lc)
+    t_ref = (time.perf_counter() - t0) * 1e3
+    assert K.same(got, want, K.LOOP_KEYS), "the device's correction differs from the reference's: " + K.diff(got, want, K.LOOP_KEYS)
+    done = [int(f < nkf - fresh) for f in range(nkf)]
+    gba = [K._adjusted(p, rng, 1.0) if done[f] else p for f, p in enumerate(poses)]
+    pos = np.array(lc["points"]["pos"], np.float32)
+    pdone = [int(done[int(r)] and rng.rand() < 0.9) for r in lc["ref_kf"]]
+    mc = K.map_case("ride", poses, gba, done, [-1] + list(range(nkf - 1)), [1] + [0] * (nkf - 1), None, pos, pos + np.float32(0.01), pdone, None, lc["ref_kf"])
+    M = K.map_device_arrays(mc)
+    t_mu, (gotm, _) = timed_fresh(lambda M, dl: K.run_device_map(mc, ext, D=M, download=dl), M)
+    t0 = time.perf_counter()
+    wantm = LR.update_map(mc)
+    t_refm = (time.perf_counter() - t0) * 1e3
+    assert K.same(gotm, wantm, K.MAP_KEYS), "the device's map update differs from the reference's: " + K.diff(gotm, wantm, K.MAP_KEYS)
+    scene = "%d key frames x %d slots (%d filled on average), %d points, %d observations" % (nkf, cap, np.mean(fill), n, nobs)
+    li, mi = got["info"], gotm["info"]
+    return ["# Loop correction on the device, resident calls, HIP events around the call alone, median of 9 after one warm-up, the",
+            "# table restored before every call.  The Python column is the literal reference of the tests (tests/loop_correct_reference.py) on one core, whose",
+            "# bytes the GPU's must equal; it is NOT ORB-SLAM2 and not a tuned baseline.  The parent commit has no such path and ORB-SLAM2 cannot be built",
+            "# here, so there is nothing measured to compare against: no target is set and no time is a pass condition.",
+            "%-150s %10s %12s" % ("call", "GPU ms", "Python ms"),
+            "%-150s %10.3f %12.1f" % ("correct_loop_poses: %s; %d members, %d points corrected (k_lc_init, k_lc_rank, k_lc_members, k_lc_claim, k_lc_points)" % (
+                scene, li[1], li[2]), t_lc, t_ref),
+            "%-150s %10.3f %12.1f" % ("global_ba_map_update: the same map, the last %d key frames not adjusted (a chain); %d key frames updated, %d recomputed, %d points "
+                                      "updated (k_mu_kf, k_mu_points)" % (fresh, mi[1], mi[2], mi[3]), t_mu, t_refm)]
+
+
+if a.loop_correct_only:
+    lines = ["# python tools/next_tier_bench.py --loop-correct-only   (MI355X)"] + loop_correct_lines()
+    print("\n".join(lines))
+    open(a.out or os.path.join(ROOT, "profiles", "next_tier_loop_correct.txt"), "w").write("\n".join(lines) + "\n")
+    sys.exit(0)
 if a.cull_only:
     lines = ["# python tools/next_tier_bench.py --cull-only   (MI355X)"] + cull_lines()
     print("\n".join(lines))

@@ -1712,6 +1712,143 @@ int  pgorb_global_ba_map_update_device(pgorb_ctx* ctx,
         const int32_t* d_ref_kf, pgorb_kf_pose* d_pose_out, uint8_t* d_kf_updated, uint8_t* d_point_updated, int32_t* d_info,
         void* hip_stream);
 
+/* ---- The trajectory read-out: Tracking's pose record and System::GetTrajectory (csrc/track_pose.hip) ---------------------------
+ * The pose bookkeeping at the head and the tail of Tracking::Track and the function that turns it into the trajectory, on resident
+ * arrays, so that predict -> SearchByProjection(last frame) -> PoseOptimization -> UpdateLocalMap -> SearchLocalPoints ->
+ * PoseOptimization -> commit runs frame after frame without a pose leaving the device, and the finished ride is read out in the
+ * layout pgorb_smooth_heading_directions / pgorb_trajectory_pca / pgorb_project_directions take.  Restates (thirdparty/orb-slam2):
+ *   Tracking::UpdateLastFrame (monocular return)     src/Tracking.cc:792-798      Tlr * pRef->GetPose()
+ *   TrackWithMotionModel / TrackReferenceKeyFrame    :866 / :764                   mVelocity * mLastFrame.mTcw / mLastFrame.mTcw
+ *   Tracking::Track, the motion model and the record :432-440, :493, :497-506     mTcw * LastTwc, mTcw * refKF->GetPoseInverse()
+ *   KeyFrame::SetBadFlag's mTcp                      src/KeyFrame.cc:641          Tcw * mpParent->GetPoseInverse()
+ *   System::GetTrajectory                            src/System.cc:371-412
+ * Every product is the 4 x 4 float product of DESIGN.md section 4 (gemm's small-matrix path, four terms in index order, the fourth
+ * formed), every SetPose gives Ow = -Rcw.t()*tcw with alpha = -1 applied in double, GetPoseInverse() is [Rcw' | Ow] of the pose AS
+ * GIVEN.  The library is built with -ffp-contract=off and these paths use + - x and correctly rounded square roots and divisions
+ * only: every result is exact.  The key-frame table is what the other calls take: d_pose (Tcw and Ow are read), d_kf_bad, d_parent,
+ * d_kf_id (mnId) over nkf key frames -- several rides share one table and name their key frames by table index -- plus d_tcp
+ * [nkf][12] = mTcp rows 0-2, meaningful only where kf_bad is set.
+ *
+ *   pgorb_track_state         one tracker's pose members: `last` = mLastFrame as a complete pgorb_kf_pose (has_last =
+ *       !mLastFrame.mTcw.empty()), velocity = mVelocity rows 0-2 (has_velocity), last_ref_kf = mLastFrame.mpReferenceKF.
+ *   pgorb_trajectory_record   RelativeFramePoseData (include/Tracking.h:58-64): pose = mRelativeFramePose rows 0-2 (has_pose),
+ *       ref_kf = mpReference, frame_time = mFrameTime, frame_id = mFrameId, lost = mbLost.
+ *   A tracker's records are d_traj + t * traj_cap, d_ntrajectory[t] of them (mlTrajectory).
+ *
+ *   pgorb_track_predict_batch_device   the pose the first search of a frame starts from, a thread per tracker.  d_mode [ntrack]
+ *       (NULL = `mode` for all).  PGORB_TRACK_MOTION_MODEL: UpdateLastFrame -- state.last takes Tcw = record.pose *
+ *       Tcw[last_ref_kf] of the tracker's LAST record, then SetPose's Ow, written back to the state -- then pose_out = velocity *
+ *       last.Tcw with SetPose's Ow.  PGORB_TRACK_REFERENCE_KF: pose_out = state.last as it stands, no UpdateLastFrame.
+ *       d_pose_out [ntrack] are complete records with the camera of state.last, what
+ *       pgorb_search_by_projection_last_frame_batch_device and pgorb_pose_optimization_batch_device take as d_pose.  d_status
+ *       [ntrack]: 0, or PGORB_TRACK_NO_LAST (has_last == 0), PGORB_TRACK_NO_VELOCITY (motion model with has_velocity == 0),
+ *       PGORB_TRACK_BAD_INDEX (motion model: last_ref_kf outside [0, nkf), no record, a count past traj_cap or a last record
+ *       without a pose; any mode: a mode that is neither); with a status the state is not written and pose_out is state.last
+ *       unchanged.
+ *   pgorb_track_commit_batch_device   the end of Track(), a thread per tracker, in the reference's order.  Inputs per tracker:
+ *       d_pose = the frame's final pose (as PoseOptimization wrote it), d_ok = bOK, d_ref_kf = mpReferenceKF after a possible
+ *       CreateNewKeyFrame, d_frame_time, d_frame_id.  (1) with bOK: velocity = pose.Tcw * [Rlast' | Ow_last] when has_last, else
+ *       has_velocity = 0; without bOK the velocity is LEFT AS IT IS (the reference does not clear it on a lost frame); (2) the
+ *       record (pose.Tcw * GetPoseInverse() of ref_kf, ref_kf, time, id, lost = !bOK, has_pose = 1) is appended at
+ *       d_ntrajectory[t] and the count advances; (3) state.last = pose, has_last = 1, last_ref_kf = ref_kf.  d_status: 0,
+ *       PGORB_TRACK_FULL (the count is outside [0, traj_cap)) or PGORB_TRACK_BAD_INDEX (ref_kf outside [0, nkf)); with a status
+ *       NOTHING is written, neither state, record nor count.
+ *   pgorb_keyframe_tcp_device   mTcp of every record of a pgorb_keyframe_culling_device call whose action is
+ *       PGORB_CULL_KF_CULLED: reads d_record [list_cap][4] and d_cull_info (that call's d_info: nothing is done with
+ *       PGORB_CULL_LIMIT, else min(d_cull_info[1], list_cap) records are looked at) where that call left them, d_pose and d_parent;
+ *       writes d_tcp[A] = Tcw[A] * GetPoseInverse(parent[A]) for the culled A only, every other row keeps its bytes.  A key
+ *       frame outside [0, nframes) or a parent outside it (-1 = none) leaves the row untouched and counts.  d_info_out
+ *       [PGORB_TCP_INFO] = (0, rows written, rows skipped).  IT MUST RUN AFTER THE CULLING AND BEFORE THE NEXT CALL THAT MOVES A
+ *       POSE (local bundle adjustment, loop correction, the map update after global bundle adjustment): mTcp is the relative pose
+ *       frozen at the moment of the cull, and the culling keeps parent[A] for exactly this.  A thread per record.
+ *   pgorb_get_trajectory_device   System::GetTrajectory over the first min(n, *d_count) records of d_traj (d_count NULL = n;
+ *       d_ntrajectory + t of a tracker), to be launched once per tracker.  k_traj_origin (one workgroup) finds Two =
+ *       GetPoseInverse() of the key frame with the smallest d_kf_id among kf_bad == 0 (the smaller index on equal ids) --
+ *       Map::GetAllKeyFrames sorted by lId, from which erased key frames are gone -- and leaves its index in d_info[1]; no live key
+ *       frame: d_info[0] = PGORB_TRAJ_NO_ORIGIN and no output is written.  k_traj_records, a thread per record: time_usec =
+ *       (int64)(frame_time * 1e6), one double product truncated toward zero (NaN or outside int64: INT64_MIN, what x86-64's
+ *       cvttsd2si returns, and PGORB_TRAJ_BAD_TIME), frame_id, is_lost; a lost record gives seven zeros (Pose() is
+ *       value-initialised) and its pose is not read.  Otherwise Trw = eye(4); while kf_bad[k]: Trw = Trw * mTcp[k], k = parent[k]
+ *       (the product with the identity is formed: it decides the sign of a zero); then Tcw = record.pose * ((Trw * Tcw[k]) * Two);
+ *       quat_wxyz = Eigen's Quaterniond of the TRANSPOSED 3 x 3 block widened to double; translation = -R' * t on gemm's
+ *       small-matrix path with alpha = -1 in double, rounded to float, widened.  The walk is bounded by nkf steps:
+ *       a parent of -1 under a bad key frame, an index outside [0, nkf), a cycle of bad key frames, or has_pose == 0 on a record
+ *       that is not lost gives PGORB_TRAJ_BROKEN in d_status[i] and seven zeros, the other records unaffected.  Outputs
+ *       d_quat_wxyz [n][4], d_translation [n][3] (double), d_time_usec, d_frame_id [n] (int64), d_is_lost [n] (uint8), d_status
+ *       [n]; entries at or past the count keep their bytes.  d_info [PGORB_TRAJ_INFO] = (status, origin key frame or -1, broken
+ *       records, records).
+ *   pgorb_track_predict / pgorb_track_commit / pgorb_keyframe_tcp / pgorb_get_trajectory   the same from host buffers, checked on
+ *       the host before anything else, byte for byte equal to the device forms.  predict and commit take ONE tracker (its state
+ *       in/out, for predict its last record or NULL, for commit its record array and count in/out) and return its status;
+ *       keyframe_tcp takes nrecord records and returns the rows written; get_trajectory returns the number of records that are
+ *       neither lost nor broken.  PGORB_E_ARG: a negative count, a NULL array that is read or written, an unknown mode; and for
+ *       pgorb_get_trajectory also: no live key frame, a record that is not lost with ref_kf outside [0, nkf), a bad key frame whose
+ *       parent is -1 or out of range, a frame_time that is not finite or whose product with 1e6 lies outside int64.
+ * Left to the caller: bOK itself and the nmatches retries, NeedNewKeyFrame / CreateNewKeyFrame, CheckReplacedInLastFrame, the
+ * relocalisation bookkeeping (mnLastRelocFrameId), System::Reset, and the stereo / RGB-D and mbOnlyTracking branches of
+ * UpdateLastFrame.
+ * Limits (PGORB_E_LIMIT): nkf <= PGORB_COVIS_MAX_KF, n and traj_cap <= PGORB_TRAJ_MAX_RECORDS, ntrack <= PGORB_TRACK_MAX, list_cap
+ * <= PGORB_COVIS_MAX_KF.  No scratch arena: the origin reduction's result lives in d_info.  Determinism: a result depends on its
+ * inputs alone, not on the batch size, the stream or a repeat. */
+#define PGORB_TRACK_MOTION_MODEL  0
+#define PGORB_TRACK_REFERENCE_KF  1
+#define PGORB_TRACK_NO_LAST       1
+#define PGORB_TRACK_NO_VELOCITY   2
+#define PGORB_TRACK_BAD_INDEX     4
+#define PGORB_TRACK_FULL          8
+#define PGORB_TRACK_MAX           4096
+#define PGORB_TRAJ_BROKEN         1
+#define PGORB_TRAJ_BAD_TIME       2
+#define PGORB_TRAJ_NO_ORIGIN      4
+#define PGORB_TRAJ_INFO           4
+#define PGORB_TRAJ_MAX_RECORDS    (1 << 22)
+#define PGORB_TCP_INFO            4
+typedef struct pgorb_track_state {
+    pgorb_kf_pose last;      /* mLastFrame: mTcw rows 0-2, mOw, the camera */
+    float velocity[12];      /* mVelocity rows 0-2 */
+    int32_t last_ref_kf;     /* mLastFrame.mpReferenceKF */
+    uint8_t has_last, has_velocity, pad[2];
+} pgorb_track_state;
+typedef struct pgorb_trajectory_record {
+    float pose[12];          /* mRelativeFramePose rows 0-2 */
+    int32_t ref_kf;          /* mpReference */
+    uint8_t has_pose, lost, pad[2];
+    double frame_time;       /* mFrameTime */
+    int64_t frame_id;        /* mFrameId */
+} pgorb_trajectory_record;
+int  pgorb_track_predict(pgorb_ctx* ctx,
+        int mode, pgorb_track_state* state /*in and out*/, const pgorb_trajectory_record* last_record /*or NULL*/,
+        int nkf, const pgorb_kf_pose* kf_pose /*[nkf]*/, pgorb_kf_pose* pose_out);
+int  pgorb_track_predict_batch_device(pgorb_ctx* ctx,
+        int ntrack, int mode, const int32_t* d_mode /*[ntrack] or NULL*/, pgorb_track_state* d_state,
+        const pgorb_trajectory_record* d_traj /*[ntrack][traj_cap]*/, int traj_cap, const int32_t* d_ntrajectory /*[ntrack]*/,
+        int nkf, const pgorb_kf_pose* d_kf_pose, pgorb_kf_pose* d_pose_out /*[ntrack]*/, int32_t* d_status /*[ntrack]*/, void* hip_stream);
+int  pgorb_track_commit(pgorb_ctx* ctx,
+        pgorb_track_state* state /*in and out*/, const pgorb_kf_pose* pose, int ok, int ref_kf, double frame_time, int64_t frame_id,
+        int nkf, const pgorb_kf_pose* kf_pose /*[nkf]*/, pgorb_trajectory_record* traj /*[traj_cap]*/, int traj_cap,
+        int32_t* ntrajectory /*in and out*/);
+int  pgorb_track_commit_batch_device(pgorb_ctx* ctx,
+        int ntrack, pgorb_track_state* d_state, const pgorb_kf_pose* d_pose /*[ntrack]*/, const uint8_t* d_ok, const int32_t* d_ref_kf,
+        const double* d_frame_time, const int64_t* d_frame_id /*[ntrack]*/, int nkf, const pgorb_kf_pose* d_kf_pose,
+        pgorb_trajectory_record* d_traj /*[ntrack][traj_cap]*/, int traj_cap, int32_t* d_ntrajectory /*[ntrack]*/,
+        int32_t* d_status /*[ntrack]*/, void* hip_stream);
+int  pgorb_keyframe_tcp(pgorb_ctx* ctx,
+        int nkf, const pgorb_kf_pose* pose /*[nkf]*/, const int32_t* parent /*[nkf]*/, int nrecord, const int32_t* record /*[nrecord][4]*/,
+        float* tcp /*[nkf][12] in and out*/, int32_t* info_out /*[PGORB_TCP_INFO]*/);
+int  pgorb_keyframe_tcp_device(pgorb_ctx* ctx,
+        int nframes, const pgorb_kf_pose* d_pose, const int32_t* d_parent, int list_cap, const int32_t* d_record,
+        const int32_t* d_cull_info /*[PGORB_CULL_INFO]*/, float* d_tcp, int32_t* d_info_out, void* hip_stream);
+int  pgorb_get_trajectory(pgorb_ctx* ctx,
+        int nkf, const pgorb_kf_pose* pose /*[nkf]*/, const uint8_t* kf_bad /*[nkf]*/, const int32_t* parent /*[nkf]*/,
+        const uint64_t* kf_id /*[nkf]*/, const float* tcp /*[nkf][12]*/, int n, const pgorb_trajectory_record* traj /*[n]*/,
+        double* quat_wxyz /*[n][4]*/, double* translation /*[n][3]*/, int64_t* time_usec, int64_t* frame_id /*[n]*/,
+        uint8_t* is_lost /*[n]*/, int32_t* status /*[n]*/, int32_t* info /*[PGORB_TRAJ_INFO]*/);
+int  pgorb_get_trajectory_device(pgorb_ctx* ctx,
+        int nkf, const pgorb_kf_pose* d_pose, const uint8_t* d_kf_bad, const int32_t* d_parent, const uint64_t* d_kf_id,
+        const float* d_tcp, int n, const pgorb_trajectory_record* d_traj, const int32_t* d_count /*[1] or NULL*/,
+        double* d_quat_wxyz, double* d_translation, int64_t* d_time_usec, int64_t* d_frame_id, uint8_t* d_is_lost,
+        int32_t* d_status, int32_t* d_info /*[PGORB_TRAJ_INFO]*/, void* hip_stream);
+
 /* ---- ORB vocabulary (DBoW2 TemplatedVocabulary<FORB::TDescriptor, FORB>) -----------------
  *   pgorb_vocab_load_text     ORBVocabulary(text_file) -> TemplatedVocabulary::loadFromTextFile
  *                             thirdparty/orb-slam2/src/ORBVocabulary.cc:7-9,

@@ -27,4 +27,7 @@ from .orb import (CULL_INFO, CULL_KF_CULLED, CULL_KF_ID0, CULL_KF_KEEP, CULL_KF_
                   CULL_MP_AGED, CULL_MP_FEW_OBS, CULL_MP_FOUND_RATIO, CULL_MP_KEEP, CULL_MP_NONE, CULL_MP_WAS_BAD, CULL_ROW_CLEARED,
                   CULL_ROW_ERASED, CULL_ROW_REPARENTED, compact_observations)
 from .orb import LC_BAD_INDEX, LC_INFO, LC_OVER_OBS, MU_INFO, LoopClosing  # noqa: F401
+from .orb import (TCP_INFO, TRACK_BAD_INDEX, TRACK_FULL, TRACK_MAX, TRACK_MOTION_MODEL, TRACK_NO_LAST, TRACK_NO_VELOCITY,  # noqa: F401
+                  TRACK_REFERENCE_KF, TRACK_STATE_DTYPE, TRAJ_BAD_TIME, TRAJ_BROKEN, TRAJ_INFO, TRAJ_MAX_RECORDS, TRAJ_NO_ORIGIN,
+                  TRAJECTORY_RECORD_DTYPE, System)
 from .place import KeyFrameDatabase  # noqa: F401

@@ -6,6 +6,8 @@ pilotguru_amd/libpgorb.so raises immediately -- there is no Python or CPU fallba
 import ctypes as C
 import os
 
+import numpy as np
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # PGORB_LIBRARY: a developer build of the same ABI (e.g. a timing build made with make EXTRA=...), for the scripts under tools/experiments
 LIB_PATH = os.environ.get("PGORB_LIBRARY") or os.path.join(_HERE, "libpgorb.so")
@@ -44,6 +46,8 @@ SYMBOLS = (
     "pgorb_compact_observations_device", "pgorb_map_point_culling", "pgorb_map_point_culling_device",
     "pgorb_keyframe_culling", "pgorb_keyframe_culling_device",
     "pgorb_correct_loop_poses", "pgorb_correct_loop_poses_device", "pgorb_global_ba_map_update", "pgorb_global_ba_map_update_device",
+    "pgorb_track_predict", "pgorb_track_predict_batch_device", "pgorb_track_commit", "pgorb_track_commit_batch_device",
+    "pgorb_keyframe_tcp", "pgorb_keyframe_tcp_device", "pgorb_get_trajectory", "pgorb_get_trajectory_device",
     "pgorb_bow_vectors_batch_device", "pgorb_bow_score_l1_batch_device",
     "pgorb_detect_relocalization_candidates", "pgorb_detect_relocalization_candidates_batch_device",
     "pgorb_detect_loop_candidates", "pgorb_detect_loop_candidates_batch_device",
@@ -70,6 +74,20 @@ SYMBOLS = (
     "pgorb_comm_library", "pgorb_comm_unique_id", "pgorb_comm_create_local", "pgorb_comm_create_rank", "pgorb_comm_ranks", "pgorb_vocab_broadcast", "pgorb_comm_destroy",
     "pgorb_kahan_sum", "pgorb_fit_num_windows", "pgorb_fit_velocity_windows", "pgorb_calibrator_eval", "pgorb_fit_motion_velocities",
 )
+
+
+# the records of the trajectory read-out (include/pgorb.h: pgorb_kf_pose, pgorb_track_state, pgorb_trajectory_record) and its constants
+KF_POSE_DTYPE = np.dtype([("Tcw", "<f4", (12,)), ("Ow", "<f4", (3,)), ("fx", "<f4"), ("fy", "<f4"), ("cx", "<f4"), ("cy", "<f4"),
+                          ("invfx", "<f4"), ("invfy", "<f4")])
+TRACK_STATE_DTYPE = np.dtype([("last", KF_POSE_DTYPE), ("velocity", "<f4", (12,)), ("last_ref_kf", "<i4"), ("has_last", "u1"),
+                              ("has_velocity", "u1"), ("pad", "u1", (2,))])
+TRAJECTORY_RECORD_DTYPE = np.dtype([("pose", "<f4", (12,)), ("ref_kf", "<i4"), ("has_pose", "u1"), ("lost", "u1"), ("pad", "u1", (2,)),
+                                    ("frame_time", "<f8"), ("frame_id", "<i8")])
+assert (KF_POSE_DTYPE.itemsize, TRACK_STATE_DTYPE.itemsize, TRAJECTORY_RECORD_DTYPE.itemsize) == (84, 140, 72)
+PGORB_TRACK_MOTION_MODEL, PGORB_TRACK_REFERENCE_KF = 0, 1
+PGORB_TRACK_NO_LAST, PGORB_TRACK_NO_VELOCITY, PGORB_TRACK_BAD_INDEX, PGORB_TRACK_FULL, PGORB_TRACK_MAX = 1, 2, 4, 8, 4096
+PGORB_TRAJ_BROKEN, PGORB_TRAJ_BAD_TIME, PGORB_TRAJ_NO_ORIGIN, PGORB_TRAJ_INFO, PGORB_TRAJ_MAX_RECORDS = 1, 2, 4, 4, 1 << 22
+PGORB_TCP_INFO = 4
 
 
 class PgorbParams(C.Structure):
@@ -338,6 +356,20 @@ def lib():
     #  kf_updated, point_updated, info[, stream])
     L.pgorb_global_ba_map_update.argtypes = [vp, C.c_int] + [vp] * 6 + [C.c_int] + [vp] * 9
     L.pgorb_global_ba_map_update_device.argtypes = [vp, C.c_int] + [vp] * 6 + [C.c_int] + [vp] * 10
+    # (ctx, mode, state, last_record, nkf, kf_pose, pose_out)
+    L.pgorb_track_predict.argtypes = [vp, C.c_int, vp, vp, C.c_int, vp, vp]
+    # (ctx, ntrack, mode, modes, state, traj, traj_cap, ntrajectory, nkf, kf_pose, pose_out, status, stream)
+    L.pgorb_track_predict_batch_device.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, C.c_int, vp, vp, vp, vp]
+    # (ctx, state, pose, ok, ref_kf, frame_time, frame_id, nkf, kf_pose, traj, traj_cap, ntrajectory)
+    L.pgorb_track_commit.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_double, C.c_int64, C.c_int, vp, vp, C.c_int, vp]
+    # (ctx, ntrack, state, pose, ok, ref_kf, frame_time, frame_id, nkf, kf_pose, traj, traj_cap, ntrajectory, status, stream)
+    L.pgorb_track_commit_batch_device.argtypes = [vp, C.c_int] + [vp] * 6 + [C.c_int, vp, vp, C.c_int, vp, vp, vp]
+    # (ctx, nkf, pose, parent, nrecord | list_cap, record, [cull_info,] tcp, info_out[, stream])
+    L.pgorb_keyframe_tcp.argtypes = [vp, C.c_int, vp, vp, C.c_int, vp, vp, vp]
+    L.pgorb_keyframe_tcp_device.argtypes = [vp, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp, vp]
+    # (ctx, nkf, pose, kf_bad, parent, kf_id, tcp, n, traj, [count,] quat_wxyz, translation, time_usec, frame_id, is_lost, status, info[, stream])
+    L.pgorb_get_trajectory.argtypes = [vp, C.c_int] + [vp] * 5 + [C.c_int] + [vp] * 8
+    L.pgorb_get_trajectory_device.argtypes = [vp, C.c_int] + [vp] * 5 + [C.c_int] + [vp] * 10
     # (ctx, word, weight, n, nframes, cap, bow_id, bow_val, nbow, stream)
     L.pgorb_bow_vectors_batch_device.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp]
     # (ctx, bow_id, bow_val, nbow, nframes, cap, pair_a, pair_b, npairs, score, stream)

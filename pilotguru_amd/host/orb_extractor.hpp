@@ -1246,6 +1246,35 @@ class Tracking {
         r.refKf = ref; r.status = status;
         return r;
     }
+    // The pose the first search of a frame starts from: UpdateLastFrame (Tracking.cc:792-798) from lastRecord = mlTrajectory.back()
+    // and the key-frame poses, then mVelocity * mLastFrame.mTcw (:866) in PGORB_TRACK_MOTION_MODEL; mLastFrame.mTcw (:764) in
+    // PGORB_TRACK_REFERENCE_KF.  `state` is updated; returns the PGORB_TRACK_* status (with one, poseOut is the state's last pose).
+    int PredictPose(pgorb_track_state& state, int mode, const std::vector<pgorb_kf_pose>& kfPoses, const pgorb_trajectory_record* lastRecord,
+                    pgorb_kf_pose& poseOut)
+    {
+        const char* fn = "Tracking::PredictPose";
+        auto fail = [&](const char* what) { throw std::invalid_argument(std::string(fn) + ": " + what); };
+        if (mode != PGORB_TRACK_MOTION_MODEL && mode != PGORB_TRACK_REFERENCE_KF) fail("an unknown mode");
+        if (kfPoses.size() > PGORB_COVIS_MAX_KF) fail("more than PGORB_COVIS_MAX_KF key frames");
+        const int rc = pgorb_track_predict(ctx_, mode, &state, lastRecord, (int)kfPoses.size(), kfPoses.data(), &poseOut);
+        if (rc < 0) throw std::runtime_error(pgorb_last_error(ctx_));
+        return rc;
+    }
+    // The end of Tracking::Track (:432-440, :493, :497-506): the motion model, the record appended at trajectory[count] (the vector's
+    // size is the capacity) and mLastFrame.  Returns the PGORB_TRACK_* status (PGORB_TRACK_FULL | PGORB_TRACK_BAD_INDEX: nothing changed).
+    int CommitFrame(pgorb_track_state& state, const pgorb_kf_pose& pose, bool ok, int refKf, double frameTime, int64_t frameId,
+                    const std::vector<pgorb_kf_pose>& kfPoses, std::vector<pgorb_trajectory_record>& trajectory, int32_t& count)
+    {
+        const char* fn = "Tracking::CommitFrame";
+        auto fail = [&](const char* what) { throw std::invalid_argument(std::string(fn) + ": " + what); };
+        if (kfPoses.size() > PGORB_COVIS_MAX_KF || trajectory.size() > (size_t)PGORB_TRAJ_MAX_RECORDS)
+            fail("more than PGORB_COVIS_MAX_KF key frames or PGORB_TRAJ_MAX_RECORDS records");
+        if (count < 0) fail("a negative count");
+        const int rc = pgorb_track_commit(ctx_, &state, &pose, ok ? 1 : 0, refKf, frameTime, frameId, (int)kfPoses.size(), kfPoses.data(), trajectory.data(),
+                                          (int)trajectory.size(), &count);
+        if (rc < 0) throw std::runtime_error(pgorb_last_error(ctx_));
+        return rc;
+    }
  private:
     pgorb_ctx* ctx_;
 };
@@ -1473,6 +1502,54 @@ class LoopClosing {
         return std::isfinite(P.Ow[0]) && std::isfinite(P.Ow[1]) && std::isfinite(P.Ow[2]);
     }
     static bool posFinite(const float* p) { return std::isfinite(p[0]) && std::isfinite(p[1]) && std::isfinite(p[2]); }
+    pgorb_ctx* ctx_;
+};
+
+// what System::GetTrajectory returns, in the layout pgorb_smooth_heading_directions / pgorb_trajectory_pca take
+struct TrajectoryResult {
+    std::vector<double> quatWxyz, translation;       // [n][4], [n][3]
+    std::vector<int64_t> timeUsec, frameId;
+    std::vector<uint8_t> isLost;
+    std::vector<int32_t> status;                     // PGORB_TRAJ_BROKEN per record
+    std::array<int32_t, PGORB_TRAJ_INFO> info{};     // status, origin key frame, broken records, records
+};
+
+class System {
+ public:
+    explicit System(pgorb_ctx* ctx) : ctx_(ctx) {}
+    // System::GetTrajectory (System.cc:371-412) over the key-frame table (poses, kfBad, parent, kfId = mnId, tcp [nkf][12] = mTcp rows
+    // 0-2, read where kfBad is set) and one tracker's records.
+    TrajectoryResult GetTrajectory(const std::vector<pgorb_kf_pose>& poses, const std::vector<uint8_t>& kfBad, const std::vector<int32_t>& parent,
+                                   const std::vector<uint64_t>& kfId, const std::vector<float>& tcp, const std::vector<pgorb_trajectory_record>& trajectory)
+    {
+        const char* fn = "System::GetTrajectory";
+        auto fail = [&](const char* what) { throw std::invalid_argument(std::string(fn) + ": " + what); };
+        const size_t nkf = parent.size(), n = trajectory.size();
+        if (nkf > PGORB_COVIS_MAX_KF || n > (size_t)PGORB_TRAJ_MAX_RECORDS) fail("more than PGORB_COVIS_MAX_KF key frames or PGORB_TRAJ_MAX_RECORDS records");
+        if (poses.size() != nkf || kfBad.size() != nkf || kfId.size() != nkf || tcp.size() != 12 * nkf) fail("poses, kfBad, kfId and tcp need one entry per key frame");
+        bool live = false;
+        for (size_t k = 0; k < nkf; k++) {
+            if (!kfBad[k]) live = true;
+            else if (parent[k] < 0 || parent[k] >= (int64_t)nkf) fail("a bad key frame has no parent or one out of range");
+        }
+        if (!live) fail("no live key frame");
+        for (const pgorb_trajectory_record& r : trajectory) {
+            const double us = r.frame_time * 1e6;
+            if (!std::isfinite(r.frame_time) || !(us >= -9223372036854775808.0 && us < 9223372036854775808.0))
+                fail("a frame time is not finite or outside int64 microseconds");
+            if (!r.lost && (r.ref_kf < 0 || r.ref_kf >= (int64_t)nkf)) fail("a record's reference key frame is out of range");
+        }
+        TrajectoryResult out;
+        out.quatWxyz.assign(4 * n + 4, 0.0); out.translation.assign(3 * n + 3, 0.0); out.timeUsec.assign(n + 1, 0); out.frameId.assign(n + 1, 0);
+        out.isLost.assign(n + 1, 0); out.status.assign(n + 1, 0);
+        const int rc = pgorb_get_trajectory(ctx_, (int)nkf, poses.data(), kfBad.data(), parent.data(), kfId.data(), tcp.data(), (int)n, trajectory.data(),
+                                            out.quatWxyz.data(), out.translation.data(), out.timeUsec.data(), out.frameId.data(), out.isLost.data(),
+                                            out.status.data(), out.info.data());
+        if (rc < 0) throw std::runtime_error(pgorb_last_error(ctx_));
+        out.quatWxyz.resize(4 * n); out.translation.resize(3 * n); out.timeUsec.resize(n); out.frameId.resize(n); out.isLost.resize(n); out.status.resize(n);
+        return out;
+    }
+ private:
     pgorb_ctx* ctx_;
 };
 

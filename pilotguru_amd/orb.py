@@ -741,8 +741,7 @@ class ORBmatcher:
 
 
 # pgorb_kf_pose: a key frame's GetPose() rows 0-2 ([R | t] row-major), GetCameraCenter() and camera (include/pgorb.h)
-KF_POSE_DTYPE = np.dtype([("Tcw", "<f4", (12,)), ("Ow", "<f4", (3,)), ("fx", "<f4"), ("fy", "<f4"), ("cx", "<f4"), ("cy", "<f4"),
-                          ("invfx", "<f4"), ("invfy", "<f4")])
+KF_POSE_DTYPE = _lib.KF_POSE_DTYPE
 # pgorb_new_map_point: one point of CreateNewMapPoints
 NEW_MAP_POINT_DTYPE = np.dtype([("neighbour", "<i4"), ("idx1", "<i4"), ("idx2", "<i4"), ("pos", "<f4", (3,)), ("normal", "<f4", (3,)),
                                 ("min_distance", "<f4"), ("max_distance", "<f4")])
@@ -2124,6 +2123,30 @@ class LocalMapping:
         return dict(kf_point=slots, point_bad=pb[:n], obs_live=live[:int(st[-1])], ref_obs=ro[:n], kf_bad=kb[:nkf], kf_to_be_erased=tbe[:nkf],
                     record=record[:nl].copy(), row_status=status[:nkf].copy(), info=info)
 
+    @staticmethod
+    def KeyFrameTcp(ext, poses, parent, record, tcp=None):
+        """KeyFrame::SetBadFlag's mTcp = Tcw * mpParent->GetPoseInverse() (src/KeyFrame.cc:641) for every row of `record`
+        (KeyFrameCulling's, [m][4]) whose action is CULL_KF_CULLED; poses / parent as they stand right after that culling, before any
+        call that moves a pose.  tcp [nkf][12] = the rows so far (None = zeros); a copy is updated.  Returns a dict: tcp, info
+        [TCP_INFO] = (0, written, skipped), written.  Raises ValueError for everything pgorb_keyframe_tcp refuses."""
+        fn = "LocalMapping.KeyFrameTcp"
+        par = np.ascontiguousarray(parent, np.int32).reshape(-1)
+        nkf = len(par)
+        rec = np.ascontiguousarray(record, np.int32).reshape(-1, 4)
+        if nkf > COVIS_MAX_KF or len(rec) > COVIS_MAX_KF:
+            raise ValueError(fn + ": more than COVIS_MAX_KF key frames or records")
+        P = np.ascontiguousarray(poses, KF_POSE_DTYPE).reshape(-1)
+        if len(P) != nkf:
+            raise ValueError(fn + ": one pose per key frame")
+        out = np.zeros((max(nkf, 1), 12), np.float32)
+        if tcp is not None:
+            out[:nkf] = _arr(tcp, np.float32, nkf, "tcp", 12)
+        info = np.zeros(TCP_INFO, np.int32)
+        pad = lambda x, dt: x if len(x) else np.zeros(1, dt)
+        ret = ext._check(ext._L.pgorb_keyframe_tcp(ext._h, nkf, _p(pad(P, KF_POSE_DTYPE)), _p(pad(par, np.int32)), len(rec),
+                                                   _p(rec if len(rec) else np.zeros((1, 4), np.int32)), _p(out), _p(info)))
+        return dict(tcp=out[:nkf].copy(), info=info, written=int(ret))
+
 
 # the cullings (include/pgorb.h): MapPointCulling's and KeyFrameCulling's action codes, the row status bits
 CULL_MP_KEEP, CULL_MP_WAS_BAD, CULL_MP_FOUND_RATIO, CULL_MP_FEW_OBS, CULL_MP_AGED, CULL_MP_NONE = 0, 1, 2, 3, 4, 5
@@ -2349,6 +2372,114 @@ class Tracking:
             _p(outs[1]), int(qcap), _p(q), _p(outs[2]), _p(outs[3])))
         return dict(kp_point=kpo[:len(kp)].copy(), local_kf=lk[:int(outs[0][0])].copy(), ref_kf=int(outs[1][0]), queries=q[:int(outs[2][0])].copy(),
                     status=int(outs[3][0]))
+
+    @staticmethod
+    def _kf_poses(fn, kf_poses):
+        P = np.ascontiguousarray(kf_poses, KF_POSE_DTYPE).reshape(-1)
+        if len(P) > COVIS_MAX_KF:
+            raise ValueError(fn + ": more than COVIS_MAX_KF key frames")
+        return P, (P if len(P) else np.zeros(1, KF_POSE_DTYPE))
+
+    @staticmethod
+    def PredictPose(ext, state, mode, kf_poses, last_record=None):
+        """The pose the first search of a frame starts from (Tracking.cc:792-798 + :866, or :764).  state = a TRACK_STATE_DTYPE
+        record, mode = TRACK_MOTION_MODEL (UpdateLastFrame from last_record = mlTrajectory.back() and the key-frame poses, then
+        mVelocity * mLastFrame.mTcw) or TRACK_REFERENCE_KF (mLastFrame.mTcw).  Nothing passed in is changed.  Returns a dict: pose
+        (a complete KF_POSE_DTYPE record), state (afterwards), status (TRACK_NO_LAST | TRACK_NO_VELOCITY | TRACK_BAD_INDEX; with
+        one the pose is the state's last pose and the state is unchanged).  Raises ValueError for what pgorb_track_predict refuses."""
+        fn = "Tracking.PredictPose"
+        if int(mode) not in (TRACK_MOTION_MODEL, TRACK_REFERENCE_KF):
+            raise ValueError(fn + ": an unknown mode")
+        P, Pp = Tracking._kf_poses(fn, kf_poses)
+        st = np.array(np.ascontiguousarray(state, TRACK_STATE_DTYPE).reshape(()))
+        rec = None if last_record is None else np.ascontiguousarray(last_record, TRAJECTORY_RECORD_DTYPE).reshape(())
+        out = np.zeros((), KF_POSE_DTYPE)
+        status = ext._check(ext._L.pgorb_track_predict(ext._h, int(mode), _p(st), None if rec is None else _p(rec), len(P), _p(Pp), _p(out)))
+        return dict(pose=out, state=st, status=int(status))
+
+    @staticmethod
+    def CommitFrame(ext, state, pose, ok, ref_kf, frame_time, frame_id, kf_poses, trajectory, ntrajectory):
+        """The end of Tracking::Track (Tracking.cc:432-440, :493, :497-506): the motion model, the trajectory record appended at
+        trajectory[ntrajectory] (a TRAJECTORY_RECORD_DTYPE array, its length is the capacity) and mLastFrame.  Nothing passed in is
+        changed.  Returns a dict: state, trajectory, ntrajectory (afterwards), status (TRACK_FULL | TRACK_BAD_INDEX: nothing
+        changed).  Raises ValueError for what pgorb_track_commit refuses."""
+        fn = "Tracking.CommitFrame"
+        P, Pp = Tracking._kf_poses(fn, kf_poses)
+        traj = np.array(np.ascontiguousarray(trajectory, TRAJECTORY_RECORD_DTYPE).reshape(-1))
+        if len(traj) > TRAJ_MAX_RECORDS or int(ntrajectory) < 0:
+            raise ValueError(fn + ": more than TRAJ_MAX_RECORDS records, or a negative count")
+        st = np.array(np.ascontiguousarray(state, TRACK_STATE_DTYPE).reshape(()))
+        po = np.ascontiguousarray(pose, KF_POSE_DTYPE).reshape(())
+        cnt = np.array([int(ntrajectory)], np.int32)
+        status = ext._check(ext._L.pgorb_track_commit(
+            ext._h, _p(st), _p(po), int(bool(ok)), int(ref_kf), float(frame_time), int(frame_id), len(P), _p(Pp),
+            _p(traj if len(traj) else np.zeros(1, TRAJECTORY_RECORD_DTYPE)), len(traj), _p(cnt)))
+        return dict(state=st, trajectory=traj, ntrajectory=int(cnt[0]), status=int(status))
+
+
+# the trajectory read-out (include/pgorb.h): the records, the modes, the status bits and the limits
+TRACK_STATE_DTYPE, TRAJECTORY_RECORD_DTYPE = _lib.TRACK_STATE_DTYPE, _lib.TRAJECTORY_RECORD_DTYPE
+TRACK_MOTION_MODEL, TRACK_REFERENCE_KF = 0, 1
+TRACK_NO_LAST, TRACK_NO_VELOCITY, TRACK_BAD_INDEX, TRACK_FULL, TRACK_MAX = 1, 2, 4, 8, 4096
+TRAJ_BROKEN, TRAJ_BAD_TIME, TRAJ_NO_ORIGIN, TRAJ_INFO, TRAJ_MAX_RECORDS = 1, 2, 4, 4, 1 << 22
+TCP_INFO = 4
+
+
+class System:
+    """System::GetTrajectory (thirdparty/orb-slam2/src/System.cc:371-412) on the GPU, and the text form of its result that
+    optical_trajectories --poses_in reads."""
+
+    @staticmethod
+    def GetTrajectory(ext, poses, kf_bad, parent, kf_id, tcp, trajectory):
+        """poses / kf_bad / parent / kf_id (mnId) / tcp [nkf][12] (mTcp, read where kf_bad is set; None = zeros) = the key-frame
+        table, trajectory = the TRAJECTORY_RECORD_DTYPE records of one tracker.  Returns a dict of the arrays
+        pgorb_smooth_heading_directions / pgorb_trajectory_pca take as they are: quat_wxyz [n][4], translation [n][3] (float64),
+        time_usec, frame_id (int64), is_lost (uint8), status (TRAJ_BROKEN per record), info [TRAJ_INFO], origin (key frame).
+        Raises ValueError for everything pgorb_get_trajectory refuses."""
+        fn = "System.GetTrajectory"
+        par = np.ascontiguousarray(parent, np.int32).reshape(-1)
+        nkf = len(par)
+        traj = np.ascontiguousarray(trajectory, TRAJECTORY_RECORD_DTYPE).reshape(-1)
+        n = len(traj)
+        if nkf > COVIS_MAX_KF or n > TRAJ_MAX_RECORDS:
+            raise ValueError(fn + ": more than COVIS_MAX_KF key frames or TRAJ_MAX_RECORDS records")
+        P = np.ascontiguousarray(poses, KF_POSE_DTYPE).reshape(-1)
+        if len(P) != nkf:
+            raise ValueError(fn + ": one pose per key frame")
+        kb, ids = _arr(kf_bad, np.uint8, nkf, "kf_bad"), _arr(kf_id, np.uint64, nkf, "kf_id")
+        tc = np.zeros((nkf, 12), np.float32) if tcp is None else _arr(tcp, np.float32, nkf, "tcp", 12)
+        bad = kb != 0
+        if not nkf or bad.all():
+            raise ValueError(fn + ": no live key frame")
+        if np.any((par[bad] < 0) | (par[bad] >= nkf)):
+            raise ValueError(fn + ": a bad key frame has no parent or one out of range")
+        t = traj["frame_time"]
+        with np.errstate(over="ignore", invalid="ignore"):
+            us = t * 1e6
+        if not (np.isfinite(t).all() and np.all((us >= -2.0 ** 63) & (us < 2.0 ** 63))):
+            raise ValueError(fn + ": a frame time is not finite or outside int64 microseconds")
+        live = traj["lost"] == 0
+        if np.any((traj["ref_kf"][live] < 0) | (traj["ref_kf"][live] >= nkf)):
+            raise ValueError(fn + ": a record's reference key frame is out of range")
+        n1 = max(n, 1)
+        q, tr = np.zeros((n1, 4), np.float64), np.zeros((n1, 3), np.float64)
+        tu, fi, lost, status, info = np.zeros(n1, np.int64), np.zeros(n1, np.int64), np.zeros(n1, np.uint8), np.zeros(n1, np.int32), \
+            np.zeros(TRAJ_INFO, np.int32)
+        ext._check(ext._L.pgorb_get_trajectory(ext._h, nkf, _p(P), _p(kb), _p(par), _p(ids), _p(tc), n,
+                                               _p(traj if n else np.zeros(1, TRAJECTORY_RECORD_DTYPE)), _p(q), _p(tr), _p(tu), _p(fi), _p(lost),
+                                               _p(status), _p(info)))
+        return dict(quat_wxyz=q[:n], translation=tr[:n], time_usec=tu[:n], frame_id=fi[:n], is_lost=lost[:n], status=status[:n], info=info,
+                    origin=int(info[1]))
+
+    @staticmethod
+    def write_poses(path, traj):
+        """One `time_usec is_lost frame_id tx ty tz qw qx qy qz` line per record of a GetTrajectory result, the doubles with %.17g
+        so that they round-trip: what optical_trajectories --poses_in=path reads."""
+        with open(path, "w") as f:
+            for i in range(len(traj["time_usec"])):
+                v = list(traj["translation"][i]) + list(traj["quat_wxyz"][i])
+                f.write("%d %d %d %s\n" % (int(traj["time_usec"][i]), int(traj["is_lost"][i]), int(traj["frame_id"][i]),
+                                           " ".join("%.17g" % float(x) for x in v)))
 
 
 # loop correction (include/pgorb.h): the status bits and the info lengths

@@ -99,8 +99,11 @@ next to each, the oracle's CPU time for the same work (1 thread, a few frames, s
                GlobalBundleAdjustment (:679-742) of the same map with the last 50 key frames made while the adjustment ran.  The parent commit
                has no such path and ORB-SLAM2 cannot be built here, so there is nothing measured to compare against: no target is set, the rows
                record what was measured.  --loop-correct-only runs these rows alone (profiles/next_tier_loop_correct.txt).
+  trajectory   the trajectory read-out on the device (csrc/track_pose.hip), HIP events: predict + commit over 8 and 128 trackers next to
+               the same hand-off through the host (download, numpy products, upload), and GetTrajectory of 108 000 records over 2 000 key
+               frames with 30 % of them culled.  No target is set.  --trajectory-only runs these rows alone (profiles/next_tier_trajectory.txt).
 
-usage: python tools/next_tier_bench.py [--batch 128] [--out profiles/r02_next_tier.txt] [--refresh-only | --place-only | --loop-only | --track-only | --pose-only | --sim3-only | --pnp-only | --optsim3-only | --lba-only | --eg-only | --gba-only | --covis-only | --cull-only | --loop-correct-only]"""
+usage: python tools/next_tier_bench.py [--batch 128] [--out profiles/r02_next_tier.txt] [--refresh-only | --place-only | --loop-only | --track-only | --pose-only | --sim3-only | --pnp-only | --optsim3-only | --lba-only | --eg-only | --gba-only | --covis-only | --cull-only | --loop-correct-only | --trajectory-only]"""
 import argparse, ctypes as C, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -130,6 +133,8 @@ ap.add_argument("--covis-only", action="store_true", help="the covisibility-grap
 ap.add_argument("--cull-only", action="store_true", help="the culling rows alone (no ride, no vocabulary)")
 ap.add_argument("--loop-correct-only", action="store_true", help="the loop-correction rows alone (no ride, no vocabulary); writes "
                 "profiles/next_tier_loop_correct.txt unless --out names another file")
+ap.add_argument("--trajectory-only", action="store_true", help="the trajectory read-out rows alone (no ride, no vocabulary); writes "
+                "profiles/next_tier_trajectory.txt unless --out names another file")
 a = ap.parse_args()
 w, h, nf, B = 1920, 1080, a.features, a.batch
 
@@ -958,6 +963,106 @@ def loop_correct_lines(nkf=200, cap=2000, nlist=30, fresh=50):
                                       "updated (k_mu_kf, k_mu_points)" % (fresh, mi[1], mi[2], mi[3]), t_mu, t_refm)]
 
 
+def trajectory_lines():
+    """The trajectory read-out: predict + commit over 8 and 128 trackers, the same hand-off done on the host, and GetTrajectory of an
+    hour's records; the results are held against the numpy reference of the tests."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import track_pose_cases as K
+    import track_pose_reference as TR
+    ext = pg.ORBextractor(2000, 1.2, 8, 20, 7, max_width=640, max_height=480)
+    L, h, q = ext._L, ext._h, K._q
+    s = torch.cuda.current_stream()
+    sp = C.c_void_p(s.cuda_stream)
+
+    def events(run, reps=9, inner=50):
+        # the calls take tens of microseconds: an event pair spans `inner` back-to-back calls and the row reports the time per call
+        ms = []
+        for r in range(reps + 1):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(inner):
+                run()
+            e1.record(); torch.cuda.synchronize()
+            ms.append(e0.elapsed_time(e1) / inner)
+        return float(np.median(ms[1:]))
+    ref = K.run_sequences_reference()
+    state, frames = K.track_sequences()
+    fr, x, cap = frames[3], frames[3]["trackers"], 4096
+    rows = []
+    for ntrack in (8, 128):
+        rep = ntrack // 2
+        S0 = K._up(ref[2]["state"]).repeat(rep)
+        T = torch.zeros(ntrack * cap * 72, dtype=torch.uint8, device="cuda")
+        T.view(ntrack, cap * 72)[:, :K.CAP * 72] = K._up(ref[2]["traj"]).view(2, K.CAP * 72).repeat(rep, 1)
+        N0 = K._up(ref[2]["count"]).repeat(rep)
+        S, N = S0.clone(), N0.clone()
+        kf, modes = K._up(fr["kf"]), K._up(np.array([v["mode"] for v in x], np.int32)).repeat(rep)
+        pred, ps, cs = K._sent(ntrack * 84), K._sent(ntrack * 4), K._sent(ntrack * 4)
+        ok, rk = K._up(np.array([v["ok"] for v in x], np.uint8)).repeat(rep), K._up(np.array([v["ref_kf"] for v in x], np.int32)).repeat(rep)
+        tm, ids = K._up(np.array([v["time"] for v in x], np.float64)).repeat(rep), K._up(np.array([v["id"] for v in x], np.int64)).repeat(rep)
+
+        def device():
+            S.copy_(S0); N.copy_(N0)
+            assert L.pgorb_track_predict_batch_device(h, ntrack, 0, q(modes), q(S), q(T), cap, q(N), 4, q(kf), q(pred), q(ps), sp) == 0
+            # the predicted pose stands in for PoseOptimization's result: commit reads it where predict left it
+            assert L.pgorb_track_commit_batch_device(h, ntrack, q(S), q(pred), q(ok), q(rk), q(tm), q(ids), 4, q(kf), q(T), cap, q(N), q(cs), sp) == 0
+        t_dev = events(device)
+        assert torch.equal(pred, K._up(ref[3]["pred"]).repeat(rep)) and int(N.view(torch.int32).min()) == int(N.view(torch.int32).max()) == 4, "predict / commit differ from the reference"
+
+        kf_h = fr["kf"]
+
+        def host():
+            # the old way: download the last pose and record, form the products in numpy, upload the prediction; after the
+            # optimisation download its pose, form velocity and record on the host, upload
+            st = np.frombuffer(S0.cpu().numpy().tobytes(), K.TRACK_STATE_DTYPE).copy()
+            rec = np.frombuffer(T.view(ntrack, cap * 72)[:, 2 * 72:3 * 72].contiguous().cpu().numpy().tobytes(), K.TRAJECTORY_RECORD_DTYPE)
+            out = np.zeros(ntrack, K.KF_POSE_DTYPE)
+            for t in range(ntrack):
+                trk = TR.Tracker(st[t], [rec[t]])
+                out[t], _ = TR.predict(trk, int(x[t % 2]["mode"]), kf_h)
+                st[t] = trk.state()
+            d = K._up(out)
+            back = np.frombuffer(d.cpu().numpy().tobytes(), K.KF_POSE_DTYPE)
+            for t in range(ntrack):
+                trk = TR.Tracker(st[t], [rec[t]])
+                TR.commit(trk, back[t], x[t % 2]["ok"], x[t % 2]["ref_kf"], x[t % 2]["time"], x[t % 2]["id"], kf_h, cap)
+                st[t] = trk.state()
+            K._up(st)
+        t0 = time.perf_counter()
+        host()
+        t_host = (time.perf_counter() - t0) * 1e3
+        rows.append("%-150s %10.4f %12.2f" % ("track_predict + track_commit, %d trackers, resident (k_tp_predict, k_tp_commit) | the same hand-off through the "
+                                              "host: 2 downloads, numpy products, 2 uploads" % ntrack, t_dev, t_host))
+    w = K.random_world(1, 108000, 2000, culled=0.3, exact=True)
+    t0 = time.perf_counter()
+    want = TR.get_trajectory_batched(w)
+    t_ref = (time.perf_counter() - t0) * 1e3
+    D, n = K.table_device_arrays(w), len(w["traj"])
+    traj = K._up(w["traj"])
+    O = dict(quat_wxyz=K._sent(n * 32), translation=K._sent(n * 24), time_usec=K._sent(n * 8), frame_id=K._sent(n * 8), is_lost=K._sent(n), status=K._sent(n * 4),
+             info=K._sent(16))
+
+    def read_out():
+        assert L.pgorb_get_trajectory_device(h, 2000, q(D["pose"]), q(D["bad"]), q(D["par"]), q(D["ids"]), q(D["tcp"]), n, q(traj), None, q(O["quat_wxyz"]),
+                                             q(O["translation"]), q(O["time_usec"]), q(O["frame_id"]), q(O["is_lost"]), q(O["status"]), q(O["info"]), sp) == 0
+    t_traj = events(read_out)
+    assert K.same(K.download_trajectory(O, n), want), "the device's trajectory differs from the reference's"
+    depth = max(TR.chain_depth(w, i) for i in range(0, n, 97))
+    rows.append("%-150s %10.4f %12.2f" % ("get_trajectory: %d records over 2000 key frames, %d culled, chains up to %d deep in a sample; %d lost (k_traj_origin, "
+                                          "k_traj_records) | the batched numpy reference" % (n, int(w["kf_bad"].sum()), depth, int(want["is_lost"].sum())), t_traj, t_ref))
+    return ["# The trajectory read-out on the device (csrc/track_pose.hip), resident calls, HIP events around 50 back-to-back calls, time per call, median of 9",
+            "# after one warm-up (predict + commit: the two launches and the reset of the state and the count in front of them).",
+            "# The second column is the same work on the host in numpy on one core (the restatement of the tests, whose bytes the GPU's must equal), wall",
+            "# clock, one run, transfers included where the row says so; it is NOT ORB-SLAM2 and not a tuned baseline.  The parent commit has no such path, so",
+            "# there is nothing measured to compare against: no target is set and no time is a pass condition.",
+            "%-150s %10s %12s" % ("call", "GPU ms", "host ms")] + rows
+
+
+if a.trajectory_only:
+    lines = ["# python tools/next_tier_bench.py --trajectory-only   (MI355X)"] + trajectory_lines()
+    print("\n".join(lines))
+    open(a.out or os.path.join(ROOT, "profiles", "next_tier_trajectory.txt"), "w").write("\n".join(lines) + "\n")
+    sys.exit(0)
 if a.loop_correct_only:
     lines = ["# python tools/next_tier_bench.py --loop-correct-only   (MI355X)"] + loop_correct_lines()
     print("\n".join(lines))

@@ -1612,6 +1612,153 @@ int  pgorb_keyframe_culling_device(pgorb_ctx* ctx,
         int conn_cap, int32_t* d_conn_kf, int32_t* d_conn_w, int32_t* d_nconn, int32_t* d_ord_kf, int32_t* d_ord_w, int32_t* d_nord,
         int32_t* d_parent, int list_cap, int32_t* d_record, int32_t* d_row_status, int32_t* d_info, void* hip_stream);
 
+/* ---- Map edits: MapPoint::AddObservation, Replace and EraseObservation with their KeyFrame slot writes (csrc/map_edit.hip) ------
+ * The writer the resident table lacked: the cullings can shrink the observation lists, this block grows and merges them, from an
+ * ORDERED edit list on the device.  The conventions of the covisibility and culling blocks hold: key frames are the nframes frames
+ * of one resident batch with their slots d_kf_point [nframes][cap_per_frame] + d_n, d_kf_order [nframes] = the rank of each key
+ * frame's address (NULL = index order), the lists are the CSR d_obs_start / d_obs_frame / d_obs_idx masked by d_obs_live, IN THE
+ * ORDER std::map<KeyFrame*, size_t> ITERATES, with d_ref_obs = the position of mpRefKF in the unmasked list.
+ *
+ *   pgorb_apply_map_edits_device   applies d_edits [0 .. nedits) -- d_nedits [1], when not NULL, bounds the list from the device --
+ *       WITH THE RESULT OF APPLYING THEM ONE AFTER ANOTHER IN LIST ORDER.  In/out: d_kf_point, d_point_bad, d_visible and d_found
+ *       (int32, NULL = not carried: read as 0), d_replaced [npoints] (mpReplaced, -1 = none; NULL = not carried).  Read: the CSR
+ *       with nobs as the bound, d_obs_live (NULL = all live; a dead entry, or one that names nothing of the batch, does not exist)
+ *       and d_ref_obs (one that names a dead entry names no key frame).  Written: a FRESH CSR d_obs_start_out [npoints + 1] /
+ *       d_obs_frame_out / d_obs_idx_out with room for obs_cap_out entries and d_ref_obs_out [npoints]; they must not alias the
+ *       inputs (PGORB_E_ARG for the same pointer).  The call is therefore also the compaction: a culling followed by an edit needs
+ *       no pgorb_compact_observations_device.  The lists of points that an edit names come out sorted by address rank; the others
+ *       keep their input order, which the convention above makes the same.
+ *         PGORB_EDIT_NOP       padding: producers write fixed positions, nothing is compacted
+ *         PGORB_EDIT_ADD       a = point, b = key frame, c = keypoint.  AddObservation (src/MapPoint.cc:119-130): the list is left
+ *             alone if it holds b (PGORB_EDIT_ALREADY), else (b, c) joins it; then KeyFrame::AddMapPoint (src/KeyFrame.cc:313-317)
+ *             kf_point[b][c] = a, whatever the list did.  No bad test.
+ *         PGORB_EDIT_REPLACE   a = loser, b = survivor: a->Replace(b) (:196-232).  a == b: nothing (PGORB_EDIT_SELF).  Else the
+ *             loser's list is taken and cleared, the loser goes bad, replaced[a] = b; for each (kf, idx) of it: the survivor does
+ *             not hold kf (tested BY ITS LIST, IsInKeyFrame, not by the slot) -> kf_point[kf][idx] = b and (kf, idx) joins the
+ *             survivor, else kf_point[kf][idx] = -1; then found[b] += found[a], visible[b] += visible[a].  No bad test on either
+ *             side: a loser that is already bad has an empty list and hands its counters over again, as the reference does.  The
+ *             ComputeDistinctiveDescriptors at :231 is NOT run; the survivor is reported in d_touched.
+ *         PGORB_EDIT_ERASE     a = point, b = key frame.  KeyFrame::EraseMapPointMatch(MapPoint*) (src/KeyFrame.cc:326-331: the index
+ *             comes from the POINT's list) and EraseObservation (:132-158): if the list holds (b, idx): kf_point[b][idx] = -1, the
+ *             entry leaves; mpRefKF == b becomes the first entry of what is left -- the reference dereferences begin() of an empty
+ *             map there, HERE THE REFERENCE KEY FRAME BECOMES NONE; with two or fewer entries left SetBadFlag (:172-187) runs: bad,
+ *             the slot of every remaining entry = -1 whatever it holds, the list cleared, mpRefKF kept (PGORB_EDIT_WENT_BAD).  A
+ *             point that does not list b is untouched (PGORB_EDIT_NOT_OBSERVED), so later erasures of a point that went bad do nothing.
+ *         PGORB_EDIT_SET_REF   a = point, b = key frame: mpRefKF = b (the MapPoint constructor, :47).
+ *       The reference key frame is tracked BY KEY FRAME: d_ref_obs_out[p] = its position in the new list, -1 when that list does
+ *       not hold it (always for an empty list).  A point or key frame out of range, a keypoint outside [0, d_n[kf]) or an unknown
+ *       op makes the edit a no-op with PGORB_EDIT_BAD_INDEX; nothing is read or written out of bounds.
+ *       d_edit_status [nedits]: PGORB_EDIT_APPLIED (carried out: ADD also when ALREADY) | ALREADY | SELF | NOT_OBSERVED | WENT_BAD |
+ *       BAD_INDEX; 0 for NOP and past d_nedits.  d_touched [npoints]: PGORB_EDIT_TOUCH_CHANGED (the list changed), TOUCH_SURVIVOR
+ *       (survivor of a REPLACE: a descriptor is due), TOUCH_STALE (an ADD or ERASE changed the list after the point's last REPLACE
+ *       as survivor: the reference's descriptor would be older than its list; counted, not hidden).  d_select_out [sel_cap] (sel_cap
+ *       0 = none): the points with d_touched & select_bits, ascending, padded with -1 -- pgorb_refresh_map_points_batch_device
+ *       takes -1 as a no-op, so nsel = sel_cap chains without a download.  d_info [PGORB_EDIT_INFO] = (0, the new list length,
+ *       edits with APPLIED, points whose bad flag rose, components, slot writes the reference makes, points with TOUCH_STALE, points
+ *       selected).  PGORB_EDIT_LIMIT in d_info[0] AND NOTHING ELSE WRITTEN, no in/out byte either: the new lists exceed
+ *       obs_cap_out, the selection exceeds sel_cap, a component's live input entries plus its ADD edits exceed
+ *       PGORB_EDIT_MAX_BAG, or more than PGORB_EDIT_MAX_EDITS edits are carried out.  The plan finishes in scratch before the first in/out byte changes.
+ *       How: no edit reads a slot, so the points linked by REPLACE edits form components that share no state and run independently
+ *       (k_edit_components, k_edit_bucket: one workgroup each); k_edit_plan, a wave per component, walks its edits in order over
+ *       one bag of (point, key frame, keypoint) in LDS (2 x 24 KiB of the CU's 160 KiB: three waves per CU); a slot takes the value
+ *       of the LAST EDIT IN LIST ORDER that writes it, within a component in the bag, across components by an atomicMax of the edit
+ *       index whose result no order of execution changes (k_edit_mark, k_edit_commit).  Integers only.  Does not synchronise the stream.
+ *   pgorb_apply_map_edits   the same from host buffers (kf_point[f] [n[f]]), checked: returns the number of edits applied (0 with
+ *       PGORB_EDIT_LIMIT), or PGORB_E_ARG for a negative count, a NULL array that is read or written, obs_start not rising from 0, a
+ *       live observation out of range, a key frame twice in one list, kf_order not a permutation, ref_obs outside its list, an
+ *       output overlapping an input, an unknown op; PGORB_E_LIMIT for more than PGORB_EDIT_MAX_EDITS edits that are not NOP.  Byte for byte the device form; output bytes it does not write keep their values.
+ *
+ * Limits.  PGORB_EDIT_MAX_EDITS bounds the edits that are CARRIED OUT (not NOP, indices in range: the bucket sorts them in LDS), not
+ * the length of the list: producers write fixed positions, so a list is as long as its producer's array (cap_per_frame, 2 * qcap,
+ * nobs) and mostly NOP.  The device form cannot know the count before it runs: more than PGORB_EDIT_MAX_EDITS such edits give
+ * PGORB_EDIT_LIMIT in d_info[0] and nothing else written, like the other capacities; the host form counts the edits that are not NOP
+ * and returns PGORB_E_LIMIT.  PGORB_E_LIMIT also for nedits > PGORB_EDIT_MAX_LIST, nframes > PGORB_COVIS_MAX_KF, cap_per_frame > 16000,
+ * npoints > 2^30.  THE SLOTS MUST HOLD -1 OR VALUES BELOW 2^30: k_edit_mark keeps its marks (2^30 | edit index) in the slots themselves
+ * between two launches, and a slot that already holds a larger value keeps it.  Cost that does not depend on the edits: k_edit_init
+ * and k_edit_commit are a thread per point, and k_edit_scan is ONE workgroup of 256 threads that walks all npoints (the lengths, the
+ * selection, the counts); with npoints = point_cap of 10^5 that is some 400 points a thread on every call, however short the list.  It
+ * has not been measured against a multi-block scan.  Scratch arena: 64 + 40 * npoints + 4 * (nedits + 1) + 8 * (m + 1) + 20 * (nobs + m)
+ * bytes with m = min(nedits, PGORB_EDIT_MAX_EDITS), each array rounded up to 64.  Determinism: a result depends on its inputs alone --
+ * not on the stream, a repeat, or NOP padding in the list. */
+typedef struct pgorb_map_edit { int32_t op, a, b, c; } pgorb_map_edit;
+#define PGORB_EDIT_NOP            0
+#define PGORB_EDIT_ADD            1
+#define PGORB_EDIT_REPLACE        2
+#define PGORB_EDIT_ERASE          3
+#define PGORB_EDIT_SET_REF        4
+#define PGORB_EDIT_APPLIED        1
+#define PGORB_EDIT_ALREADY        2
+#define PGORB_EDIT_SELF           4
+#define PGORB_EDIT_NOT_OBSERVED   8
+#define PGORB_EDIT_WENT_BAD       16
+#define PGORB_EDIT_BAD_INDEX      32
+#define PGORB_EDIT_LIMIT          64
+#define PGORB_EDIT_TOUCH_CHANGED  1
+#define PGORB_EDIT_TOUCH_SURVIVOR 2
+#define PGORB_EDIT_TOUCH_STALE    4
+#define PGORB_EDIT_INFO           8
+#define PGORB_EDIT_MAX_BAG        2048
+#define PGORB_EDIT_MAX_EDITS      4096
+#define PGORB_EDIT_MAX_LIST       4194304
+int  pgorb_apply_map_edits(pgorb_ctx* ctx,
+        const pgorb_map_edit* edits, int nedits, int nkf, int32_t* const* kf_point, const int32_t* n /*[nkf]*/,
+        const int32_t* kf_order /*[nkf] or NULL*/, int npoints, uint8_t* point_bad, int32_t* visible, int32_t* found, int32_t* replaced,
+        const int32_t* obs_start /*[npoints + 1]*/, const int32_t* obs_frame, const int32_t* obs_idx, const uint8_t* obs_live /*or NULL*/,
+        const int32_t* ref_obs /*[npoints]*/, int obs_cap_out, int32_t* obs_start_out, int32_t* obs_frame_out, int32_t* obs_idx_out,
+        int32_t* ref_obs_out, int32_t* edit_status /*[nedits]*/, int32_t* touched /*[npoints]*/, int select_bits, int sel_cap,
+        int32_t* select_out /*[sel_cap]*/, int32_t* info /*[PGORB_EDIT_INFO]*/);
+int  pgorb_apply_map_edits_device(pgorb_ctx* ctx,
+        const pgorb_map_edit* d_edits, int nedits, const int32_t* d_nedits /*[1] or NULL*/, int32_t* d_kf_point, const int32_t* d_n,
+        int nframes, int cap_per_frame, const int32_t* d_kf_order, int npoints, uint8_t* d_point_bad, int32_t* d_visible, int32_t* d_found,
+        int32_t* d_replaced, const int32_t* d_obs_start, const int32_t* d_obs_frame, const int32_t* d_obs_idx, int nobs,
+        const uint8_t* d_obs_live, const int32_t* d_ref_obs, int obs_cap_out, int32_t* d_obs_start_out, int32_t* d_obs_frame_out,
+        int32_t* d_obs_idx_out, int32_t* d_ref_obs_out, int32_t* d_edit_status, int32_t* d_touched, int select_bits, int sel_cap,
+        int32_t* d_select_out, int32_t* d_info /*[PGORB_EDIT_INFO]*/, void* hip_stream);
+/* The producers: each turns one step's device output into edits AT FIXED POSITIONS, PGORB_EDIT_NOP where nothing happens, so the
+ * list order is the reference's loop order and nothing is downloaded between the step and pgorb_apply_map_edits_device.  They do
+ * not check their inputs beyond NULL and the counts: an index out of range becomes a NOP or an edit that the executor refuses with
+ * PGORB_EDIT_BAD_INDEX.  Asynchronous on hip_stream, no scratch.  The tail of CreateNewMapPoints (src/LocalMapping.cc:436-449) has no
+ * producer: appending its rows to the table and writing SET_REF(new, kf1), ADD(new, kf1, idx1), ADD(new, kf2, idx2) per record is the caller's.
+ *   pgorb_map_edits_from_keyframe_device   LocalMapping::ProcessNewKeyFrame's loop (src/LocalMapping.cc:142-161) for key frame kf:
+ *       d_edits [cap_per_frame], d_slot_class [cap_per_frame].  Slot i holding an in-range, not-bad point P: P does not list kf
+ *       (live entries only) and no lower slot of kf holds P -> ADD(P, kf, i) at edit i, class 1; else NOP, class 2 (the else branch
+ *       of :155: mlpRecentAddedMapPoints.push_back) -- a lower slot's ADD makes IsInKeyFrame true.  Every other slot: NOP, class
+ *       0.  UpdateNormalAndDepth / ComputeDistinctiveDescriptors of the class-1 points is the refresh that follows the apply.  A
+ *       thread per slot; it looks through the lower slots itself.
+ *   pgorb_map_edits_from_fuse_device   ONE problem of pgorb_fuse_batch_device (src/ORBmatcher.cc:961-979): d_nq [1], d_queries,
+ *       d_action, d_best_idx [qcap] are that problem's rows, kf its key frame.  d_replace_point == NULL, d_edits [qcap]: ADDED ->
+ *       ADD(query, kf, best_idx); MERGED_INTO_KF_POINT -> REPLACE(query, occupant); REPLACED_KF_POINT -> REPLACE(occupant, query),
+ *       the occupant being the slot's RUNNING occupant: its entry value, or the latest earlier query with the same best_idx and
+ *       action ADDED or REPLACED_KF_POINT.  With d_replace_point (one problem of pgorb_fuse_sim3_batch_device,
+ *       src/LoopClosing.cc:601-615), d_edits [2 * qcap]: the ADDs at [0, qcap) and REPLACE(replace_point[q], query) at [qcap,
+ *       2 qcap): Fuse runs to its end before the replacements.
+ *   pgorb_map_edits_from_lba_erase_device   src/Optimizer.cc:748-757 for one window of pgorb_local_bundle_adjustment_batch_device:
+ *       CSR position j with d_erase[j] set -> ERASE(the point of j, obs_frame[j]) at edit j of d_edits [nobs].  A point's erasures
+ *       stay in list order, the order of the reference's edges.
+ *   pgorb_map_edits_from_loop_matches_device   src/LoopClosing.cc:520-537: d_matched [cap_per_frame] = mvpCurrentMatchedPoints as
+ *       table indices (-1 = NULL) for cur_kf; a slot with an occupant -> REPLACE(occupant, matched), an empty one -> ADD(matched,
+ *       cur_kf, i), at edit i of d_edits [cap_per_frame].  Taken from the entry state, which is exact: an occupant lists cur_kf
+ *       only at its own slot, so no earlier edit of the loop writes slot i.
+ *   pgorb_observation_ids_device   d_obs_kf_out[o] = d_kf_id[obs_frame[o]], each list sorted ascending: the obs_kf CSR that
+ *       pgorb_fuse_batch_device reads, so that edit -> refresh -> the next target's Fuse chains without a download. */
+int  pgorb_map_edits_from_keyframe_device(pgorb_ctx* ctx,
+        const int32_t* d_kf_point, const int32_t* d_n, int nframes, int cap_per_frame, int npoints, const uint8_t* d_point_bad,
+        const int32_t* d_obs_start, const int32_t* d_obs_frame, int nobs, const uint8_t* d_obs_live /*or NULL*/, int kf,
+        pgorb_map_edit* d_edits, int32_t* d_slot_class, void* hip_stream);
+int  pgorb_map_edits_from_fuse_device(pgorb_ctx* ctx,
+        const int32_t* d_kf_point, const int32_t* d_n, int nframes, int cap_per_frame, int npoints, int kf, int qcap,
+        const int32_t* d_nq, const int32_t* d_queries, const int32_t* d_action, const int32_t* d_best_idx,
+        const int32_t* d_replace_point /*or NULL*/, pgorb_map_edit* d_edits, void* hip_stream);
+int  pgorb_map_edits_from_lba_erase_device(pgorb_ctx* ctx,
+        int npoints, const int32_t* d_obs_start, const int32_t* d_obs_frame, int nobs, const uint8_t* d_erase, pgorb_map_edit* d_edits,
+        void* hip_stream);
+int  pgorb_map_edits_from_loop_matches_device(pgorb_ctx* ctx,
+        const int32_t* d_kf_point, const int32_t* d_n, int nframes, int cap_per_frame, int npoints, int cur_kf,
+        const int32_t* d_matched, pgorb_map_edit* d_edits, void* hip_stream);
+int  pgorb_observation_ids_device(pgorb_ctx* ctx,
+        int npoints, const int32_t* d_obs_start, const int32_t* d_obs_frame, int nobs, const uint64_t* d_kf_id, int nframes,
+        uint64_t* d_obs_kf_out, void* hip_stream);
+
 /* ---- Loop correction: CorrectLoop's propagation and the map update after global bundle adjustment (csrc/loop_correct.hip) ------
  * The two map rewrites between loop closing's numerical steps, on the arrays those steps read and write, so that ComputeSim3 ->
  * correction -> Fuse(Sim3) -> UpdateConnections -> OptimizeEssentialGraph -> GlobalBundleAdjustment -> map update -> refresh is one

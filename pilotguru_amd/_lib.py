@@ -45,6 +45,9 @@ SYMBOLS = (
     "pgorb_update_local_map", "pgorb_update_local_map_batch_device",
     "pgorb_compact_observations_device", "pgorb_map_point_culling", "pgorb_map_point_culling_device",
     "pgorb_keyframe_culling", "pgorb_keyframe_culling_device",
+    "pgorb_apply_map_edits", "pgorb_apply_map_edits_device", "pgorb_map_edits_from_keyframe_device",
+    "pgorb_map_edits_from_fuse_device", "pgorb_map_edits_from_lba_erase_device", "pgorb_map_edits_from_loop_matches_device",
+    "pgorb_observation_ids_device",
     "pgorb_correct_loop_poses", "pgorb_correct_loop_poses_device", "pgorb_global_ba_map_update", "pgorb_global_ba_map_update_device",
     "pgorb_track_predict", "pgorb_track_predict_batch_device", "pgorb_track_commit", "pgorb_track_commit_batch_device",
     "pgorb_keyframe_tcp", "pgorb_keyframe_tcp_device", "pgorb_get_trajectory", "pgorb_get_trajectory_device",
@@ -344,6 +347,23 @@ def lib():
     #  kf_not_erase, kf_bad, kf_to_be_erased, cur_kf, conn_cap, 6 row arrays, parent, list_cap, record, row_status, info, stream)
     L.pgorb_keyframe_culling_device.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int] + [vp] * 7 + \
         [C.c_int, C.c_int] + [vp] * 7 + [C.c_int, vp, vp, vp, vp]
+    # (ctx, edits, nedits, nkf, kf_point[], n, kf_order, npoints, point_bad, visible, found, replaced, obs_start, obs_frame, obs_idx, obs_live,
+    #  ref_obs, obs_cap_out, obs_start_out, obs_frame_out, obs_idx_out, ref_obs_out, edit_status, touched, select_bits, sel_cap, select_out, info)
+    L.pgorb_apply_map_edits.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp, C.c_int] + [vp] * 9 + [C.c_int] + [vp] * 6 + [C.c_int, C.c_int, vp, vp]
+    # (ctx, edits, nedits, nedits_dev, kf_point, n, nframes, cap, kf_order, npoints, point_bad, visible, found, replaced, obs_start, obs_frame,
+    #  obs_idx, nobs, obs_live, ref_obs, obs_cap_out, 4 CSR outputs, edit_status, touched, select_bits, sel_cap, select_out, info, stream)
+    L.pgorb_apply_map_edits_device.argtypes = [vp, vp, C.c_int, vp, vp, vp, C.c_int, C.c_int, vp, C.c_int] + [vp] * 7 + [C.c_int, vp, vp, C.c_int] + \
+        [vp] * 6 + [C.c_int, C.c_int, vp, vp, vp]
+    # (ctx, kf_point, n, nframes, cap, npoints, point_bad, obs_start, obs_frame, nobs, obs_live, kf, edits, slot_class, stream)
+    L.pgorb_map_edits_from_keyframe_device.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, C.c_int, vp, vp, vp]
+    # (ctx, kf_point, n, nframes, cap, npoints, kf, qcap, nq, queries, action, best_idx, replace_point, edits, stream)
+    L.pgorb_map_edits_from_fuse_device.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int] + [vp] * 7
+    # (ctx, npoints, obs_start, obs_frame, nobs, erase, edits, stream)
+    L.pgorb_map_edits_from_lba_erase_device.argtypes = [vp, C.c_int, vp, vp, C.c_int, vp, vp, vp]
+    # (ctx, kf_point, n, nframes, cap, npoints, cur_kf, matched, edits, stream)
+    L.pgorb_map_edits_from_loop_matches_device.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]
+    # (ctx, npoints, obs_start, obs_frame, nobs, kf_id, nframes, obs_kf_out, stream)
+    L.pgorb_observation_ids_device.argtypes = [vp, C.c_int, vp, vp, C.c_int, vp, C.c_int, vp, vp]
     # (ctx, nkf, kps[], n, pose, cur_kf, scw, nlist, list, kf_order, kf_point[], npoints, points, point_bad, obs_start, obs_frame, obs_idx,
     #  ref_obs, ref_kf, has_corrected, corrected, has_non_corrected, non_corrected, pose_out, corrected_by, point_ref_kf, info)
     L.pgorb_correct_loop_poses.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int, vp, C.c_int, vp, vp, vp, C.c_int] + [vp] * 15

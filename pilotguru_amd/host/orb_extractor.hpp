@@ -281,6 +281,80 @@ class LocalMapping {
                         std::vector<uint8_t>& obsLive, std::vector<int32_t>& refObs, const std::vector<uint8_t>& kfNotErase,
                         std::vector<uint8_t>& kfBad, std::vector<uint8_t>& kfToBeErased, int listCap, std::vector<int32_t>& record,
                         std::vector<int32_t>& rowStatus, std::array<int32_t, PGORB_CULL_INFO>* info = nullptr);
+    // MapPoint::AddObservation / Replace / EraseObservation with their KeyFrame slot writes (MapPoint.cc:119-232, KeyFrame.cc:313-336)
+    // from an ordered edit list, with the result of applying the edits one after another (include/pgorb.h).  kfPoint, pointBad,
+    // visible, found and replaced (one entry per point) are updated in place; obs with obs.refObs, masked by obsLive (empty = all
+    // live), is read and obsOut (another object) receives the fresh lists and refObs; kfOrder empty = index order.  editStatus[e] =
+    // PGORB_EDIT_* bits, touched[p] = PGORB_EDIT_TOUCH_* bits, selected = the points with touched & selectBits.  Returns the number
+    // of edits applied; info[0] == PGORB_EDIT_LIMIT: a component is larger than PGORB_EDIT_MAX_BAG and nothing was done.
+    int ApplyMapEdits(const std::vector<pgorb_map_edit>& edits, std::vector<std::vector<int32_t>>& kfPoint, const std::vector<int32_t>& kfOrder,
+                      std::vector<uint8_t>& pointBad, std::vector<int32_t>& visible, std::vector<int32_t>& found, std::vector<int32_t>& replaced,
+                      const MapPointObservations& obs, const std::vector<uint8_t>& obsLive, MapPointObservations& obsOut,
+                      std::vector<int32_t>& editStatus, std::vector<int32_t>& touched, int selectBits, std::vector<int32_t>& selected,
+                      std::array<int32_t, PGORB_EDIT_INFO>* info = nullptr)
+    {
+        const char* fn = "LocalMapping::ApplyMapEdits";
+        auto fail = [&](const char* what) { throw std::invalid_argument(std::string(fn) + ": " + what); };
+        const size_t np = pointBad.size(), nkf = kfPoint.size(), ne = edits.size();
+        size_t real = 0;
+        for (const pgorb_map_edit& e : edits) {
+            if (e.op < PGORB_EDIT_NOP || e.op > PGORB_EDIT_SET_REF) fail("an unknown op");
+            real += e.op != PGORB_EDIT_NOP;
+        }
+        if (ne > PGORB_EDIT_MAX_LIST || real > PGORB_EDIT_MAX_EDITS) fail("more than PGORB_EDIT_MAX_EDITS edits that are not NOP");
+        if (visible.size() != np || found.size() != np || replaced.size() != np || obs.refObs.size() != np || obs.obsStart.size() != np + 1)
+            fail("visible, found, replaced, refObs and obsStart need one entry per point");
+        if (&obsOut == &obs) fail("obsOut aliases obs");
+        if (!kfOrder.empty()) {
+            if (kfOrder.size() != nkf) fail("kfOrder is not a permutation");
+            std::vector<uint8_t> seen(nkf, 0);
+            for (int32_t r : kfOrder) {
+                if (r < 0 || r >= (int64_t)nkf || seen[r]) fail("kfOrder is not a permutation");
+                seen[r] = 1;
+            }
+        }
+        if (obs.obsStart[0] != 0) fail("obsStart must rise from 0");
+        for (size_t p = 0; p < np; p++)
+            if (obs.obsStart[p + 1] < obs.obsStart[p]) fail("obsStart must rise from 0");
+        const size_t m = (size_t)obs.obsStart[np];
+        if (obs.obsFrame.size() < m || obs.obsIdx.size() < m || (!obsLive.empty() && obsLive.size() < m)) fail("obsFrame, obsIdx and obsLive need one entry per observation");
+        size_t live = 0, adds = 0;
+        std::vector<int64_t> seenAt(nkf + 1, -1);
+        for (size_t p = 0; p < np; p++) {
+            const int len = obs.obsStart[p + 1] - obs.obsStart[p];
+            if (len && (obs.refObs[p] < -1 || obs.refObs[p] >= len)) fail("refObs lies outside the point's list");
+            for (int o = obs.obsStart[p]; o < obs.obsStart[p + 1]; o++) {
+                if (!obsLive.empty() && !obsLive[o]) continue;
+                const int f = obs.obsFrame[o];
+                if (f < 0 || f >= (int64_t)nkf || obs.obsIdx[o] < 0 || obs.obsIdx[o] >= (int64_t)kfPoint[f].size()) fail("an observation names a key frame or keypoint out of range");
+                if (seenAt[f] == (int64_t)p) fail("a list names a key frame twice");
+                seenAt[f] = (int64_t)p;
+                live++;
+            }
+        }
+        for (const pgorb_map_edit& e : edits) adds += e.op == PGORB_EDIT_ADD;
+        std::vector<int32_t*> slots(nkf + 1, nullptr);
+        std::vector<int32_t> n(nkf + 1, 0);
+        for (size_t f = 0; f < nkf; f++) { slots[f] = kfPoint[f].data(); n[f] = (int32_t)kfPoint[f].size(); }
+        const size_t capOut = live + adds;
+        obsOut.obsStart.assign(np + 1, 0);
+        obsOut.obsFrame.assign(capOut + 1, 0); obsOut.obsIdx.assign(capOut + 1, 0); obsOut.refObs.assign(np + 1, -1);
+        editStatus.assign(ne + 1, 0); touched.assign(np + 1, 0); selected.assign(np + 1, -1);
+        std::array<int32_t, PGORB_EDIT_INFO> inf{};
+        pgorb_map_edit none{};
+        uint8_t one = 0;
+        const int rc = pgorb_apply_map_edits(ctx_, ne ? edits.data() : &none, (int)ne, (int)nkf, slots.data(), n.data(), kfOrder.empty() ? nullptr : kfOrder.data(),
+                                             (int)np, np ? pointBad.data() : &one, visible.data(), found.data(), replaced.data(), obs.obsStart.data(),
+                                             obs.obsFrame.data(), obs.obsIdx.data(), obsLive.empty() ? nullptr : obsLive.data(), obs.refObs.data(), (int)capOut,
+                                             obsOut.obsStart.data(), obsOut.obsFrame.data(), obsOut.obsIdx.data(), obsOut.refObs.data(), editStatus.data(),
+                                             touched.data(), selectBits, (int)np, selected.data(), inf.data());
+        if (rc < 0) throw std::runtime_error(pgorb_last_error(ctx_));
+        const bool done = inf[0] != PGORB_EDIT_LIMIT;
+        obsOut.obsFrame.resize(done ? (size_t)inf[1] : 0); obsOut.obsIdx.resize(done ? (size_t)inf[1] : 0); obsOut.refObs.resize(np);
+        editStatus.resize(ne); touched.resize(np); selected.resize(done ? (size_t)inf[7] : 0);
+        if (info) *info = inf;
+        return rc;
+    }
     // MapPoint::ComputeDistinctiveDescriptors (MapPoint.cc:259-324) and MapPoint::UpdateNormalAndDepth (:347-388) of many points in
     // one call, as LocalMapping.cc:444-446 and :519-532 run them.  keyFrames: frame (mvKeysUn, mDescriptors) and pose are read;
     // kfBad[f] = isBad() (empty = none); points / descriptors (32 bytes each) / pointBad (empty = none) are the table, refreshed

@@ -2124,6 +2124,15 @@ class LocalMapping:
                     record=record[:nl].copy(), row_status=status[:nkf].copy(), info=info)
 
     @staticmethod
+    def ProcessNewKeyFrame(ext, kf, kf_point, npoints, point_bad, visible, found, replaced, obs_start, obs_frame, obs_idx, obs_live, ref_obs,
+                           kf_order=None):
+        """LocalMapping::ProcessNewKeyFrame's AddObservation loop (src/LocalMapping.cc:142-161) for key frame kf, as map edits
+        (map_edit.process_new_key_frame): the dict of apply_map_edits with slot_class added."""
+        from .map_edit import process_new_key_frame
+        return process_new_key_frame(ext, kf, kf_point, npoints, point_bad, visible, found, replaced, obs_start, obs_frame, obs_idx, obs_live,
+                                     ref_obs, kf_order)
+
+    @staticmethod
     def KeyFrameTcp(ext, poses, parent, record, tcp=None):
         """KeyFrame::SetBadFlag's mTcp = Tcw * mpParent->GetPoseInverse() (src/KeyFrame.cc:641) for every row of `record`
         (KeyFrameCulling's, [m][4]) whose action is CULL_KF_CULLED; poses / parent as they stand right after that culling, before any

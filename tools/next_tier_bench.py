@@ -103,7 +103,7 @@ next to each, the oracle's CPU time for the same work (1 thread, a few frames, s
                the same hand-off through the host (download, numpy products, upload), and GetTrajectory of 108 000 records over 2 000 key
                frames with 30 % of them culled.  No target is set.  --trajectory-only runs these rows alone (profiles/next_tier_trajectory.txt).
 
-usage: python tools/next_tier_bench.py [--batch 128] [--out profiles/r02_next_tier.txt] [--refresh-only | --place-only | --loop-only | --track-only | --pose-only | --sim3-only | --pnp-only | --optsim3-only | --lba-only | --eg-only | --gba-only | --covis-only | --cull-only | --loop-correct-only | --trajectory-only]"""
+usage: python tools/next_tier_bench.py [--batch 128] [--out profiles/r02_next_tier.txt] [--refresh-only | --place-only | --loop-only | --track-only | --pose-only | --sim3-only | --pnp-only | --optsim3-only | --lba-only | --eg-only | --gba-only | --covis-only | --cull-only | --loop-correct-only | --trajectory-only | --edit-only]"""
 import argparse, ctypes as C, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -133,6 +133,7 @@ ap.add_argument("--covis-only", action="store_true", help="the covisibility-grap
 ap.add_argument("--cull-only", action="store_true", help="the culling rows alone (no ride, no vocabulary)")
 ap.add_argument("--loop-correct-only", action="store_true", help="the loop-correction rows alone (no ride, no vocabulary); writes "
                 "profiles/next_tier_loop_correct.txt unless --out names another file")
+ap.add_argument("--edit-only", action="store_true", help="the map-edit rows alone (no ride, no vocabulary); writes profiles/next_tier_map_edit.txt")
 ap.add_argument("--trajectory-only", action="store_true", help="the trajectory read-out rows alone (no ride, no vocabulary); writes "
                 "profiles/next_tier_trajectory.txt unless --out names another file")
 a = ap.parse_args()
@@ -1058,6 +1059,65 @@ def trajectory_lines():
             "%-150s %10s %12s" % ("call", "GPU ms", "host ms")] + rows
 
 
+def edit_lines():
+    """The map edits: three list shapes through pgorb_apply_map_edits_device, next to the host replay of tests/map_edit_reference.py."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import map_edit_cases as K
+    import map_edit_reference as R
+    import time
+    rng = np.random.RandomState(23)
+    nkf, nslots, npts = 24, 1200, 4000
+    free = [list(rng.permutation(nslots - 1)) for _ in range(nkf)]              # the last slot of every key frame stays free
+    lists = []
+    for p in range(npts):
+        f0, ln = int(rng.randint(0, nkf - 1)), int(rng.randint(2, 7))
+        lists.append([(f, int(free[f].pop())) for f in range(f0, min(f0 + ln, nkf - 1))])        # nobody sees the last key frame yet
+    a = K.world(nkf, nslots, lists, list(rng.permutation(nkf)))
+    new = nkf - 1
+    shapes = []
+    adds = rng.choice(npts, 500, replace=False)
+    shapes.append(("500 independent ADDs (a new key frame: ProcessNewKeyFrame)", K.E(*[(R.ADD, int(p), new, i) for i, p in enumerate(adds)])))
+    rows, used = [], set()
+    for k in range(200):                                                        # Fuse-shaped: ADDED / MERGED / REPLACED over pairs of points, NOP in between
+        x, y = (int(v) for v in rng.choice(npts, 2, replace=False))
+        u = rng.rand()
+        rows.append((R.NOP, 0, 0, 0) if u < 0.3 or x in used or y in used else (R.ADD, x, new, 600 + k, ) if u < 0.55 else (R.REPLACE, x, y, 0))
+        used.update((x, y))
+    shapes.append(("a Fuse-shaped list of 200 mixed edits (ADD, REPLACE, NOP)", K.E(*rows)))
+    star = rng.choice(npts, 201, replace=False)
+    shapes.append(("200 REPLACEs into one survivor (one component, one wave)", K.E(*[(R.REPLACE, int(p), int(star[0]), 0) for p in star[1:]])))
+    ext = pg.ORBextractor(2000, 1.2, 8, 20, 7, max_width=640, max_height=480)
+    out = []
+    for name, edits in shapes:
+        c = K.Case(name, a, edits)
+        t0 = time.perf_counter()
+        e = K.expected(c, exact=False)
+        t_ref = (time.perf_counter() - t0) * 1e3
+        d = K.upload(c, e)
+        keep = {k: d[k].clone() for k in ("kf_point", "point_bad", "visible", "found", "replaced")}
+        ms = []
+        for rep in range(10):
+            for k, v in keep.items():
+                d[k].copy_(v)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(); K.run_device(c, ext, e, d=d); e1.record(); torch.cuda.synchronize()
+            ms.append(e0.elapsed_time(e1))
+        got = K.download(d)
+        assert K.same(got, e), ("the device's result differs from the reference's", name, K.diff(got, e))
+        out.append("%-150s %10.4f %12.2f" % ("apply_map_edits: %s; %d points, %d observations, %d components, %d slot writes" %
+                                             (name, npts, a["nobs"], int(e["info"][4]), int(e["info"][5])), float(np.median(ms[1:])), t_ref))
+    return ["# The map edits on the device (csrc/map_edit.hip), resident calls, HIP events around one call (seven launches and two memsets), median of 9 after one",
+            "# warm-up, the in/out state restored before every call.  The second column is the host replay of the same list by the literal Python objects of the",
+            "# tests (tests/map_edit_reference.py; building the objects from the arrays and back included) on one core, wall clock, one run; NOT ORB-SLAM2 and not a tuned baseline.  The parent commit has no device",
+            "# form, so there is nothing measured to compare against: NEITHER NUMBER IS A TARGET and no time is a pass condition.",
+            "%-150s %10s %12s" % ("call", "GPU ms", "Python ms")] + out
+
+
+if a.edit_only:
+    lines = ["# python tools/next_tier_bench.py --edit-only   (MI355X)"] + edit_lines()
+    print("\n".join(lines))
+    open(a.out or os.path.join(ROOT, "profiles", "next_tier_map_edit.txt"), "w").write("\n".join(lines) + "\n")
+    sys.exit(0)
 if a.trajectory_only:
     lines = ["# python tools/next_tier_bench.py --trajectory-only   (MI355X)"] + trajectory_lines()
     print("\n".join(lines))

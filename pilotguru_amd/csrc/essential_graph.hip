@@ -12,7 +12,9 @@
 // in double, under the readings of DESIGN.md section 4 (the OptimizeEssentialGraph rows).  LinearSolverEigen's SimplicialLDLT with a
 // fill-reducing ordering is READ as a Cholesky L L' in index order; it is stored as a block skyline (row i keeps its 7 x 7 blocks from
 // its lowest connected neighbour to i; fill never leaves that envelope), and every entry receives its products in the order of the
-// dense index-order factorisation, so skipping the structural zeros changes no bit.
+// dense index-order factorisation, so skipping the structural zeros changes no bit.  Levenberg's step control, the block reduction and
+// the finite test are g2o_lm.h's single copies (shared with pose_opt.hip, optimize_sim3.hip, local_ba.hip, global_ba.hip); Sim3 is
+// g2o_sim3.h's (shared with optimize_sim3.hip and loop_pose.h).
 //
 // Launches (no host round trip, no cooperative launch, no wait between workgroups; every loop is bounded by a capacity or a constant):
 //   k_eg_prepare    one workgroup: the vertices, the filtered candidates with their ranks (= the edge order), the measurements, the
@@ -36,7 +38,6 @@
 #define EG_LIN_EDGES 16
 #define EG_LIN_T (EG_LIN_EDGES * 14)
 #define EG_PANEL 64               // blocks of a pivot column kept in LDS
-#define EG_DBL_MAX 1.7976931348623157e308
 // per edge doubles: the error, chi2, b of both sides, the three blocks (169, kept at an even count)
 #define ED_ERR 0
 #define ED_CHI 7
@@ -50,7 +51,7 @@
 struct EgEdge { int32_t v0, v1, kind, pad; OsSim C; };
 static_assert(sizeof(EgEdge) == 80 && sizeof(OsSim) == sizeof(pgorb_sim3d), "the edge record; pgorb_sim3d is g2o::Sim3's r, t, s");
 
-struct EgState { int32_t status, stop, nVert, nFree, nEdges, nKind[4], its, trials, env, ni, nBad, iter, pad; double lambda; };
+struct EgState { int32_t status, stop, nVert, nFree, nEdges, nKind[4], its, trials, env, iter, pad; G2oLm lm; };
 
 struct EgArgs {
     int nkf; const uint64_t* id; const pgorb_kf_pose* pose; const uint8_t* bad; int loopKf, curKf, fixScale;
@@ -68,7 +69,6 @@ struct EgArgs {
     double* A; double* L; double* b; double* x;
 };
 
-__device__ __forceinline__ bool eg_finite(double v) { return fabs(v) <= EG_DBL_MAX; }
 __device__ __forceinline__ bool eg_bad(const EgArgs& G, int i) { return G.bad && G.bad[i]; }
 __device__ __forceinline__ bool eg_kf(const EgArgs& G, int i) { return i >= 0 && i < G.nkf && !eg_bad(G, i); }
 
@@ -156,13 +156,7 @@ __global__ __launch_bounds__(EG_PREP_T) void k_eg_prepare(EgArgs G)
     for (int i = tid; i < nkf; i += EG_PREP_T) {
         OsSim S;
         if (G.hasCor && G.hasCor[i]) S = G.cor[i];
-        else {
-            const pgorb_kf_pose P = G.pose[i];
-            const double R[9] = {(double)P.Tcw[0], (double)P.Tcw[1], (double)P.Tcw[2], (double)P.Tcw[4], (double)P.Tcw[5], (double)P.Tcw[6],
-                                 (double)P.Tcw[8], (double)P.Tcw[9], (double)P.Tcw[10]};
-            os_quat_from_matrix(R, S);
-            S.tx = (double)P.Tcw[3]; S.ty = (double)P.Tcw[7]; S.tz = (double)P.Tcw[11]; S.s = 1.0;
-        }
+        else S = lp_sim3_from_pose(G.pose[i].Tcw);
         G.scw[i] = S; G.est[i] = S; G.trial[i] = S;
         G.sys[i] = -1; G.deg[i] = 0; G.cursor[i] = 0;
     }
@@ -263,7 +257,7 @@ __global__ __launch_bounds__(EG_PREP_T) void k_eg_prepare(EgArgs G)
         if (nE == 0 || nFree == 0) S.status = PGORB_EG_NOTHING;
         else if (!fits) S.status = PGORB_EG_LIMIT;
         S.stop = (S.status || G.iterations <= 0) ? 1 : 0;
-        S.ni = 2;
+        S.lm.ni = 2;
         *G.st = S;
     }
 }
@@ -365,17 +359,6 @@ __global__ __launch_bounds__(64) void k_eg_assemble(EgArgs G)
 }
 
 struct EgStepShared { double part[EG_T / 64]; double panel[EG_PANEL][49]; double diag[49]; int ok; };
-
-// the fixed tree: a lane's items in increasing index, a butterfly inside the wave, then (w0 + w1) + (w2 + w3)
-__device__ __forceinline__ double eg_block_sum(EgStepShared& S, double v)
-{
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) S.part[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (S.part[0] + S.part[1]) + (S.part[2] + S.part[3]);
-}
 
 __device__ __forceinline__ double* eg_block(const EgArgs& G, double* M, int row, int col) { return M + ((int64_t)G.off[row] + (col - G.first[row])) * 49; }
 
@@ -503,18 +486,19 @@ __global__ __launch_bounds__(EG_T) void k_eg_step(EgArgs G)
     // activeRobustChi2 at the estimates (k_eg_linearize left each edge's chi2)
     double acc = 0.0;
     for (int e = tid; e < nE; e += EG_T) acc += G.ed[(int64_t)e * EG_ED + ED_CHI];
-    double currentChi = eg_block_sum(S, acc);
+    double currentChi = g2o_block_sum(S.part, acc);
     const double iniChi = currentChi;
-    if (!eg_finite(currentChi)) {
+    if (!g2o_finite(currentChi)) {
         if (tid == 0) { G.st->status = PGORB_EG_NONFINITE; G.st->stop = 1; }
         return;
     }
-    double lambda = st.lambda;
-    int ni = st.ni, nBad = st.nBad, trials = st.trials;
-    if (st.iter == 0) { lambda = 1e-16; ni = 2; nBad = 0; }                         // computeLambdaInit: _userLambdaInit > 0
+    G2oLm lm = st.lm;
+    int trials = st.trials;
+    if (st.iter == 0) g2o_lm_begin(lm, 1e-16);                                       // computeLambdaInit: _userLambdaInit > 0
     double rho = 0.0;
     int qmax = 0;
     do {
+        const double lambda = lm.lambda;
         const bool ok2 = eg_factor(G, S, n, lambda);
         if (ok2) eg_solve(G, S, n);
         else {
@@ -534,7 +518,7 @@ __global__ __launch_bounds__(EG_T) void k_eg_step(EgArgs G)
         __syncthreads();
         double sc = 0.0;
         for (int k = tid; k < n * 7; k += EG_T) sc += G.x[k] * (lambda * G.x[k] + G.b[k]);
-        const double scale = eg_block_sum(S, sc) + 1e-3;
+        const double scale = g2o_block_sum(S.part, sc);
         acc = 0.0;
         for (int e = tid; e < nE; e += EG_T) {
             const EgEdge& E = G.edges[e];
@@ -542,30 +526,19 @@ __global__ __launch_bounds__(EG_T) void k_eg_step(EgArgs G)
             eg_error(E.C, G.trial[E.v0], G.trial[E.v1], er);
             acc += eg_chi2(er);
         }
-        double tempChi = eg_block_sum(S, acc);
-        if (!ok2) tempChi = EG_DBL_MAX;
-        rho = (currentChi - tempChi) / scale;
-        if (rho > 0.0 && eg_finite(tempChi)) {
-            const double t = 2.0 * rho - 1.0;
-            double alpha = 1.0 - (t * t) * t;                                        // pow(2 * rho - 1, 3) read as two products
-            alpha = fmin(alpha, 2.0 / 3.0);
-            lambda *= fmax(1.0 / 3.0, alpha); ni = 2; currentChi = tempChi;
+        const double tempChi = g2o_block_sum(S.part, acc);
+        if (g2o_lm_decide(lm, currentChi, tempChi, ok2, scale, rho)) {
             for (int r = tid; r < n; r += EG_T) { const int v = G.rowKf[r]; G.est[v] = G.trial[v]; }      // discardTop
         } else {
-            lambda *= (double)ni; ni *= 2;                                           // pop
-            for (int r = tid; r < n; r += EG_T) { const int v = G.rowKf[r]; G.trial[v] = G.est[v]; }
+            for (int r = tid; r < n; r += EG_T) { const int v = G.rowKf[r]; G.trial[v] = G.est[v]; }      // pop
         }
         __syncthreads();
         qmax++; trials++;
-    } while (rho < 0.0 && qmax < 10);
-    bool stop = qmax == 10 || rho == 0.0;                                            // Terminate
-    if (!stop) {
-        if ((iniChi - currentChi) * 1e3 < iniChi) nBad++; else nBad = 0;
-        stop = nBad >= 3;
-    }
+    } while (g2o_lm_again(rho, qmax));
+    const bool stop = g2o_lm_stop(lm, iniChi, currentChi, qmax, rho);
     if (tid == 0) {
         EgState* P = G.st;
-        P->lambda = lambda; P->ni = ni; P->nBad = nBad; P->trials = trials; P->its = st.its + 1; P->iter = st.iter + 1;
+        P->lm = lm; P->trials = trials; P->its = st.its + 1; P->iter = st.iter + 1;
         P->stop = (stop || st.iter + 1 >= G.iterations) ? 1 : 0;
     }
 }

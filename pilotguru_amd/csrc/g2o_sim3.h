@@ -1,60 +1,10 @@
-// g2o_sim3.h -- g2o::Sim3 (g2o/types/sim3.h) and the pieces of Eigen's quaternion under it that the Sim3 optimisers share
-// (optimize_sim3.hip, essential_graph.hip), in double and in the sources' operation order: DESIGN.md section 4 lists the readings.
+// g2o_sim3.h -- g2o::Sim3 (g2o/types/sim3.h) as the Sim3 optimisers and loop closing share it (optimize_sim3.hip,
+// essential_graph.hip, and through loop_pose.h loop_correct.hip, track_pose.hip and map_point.hip).  The quaternion under it is
+// g2o_lm.h's, the same copy that g2o_se3.h uses.  In double and in the sources' operation order: DESIGN.md section 4 lists the readings.
 #pragma once
-#include <hip/hip_runtime.h>
-#include <math.h>
+#include "g2o_lm.h"
 
 struct OsSim { double qx, qy, qz, qw, tx, ty, tz, s; };                 // g2o::Sim3: r (not renormalised), t, s
-
-// Eigen's Quaterniond(Matrix3d); m row-major
-__device__ __forceinline__ void os_quat_from_matrix(const double (&m)[9], OsSim& P)
-{
-    double t = (m[0] + m[4]) + m[8];
-    if (t > 0.0) {
-        t = __dsqrt_rn(t + 1.0);
-        P.qw = 0.5 * t;
-        t = 0.5 / t;
-        P.qx = (m[7] - m[5]) * t; P.qy = (m[2] - m[6]) * t; P.qz = (m[3] - m[1]) * t;
-    } else {
-        int i = 0;
-        if (m[4] > m[0]) i = 1;
-        if (m[8] > (i ? m[4] : m[0])) i = 2;
-        if (i == 0) {
-            t = __dsqrt_rn(((m[0] - m[4]) - m[8]) + 1.0);
-            P.qx = 0.5 * t; t = 0.5 / t;
-            P.qw = (m[7] - m[5]) * t; P.qy = (m[3] + m[1]) * t; P.qz = (m[6] + m[2]) * t;
-        } else if (i == 1) {
-            t = __dsqrt_rn(((m[4] - m[8]) - m[0]) + 1.0);
-            P.qy = 0.5 * t; t = 0.5 / t;
-            P.qw = (m[2] - m[6]) * t; P.qz = (m[7] + m[5]) * t; P.qx = (m[1] + m[3]) * t;
-        } else {
-            t = __dsqrt_rn(((m[8] - m[0]) - m[4]) + 1.0);
-            P.qz = 0.5 * t; t = 0.5 / t;
-            P.qw = (m[3] - m[1]) * t; P.qx = (m[2] + m[6]) * t; P.qy = (m[5] + m[7]) * t;
-        }
-    }
-}
-
-// Eigen's Quaternion::toRotationMatrix, row-major
-__device__ __forceinline__ void os_matrix_from_quat(const OsSim& P, double (&m)[9])
-{
-    const double tx = 2.0 * P.qx, ty = 2.0 * P.qy, tz = 2.0 * P.qz;
-    const double twx = tx * P.qw, twy = ty * P.qw, twz = tz * P.qw, txx = tx * P.qx, txy = ty * P.qx, txz = tz * P.qx;
-    const double tyy = ty * P.qy, tyz = tz * P.qy, tzz = tz * P.qz;
-    m[0] = 1.0 - (tyy + tzz); m[1] = txy - twz; m[2] = txz + twy;
-    m[3] = txy + twz; m[4] = 1.0 - (txx + tzz); m[5] = tyz - twx;
-    m[6] = txz - twy; m[7] = tyz + twx; m[8] = 1.0 - (txx + tyy);
-}
-
-// Eigen's quaternion * vector: uv = vec x v; uv += uv; v + w * uv + vec x uv
-__device__ __forceinline__ void os_rotate(double qx, double qy, double qz, double qw, double X, double Y, double Z, double& rx, double& ry, double& rz)
-{
-    double ux = qy * Z - qz * Y, uy = qz * X - qx * Z, uz = qx * Y - qy * X;
-    ux += ux; uy += uy; uz += uz;
-    rx = (X + qw * ux) + (qy * uz - qz * uy);
-    ry = (Y + qw * uy) + (qz * ux - qx * uz);
-    rz = (Z + qw * uz) + (qx * uy - qy * ux);
-}
 
 // Sim3::operator*: r = a.r * b.r, t = a.s * (a.r * b.t) + a.t, s = a.s * b.s; no renormalisation
 __device__ __forceinline__ OsSim os_mul(const OsSim& a, const OsSim& b)
@@ -65,7 +15,7 @@ __device__ __forceinline__ OsSim os_mul(const OsSim& a, const OsSim& b)
     O.qx = ((a.qw * b.qx + a.qx * b.qw) + a.qy * b.qz) - a.qz * b.qy;
     O.qy = ((a.qw * b.qy + a.qy * b.qw) + a.qz * b.qx) - a.qx * b.qz;
     O.qz = ((a.qw * b.qz + a.qz * b.qw) + a.qx * b.qy) - a.qy * b.qx;
-    os_rotate(a.qx, a.qy, a.qz, a.qw, b.tx, b.ty, b.tz, rx, ry, rz);
+    g2o_rotate(a, b.tx, b.ty, b.tz, rx, ry, rz);
     O.tx = a.s * rx + a.tx; O.ty = a.s * ry + a.ty; O.tz = a.s * rz + a.tz;
     O.s = a.s * b.s;
     return O;
@@ -77,7 +27,7 @@ __device__ __forceinline__ OsSim os_inverse(const OsSim& a)
     OsSim O;
     const double k = -1.0 / a.s;
     O.qx = -a.qx; O.qy = -a.qy; O.qz = -a.qz; O.qw = a.qw;
-    os_rotate(O.qx, O.qy, O.qz, O.qw, k * a.tx, k * a.ty, k * a.tz, O.tx, O.ty, O.tz);
+    g2o_rotate(O, k * a.tx, k * a.ty, k * a.tz, O.tx, O.ty, O.tz);
     O.s = 1.0 / a.s;
     return O;
 }
@@ -127,7 +77,7 @@ __device__ __forceinline__ OsSim os_exp(const double (&u)[7])
             Bc = (Cc - ((b - 1.0) * sigma + a * theta) / c) / theta2;
         }
     }
-    os_quat_from_matrix(R, E);
+    g2o_quat_from_matrix(R, E);
     double W[9];
 #pragma unroll
     for (int k = 0; k < 9; k++) W[k] = (A * Om[k] + Bc * Om2[k]) + Cc * (k % 4 == 0 ? 1.0 : 0.0);
@@ -144,7 +94,7 @@ __device__ __forceinline__ void os_log(const OsSim& P, double (&res)[7])
 {
     const double sigma = log(P.s);
     double R[9];
-    os_matrix_from_quat(P, R);
+    g2o_matrix_from_quat(P, R);
     const double d = 0.5 * (((R[0] + R[4]) + R[8]) - 1.0);
     const double dR[3] = {R[7] - R[5], R[2] - R[6], R[3] - R[1]};
     const double eps = 0.00001;

@@ -12,7 +12,10 @@
 //   OptimizationAlgorithmLevenberg::solve         g2o/core/optimization_algorithm_levenberg.cpp:61-189
 //   KeyFrame::SetPose                             src/KeyFrame.cc
 // in double, under the readings of DESIGN.md sections 4 and 5 (the local-bundle-adjustment rows and the global ones).  The edge
-// arithmetic is local_ba.hip's, expression for expression; LinearSolverEigen is READ, as in essential_graph.hip, as a Cholesky L L' in
+// arithmetic is local_ba.hip's: both call g2o_se3.h's one copy of EdgeSE3ProjectXYZ's error and linearisation, of toSE3Quat and of
+// SetPose (pose_opt.hip shares all but the linearisation).  Huber, the block reductions, the 3 x 3 inverse and Levenberg's step
+// control (here on the state record: k_gba_begin, k_gba_decide) are g2o_lm.h's, shared with pose_opt.hip, optimize_sim3.hip,
+// local_ba.hip and essential_graph.hip.  LinearSolverEigen is READ, as in essential_graph.hip, as a Cholesky L L' in
 // index order on a block skyline (row i keeps its 6 x 6 blocks from the lowest-indexed camera that shares a point with it to i).
 //
 // Launches (no host round trip, no cooperative launch, no wait between workgroups; every loop is bounded by a capacity or a constant):
@@ -51,16 +54,15 @@
 #define GBA_CHUNKS 256            // k_gba_prepare splits the observations into this many runs to build the cameras' lists in order
 #define GBA_MAX_N 16000           // keypoints per frame, as for the matchers
 #define GBA_PANEL 64              // blocks of a pivot column kept in LDS
-#define GBA_TRIALS 10
-#define GBA_DBL_MAX 1.7976931348623157e308
 #define GBA_DELTA ((double)0x1.3945f6p+1f)        /* const float thHuber2D = sqrt(5.99) = 2.4474475f (Optimizer.cc:57) */
 
 struct GbaEdge { int32_t frame /* < 0: the observation is no edge */, pt, row, pad; float ox, oy, w, pad1; };
 static_assert(sizeof(GbaEdge) == 32, "two dwordx4");
 struct GbaCam { PoSE3 est[2]; double fx, fy, cx, cy; };
 struct GbaState {
-    int32_t status, stop, nE, nPts, nVert, nFree, env, its, trials, ni, nBad, iter, qmax, ok2, cur, pad;
-    double lambda, currentChi, iniChi, camScale;
+    int32_t status, stop, nE, nPts, nVert, nFree, env, its, trials, iter, qmax, ok2, cur, pad;
+    G2oLm lm;
+    double currentChi, iniChi, camScale;
 };
 // a point's doubles: Hll, bl
 enum { GP_HLL = 0, GP_BL = 9, GBA_PT_D = 12 };
@@ -90,31 +92,12 @@ __device__ __forceinline__ int2 gba_range(const GbaArgs& G, int p)
     return make_int2(a, b);
 }
 
-// the fixed tree: a butterfly inside the wave (a + b is b + a bit for bit, so every lane ends with the same sum), then (w0 + w1) + (w2 + w3)
-__device__ __forceinline__ double gba_block_sum(double* part, double v)
-{
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (part[0] + part[1]) + (part[2] + part[3]);
-}
-__device__ __forceinline__ double gba_block_max(double* part, double v)
-{
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v = fmax(v, __shfl_xor(v, m, 64));
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return fmax(fmax(part[0], part[1]), fmax(part[2], part[3]));
-}
 // n partials: thread t takes t, t + 256, ... in that order, then the tree
 __device__ __forceinline__ double gba_reduce_sum(double* part, const double* v, int n)
 {
     double acc = 0.0;
     for (int k = threadIdx.x; k < n; k += GBA_T) acc += v[k];
-    return gba_block_sum(part, acc);
+    return g2o_block_sum(part, acc);
 }
 
 // exclusive scan of in[0 .. n) into out (may be in), every thread of the workgroup calls it; returns the total
@@ -140,18 +123,6 @@ __device__ int gba_scan(const int32_t* in, int32_t* out, int n, int32_t* part /*
     return total;
 }
 
-// Converter::toSE3Quat of a float Tcw
-__device__ __forceinline__ PoSE3 gba_to_se3(const pgorb_kf_pose& in)
-{
-    const double R[9] = {(double)in.Tcw[0], (double)in.Tcw[1], (double)in.Tcw[2], (double)in.Tcw[4], (double)in.Tcw[5], (double)in.Tcw[6],
-                         (double)in.Tcw[8], (double)in.Tcw[9], (double)in.Tcw[10]};
-    PoSE3 E;
-    po_quat_from_matrix(R, E);
-    E.tx = (double)in.Tcw[3]; E.ty = (double)in.Tcw[7]; E.tz = (double)in.Tcw[11];
-    po_normalize(E);
-    return E;
-}
-
 // ---- the sets of Optimizer.cc:71-110 as flags, and the lists the solver walks
 __global__ __launch_bounds__(GBA_PREP_T) void k_gba_prepare(GbaArgs G)
 {
@@ -163,7 +134,7 @@ __global__ __launch_bounds__(GBA_PREP_T) void k_gba_prepare(GbaArgs G)
         GbaCam C;
         memset(&C, 0, sizeof(C));
         C.est[0].qw = 1.0;
-        if (!gba_bad(G, f)) C.est[0] = gba_to_se3(in);
+        if (!gba_bad(G, f)) C.est[0] = po_from_pose(in);
         C.est[1] = C.est[0];
         C.fx = (double)in.fx; C.fy = (double)in.fy; C.cx = (double)in.cx; C.cy = (double)in.cy;
         G.cams[f] = C;
@@ -288,64 +259,20 @@ __global__ __launch_bounds__(GBA_PREP_T) void k_gba_prepare(GbaArgs G)
         if (nE == 0 || nFree == 0) S.status = PGORB_GBA_NOTHING;
         else if (!fits) S.status = PGORB_GBA_LIMIT;
         S.stop = (S.status || G.iterations <= 0) ? 1 : 0;
-        S.ni = 2;
+        S.lm.ni = 2;
         *G.st = S;
     }
 }
 
-// computeError: obs - cam_project(v1->estimate().map(v2->estimate())); (x, y, z) = the mapped point
-__device__ __forceinline__ void gba_error(const PoSE3& P, const GbaCam& C, const double* X, const GbaEdge& e, double& x, double& y, double& z,
-                                          double& e0, double& e1)
+// one edge at P and X through g2o_se3.h's single copies: the linearisation, and the error alone
+__device__ __forceinline__ void gba_linearize_edge(const PoSE3& P, const GbaCam& C, const double* X, const GbaEdge& e, bool robust, PoLin& L)
 {
-    double rx, ry, rz;
-    po_rotate(P, X[0], X[1], X[2], rx, ry, rz);
-    x = rx + P.tx; y = ry + P.ty; z = rz + P.tz;
-    e0 = (double)e.ox - ((x / z) * C.fx + C.cx);
-    e1 = (double)e.oy - ((y / z) * C.fy + C.cy);
+    po_linearize_xyz(P, C.fx, C.fy, C.cx, C.cy, X, (double)e.ox, (double)e.oy, (double)e.w, robust, GBA_DELTA, L);
 }
-// RobustKernelHuber::robustify with the global delta
-__device__ __forceinline__ void gba_huber(double e, double& rho0, double& rho1)
+__device__ __forceinline__ void gba_error(const PoSE3& P, const GbaCam& C, const double* X, const GbaEdge& e, double& e0, double& e1)
 {
-    const double dsqr = GBA_DELTA * GBA_DELTA;
-    if (e <= dsqr) { rho0 = e; rho1 = 1.0; }
-    else {
-        const double sqrte = __dsqrt_rn(e);
-        rho0 = 2.0 * sqrte * GBA_DELTA - dsqr;
-        rho1 = GBA_DELTA / sqrte;
-    }
-}
-// one edge at the estimates: the error, the robustified chi2, constructQuadraticForm's weights and the pose Jacobian (linearizeOplus)
-struct GbaLin { double x, y, z, rho0, wO, r0, r1, Jj0[6], Jj1[6]; };
-__device__ __forceinline__ void gba_linearize_edge(const PoSE3& P, const GbaCam& C, const double* X, const GbaEdge& e, bool robust, GbaLin& L)
-{
-    double e0, e1;
-    gba_error(P, C, X, e, L.x, L.y, L.z, e0, e1);
-    const double x = L.x, y = L.y, z = L.z, fx = C.fx, fy = C.fy;
-    const double wgt = (double)e.w;
-    const double c2 = po_chi2(e0, e1, wgt);
-    double rho0 = c2, rho1 = 1.0;
-    if (robust) gba_huber(c2, rho0, rho1);
-    L.rho0 = rho0;
-    const double z2 = z * z;
-    const double Jj0[6] = {x * y / z2 * fx, -(1.0 + (x * x / z2)) * fx, y / z * fx, -1.0 / z * fx, 0.0, x / z2 * fx};
-    const double Jj1[6] = {(1.0 + y * y / z2) * fy, -x * y / z2 * fy, -x / z * fy, 0.0, -1.0 / z * fy, y / z2 * fy};
-#pragma unroll
-    for (int a = 0; a < 6; a++) { L.Jj0[a] = Jj0[a]; L.Jj1[a] = Jj1[a]; }
-    // constructQuadraticForm: omega_r = -omega * _error (times rho[1]), weightedOmega = rho[1] * omega
-    L.wO = rho1 * wgt; L.r0 = -(wgt * e0) * rho1; L.r1 = -(wgt * e1) * rho1;
-}
-
-// Eigen's fixed-size 3 x 3 inverse (Inverse.h compute_inverse<Matrix3d>): cofactors, the determinant from the first cofactor column, no test
-__device__ __forceinline__ void gba_inverse3(const double (&D)[9], double (&I)[9])
-{
-#define GBA_COF(i, j) (D[((i + 1) % 3) * 3 + (j + 1) % 3] * D[((i + 2) % 3) * 3 + (j + 2) % 3] - D[((i + 1) % 3) * 3 + (j + 2) % 3] * D[((i + 2) % 3) * 3 + (j + 1) % 3])
-    const double c00 = GBA_COF(0, 0), c10 = GBA_COF(1, 0), c20 = GBA_COF(2, 0);
-    const double det = (c00 * D[0] + c10 * D[3]) + c20 * D[6];
-    const double inv = 1.0 / det;
-    I[0] = c00 * inv; I[1] = c10 * inv; I[2] = c20 * inv;
-    I[3] = GBA_COF(0, 1) * inv; I[4] = GBA_COF(1, 1) * inv; I[5] = GBA_COF(2, 1) * inv;
-    I[6] = GBA_COF(0, 2) * inv; I[7] = GBA_COF(1, 2) * inv; I[8] = GBA_COF(2, 2) * inv;
-#undef GBA_COF
+    double x, y, z;
+    po_error(P, C.fx, C.fy, C.cx, C.cy, X[0], X[1], X[2], (double)e.ox, (double)e.oy, x, y, z, e0, e1);
 }
 // Dinv = (Hll + lambda I)^-1 of point p (setLambda on the landmark diagonal, block_solver.hpp:385-395)
 __device__ __forceinline__ void gba_dinv(const GbaArgs& G, int p, double lambda, double (&I)[9])
@@ -355,7 +282,7 @@ __device__ __forceinline__ void gba_dinv(const GbaArgs& G, int p, double lambda,
 #pragma unroll
     for (int m = 0; m < 9; m++) D[m] = PH[GP_HLL + m];
     D[0] += lambda; D[4] += lambda; D[8] += lambda;
-    gba_inverse3(D, I);
+    g2o_inverse3(D, I);
 }
 
 struct GbaLinShared { double part[GBA_T / 64]; double J[GBA_T][15]; double dg[6]; };
@@ -383,19 +310,11 @@ __global__ __launch_bounds__(GBA_T) void k_gba_linearize(GbaArgs G)
                 if (e.frame < 0) continue;
                 const GbaCam& C = G.cams[e.frame];
                 const PoSE3 P = C.est[cur];
-                GbaLin L;
+                PoLin L;
                 gba_linearize_edge(P, C, X, e, robust, L);
                 chiP += L.rho0;
-                // linearizeOplus (types_six_dof_expmap.cpp:103-139): _jacobianOplusXi = -1./z * tmp * R
-                const double s = -1.0 / L.z;
-                const double t0[3] = {s * C.fx, s * 0.0, s * (-L.x / L.z * C.fx)}, t1[3] = {s * 0.0, s * C.fy, s * (-L.y / L.z * C.fy)};
-                double R[9], Ji0[3], Ji1[3];
-                po_matrix_from_quat(P, R);
-#pragma unroll
-                for (int m = 0; m < 3; m++) {
-                    Ji0[m] = (t0[0] * R[m] + t0[1] * R[3 + m]) + t0[2] * R[6 + m];
-                    Ji1[m] = (t1[0] * R[m] + t1[1] * R[3 + m]) + t1[2] * R[6 + m];
-                }
+                double Ji0[3], Ji1[3];
+                po_point_jacobian(P, C.fx, C.fy, L, Ji0, Ji1);
 #pragma unroll
                 for (int a = 0; a < 3; a++) {
 #pragma unroll
@@ -415,8 +334,8 @@ __global__ __launch_bounds__(GBA_T) void k_gba_linearize(GbaArgs G)
             for (int m = 0; m < 3; m++) PH[GP_BL + m] = bl[m];
             maxd = fmax(fmax(fabs(Hl[0]), fabs(Hl[4])), fabs(Hl[8]));
         }
-        const double chi = gba_block_sum(S.part, chiP);
-        const double md = gba_block_max(S.part, maxd);
+        const double chi = g2o_block_sum(S.part, chiP);
+        const double md = g2o_block_max(S.part, maxd);
         if (tid == 0) { G.chiPart[blockIdx.x] = chi; G.maxPart[blockIdx.x] = md; }
         return;
     }
@@ -434,7 +353,7 @@ __global__ __launch_bounds__(GBA_T) void k_gba_linearize(GbaArgs G)
         if (tid < m) {
             const int k = G.camEdge[base + tid];
             const GbaEdge e = G.eI[k];
-            GbaLin L;
+            PoLin L;
             gba_linearize_edge(P, C, gba_x(G, cur, e.pt), e, robust, L);
 #pragma unroll
             for (int q = 0; q < 6; q++) { S.J[tid][q] = L.Jj0[q]; S.J[tid][6 + q] = L.Jj1[q]; }
@@ -463,11 +382,11 @@ __global__ __launch_bounds__(GBA_T) void k_gba_begin(GbaArgs G)
     const double chi = gba_reduce_sum(part, G.chiPart, G.ptBlocks);
     double md = 0.0;
     for (int k = tid; k < G.ptBlocks + st.nFree; k += GBA_T) md = fmax(md, G.maxPart[k]);
-    md = gba_block_max(part, md);
+    md = g2o_block_max(part, md);
     if (tid) return;
     GbaState* P = G.st;
-    if (!po_finite(chi)) { P->status = PGORB_GBA_NONFINITE; P->stop = 1; return; }
-    if (st.iter == 0) { P->lambda = 1e-5 * md; P->ni = 2; P->nBad = 0; }       // computeLambdaInit over every active vertex
+    if (!g2o_finite(chi)) { P->status = PGORB_GBA_NONFINITE; P->stop = 1; return; }
+    if (st.iter == 0) g2o_lm_begin(P->lm, g2o_lm_lambda_init(md));       // computeLambdaInit over every active vertex
     P->currentChi = chi; P->iniChi = chi; P->qmax = 0;
 }
 
@@ -481,7 +400,7 @@ __global__ __launch_bounds__(GBA_T) void k_gba_schur(GbaArgs G, int it)
     if (st.stop || st.iter != it) return;
     const int r = blockIdx.x, tid = threadIdx.x;
     if (r >= st.nFree) return;
-    const double lambda = st.lambda;
+    const double lambda = st.lm.lambda;
     const int f = G.rowKf[r], cs = G.camStart[f], ce = G.camStart[f + 1], lo = G.first[r];
     double* Row = G.A + (int64_t)G.off[r] * 36;
     for (int q = tid; q < (r - lo + 1) * 36; q += GBA_T) Row[q] = 0.0;
@@ -656,8 +575,8 @@ __global__ __launch_bounds__(GBA_T) void k_gba_solve(GbaArgs G, int it)
         C.est[cur ^ 1] = ok2 ? po_oplus(C.est[cur], u) : C.est[cur];
     }
     double sc = 0.0;
-    for (int k = tid; k < n * 6; k += GBA_T) sc += G.x[k] * (st.lambda * G.x[k] + G.bp[k]);
-    sc = gba_block_sum(S.part, sc);
+    for (int k = tid; k < n * 6; k += GBA_T) sc += G.x[k] * (st.lm.lambda * G.x[k] + G.bp[k]);
+    sc = g2o_block_sum(S.part, sc);
     if (tid == 0) { G.st->ok2 = ok2 ? 1 : 0; G.st->camScale = sc; }
 }
 
@@ -669,7 +588,7 @@ __global__ __launch_bounds__(GBA_T) void k_gba_try(GbaArgs G, int it)
     if (st.stop || st.iter != it) return;
     const int tid = threadIdx.x, cur = st.cur, p = blockIdx.x * GBA_T + tid;
     const bool robust = G.robust != 0, ok2 = st.ok2 != 0;
-    const double lambda = st.lambda;
+    const double lambda = st.lm.lambda;
     double chiP = 0.0, sc = 0.0;
     if (p < G.npoints && G.pInc[p]) {
         const double* PH = G.pH + (int64_t)p * GBA_PT_D;
@@ -704,15 +623,15 @@ __global__ __launch_bounds__(GBA_T) void k_gba_try(GbaArgs G, int it)
             const GbaEdge e = G.eI[k];
             if (e.frame < 0) continue;
             const GbaCam& C = G.cams[e.frame];
-            double x, y, z, e0, e1;
-            gba_error(C.est[e.row >= 0 ? cur ^ 1 : cur], C, xt, e, x, y, z, e0, e1);
-            double c2 = po_chi2(e0, e1, (double)e.w), r0 = c2, r1;
-            if (robust) gba_huber(c2, r0, r1);
+            double e0, e1;
+            gba_error(C.est[e.row >= 0 ? cur ^ 1 : cur], C, xt, e, e0, e1);
+            double c2 = g2o_chi2(e0, e1, (double)e.w), r0 = c2, r1;
+            if (robust) g2o_huber(c2, GBA_DELTA, r0, r1);
             chiP += r0;
         }
     }
-    const double chi = gba_block_sum(part, chiP);
-    const double scs = gba_block_sum(part, sc);
+    const double chi = g2o_block_sum(part, chiP);
+    const double scs = g2o_block_sum(part, sc);
     if (tid == 0) { G.chiPart[blockIdx.x] = chi; G.scPart[blockIdx.x] = scs; }
 }
 
@@ -722,27 +641,14 @@ __global__ __launch_bounds__(GBA_T) void k_gba_decide(GbaArgs G, int it)
     __shared__ double part[GBA_T / 64];
     GbaState st = *G.st;
     if (st.stop || st.iter != it) return;
-    double tempChi = gba_reduce_sum(part, G.chiPart, G.ptBlocks);
-    const double scale = (st.camScale + gba_reduce_sum(part, G.scPart, G.ptBlocks)) + 1e-3;
+    const double tempChi = gba_reduce_sum(part, G.chiPart, G.ptBlocks);
+    const double scale = st.camScale + gba_reduce_sum(part, G.scPart, G.ptBlocks);
     if (threadIdx.x) return;
-    if (!st.ok2) tempChi = GBA_DBL_MAX;
-    const double rho = (st.currentChi - tempChi) / scale;
-    if (rho > 0.0 && po_finite(tempChi)) {
-        const double t = 2.0 * rho - 1.0;
-        double alpha = 1.0 - (t * t) * t;                               // pow(2 * rho - 1, 3) read as two products
-        alpha = fmin(alpha, 2.0 / 3.0);
-        st.lambda *= fmax(1.0 / 3.0, alpha); st.ni = 2; st.currentChi = tempChi;
-        st.cur ^= 1;                                                    // discardTop: the trial estimates are the estimates
-    } else {
-        st.lambda *= (double)st.ni; st.ni *= 2;                         // pop
-    }
+    double rho;
+    if (g2o_lm_decide(st.lm, st.currentChi, tempChi, st.ok2 != 0, scale, rho)) st.cur ^= 1;      // discardTop: the trial estimates are the estimates; else pop
     st.qmax++; st.trials++;
-    if (!(rho < 0.0 && st.qmax < GBA_TRIALS)) {
-        bool stop = st.qmax == GBA_TRIALS || rho == 0.0;                // Terminate
-        if (!stop) {
-            if ((st.iniChi - st.currentChi) * 1e3 < st.iniChi) st.nBad++; else st.nBad = 0;
-            stop = st.nBad >= 3;
-        }
+    if (!g2o_lm_again(rho, st.qmax)) {
+        const bool stop = g2o_lm_stop(st.lm, st.iniChi, st.currentChi, st.qmax, rho);
         st.its++; st.iter++;
         if (stop || st.iter >= G.iterations) st.stop = 1;
     }
@@ -762,18 +668,8 @@ __global__ __launch_bounds__(GBA_T) void k_gba_finish(GbaArgs G)
         const bool live = !gba_bad(G, f);
         if (live) {
             // Converter::toCvMat(vSE3->estimate()), then SetPose's Ow = -Rcw.t()*tcw; under a status the estimate is toSE3Quat(pose)
-            const PoSE3 E = keepIn ? gba_to_se3(o) : G.cams[f].est[cur];
-            double R[9];
-            po_matrix_from_quat(E, R);
-#pragma unroll
-            for (int r = 0; r < 3; r++) {
-#pragma unroll
-                for (int c = 0; c < 3; c++) o.Tcw[r * 4 + c] = __double2float_rn(R[r * 3 + c]);
-            }
-            o.Tcw[3] = __double2float_rn(E.tx); o.Tcw[7] = __double2float_rn(E.ty); o.Tcw[11] = __double2float_rn(E.tz);
-#pragma unroll
-            for (int i = 0; i < 3; i++)
-                o.Ow[i] = cnm_f(__dmul_rn((double)cnm_dot3f(o.Tcw[i], o.Tcw[4 + i], o.Tcw[8 + i], o.Tcw[3], o.Tcw[7], o.Tcw[11]), -1.0));
+            const PoSE3 E = keepIn ? po_from_pose(o) : G.cams[f].est[cur];
+            po_set_pose(E, o);
         }
         G.poseOut[f] = o;
         G.kfDone[f] = live ? 1 : 0;
@@ -796,9 +692,9 @@ __global__ __launch_bounds__(GBA_T) void k_gba_finish(GbaArgs G)
         const GbaEdge e = G.eI[g];
         if (!keepIn && e.frame >= 0) {
             const GbaCam& C = G.cams[e.frame];
-            double x, y, z, e0, e1;
-            gba_error(C.est[cur], C, gba_x(G, cur, e.pt), e, x, y, z, e0, e1);
-            c2 = __double2float_rn(po_chi2(e0, e1, (double)e.w));
+            double e0, e1;
+            gba_error(C.est[cur], C, gba_x(G, cur, e.pt), e, e0, e1);
+            c2 = __double2float_rn(g2o_chi2(e0, e1, (double)e.w));
         }
         G.chi2[g] = c2;
     }
@@ -866,7 +762,7 @@ int pgorb_global_bundle_adjustment_device(pgorb_ctx* c, const pgorb_keypoint* d_
         for (int it = 0; it < iterations; it++) {
             hipLaunchKernelGGL(k_gba_linearize, dim3((unsigned)(G.ptBlocks + nframes)), dim3(GBA_T), 0, s, G);
             hipLaunchKernelGGL(k_gba_begin, dim3(1), dim3(GBA_T), 0, s, G);
-            for (int q = 0; q < GBA_TRIALS; q++) {
+            for (int q = 0; q < G2O_LM_TRIALS; q++) {
                 hipLaunchKernelGGL(k_gba_schur, dim3((unsigned)nframes), dim3(GBA_T), 0, s, G, it);
                 hipLaunchKernelGGL(k_gba_solve, dim3(1), dim3(GBA_T), 0, s, G, it);
                 hipLaunchKernelGGL(k_gba_try, dim3((unsigned)G.ptBlocks), dim3(GBA_T), 0, s, G, it);

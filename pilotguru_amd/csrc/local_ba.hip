@@ -14,6 +14,9 @@
 //   KeyFrame::SetPose                             src/KeyFrame.cc
 // in double, under the ten readings of DESIGN.md section 5 (the local-bundle-adjustment rows of section 4).  This is the project's
 // reading of g2o and Eigen, anchored by the CPU tests of tests/test_local_bundle_adjustment.py and not pinned to a g2o build.
+// Shared, each in one copy: Huber, Levenberg's step control, the block reductions and the 3 x 3 inverse are g2o_lm.h's (with
+// pose_opt.hip, optimize_sim3.hip, essential_graph.hip, global_ba.hip); SE3Quat, EdgeSE3ProjectXYZ's error and linearisation,
+// toSE3Quat and SetPose are g2o_se3.h's (the linearisation with global_ba.hip, the rest with pose_opt.hip as well).
 //
 // k_lba_prepare, one workgroup per window: the flags (role per frame, is_local per point), the window's point list in table order
 // with each point's CSR range, its cameras in frame order, the integer half of every edge record, and each free camera's edge list.
@@ -71,37 +74,6 @@ struct LbaShared {
     double bp[6 * PGORB_LBA_MAX_LOCAL_KF], x[6 * PGORB_LBA_MAX_LOCAL_KF];
 };
 
-__device__ __forceinline__ int lba_block_sum(LbaShared& S, int v)
-{
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    if ((threadIdx.x & 63) == 0) S.cnt[threadIdx.x >> 6] = v;
-    __syncthreads();
-    const int r = (S.cnt[0] + S.cnt[1]) + (S.cnt[2] + S.cnt[3]);
-    __syncthreads();
-    return r;
-}
-// the fixed tree: a butterfly inside the wave (a + b is b + a bit for bit, so every lane ends with the same sum), then (w0 + w1) + (w2 + w3)
-__device__ __forceinline__ double lba_block_sum(LbaShared& S, double v)
-{
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    if ((threadIdx.x & 63) == 0) S.part[threadIdx.x >> 6] = v;
-    __syncthreads();
-    const double r = (S.part[0] + S.part[1]) + (S.part[2] + S.part[3]);
-    __syncthreads();
-    return r;
-}
-__device__ __forceinline__ double lba_block_max(LbaShared& S, double v)
-{
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v = fmax(v, __shfl_xor(v, m, 64));
-    if ((threadIdx.x & 63) == 0) S.part[threadIdx.x >> 6] = v;
-    __syncthreads();
-    const double r = fmax(fmax(S.part[0], S.part[1]), fmax(S.part[2], S.part[3]));
-    __syncthreads();
-    return r;
-}
 // the place of a flagged thread among the block's flagged threads, in thread order; total = how many there are
 __device__ __forceinline__ int lba_rank(int* cnt, bool in, int& total)
 {
@@ -190,7 +162,7 @@ __global__ __launch_bounds__(LBA_T) void k_lba_prepare(LbaBatch B)
             B.eI[k].cam = ok ? -2 : -1;
         }
     }
-    const int nE = lba_block_sum(S, cnt);                               // (its barriers also publish the roles)
+    const int nE = g2o_block_sum(S.cnt, cnt);                               // (its barriers also publish the roles)
     // the cameras in frame order; the free ones (local and not the key frame with mnId 0, :529) get the columns of the reduced system
     int nCam = 0, nFree = 0, nLocal = 0;
     for (int f0 = 0; f0 < B.nframes; f0 += LBA_T) {
@@ -262,32 +234,6 @@ __global__ __launch_bounds__(LBA_T) void k_lba_prepare(LbaBatch B)
     }
 }
 
-struct LbaCamD { PoSE3 P; double fx, fy, cx, cy; };
-
-// computeError: obs - cam_project(v1->estimate().map(v2->estimate())); (x, y, z) = the mapped point
-__device__ __forceinline__ void lba_error(const PoSE3& P, double fx, double fy, double cx, double cy, const double* X, const LbaEdgeI& e,
-                                          double& x, double& y, double& z, double& e0, double& e1)
-{
-    double rx, ry, rz;
-    po_rotate(P, X[0], X[1], X[2], rx, ry, rz);
-    x = rx + P.tx; y = ry + P.ty; z = rz + P.tz;
-    e0 = (double)e.ox - ((x / z) * fx + cx);
-    e1 = (double)e.oy - ((y / z) * fy + cy);
-}
-
-// Eigen's fixed-size 3 x 3 inverse (Inverse.h compute_inverse<Matrix3d>): cofactors, the determinant from the first cofactor column, no test
-__device__ __forceinline__ void lba_inverse3(const double (&D)[9], double (&I)[9])
-{
-#define LBA_COF(i, j) (D[((i + 1) % 3) * 3 + (j + 1) % 3] * D[((i + 2) % 3) * 3 + (j + 2) % 3] - D[((i + 1) % 3) * 3 + (j + 2) % 3] * D[((i + 2) % 3) * 3 + (j + 1) % 3])
-    const double c00 = LBA_COF(0, 0), c10 = LBA_COF(1, 0), c20 = LBA_COF(2, 0);
-    const double det = (c00 * D[0] + c10 * D[3]) + c20 * D[6];
-    const double inv = 1.0 / det;
-    I[0] = c00 * inv; I[1] = c10 * inv; I[2] = c20 * inv;
-    I[3] = LBA_COF(0, 1) * inv; I[4] = LBA_COF(1, 1) * inv; I[5] = LBA_COF(2, 1) * inv;
-    I[6] = LBA_COF(0, 2) * inv; I[7] = LBA_COF(1, 2) * inv; I[8] = LBA_COF(2, 2) * inv;
-#undef LBA_COF
-}
-
 // activeRobustChi2 at the trial estimates (computeActiveErrors stores every active edge's _error: reading 6)
 __device__ __forceinline__ double lba_trial_chi2(LbaShared& S, const LbaBatch& B, const LbaWin& W, int nP, bool robust)
 {
@@ -303,16 +249,16 @@ __device__ __forceinline__ double lba_trial_chi2(LbaShared& S, const LbaBatch& B
             if (e.cam < 0 || e.level) continue;
             const LbaCam& C = W.cams[e.cam];
             double x, y, z, e0, e1;
-            lba_error(C.trial, C.fx, C.fy, C.cx, C.cy, PD + LP_XT, e, x, y, z, e0, e1);
+            po_error(C.trial, C.fx, C.fy, C.cx, C.cy, PD[LP_XT], PD[LP_XT + 1], PD[LP_XT + 2], (double)e.ox, (double)e.oy, x, y, z, e0, e1);
             double* ED = B.eD + (int64_t)k * LBA_EDGE_D;
             ED[LE_ERR] = e0; ED[LE_ERR + 1] = e1;
-            double c2 = po_chi2(e0, e1, (double)e.w), r0 = c2, r1;
-            if (robust) po_huber(c2, r0, r1);
+            double c2 = g2o_chi2(e0, e1, (double)e.w), r0 = c2, r1;
+            if (robust) g2o_huber(c2, PO_DELTA, r0, r1);
             chiP += r0;
         }
         acc += chiP;
     }
-    return lba_block_sum(S, acc);
+    return g2o_block_sum(S.part, acc);
 }
 
 // e->chi2() > 5.991 || !e->isDepthPositive() over every edge: chi2 of the stored _error, the depth at the estimates (readings 6, 7).
@@ -328,11 +274,11 @@ __device__ __forceinline__ int lba_classify(LbaShared& S, const LbaBatch& B, con
             const LbaEdgeI e = B.eI[k];
             if (e.cam < 0) continue;
             const double* ED = B.eD + (int64_t)k * LBA_EDGE_D;
-            const double c2 = po_chi2(ED[LE_ERR], ED[LE_ERR + 1], (double)e.w);
-            if (!po_finite(c2)) nonfinite = 1;
+            const double c2 = g2o_chi2(ED[LE_ERR], ED[LE_ERR + 1], (double)e.w);
+            if (!g2o_finite(c2)) nonfinite = 1;
             const LbaCam& C = W.cams[e.cam];
             double rx, ry, rz;
-            po_rotate(C.est, PD[LP_X], PD[LP_X + 1], PD[LP_X + 2], rx, ry, rz);
+            g2o_rotate(C.est, PD[LP_X], PD[LP_X + 1], PD[LP_X + 2], rx, ry, rz);
             const int out = (c2 > 5.991 || !(rz + C.est.tz > 0.0)) ? 1 : 0;
             bad += out;
             if (!final) B.eI[k].level = out;
@@ -343,7 +289,7 @@ __device__ __forceinline__ int lba_classify(LbaShared& S, const LbaBatch& B, con
         }
     }
     if (__syncthreads_or(nonfinite)) return -1;
-    return lba_block_sum(S, bad);
+    return g2o_block_sum(S.cnt, bad);
 }
 
 __global__ __launch_bounds__(LBA_T) void k_lba(LbaBatch B)
@@ -359,12 +305,7 @@ __global__ __launch_bounds__(LBA_T) void k_lba(LbaBatch B)
     for (int c = tid; c < nCam; c += LBA_T) {
         LbaCam& C = W.cams[c];
         const pgorb_kf_pose in = B.pose[C.frame];
-        const double R[9] = {(double)in.Tcw[0], (double)in.Tcw[1], (double)in.Tcw[2], (double)in.Tcw[4], (double)in.Tcw[5], (double)in.Tcw[6],
-                             (double)in.Tcw[8], (double)in.Tcw[9], (double)in.Tcw[10]};
-        PoSE3 E;
-        po_quat_from_matrix(R, E);
-        E.tx = (double)in.Tcw[3]; E.ty = (double)in.Tcw[7]; E.tz = (double)in.Tcw[11];
-        po_normalize(E);
+        const PoSE3 E = po_from_pose(in);
         C.est = E; C.trial = E;
         C.fx = (double)in.fx; C.fy = (double)in.fy; C.cx = (double)in.cx; C.cy = (double)in.cy;
         if (C.col >= 0) S.freeCam[C.col] = c;
@@ -398,11 +339,10 @@ __global__ __launch_bounds__(LBA_T) void k_lba(LbaBatch B)
             B.pAct[W.ptList[j]] = a > 0;
             nAct += a;
         }
-        nAct = lba_block_sum(S, nAct);
+        nAct = g2o_block_sum(S.cnt, nAct);
         if (nAct == 0) continue;                                        // optimize() over an empty active set returns at once
 
-        double lambda = 0.0;
-        int ni = 2, nBad = 0;
+        G2oLm lm = {0.0, 2, 0};
         for (int iter = 0; iter < iterations && !status; iter++) {
             // computeActiveErrors, activeRobustChi2, buildSystem: the landmark half, point by point
             double acc = 0.0, maxd = 0.0;
@@ -420,41 +360,24 @@ __global__ __launch_bounds__(LBA_T) void k_lba(LbaBatch B)
                     if (e.cam < 0 || e.level) continue;
                     const LbaCam& C = W.cams[e.cam];
                     const PoSE3 P = C.est;
-                    const double fx = C.fx, fy = C.fy;
-                    double x, y, z, e0, e1;
-                    lba_error(P, fx, fy, C.cx, C.cy, PD + LP_X, e, x, y, z, e0, e1);
-                    const double wgt = (double)e.w;
-                    const double c2 = po_chi2(e0, e1, wgt);
-                    double rho0 = c2, rho1 = 1.0;
-                    if (robust) po_huber(c2, rho0, rho1);
-                    chiP += rho0;
-                    // linearizeOplus (types_six_dof_expmap.cpp:103-139): _jacobianOplusXi = -1./z * tmp * R, _jacobianOplusXj analytic
-                    const double z2 = z * z, s = -1.0 / z;
-                    const double t0[3] = {s * fx, s * 0.0, s * (-x / z * fx)}, t1[3] = {s * 0.0, s * fy, s * (-y / z * fy)};
-                    double R[9], Ji0[3], Ji1[3];
-                    po_matrix_from_quat(P, R);
-#pragma unroll
-                    for (int m = 0; m < 3; m++) {
-                        Ji0[m] = (t0[0] * R[m] + t0[1] * R[3 + m]) + t0[2] * R[6 + m];
-                        Ji1[m] = (t1[0] * R[m] + t1[1] * R[3 + m]) + t1[2] * R[6 + m];
-                    }
-                    const double Jj0[6] = {x * y / z2 * fx, -(1.0 + (x * x / z2)) * fx, y / z * fx, -1.0 / z * fx, 0.0, x / z2 * fx};
-                    const double Jj1[6] = {(1.0 + y * y / z2) * fy, -x * y / z2 * fy, -x / z * fy, 0.0, -1.0 / z * fy, y / z2 * fy};
-                    // constructQuadraticForm: omega_r = -omega * _error (times rho[1]), weightedOmega = rho[1] * omega
-                    const double wO = rho1 * wgt, r0 = -(wgt * e0) * rho1, r1 = -(wgt * e1) * rho1;
+                    PoLin L;
+                    double Ji0[3], Ji1[3];
+                    po_linearize_xyz(P, C.fx, C.fy, C.cx, C.cy, PD + LP_X, (double)e.ox, (double)e.oy, (double)e.w, robust, PO_DELTA, L);
+                    po_point_jacobian(P, C.fx, C.fy, L, Ji0, Ji1);
+                    chiP += L.rho0;
 #pragma unroll
                     for (int a = 0; a < 3; a++) {
 #pragma unroll
-                        for (int b = 0; b < 3; b++) Hl[a * 3 + b] += (Ji0[a] * wO) * Ji0[b] + (Ji1[a] * wO) * Ji1[b];
-                        bl[a] += Ji0[a] * r0 + Ji1[a] * r1;
+                        for (int b = 0; b < 3; b++) Hl[a * 3 + b] += (Ji0[a] * L.wO) * Ji0[b] + (Ji1[a] * L.wO) * Ji1[b];
+                        bl[a] += Ji0[a] * L.r0 + Ji1[a] * L.r1;
                     }
                     double* ED = B.eD + (int64_t)k * LBA_EDGE_D;
-                    ED[LE_ERR] = e0; ED[LE_ERR + 1] = e1; ED[LE_WO] = wO; ED[LE_R] = r0; ED[LE_R + 1] = r1;
+                    ED[LE_ERR] = L.e0; ED[LE_ERR + 1] = L.e1; ED[LE_WO] = L.wO; ED[LE_R] = L.r0; ED[LE_R + 1] = L.r1;
 #pragma unroll
                     for (int a = 0; a < 6; a++) {
-                        ED[LE_JJ + a] = Jj0[a]; ED[LE_JJ + 6 + a] = Jj1[a];
+                        ED[LE_JJ + a] = L.Jj0[a]; ED[LE_JJ + 6 + a] = L.Jj1[a];
 #pragma unroll
-                        for (int m = 0; m < 3; m++) ED[LE_W + a * 3 + m] = (Jj0[a] * wO) * Ji0[m] + (Jj1[a] * wO) * Ji1[m];
+                        for (int m = 0; m < 3; m++) ED[LE_W + a * 3 + m] = (L.Jj0[a] * L.wO) * Ji0[m] + (L.Jj1[a] * L.wO) * Ji1[m];
                     }
                 }
 #pragma unroll
@@ -464,9 +387,9 @@ __global__ __launch_bounds__(LBA_T) void k_lba(LbaBatch B)
                 maxd = fmax(fmax(fabs(Hl[0]), fabs(Hl[4])), fmax(fabs(Hl[8]), maxd));
                 acc += chiP;
             }
-            double currentChi = lba_block_sum(S, acc);
+            double currentChi = g2o_block_sum(S.part, acc);
             const double iniChi = currentChi;
-            if (!po_finite(currentChi)) { status = PGORB_LBA_NONFINITE; break; }
+            if (!g2o_finite(currentChi)) { status = PGORB_LBA_NONFINITE; break; }
             // the camera half: each row of Hpp and bp by its own thread, over the points in list order
             for (int row = tid; row < n6; row += LBA_T) {
                 const int c = row / 6, r = row % 6;
@@ -487,12 +410,13 @@ __global__ __launch_bounds__(LBA_T) void k_lba(LbaBatch B)
                 maxd = fmax(fabs(h[r]), maxd);
             }
             if (iter == 0) {                                            // computeLambdaInit over every active vertex (reading 5); the barriers publish Hpp, bp
-                lambda = 1e-5 * lba_block_max(S, maxd); ni = 2; nBad = 0;
+                g2o_lm_begin(lm, g2o_lm_lambda_init(g2o_block_max(S.part, maxd)));
             } else __syncthreads();
             its[round]++;
             double rho = 0.0;
             int qmax = 0;
             do {
+                const double lambda = lm.lambda;
                 // setLambda on both diagonals; Dinv = D->inverse(), db = Dinv * bl (block_solver.hpp:385-395)
                 for (int j = tid; j < nP; j += LBA_T) {
                     const int p = W.ptList[j];
@@ -502,7 +426,7 @@ __global__ __launch_bounds__(LBA_T) void k_lba(LbaBatch B)
 #pragma unroll
                     for (int m = 0; m < 9; m++) D[m] = PD[LP_HLL + m];
                     D[0] += lambda; D[4] += lambda; D[8] += lambda;
-                    lba_inverse3(D, I);
+                    g2o_inverse3(D, I);
 #pragma unroll
                     for (int m = 0; m < 9; m++) PD[LP_DINV + m] = I[m];
 #pragma unroll
@@ -616,15 +540,9 @@ __global__ __launch_bounds__(LBA_T) void k_lba(LbaBatch B)
                     for (int m = 0; m < 3; m++) PD[LP_XT + m] = PD[LP_X + m] + xl[m];
                     sc += (xl[0] * (lambda * xl[0] + PD[LP_BL]) + xl[1] * (lambda * xl[1] + PD[LP_BL + 1])) + xl[2] * (lambda * xl[2] + PD[LP_BL + 2]);
                 }
-                const double scale = lba_block_sum(S, sc) + 1e-3;       // (its barriers publish the trial cameras)
-                double tempChi = lba_trial_chi2(S, B, W, nP, robust);
-                if (!ok2) tempChi = 1.7976931348623157e308;
-                rho = (currentChi - tempChi) / scale;
-                if (rho > 0.0 && po_finite(tempChi)) {
-                    const double t = 2.0 * rho - 1.0;
-                    double alpha = 1.0 - (t * t) * t;                   // pow(2 * rho - 1, 3) read as two products
-                    alpha = fmin(alpha, 2.0 / 3.0);
-                    lambda *= fmax(1.0 / 3.0, alpha); ni = 2; currentChi = tempChi;
+                const double scale = g2o_block_sum(S.part, sc);         // (its barriers publish the trial cameras)
+                const double tempChi = lba_trial_chi2(S, B, W, nP, robust);
+                if (g2o_lm_decide(lm, currentChi, tempChi, ok2, scale, rho)) {
                     for (int c = tid; c < nFree; c += LBA_T) { LbaCam& C = W.cams[S.freeCam[c]]; C.est = C.trial; }      // discardTop
                     for (int j = tid; j < nP; j += LBA_T) {
                         if (!B.pAct[W.ptList[j]]) continue;
@@ -632,15 +550,11 @@ __global__ __launch_bounds__(LBA_T) void k_lba(LbaBatch B)
 #pragma unroll
                         for (int m = 0; m < 3; m++) PD[LP_X + m] = PD[LP_XT + m];
                     }
-                } else {
-                    lambda *= (double)ni; ni *= 2;                      // pop: the estimates stay, the stored errors are the trial's (reading 6)
-                }
+                }                                                       // else pop: the estimates stay, the stored errors are the trial's (reading 6)
                 __syncthreads();
                 qmax++; trials[round]++;
-            } while (rho < 0.0 && qmax < 10);
-            if (qmax == 10 || rho == 0.0) break;                        // Terminate
-            if ((iniChi - currentChi) * 1e3 < iniChi) nBad++; else nBad = 0;
-            if (nBad >= 3) break;
+            } while (g2o_lm_again(rho, qmax));
+            if (g2o_lm_stop(lm, iniChi, currentChi, qmax, rho)) break;
         }
         if (status) break;
         if (round == 0 && B.rounds >= 2) {
@@ -665,19 +579,7 @@ __global__ __launch_bounds__(LBA_T) void k_lba(LbaBatch B)
         const LbaCam& C = W.cams[c];
         if (C.role != PGORB_LBA_ROLE_LOCAL) continue;
         pgorb_kf_pose o = B.pose[C.frame];
-        if (!status) {
-            double R[9];
-            po_matrix_from_quat(C.est, R);
-#pragma unroll
-            for (int r = 0; r < 3; r++) {
-#pragma unroll
-                for (int cc = 0; cc < 3; cc++) o.Tcw[r * 4 + cc] = __double2float_rn(R[r * 3 + cc]);
-            }
-            o.Tcw[3] = __double2float_rn(C.est.tx); o.Tcw[7] = __double2float_rn(C.est.ty); o.Tcw[11] = __double2float_rn(C.est.tz);
-#pragma unroll
-            for (int i = 0; i < 3; i++)
-                o.Ow[i] = cnm_f(__dmul_rn((double)cnm_dot3f(o.Tcw[i], o.Tcw[4 + i], o.Tcw[8 + i], o.Tcw[3], o.Tcw[7], o.Tcw[11]), -1.0));
-        }
+        if (!status) po_set_pose(C.est, o);
         B.poseOut[C.frame] = o;
     }
     if (!status)

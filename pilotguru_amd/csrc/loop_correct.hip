@@ -221,7 +221,7 @@ __global__ __launch_bounds__(LC_T) void k_mu_kf(MuArgs M)
                 }
 #pragma unroll
                 for (int q = 0; q < 12; q++) out.Tcw[q] = T[q];
-                lp_set_ow(out);
+                po_set_ow(out);
                 atomicAdd(&M.info[2], 1);
             }
             atomicAdd(&M.info[1], 1);

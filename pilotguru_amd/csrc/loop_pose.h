@@ -3,22 +3,15 @@
 // product of cv::Mat, and the two pieces of MapPoint::UpdateNormalAndDepth.  DESIGN.md section 4 lists the readings.
 #pragma once
 #include "match_common.h"
+#include "g2o_se3.h"                       // po_set_ow: SetPose's Ow
 #include "g2o_sim3.h"
 
 // Sim3::map: s*(r*xyz) + t
 __device__ __forceinline__ void lp_map(const OsSim& S, double X, double Y, double Z, double& x, double& y, double& z)
 {
     double rx, ry, rz;
-    os_rotate(S.qx, S.qy, S.qz, S.qw, X, Y, Z, rx, ry, rz);
+    g2o_rotate(S, X, Y, Z, rx, ry, rz);
     x = S.s * rx + S.tx; y = S.s * ry + S.ty; z = S.s * rz + S.tz;
-}
-
-// KeyFrame::SetPose's Ow = -Rcw.t()*tcw of o.Tcw: gemm's small-matrix path times alpha = -1 in double
-__device__ __forceinline__ void lp_set_ow(pgorb_kf_pose& o)
-{
-#pragma unroll
-    for (int c = 0; c < 3; c++)
-        o.Ow[c] = cnm_f(__dmul_rn((double)cnm_dot3f(o.Tcw[c], o.Tcw[4 + c], o.Tcw[8 + c], o.Tcw[3], o.Tcw[7], o.Tcw[11]), -1.0));
 }
 
 // [R | t/s] of a Sim3 (Optimizer.cc:1001-1007, LoopClosing.cc:504-510) through Converter::toCvSE3 to float, then SetPose's Ow; the
@@ -26,7 +19,7 @@ __device__ __forceinline__ void lp_set_ow(pgorb_kf_pose& o)
 __device__ __forceinline__ void lp_pose_from_sim3(const OsSim& S, pgorb_kf_pose& o)
 {
     double R[9];
-    os_matrix_from_quat(S, R);
+    g2o_matrix_from_quat(S, R);
     const double k = 1.0 / S.s;
     const double t[3] = {S.tx * k, S.ty * k, S.tz * k};
 #pragma unroll
@@ -35,7 +28,7 @@ __device__ __forceinline__ void lp_pose_from_sim3(const OsSim& S, pgorb_kf_pose&
         for (int c = 0; c < 3; c++) o.Tcw[r * 4 + c] = __double2float_rn(R[r * 3 + c]);
         o.Tcw[r * 4 + 3] = __double2float_rn(t[r]);
     }
-    lp_set_ow(o);
+    po_set_ow(o);
 }
 
 // GetPoseInverse() of a pose as given: Twc = [Rcw' | Ow], rows 0-2
@@ -62,8 +55,7 @@ __device__ __forceinline__ void lp_mul44(const float* A, const float* B, float (
 __device__ __forceinline__ OsSim lp_sim3_from_pose(const float* T)
 {
     OsSim S;
-    const double R[9] = {(double)T[0], (double)T[1], (double)T[2], (double)T[4], (double)T[5], (double)T[6], (double)T[8], (double)T[9], (double)T[10]};
-    os_quat_from_matrix(R, S);
+    g2o_quat_from_pose(T, S);
     S.tx = (double)T[3]; S.ty = (double)T[7]; S.tz = (double)T[11]; S.s = 1.0;
     return S;
 }

@@ -13,6 +13,9 @@
 //   LinearSolverDense::solve                      g2o/solvers/linear_solver_dense.h:104-112
 // in double, in the reference's operation order per edge, under the readings of DESIGN.md section 4 (the OptimizeSim3 rows).  This is
 // the project's reading of g2o and Eigen, anchored by the CPU tests of tests/test_optimize_sim3.py and not pinned to a g2o build.
+// Shared, each in one copy: Huber, the LDLT, Levenberg's step control, the block reductions and the quaternion are g2o_lm.h's (with
+// pose_opt.hip, local_ba.hip, essential_graph.hip, global_ba.hip); Sim3 is g2o_sim3.h's (with essential_graph.hip and loop_pose.h);
+// SetPose's Ow is g2o_se3.h's.  This file's own: the two edges' computeError through Sim3::map and the numeric Jacobian.
 //
 // k_optimize_sim3, OS_T threads:
 //   1. the correspondences (a match whose two slots hold good points) are compacted in i1 order by ballot prefix into 64-byte records
@@ -23,6 +26,7 @@
 //      inside each wave and then as (w0 + w1) + (w2 + w3) through LDS -- one fixed tree, so a pair's result depends on its inputs alone;
 //   4. the Levenberg state is carried identically by every lane.  Every loop is bounded by 2 calls x 10 iterations x 10 trials.
 #include "kf_window.h"
+#include "g2o_se3.h"                        // po_set_ow: SetPose's Ow
 #include "g2o_sim3.h"
 #include <math.h>
 #include <string>
@@ -31,7 +35,6 @@
 #define OS_WAVES (OS_T / 64)
 #define OS_MAX_N 16000            // keypoints per key frame, as for the matchers
 #define OS_NRED 36                // 28 + 7 + 1
-#define OS_DBL_MAX 1.7976931348623157e308
 
 struct OsRec { float P1[3], P2[3], o1[2], o2[2], w1, w2; int32_t i1, i2, dead, pad; };
 static_assert(sizeof(OsRec) == 64, "four dwordx4");
@@ -51,26 +54,11 @@ struct OsCam { double fx, fy, cx, cy; };
 __device__ __forceinline__ void os_error(const OsSim& S, const OsCam& C, double X, double Y, double Z, double ox, double oy, double& e0, double& e1)
 {
     double rx, ry, rz;
-    os_rotate(S.qx, S.qy, S.qz, S.qw, X, Y, Z, rx, ry, rz);
+    g2o_rotate(S, X, Y, Z, rx, ry, rz);
     const double x = S.s * rx + S.tx, y = S.s * ry + S.ty, z = S.s * rz + S.tz;
     e0 = ox - ((x / z) * C.fx + C.cx);
     e1 = oy - ((y / z) * C.fy + C.cy);
 }
-// chi2 = _error.dot(information * _error), information = invSigma2 * I
-__device__ __forceinline__ double os_chi2(double e0, double e1, double w) { return e0 * (w * e0) + e1 * (w * e1); }
-
-// RobustKernelHuber::robustify: rho[0], rho[1]
-__device__ __forceinline__ void os_huber(double e, double delta, double& rho0, double& rho1)
-{
-    const double dsqr = delta * delta;
-    if (e <= dsqr) { rho0 = e; rho1 = 1.0; }
-    else {
-        const double sqrte = __dsqrt_rn(e);
-        rho0 = 2.0 * sqrte * delta - dsqr;
-        rho1 = delta / sqrte;
-    }
-}
-
 __device__ __forceinline__ OsRec os_load(const OsRec* r)
 {
     const float4* s = reinterpret_cast<const float4*>(r);
@@ -84,45 +72,10 @@ __device__ __forceinline__ OsRec os_load(const OsRec* r)
 
 struct OsShared {
     OsSim pert[14], pinv[14];             // Sim3(+delta e_d) * estimate at 2d, Sim3(-delta e_d) * estimate at 2d + 1, and their inverses
-    double part[OS_WAVES][OS_NRED];
+    double part[OS_WAVES][OS_NRED];       // part[0][0 .. 3] also serve the scalar sums
     double red[OS_NRED];
     int cnt[OS_WAVES];
 };
-
-__device__ __forceinline__ int os_block_sum(OsShared& S, int v)
-{
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    if ((threadIdx.x & 63) == 0) S.cnt[threadIdx.x >> 6] = v;
-    __syncthreads();
-    const int r = (S.cnt[0] + S.cnt[1]) + (S.cnt[2] + S.cnt[3]);
-    __syncthreads();
-    return r;
-}
-// the fixed tree: a butterfly inside the wave (a + b is b + a bit for bit, so every lane ends with the same sum), then (w0 + w1) + (w2 + w3)
-__device__ __forceinline__ double os_block_sum(OsShared& S, double v)
-{
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    if ((threadIdx.x & 63) == 0) S.part[threadIdx.x >> 6][0] = v;
-    __syncthreads();
-    const double r = (S.part[0][0] + S.part[1][0]) + (S.part[2][0] + S.part[3][0]);
-    __syncthreads();
-    return r;
-}
-__device__ __forceinline__ void os_block_sum36(OsShared& S, double (&v)[OS_NRED])
-{
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1)
-#pragma unroll
-        for (int k = 0; k < OS_NRED; k++) v[k] += __shfl_xor(v[k], m, 64);
-    if ((threadIdx.x & 63) == 0)
-#pragma unroll
-        for (int k = 0; k < OS_NRED; k++) S.part[threadIdx.x >> 6][k] = v[k];
-    __syncthreads();
-    if (threadIdx.x < OS_NRED) S.red[threadIdx.x] = (S.part[0][threadIdx.x] + S.part[1][threadIdx.x]) + (S.part[2][threadIdx.x] + S.part[3][threadIdx.x]);
-    __syncthreads();
-}
 
 // One edge into the lane's sums: computeError at the estimate, the numeric Jacobian against the 14 perturbed estimates of LDS
 // (INV: their inverses), constructQuadraticForm with the Huber kernel
@@ -132,9 +85,9 @@ __device__ __forceinline__ void os_edge(const OsShared& S, const OsSim& at, cons
 {
     double e0, e1;
     os_error(at, C, X, Y, Z, ox, oy, e0, e1);
-    const double c2 = os_chi2(e0, e1, w);
+    const double c2 = g2o_chi2(e0, e1, w);
     double rho0, rho1;
-    os_huber(c2, delta, rho0, rho1);
+    g2o_huber(c2, delta, rho0, rho1);
     const double scalar = 1.0 / (2.0 * 1e-9);
     double J0[7], J1[7];
     // The 28 estimates do not change inside the caller's loop, so the compiler would read them all ahead of it and hold 448 VGPRs
@@ -175,56 +128,14 @@ __device__ __forceinline__ double os_active_chi2(OsShared& S, const OsRec* E, in
         if (r.dead) continue;
         double e0, e1, r0, r1;
         os_error(P, C1, (double)r.P2[0], (double)r.P2[1], (double)r.P2[2], (double)r.o1[0], (double)r.o1[1], e0, e1);
-        os_huber(os_chi2(e0, e1, (double)r.w1), delta, r0, r1);
+        g2o_huber(g2o_chi2(e0, e1, (double)r.w1), delta, r0, r1);
         acc += r0;
         os_error(Pi, C2, (double)r.P1[0], (double)r.P1[1], (double)r.P1[2], (double)r.o2[0], (double)r.o2[1], e0, e1);
-        os_huber(os_chi2(e0, e1, (double)r.w2), delta, r0, r1);
+        g2o_huber(g2o_chi2(e0, e1, (double)r.w2), delta, r0, r1);
         acc += r0;
     }
-    return os_block_sum(S, acc);
+    return g2o_block_sum(S.part[0], acc);
 }
-
-// LinearSolverDense: an LDLT of the 7 x 7 in index order (no pivoting: DESIGN.md section 4); false = a factor is not positive
-__device__ __forceinline__ bool os_solve(const double (&H)[7][7], const double (&b)[7], double (&x)[7])
-{
-    double L[7][7], d[7];
-    bool ok = true;
-#pragma unroll
-    for (int j = 0; j < 7; j++) {
-        double s = H[j][j];
-#pragma unroll
-        for (int k = 0; k < j; k++) s -= (L[j][k] * L[j][k]) * d[k];
-        d[j] = s;
-        ok = ok && (s > 0.0);
-#pragma unroll
-        for (int i = j + 1; i < 7; i++) {
-            double t = H[j][i];
-#pragma unroll
-            for (int k = 0; k < j; k++) t -= (L[i][k] * L[j][k]) * d[k];
-            L[i][j] = t / s;
-        }
-    }
-    double y[7];
-#pragma unroll
-    for (int i = 0; i < 7; i++) {
-        double t = b[i];
-#pragma unroll
-        for (int k = 0; k < i; k++) t -= L[i][k] * y[k];
-        y[i] = t;
-    }
-#pragma unroll
-    for (int i = 0; i < 7; i++) y[i] = y[i] / d[i];
-#pragma unroll
-    for (int i = 6; i >= 0; i--) {
-        double t = y[i];
-#pragma unroll
-        for (int k = i + 1; k < 7; k++) t -= L[k][i] * x[k];
-        x[i] = t;
-    }
-    return ok;
-}
-
-__device__ __forceinline__ bool os_finite(double v) { return fabs(v) <= OS_DBL_MAX; }      // false for a NaN
 
 __global__ __launch_bounds__(OS_T) void k_optimize_sim3(OsBatch B)
 {
@@ -297,7 +208,7 @@ __global__ __launch_bounds__(OS_T) void k_optimize_sim3(OsBatch B)
         double R[9];
 #pragma unroll
         for (int k = 0; k < 9; k++) R[k] = (double)in.R12[k];
-        os_quat_from_matrix(R, est);
+        g2o_quat_from_matrix(R, est);
         est.tx = (double)in.t12[0]; est.ty = (double)in.t12[1]; est.tz = (double)in.t12[2]; est.s = (double)in.s12;
     }
 
@@ -308,8 +219,7 @@ __global__ __launch_bounds__(OS_T) void k_optimize_sim3(OsBatch B)
         const int iterations = call == 0 ? 5 : nMore;
         // SparseOptimizer::optimize(iterations); an empty active set returns at once
         if (nE - nBad > 0) {
-            double lambda = 0.0;
-            int ni = 2, nBadIt = 0;
+            G2oLm lm = {0.0, 2, 0};
             for (int iter = 0; iter < iterations; iter++) {
                 // linearizeOplus' perturbed estimates: oplus(+-delta e_d); under fix_scale oplusImpl zeroes add_vi[6]
                 if (tid < 14) {
@@ -336,66 +246,26 @@ __global__ __launch_bounds__(OS_T) void k_optimize_sim3(OsBatch B)
                     os_edge<false>(S, est, C1, (double)r.P2[0], (double)r.P2[1], (double)r.P2[2], (double)r.o1[0], (double)r.o1[1], (double)r.w1, B.delta, acc);
                     os_edge<true>(S, estInv, C2, (double)r.P1[0], (double)r.P1[1], (double)r.P1[2], (double)r.o2[0], (double)r.o2[1], (double)r.w2, B.delta, acc);
                 }
-                os_block_sum36(S, acc);
+                g2o_block_sum_n(S.part, S.red, acc);
                 double H[7][7], b[7];
-                {
-                    int k = 0;
-#pragma unroll
-                    for (int i = 0; i < 7; i++)
-#pragma unroll
-                        for (int j = i; j < 7; j++) { H[i][j] = S.red[k]; H[j][i] = S.red[k]; k++; }
-#pragma unroll
-                    for (int i = 0; i < 7; i++) b[i] = S.red[28 + i];
-                }
+                g2o_dense_system(S.red, H, b);
                 double currentChi = S.red[35];
                 const double iniChi = currentChi;
-                if (!os_finite(currentChi)) { status = PGORB_OS3_NONFINITE; break; }
-                if (iter == 0) {                                        // computeLambdaInit: _tau * the largest diagonal entry
-                    double md = 0.0;
-#pragma unroll
-                    for (int j = 0; j < 7; j++) md = fmax(fabs(H[j][j]), md);
-                    lambda = 1e-5 * md; ni = 2; nBadIt = 0;
-                }
+                if (!g2o_finite(currentChi)) { status = PGORB_OS3_NONFINITE; break; }
+                if (iter == 0) g2o_lm_begin(lm, g2o_lm_lambda_init(g2o_max_diagonal(H)));
                 its[call]++;
                 double rho = 0.0;
                 int qmax = 0;
                 do {
-                    double Hl[7][7], x[7];
-#pragma unroll
-                    for (int i = 0; i < 7; i++)
-#pragma unroll
-                        for (int j = 0; j < 7; j++) Hl[i][j] = i == j ? H[i][j] + lambda : H[i][j];      // setLambda
-                    const bool ok2 = os_solve(Hl, b, x);
-                    if (!ok2) {
-#pragma unroll
-                        for (int i = 0; i < 7; i++) x[i] = 0.0;                                         // (a failed factorisation: the trial stays at the estimate)
-                    }
-                    if (B.fixScale) x[6] = 0.0;                         // oplusImpl writes into the solver's x; computeScale sees it
+                    double x[7], scale;
+                    const bool ok2 = g2o_dense_trial(H, b, lm.lambda, B.fixScale != 0, x, scale);
                     const OsSim trial = os_mul(os_exp(x), est);
                     errEst = trial;
-                    double tempChi = os_active_chi2(S, E, nE, trial, C1, C2, B.delta);
-                    if (!ok2) tempChi = OS_DBL_MAX;
-                    rho = currentChi - tempChi;
-                    double scale = 0.0;                                 // computeScale
-#pragma unroll
-                    for (int j = 0; j < 7; j++) scale += x[j] * (lambda * x[j] + b[j]);
-                    scale += 1e-3;
-                    rho /= scale;
-                    if (rho > 0.0 && os_finite(tempChi)) {
-                        const double t = 2.0 * rho - 1.0;
-                        double alpha = 1.0 - (t * t) * t;               // pow(2 * rho - 1, 3) read as two products
-                        alpha = fmin(alpha, 2.0 / 3.0);
-                        const double sf = fmax(1.0 / 3.0, alpha);
-                        lambda *= sf; ni = 2; currentChi = tempChi;
-                        est = trial;                                    // discardTop
-                    } else {
-                        lambda *= (double)ni; ni *= 2;                  // pop
-                    }
+                    const double tempChi = os_active_chi2(S, E, nE, trial, C1, C2, B.delta);
+                    if (g2o_lm_decide(lm, currentChi, tempChi, ok2, scale, rho)) est = trial;       // discardTop; else pop
                     qmax++; trials[call]++;
-                } while (rho < 0.0 && qmax < 10);
-                if (qmax == 10 || rho == 0.0) break;                    // Terminate
-                if ((iniChi - currentChi) * 1e3 < iniChi) nBadIt++; else nBadIt = 0;
-                if (nBadIt >= 3) break;
+                } while (g2o_lm_again(rho, qmax));
+                if (g2o_lm_stop(lm, iniChi, currentChi, qmax, rho)) break;
             }
         }
         if (status) break;
@@ -407,10 +277,10 @@ __global__ __launch_bounds__(OS_T) void k_optimize_sim3(OsBatch B)
             if (r.dead) continue;
             double e0, e1;
             os_error(errEst, C1, (double)r.P2[0], (double)r.P2[1], (double)r.P2[2], (double)r.o1[0], (double)r.o1[1], e0, e1);
-            const double c12 = os_chi2(e0, e1, (double)r.w1);
+            const double c12 = g2o_chi2(e0, e1, (double)r.w1);
             os_error(errInv, C2, (double)r.P1[0], (double)r.P1[1], (double)r.P1[2], (double)r.o2[0], (double)r.o2[1], e0, e1);
-            const double c21 = os_chi2(e0, e1, (double)r.w2);
-            if (!os_finite(c12) || !os_finite(c21)) nonfinite = 1;
+            const double c21 = g2o_chi2(e0, e1, (double)r.w2);
+            if (!g2o_finite(c12) || !g2o_finite(c21)) nonfinite = 1;
             const int out = (c12 > B.th2 || c21 > B.th2) ? 1 : 0;
             bad += out; good += 1 - out;
             if (out) { B.matchesOut[row + r.i1] = -1; if (call == 0) E[e].dead = 1; }
@@ -419,11 +289,11 @@ __global__ __launch_bounds__(OS_T) void k_optimize_sim3(OsBatch B)
         }
         if (__syncthreads_or(nonfinite)) { status = PGORB_OS3_NONFINITE; break; }
         if (call == 0) {
-            nBad = os_block_sum(S, bad);
+            nBad = g2o_block_sum(S.cnt, bad);
             nMore = nBad > 0 ? 10 : 5;
             if (nE - nBad < 10) status = PGORB_OS3_FEW;                 // return 0 before the vertex is recovered (:1211)
         } else {
-            nIn = os_block_sum(S, good);
+            nIn = g2o_block_sum(S.cnt, good);
         }
     }
 
@@ -441,19 +311,17 @@ __global__ __launch_bounds__(OS_T) void k_optimize_sim3(OsBatch B)
         memset(&sp, 0, sizeof(sp));
         if (!status) {
             double R[9];
-            os_matrix_from_quat(est, R);
+            g2o_matrix_from_quat(est, R);
 #pragma unroll
             for (int k = 0; k < 9; k++) o.R12[k] = __double2float_rn(R[k]);
             o.t12[0] = __double2float_rn(est.tx); o.t12[1] = __double2float_rn(est.ty); o.t12[2] = __double2float_rn(est.tz);
             o.s12 = __double2float_rn(est.s);
             // mg2oScw = gScm * gSmw, gSmw = Sim3(toMatrix3d(R2w), toVector3d(t2w), 1.0); mScw = toCvMat: s * R and t as float
             OsSim mw;
-            double R2[9] = {(double)P2.Tcw[0], (double)P2.Tcw[1], (double)P2.Tcw[2], (double)P2.Tcw[4], (double)P2.Tcw[5], (double)P2.Tcw[6],
-                            (double)P2.Tcw[8], (double)P2.Tcw[9], (double)P2.Tcw[10]};
-            os_quat_from_matrix(R2, mw);
+            g2o_quat_from_pose(P2.Tcw, mw);
             mw.tx = (double)P2.Tcw[3]; mw.ty = (double)P2.Tcw[7]; mw.tz = (double)P2.Tcw[11]; mw.s = 1.0;
             const OsSim cw = os_mul(est, mw);
-            os_matrix_from_quat(cw, R);
+            g2o_matrix_from_quat(cw, R);
             float sR[9], st[3] = {__double2float_rn(cw.tx), __double2float_rn(cw.ty), __double2float_rn(cw.tz)};
 #pragma unroll
             for (int k = 0; k < 9; k++) sR[k] = __double2float_rn(cw.s * R[k]);
@@ -467,9 +335,7 @@ __global__ __launch_bounds__(OS_T) void k_optimize_sim3(OsBatch B)
                 for (int c = 0; c < 3; c++) sp.Tcw[r * 4 + c] = __fmul_rn(sR[r * 3 + c], a);
                 sp.Tcw[r * 4 + 3] = __fmul_rn(st[r], a);
             }
-#pragma unroll
-            for (int i = 0; i < 3; i++)
-                sp.Ow[i] = cnm_f(__dmul_rn((double)cnm_dot3f(sp.Tcw[i], sp.Tcw[4 + i], sp.Tcw[8 + i], sp.Tcw[3], sp.Tcw[7], sp.Tcw[11]), -1.0));
+            po_set_ow(sp);
         }
         B.estOut[p] = o;
         if (B.scwPose) B.scwPose[p] = sp;

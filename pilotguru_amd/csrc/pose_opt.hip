@@ -14,6 +14,10 @@
 //   Frame::SetPose / UpdatePoseMatrices           src/Frame.cc
 // in double, in the reference's operation order per edge, under the readings of DESIGN.md section 4 (the pose-optimisation rows).  This
 // is the project's reading of g2o and Eigen, anchored by the CPU tests of tests/test_pose_optimization.py and not pinned to a g2o build.
+// Shared, each in one copy: Huber, the LDLT, Levenberg's step control and the block reductions are g2o_lm.h's (with optimize_sim3.hip,
+// local_ba.hip, essential_graph.hip, global_ba.hip); SE3Quat, computeError, toSE3Quat and SetPose are g2o_se3.h's (with local_ba.hip,
+// global_ba.hip).  This file's own: EdgeSE3ProjectXYZOnlyPose's Jacobian, which g2o writes with invz and invz2 products where
+// EdgeSE3ProjectXYZ divides by z2 (they round differently), and b accumulated as -= (rho1 * J) * w * e where the others add J * r.
 //
 // k_pose_opt, PO_T threads:
 //   1. the slots holding a point are compacted, in keypoint order and by ballot prefix, into edge records (Xw, obs, invSigma2, keypoint,
@@ -47,14 +51,10 @@ struct PoBatch {
 
 struct PoCam { double fx, fy, cx, cy; };
 
-// computeError: obs - cam_project(estimate.map(Xw)); pc = the mapped point
-__device__ __forceinline__ void po_error(const PoSE3& P, const PoCam& C, const PoEdge& E, double& x, double& y, double& z, double& e0, double& e1)
+// computeError at P of an edge record
+__device__ __forceinline__ void po_edge_error(const PoSE3& P, const PoCam& C, const PoEdge& E, double& x, double& y, double& z, double& e0, double& e1)
 {
-    double rx, ry, rz;
-    po_rotate(P, (double)E.X[0], (double)E.X[1], (double)E.X[2], rx, ry, rz);
-    x = rx + P.tx; y = ry + P.ty; z = rz + P.tz;
-    e0 = (double)E.ox - ((x / z) * C.fx + C.cx);
-    e1 = (double)E.oy - ((y / z) * C.fy + C.cy);
+    po_error(P, C.fx, C.fy, C.cx, C.cy, (double)E.X[0], (double)E.X[1], (double)E.X[2], (double)E.ox, (double)E.oy, x, y, z, e0, e1);
 }
 __device__ __forceinline__ PoEdge po_load_edge(const PoEdge* e)
 {
@@ -66,45 +66,10 @@ __device__ __forceinline__ PoEdge po_load_edge(const PoEdge* e)
 }
 
 struct PoShared {
-    double part[PO_WAVES][PO_NRED];
+    double part[PO_WAVES][PO_NRED];        // part[0][0 .. 3] also serve the scalar sums
     double red[PO_NRED];
     int cnt[PO_WAVES];
 };
-
-__device__ __forceinline__ int po_block_sum(PoShared& S, int v)
-{
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    if ((threadIdx.x & 63) == 0) S.cnt[threadIdx.x >> 6] = v;
-    __syncthreads();
-    const int r = (S.cnt[0] + S.cnt[1]) + (S.cnt[2] + S.cnt[3]);
-    __syncthreads();
-    return r;
-}
-// the fixed tree: a butterfly inside the wave (a + b is b + a bit for bit, so every lane ends with the same sum), then (w0 + w1) + (w2 + w3)
-__device__ __forceinline__ double po_block_sum(PoShared& S, double v)
-{
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    if ((threadIdx.x & 63) == 0) S.part[threadIdx.x >> 6][0] = v;
-    __syncthreads();
-    const double r = (S.part[0][0] + S.part[1][0]) + (S.part[2][0] + S.part[3][0]);
-    __syncthreads();
-    return r;
-}
-__device__ __forceinline__ void po_block_sum28(PoShared& S, double (&v)[PO_NRED])
-{
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1)
-#pragma unroll
-        for (int k = 0; k < PO_NRED; k++) v[k] += __shfl_xor(v[k], m, 64);
-    if ((threadIdx.x & 63) == 0)
-#pragma unroll
-        for (int k = 0; k < PO_NRED; k++) S.part[threadIdx.x >> 6][k] = v[k];
-    __syncthreads();
-    if (threadIdx.x < PO_NRED) S.red[threadIdx.x] = (S.part[0][threadIdx.x] + S.part[1][threadIdx.x]) + (S.part[2][threadIdx.x] + S.part[3][threadIdx.x]);
-    __syncthreads();
-}
 
 // activeRobustChi2 at P over the lane's level-0 edges
 __device__ __forceinline__ double po_active_chi2(PoShared& S, const PoEdge* E, int nE, const PoSE3& P, const PoCam& C, bool robust)
@@ -114,52 +79,12 @@ __device__ __forceinline__ double po_active_chi2(PoShared& S, const PoEdge* E, i
         const PoEdge ed = po_load_edge(E + e);
         if (ed.level) continue;
         double x, y, z, e0, e1;
-        po_error(P, C, ed, x, y, z, e0, e1);
-        double c2 = po_chi2(e0, e1, (double)ed.w), r0 = c2, r1;
-        if (robust) po_huber(c2, r0, r1);
+        po_edge_error(P, C, ed, x, y, z, e0, e1);
+        double c2 = g2o_chi2(e0, e1, (double)ed.w), r0 = c2, r1;
+        if (robust) g2o_huber(c2, PO_DELTA, r0, r1);
         acc += r0;
     }
-    return po_block_sum(S, acc);
-}
-
-// LinearSolverDense: an LDLT of the 6 x 6 in index order (no pivoting: DESIGN.md section 4); false = a factor is not positive
-__device__ __forceinline__ bool po_solve(const double (&H)[6][6], const double (&b)[6], double (&x)[6])
-{
-    double L[6][6], d[6];
-    bool ok = true;
-#pragma unroll
-    for (int j = 0; j < 6; j++) {
-        double s = H[j][j];
-#pragma unroll
-        for (int k = 0; k < j; k++) s -= (L[j][k] * L[j][k]) * d[k];
-        d[j] = s;
-        ok = ok && (s > 0.0);
-#pragma unroll
-        for (int i = j + 1; i < 6; i++) {
-            double t = H[j][i];
-#pragma unroll
-            for (int k = 0; k < j; k++) t -= (L[i][k] * L[j][k]) * d[k];
-            L[i][j] = t / s;
-        }
-    }
-    double y[6];
-#pragma unroll
-    for (int i = 0; i < 6; i++) {
-        double t = b[i];
-#pragma unroll
-        for (int k = 0; k < i; k++) t -= L[i][k] * y[k];
-        y[i] = t;
-    }
-#pragma unroll
-    for (int i = 0; i < 6; i++) y[i] = y[i] / d[i];
-#pragma unroll
-    for (int i = 5; i >= 0; i--) {
-        double t = y[i];
-#pragma unroll
-        for (int k = i + 1; k < 6; k++) t -= L[k][i] * x[k];
-        x[i] = t;
-    }
-    return ok;
+    return g2o_block_sum(S.part[0], acc);
 }
 
 __global__ __launch_bounds__(PO_T) void k_pose_opt(PoBatch B)
@@ -204,15 +129,7 @@ __global__ __launch_bounds__(PO_T) void k_pose_opt(PoBatch B)
     __syncthreads();                                                    // a record is written by its keypoint's lane and read by its owner, lane e mod PO_T
 
     const PoCam C = {(double)in.fx, (double)in.fy, (double)in.cx, (double)in.cy};
-    // Converter::toSE3Quat: SE3Quat(R, t) of the float Tcw
-    PoSE3 est0;
-    {
-        const double R[9] = {(double)in.Tcw[0], (double)in.Tcw[1], (double)in.Tcw[2], (double)in.Tcw[4], (double)in.Tcw[5], (double)in.Tcw[6],
-                             (double)in.Tcw[8], (double)in.Tcw[9], (double)in.Tcw[10]};
-        po_quat_from_matrix(R, est0);
-        est0.tx = (double)in.Tcw[3]; est0.ty = (double)in.Tcw[7]; est0.tz = (double)in.Tcw[11];
-        po_normalize(est0);
-    }
+    const PoSE3 est0 = po_from_pose(in);                                // Converter::toSE3Quat
 
     int status = 0, rounds = 0, trials = 0, nBadEdges = 0;
     int its[4] = {0, 0, 0, 0};
@@ -225,8 +142,7 @@ __global__ __launch_bounds__(PO_T) void k_pose_opt(PoBatch B)
         PoSE3 errEst = est0;                                            // where the active edges' _error was last computed
         // SparseOptimizer::optimize(10); an empty active set returns at once
         if (nActive > 0) {
-            double lambda = 0.0;
-            int ni = 2, nBad = 0;
+            G2oLm lm = {0.0, 2, 0};
             for (int iter = 0; iter < 10; iter++) {
                 // computeActiveErrors, activeRobustChi2, buildSystem
                 double acc[PO_NRED];
@@ -236,11 +152,11 @@ __global__ __launch_bounds__(PO_T) void k_pose_opt(PoBatch B)
                     const PoEdge ed = po_load_edge(E + e);
                     if (ed.level) continue;
                     double x, y, z, e0, e1;
-                    po_error(est, C, ed, x, y, z, e0, e1);
+                    po_edge_error(est, C, ed, x, y, z, e0, e1);
                     const double w = (double)ed.w;
-                    const double c2 = po_chi2(e0, e1, w);
+                    const double c2 = g2o_chi2(e0, e1, w);
                     double rho0 = c2, rho1 = 1.0;
-                    if (robust) po_huber(c2, rho0, rho1);
+                    if (robust) g2o_huber(c2, PO_DELTA, rho0, rho1);
                     // linearizeOplus (types_six_dof_expmap.cpp:266-288)
                     const double invz = 1.0 / z, invz2 = invz * invz;
                     double J0[6], J1[6];
@@ -264,65 +180,26 @@ __global__ __launch_bounds__(PO_T) void k_pose_opt(PoBatch B)
                     }
                     acc[27] += rho0;
                 }
-                po_block_sum28(S, acc);
+                g2o_block_sum_n(S.part, S.red, acc);
                 double H[6][6], b[6];
-                {
-                    int k = 0;
-#pragma unroll
-                    for (int i = 0; i < 6; i++)
-#pragma unroll
-                        for (int j = i; j < 6; j++) { H[i][j] = S.red[k]; H[j][i] = S.red[k]; k++; }
-#pragma unroll
-                    for (int i = 0; i < 6; i++) b[i] = S.red[21 + i];
-                }
+                g2o_dense_system(S.red, H, b);
                 double currentChi = S.red[27];
                 const double iniChi = currentChi;
-                if (!po_finite(currentChi)) { status = PGORB_PO_NONFINITE; break; }
-                if (iter == 0) {                                        // computeLambdaInit: _tau * the largest diagonal entry
-                    double md = 0.0;
-#pragma unroll
-                    for (int j = 0; j < 6; j++) md = fmax(fabs(H[j][j]), md);
-                    lambda = 1e-5 * md; ni = 2; nBad = 0;
-                }
+                if (!g2o_finite(currentChi)) { status = PGORB_PO_NONFINITE; break; }
+                if (iter == 0) g2o_lm_begin(lm, g2o_lm_lambda_init(g2o_max_diagonal(H)));
                 its[it]++;
                 double rho = 0.0;
                 int qmax = 0;
                 do {
-                    double Hl[6][6], x[6];
-#pragma unroll
-                    for (int i = 0; i < 6; i++)
-#pragma unroll
-                        for (int j = 0; j < 6; j++) Hl[i][j] = i == j ? H[i][j] + lambda : H[i][j];      // setLambda
-                    const bool ok2 = po_solve(Hl, b, x);
-                    if (!ok2) {
-#pragma unroll
-                        for (int i = 0; i < 6; i++) x[i] = 0.0;                                         // (a failed factorisation: the trial stays at the estimate)
-                    }
+                    double x[6], scale;
+                    const bool ok2 = g2o_dense_trial(H, b, lm.lambda, false, x, scale);
                     const PoSE3 trial = po_oplus(est, x);
                     errEst = trial;
-                    double tempChi = po_active_chi2(S, E, nE, trial, C, robust);
-                    if (!ok2) tempChi = 1.7976931348623157e308;
-                    rho = currentChi - tempChi;
-                    double scale = 0.0;                                 // computeScale
-#pragma unroll
-                    for (int j = 0; j < 6; j++) scale += x[j] * (lambda * x[j] + b[j]);
-                    scale += 1e-3;
-                    rho /= scale;
-                    if (rho > 0.0 && po_finite(tempChi)) {
-                        const double t = 2.0 * rho - 1.0;
-                        double alpha = 1.0 - (t * t) * t;               // pow(2 * rho - 1, 3) read as two products
-                        alpha = fmin(alpha, 2.0 / 3.0);
-                        const double sf = fmax(1.0 / 3.0, alpha);
-                        lambda *= sf; ni = 2; currentChi = tempChi;
-                        est = trial;                                    // discardTop
-                    } else {
-                        lambda *= (double)ni; ni *= 2;                  // pop
-                    }
+                    const double tempChi = po_active_chi2(S, E, nE, trial, C, robust);
+                    if (g2o_lm_decide(lm, currentChi, tempChi, ok2, scale, rho)) est = trial;       // discardTop; else pop
                     qmax++; trials++;
-                } while (rho < 0.0 && qmax < 10);
-                if (qmax == 10 || rho == 0.0) break;                    // Terminate
-                if ((iniChi - currentChi) * 1e3 < iniChi) nBad++; else nBad = 0;
-                if (nBad >= 3) break;
+                } while (g2o_lm_again(rho, qmax));
+                if (g2o_lm_stop(lm, iniChi, currentChi, qmax, rho)) break;
             }
         }
         if (status) break;
@@ -331,9 +208,9 @@ __global__ __launch_bounds__(PO_T) void k_pose_opt(PoBatch B)
         for (int e = tid; e < nE; e += PO_T) {
             PoEdge ed = po_load_edge(E + e);
             double x, y, z, e0, e1;
-            po_error(ed.level ? est : errEst, C, ed, x, y, z, e0, e1);
-            const double c2 = po_chi2(e0, e1, (double)ed.w);
-            if (!po_finite(c2)) nonfinite = 1;
+            po_edge_error(ed.level ? est : errEst, C, ed, x, y, z, e0, e1);
+            const double c2 = g2o_chi2(e0, e1, (double)ed.w);
+            if (!g2o_finite(c2)) nonfinite = 1;
             const float c2f = __double2float_rn(c2);
             const int out = c2f > 5.991f;
             bad += out;
@@ -342,7 +219,7 @@ __global__ __launch_bounds__(PO_T) void k_pose_opt(PoBatch B)
             if (B.chi2) B.chi2[row + ed.kp] = c2f;
         }
         if (__syncthreads_or(nonfinite)) { status = PGORB_PO_NONFINITE; break; }
-        nBadEdges = po_block_sum(S, bad);
+        nBadEdges = g2o_block_sum(S.cnt, bad);
         nActive = nE - nBadEdges;
         rounds = it + 1;
         if (nE < 10) break;                                             // optimizer.edges().size() < 10 (:440)
@@ -361,22 +238,12 @@ __global__ __launch_bounds__(PO_T) void k_pose_opt(PoBatch B)
         if (B.kpOut) B.kpOut[o] = (out && B.discard) ? -1 : s;
         kept += (!out && (B.pobs ? B.pobs[s] != 0 : 1)) ? 1 : 0;
     }
-    kept = po_block_sum(S, kept);
+    kept = g2o_block_sum(S.cnt, kept);
     if (tid == 0) {
         pgorb_kf_pose o = in;
         if (!untouched) {
-            // Converter::toCvMat(SE3Quat), Frame::SetPose, UpdatePoseMatrices: mOw = -mRcw.t() * mtcw (gemm's small-matrix path, alpha = -1 in double)
-            double R[9];
-            po_matrix_from_quat(est, R);
-#pragma unroll
-            for (int r = 0; r < 3; r++) {
-#pragma unroll
-                for (int c = 0; c < 3; c++) o.Tcw[r * 4 + c] = __double2float_rn(R[r * 3 + c]);
-            }
-            o.Tcw[3] = __double2float_rn(est.tx); o.Tcw[7] = __double2float_rn(est.ty); o.Tcw[11] = __double2float_rn(est.tz);
-#pragma unroll
-            for (int i = 0; i < 3; i++)
-                o.Ow[i] = cnm_f(__dmul_rn((double)cnm_dot3f(o.Tcw[i], o.Tcw[4 + i], o.Tcw[8 + i], o.Tcw[3], o.Tcw[7], o.Tcw[11]), -1.0));
+            // Converter::toCvMat(SE3Quat), Frame::SetPose, UpdatePoseMatrices: mOw = -mRcw.t() * mtcw
+            po_set_pose(est, o);
         }
         B.poseOut[p] = o;
         const int inl = untouched ? 0 : nE - nBadEdges;

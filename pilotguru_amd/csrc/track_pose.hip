@@ -6,9 +6,9 @@
 //   Tracking::Track, motion model, mLastFrame, the record :432-440, :493, :497-506
 //   KeyFrame::SetBadFlag's mTcp                          src/KeyFrame.cc:641
 //   System::GetTrajectory                                src/System.cc:371-412
-// under the readings of DESIGN.md section 4; every one of them is loop_pose.h's or g2o_sim3.h's single copy: lp_mul44 (the 4 x 4
-// float product), lp_twc (GetPoseInverse), lp_set_ow (SetPose's Ow, and -rotation_mat * t of GetTrajectory, which is the same
-// expression), os_quat_from_matrix (Converter::toEigenQuaternion).
+// under the readings of DESIGN.md section 4; every one of them is a single copy in loop_pose.h, g2o_se3.h or g2o_lm.h: lp_mul44 (the 4 x 4
+// float product), lp_twc (GetPoseInverse), po_set_ow (SetPose's Ow, and -rotation_mat * t of GetTrajectory, which is the same
+// expression), g2o_quat_from_matrix (Converter::toEigenQuaternion).
 //   k_tp_predict   a thread per tracker
 //   k_tp_commit    a thread per tracker
 //   k_tp_tcp       a thread per record of a key-frame culling
@@ -55,11 +55,11 @@ __global__ __launch_bounds__(TP_T) void k_tp_predict(TpArgs A)
         float T[12];
         lp_mul44(A.traj[(int64_t)t * A.cap + cnt - 1].pose, A.kfPose[st.last_ref_kf].Tcw, T);   // Tlr*pRef->GetPose() (:798)
         tp_set(st.last.Tcw, T);
-        lp_set_ow(st.last);
+        po_set_ow(st.last);
         A.state[t].last = st.last;
         lp_mul44(st.velocity, st.last.Tcw, T);                                                  // mVelocity*mLastFrame.mTcw (:866)
         tp_set(o.Tcw, T);
-        lp_set_ow(o);
+        po_set_ow(o);
     }
     A.poseOut[t] = o;
 }
@@ -182,8 +182,8 @@ __global__ __launch_bounds__(TP_T) void k_traj_records(TrajArgs A)
             const double Rt[9] = {(double)F.Tcw[0], (double)F.Tcw[4], (double)F.Tcw[8], (double)F.Tcw[1], (double)F.Tcw[5], (double)F.Tcw[9],
                                   (double)F.Tcw[2], (double)F.Tcw[6], (double)F.Tcw[10]};       // rotation_mat = the block's .t() (:405)
             OsSim Q;
-            os_quat_from_matrix(Rt, Q);
-            lp_set_ow(F);                                                                       // -rotation_mat*Tcw.col(3) (:407)
+            g2o_quat_from_matrix(Rt, Q);
+            po_set_ow(F);                                                                       // -rotation_mat*Tcw.col(3) (:407)
             out[0] = Q.qw; out[1] = Q.qx; out[2] = Q.qy; out[3] = Q.qz;
             out[4] = (double)F.Ow[0]; out[5] = (double)F.Ow[1]; out[6] = (double)F.Ow[2];
         } else {

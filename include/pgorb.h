@@ -380,8 +380,8 @@ int  pgorb_search_by_bow_batch_device(pgorb_ctx* ctx,
  *       mnLastFrameSeen already equals this frame's id for a reason the slots do not show (the outliers discarded at
  *       Tracking.cc:781 and :904); viewing_cos_limit 0.5f, th 1, 3 or 5, nnratio 0.8f.  First loop (:1137-1153): a slot holding a
  *       bad point is cleared, any other slot marks its point as seen.  Second loop (:1158-1171): a seen or bad query is skipped,
- *       every other query runs isInFrustum.  in_view[q] = mbTrackInView (the caller does IncreaseVisible from it and from the
- *       slots); proj_x, proj_y, level, view_cos [nq] (each may be NULL) = mTrackProjX / Y, mnTrackScaleLevel, mTrackViewCos of an
+ *       every other query runs isInFrustum.  in_view[q] = mbTrackInView (IncreaseVisible from it and from the slots is
+ *       pgorb_increase_visible_batch_device); proj_x, proj_y, level, view_cos [nq] (each may be NULL) = mTrackProjX / Y, mnTrackScaleLevel, mTrackViewCos of an
  *       in-view query and 0 for any other; kp_point_out [n] (may be NULL) = the slots after the first loop; *n_to_match (may be
  *       NULL) = nToMatch.  The matcher then runs with those values, kp_has_point[i] = the slot's point after clearing has
  *       point_has_obs set.  (The reference skips the matcher when nToMatch == 0; the result, all -1 and 0, is the same.)
@@ -562,7 +562,7 @@ int  pgorb_search_for_triangulation_batch_device(pgorb_ctx* ctx,
  *       The precision of every cv::Mat step is a recalled reading of OpenCV 2.4.9, listed in DESIGN.md section 4.
  *   Inputs per key frame: keypoints (mvKeysUn), descriptors, FeatureVector CSR, has_point[i] = GetMapPoint(i) != NULL (NULL =
  *   none), the pose and camera (pgorb_kf_pose), and per neighbour medianDepthKF2 = ComputeSceneMedianDepth(2) (it reads KF2's
- *   map points, so the caller computes it).  Neighbours are distinct key frames other than KF1 (GetBestCovisibilityKeyFrames).
+ *   map points: pgorb_scene_median_depth_batch_device writes it from the slots and the table).  Neighbours are distinct key frames other than KF1 (GetBestCovisibilityKeyFrames).
  *   Equivalence with the reference's loop: the matcher has vbMatched2 never set (ORBmatcher.cc:679, 727) and no rotation
  *   histogram, so KF1's mask only decides whether keypoint idx1 is searched, not which KF2 keypoint it takes; a pair's
  *   triangulation depends only on the two key frames; a new point changes only KF1 and the current KF2.  So KF1 keypoint idx1
@@ -1931,9 +1931,9 @@ int  pgorb_global_ba_map_update_device(pgorb_ctx* ctx,
  *       neither lost nor broken.  PGORB_E_ARG: a negative count, a NULL array that is read or written, an unknown mode; and for
  *       pgorb_get_trajectory also: no live key frame, a record that is not lost with ref_kf outside [0, nkf), a bad key frame whose
  *       parent is -1 or out of range, a frame_time that is not finite or whose product with 1e6 lies outside int64.
- * Left to the caller: bOK itself and the nmatches retries, NeedNewKeyFrame / CreateNewKeyFrame, CheckReplacedInLastFrame, the
- * relocalisation bookkeeping (mnLastRelocFrameId), System::Reset, and the stereo / RGB-D and mbOnlyTracking branches of
- * UpdateLastFrame.
+ * bOK, the nmatches retry, NeedNewKeyFrame / CreateNewKeyFrame and CheckReplacedInLastFrame are the block below (csrc/track_decide.hip).
+ * Left to the caller: the relocalisation bookkeeping (mnLastRelocFrameId), System::Reset, and the stereo / RGB-D and mbOnlyTracking
+ * branches of UpdateLastFrame.
  * Limits (PGORB_E_LIMIT): nkf <= PGORB_COVIS_MAX_KF, n and traj_cap <= PGORB_TRAJ_MAX_RECORDS, ntrack <= PGORB_TRACK_MAX, list_cap
  * <= PGORB_COVIS_MAX_KF.  No scratch arena: the origin reduction's result lives in d_info.  Determinism: a result depends on its
  * inputs alone, not on the batch size, the stream or a repeat. */
@@ -1995,6 +1995,207 @@ int  pgorb_get_trajectory_device(pgorb_ctx* ctx,
         const float* d_tcp, int n, const pgorb_trajectory_record* d_traj, const int32_t* d_count /*[1] or NULL*/,
         double* d_quat_wxyz, double* d_translation, int64_t* d_time_usec, int64_t* d_frame_id, uint8_t* d_is_lost,
         int32_t* d_status, int32_t* d_info /*[PGORB_TRAJ_INFO]*/, void* hip_stream);
+
+/* ---- Tracking's decisions: point statistics, bOK, NeedNewKeyFrame, the scene median depth (csrc/track_decide.hip) ----------------
+ * The glue between the tracking thread's numeric steps, on the arrays those steps read and write, so that a monocular,
+ * mapping-enabled Tracking::Track() runs from CheckReplacedInLastFrame to the trajectory record without a per-keypoint array
+ * leaving the device: check_replaced -> predict -> SearchByProjection(last frame) -> PoseOptimization -> decide ->
+ * query_seen_from_outliers -> UpdateLocalMap -> SearchLocalPoints -> increase_visible -> PoseOptimization -> decide(LOCAL_MAP) ->
+ * finish -> commit.  Restates (thirdparty/orb-slam2):
+ *   Tracking::CheckReplacedInLastFrame                   src/Tracking.cc:735-745
+ *   SearchLocalPoints' two IncreaseVisible               :1148, :1168
+ *   the discard loops' mnLastFrameSeen                   :781, :904
+ *   bOK of TrackReferenceKeyFrame, TrackWithMotionModel, TrackLocalMap    :760, :789; :879-886, :918; :932-964
+ *   Track()'s tail                                       :445-476 with NeedNewKeyFrame :968-1052, CreateNewKeyFrame :1054-1132
+ *   KeyFrame::TrackedMapPoints, ComputeSceneMedianDepth  src/KeyFrame.cc:353-378, :736-766
+ *   CreateInitialMapMonocular's unit median depth        src/Tracking.cc:684-709
+ * Only the monocular, !mbOnlyTracking branches; stereo / RGB-D, mbVO and localisation mode are out of scope.
+ * Conventions.  "Tracker t" is row t of the [ntrack][cap_per_frame] arrays (slots, outlier flags) and entry t of the [ntrack] arrays,
+ * as in pgorb_track_predict_batch_device; its frame is d_frame[t] (NULL = frame t) of the nframes frames of one resident batch and
+ * its slot count min(max(d_n[frame], 0), cap_per_frame); a frame out of range has no slots; entries of a row at or past the count
+ * are neither read nor written.  The table is that of the map-edit block: d_point_bad (NULL = none), d_visible, d_found, d_replaced,
+ * the CSR d_obs_start / d_obs_frame bounded by nobs and masked by d_obs_live (NULL = all live; a dead entry, or one that names nothing
+ * of the batch, does not exist), and d_kf_point [nframes][cap_per_frame] + d_n; d_point_has_obs (NULL = all 1) is the array the
+ * frame's searches and PoseOptimization took.  The _batch_device / _device forms are asynchronous on hip_stream, do not synchronise
+ * it and do not check indices: a table index outside [0, npoints) counts as "no point" and is copied through unchanged; nothing is
+ * read or written out of bounds.  d_run [ntrack] (NULL = all run) gates a tracker.
+ *
+ *   pgorb_check_replaced_batch_device   in place on d_last_point: a slot p with d_replaced[p] >= 0 becomes d_replaced[p].  ONE
+ *       step: the reference does not follow chains.  A thread per slot.
+ *   pgorb_increase_visible_batch_device   from what pgorb_search_local_points_batch_device wrote: d_visible[p] += 1 for every slot of
+ *       d_kp_point (its d_kp_point_out: the slots after the bad ones were cleared) that holds a point, and for every query q <
+ *       d_nq[t] with d_in_view set; a point held by two slots of a frame counts twice, as in the reference.  int32 atomicAdd on vector
+ *       memory: the result does not depend on the order of execution.
+ *   pgorb_query_seen_from_outliers_batch_device   the d_query_seen of pgorb_search_local_points: d_query_seen[t][q] = 1 iff some slot
+ *       i of tracker t was DISCARDED and d_kp_point[i] == d_queries[t][q], for q < d_nq[t].  d_kp_point is the first stage's slots
+ *       BEFORE the discard (what PoseOptimization was given).  A slot counts as discarded when d_outlier[i] is set (d_outlier NULL =
+ *       no flags) or when d_kp_point_opt[i] != d_kp_point[i] (d_kp_point_opt NULL = not compared); one of the two is required.
+ *       PoseOptimization with discard_outliers = 1 CLEARS the flags of the slots it empties, so after that run the flags say
+ *       nothing and d_kp_point_opt = its d_kp_point_out is the input to pass (d_outlier NULL or its zeros); the flags serve a
+ *       discard_outliers = 0 run.  One bit per table point and tracker in scratch: memset, a thread per slot (atomicOr), a thread
+ *       per query.
+ *   pgorb_track_decide_batch_device   bOK of one stage and what the reference leaves in mCurrentFrame, a workgroup per tracker.  d_mode
+ *       [ntrack] (NULL = `mode` for all); PGORB_DECIDE_MOTION_MODEL and PGORB_DECIDE_REFERENCE_KF equal the PGORB_TRACK_ modes, so
+ *       predict's d_mode serves.  Inputs: d_nmatches = the count of the search that counts, d_nmatches_map = PoseOptimization's
+ *       (discard_outliers = 1), d_pose_opt / d_kp_point_opt = PoseOptimization's d_pose_out / d_kp_point_out, d_pose_before /
+ *       d_kp_point_before = what the frame holds when the stage returns early.
+ *         PGORB_DECIDE_REFERENCE_KF: nmatches < 15 (int) -> ok = 0, final = before (the frame's entry slots and entry pose, byte
+ *             for byte: the reference returns before either is assigned); else ok = nmatches_map >= 10, final = opt.
+ *         PGORB_DECIDE_MOTION_MODEL: before = the PREDICTED pose (SetPose at :866 ran) and the search's slots.  nmatches < 20 -> ok
+ *             = 0, final = before (PoseOptimization did not run); else ok = nmatches_map >= 10, final = opt.  d_retry[t] = nmatches
+ *             < 20 when after_retry == 0 (the first search's verdict: the caller searches again with 2 * th and decides again with
+ *             after_retry = 1), 0 when after_retry != 0.
+ *         PGORB_DECIDE_LOCAL_MAP: d_kp_point_opt / d_outlier = PoseOptimization's (discard_outliers = 0).  d_found[p] += 1 (NULL =
+ *             not carried) for every slot with a point and no outlier flag, the atomics of increase_visible; d_inliers[t] =
+ *             mnMatchesInliers = those whose point has d_point_has_obs; ok = !(mnId < mnLastRelocFrameId + mMaxFrames && inliers <
+ *             50) && inliers >= 30; final = opt.  d_inliers is written in this mode only, d_retry in MOTION_MODEL only.
+ *       A tracker with d_run[t] == 0 gets d_ok = 0 and nothing else is read, counted or written, in every mode.
+ *       INTEGER WIDTHS (include/Tracking.h, include/Frame.h): mnId is long unsigned int, mnLastRelocFrameId and mnLastKeyFrameId
+ *       unsigned int, mMaxFrames and mMinFrames int.  Every `id + frames` sum is therefore formed in 32-bit UNSIGNED arithmetic (the
+ *       int converts to unsigned) and WRAPS modulo 2^32, and only then is widened to 64 bits for the comparison with mnId.
+ *   pgorb_track_counters   one tracker's scalar members: frame_id = mCurrentFrame.mnId (the caller's to set per frame),
+ *       last_reloc_frame_id = mnLastRelocFrameId, last_kf_frame_id = mnLastKeyFrameId, max_frames / min_frames = mMaxFrames /
+ *       mMinFrames, nkfs = mpMap->KeyFramesInMap(), ref_kf = mpReferenceKF (a frame index), next_kf_id = KeyFrame::nNextId, and the
+ *       local mapper's answers as bytes: stopped = isStopped(), stop_requested = stopRequested(), accept_keyframes =
+ *       AcceptKeyFrames(), set_not_stop_ok = what SetNotStop(true) would return.
+ *   pgorb_track_finish_batch_device   the tail of Track() (:445-476) for the trackers with d_ok, a workgroup per tracker, in the
+ *       reference's order.  (a) :445-454: a slot whose point has d_point_has_obs == 0 becomes -1 and its d_outlier flag is cleared
+ *       (d_outlier is in/out).  (b) NeedNewKeyFrame, monocular: false when stopped or stop_requested, or when mnId <
+ *       mnLastRelocFrameId + mMaxFrames && nkfs > max_frames; nMinObs = nkfs <= 2 ? 2 : 3; nRefMatches = TrackedMapPoints(nMinObs) of
+ *       row counters.ref_kf of d_kf_point: the slots whose point is in range, not bad and has at least nMinObs LIVE observations (a
+ *       ref_kf out of range: 0); c1a = mnId >= mnLastKeyFrameId + mMaxFrames; c1b = mnId >= mnLastKeyFrameId + mMinFrames &&
+ *       accept_keyframes; c1c is false for monocular; c2 = (float)inliers < (float)nRefMatches * 0.9f && inliers > 15 -- the int
+ *       converts to float and the product is ONE FLOAT product, not double; the result is accept_keyframes when (c1a || c1b) && c2.
+ *       d_interrupt_ba[t] = 1 when the condition held and accept_keyframes was 0: InterruptBA() at :1038, reported, not acted on.
+ *       (c) CreateNewKeyFrame when (b) said yes and set_not_stop_ok: a key frame IS a frame of the batch, so the tracker's frame f
+ *       becomes it: d_kf_point[f] = the slots as they stand now (outlier slots still present, "so that bundle adjustment will
+ *       finally decide"), d_kf_pose[f] = d_pose_final[t], d_kf_id[f] = next_kf_id; then next_kf_id += 1, ref_kf = f,
+ *       last_kf_frame_id = (uint32_t)frame_id, nkfs += 1.  ProcessNewKeyFrame's edits are pgorb_map_edits_from_keyframe_device with kf
+ *       = d_new_kf[t].  (d) :472-476: d_kp_point_out = the slots with every outlier slot -1: the next frame's d_last_point.  Outputs
+ *       per tracker: d_ref_kf_out = mpReferenceKF as pgorb_track_commit_batch_device takes it, d_new_kf = f or -1, d_interrupt_ba.
+ *       A tracker without d_ok: d_kp_point_out = d_kp_point, d_ref_kf_out = counters.ref_kf, d_new_kf = -1, d_interrupt_ba = 0,
+ *       nothing else written.  TWO TRACKERS OF ONE CALL MUST NOT NAME THE SAME FRAME ROW, and no tracker's ref_kf may be a frame row of
+ *       the call (both would race on d_kf_point; the host form refuses them, this form does not look).  The counts are wave
+ *       reductions and one LDS step, the decision is one lane's, the rows are copied by all lanes.
+ *   pgorb_scene_median_depth_batch_device   KeyFrame::ComputeSceneMedianDepth(q) for every entry of d_kf [nlist]; an entry of -1
+ *       (or out of range) writes nothing, so the d_neigh [nkf][max_neigh] of pgorb_create_new_map_points_batch_device can be passed
+ *       flat with nlist = nkf * max_neigh and d_median_depth IS its d_median_depth.  Over every slot with a point in range -- NO
+ *       isBad() test, as in the reference -- z = (float)(Rcw2.dot(x3Dw) + zcw): Mat::dot on CV_32F is a double sum from 0 in
+ *       row-major order of the widened products, zcw is widened and added in double, and the sum is rounded to float once.  The
+ *       result is the element at index (count - 1) / q (integer division) of the ascending order.  count == 0 is an out-of-bounds
+ *       read in the reference: here -1.0f with PGORB_DEPTH_EMPTY in d_status.  A NaN depth makes std::sort undefined: here -1.0f with
+ *       PGORB_DEPTH_NAN.  A zero of either sign is returned as +0.0f: operator< cannot tell them apart and std::sort is not stable,
+ *       so which zero the reference returns is unspecified -- the one place where it is.  A workgroup per entry: the depths as
+ *       order-preserving uint32 keys in LDS (cap_per_frame * 4 + 4128 bytes), then an exact radix select in four 8-bit histogram
+ *       passes, a histogram per wave merged by one step (equal depths contend inside one wave only); no sort, no rank count.
+ *   pgorb_scale_initial_map_device   CreateInitialMapMonocular, :684-709.  medianDepth = ComputeSceneMedianDepth(2) of kf_ini as above,
+ *       invMedianDepth = 1.0f / medianDepth (float).  d_info [PGORB_DECIDE_INFO] = (status, the median's float bits,
+ *       TrackedMapPoints(1) of kf_cur, points scaled); status = PGORB_DECIDE_WRONG_INIT | PGORB_DEPTH_* when medianDepth < 0 (EMPTY and
+ *       NAN give -1) || tracked < 100: NOTHING else is written then (the reference resets).  Otherwise kf_cur's translation column is
+ *       multiplied by invMedianDepth -- a float product: the MatExpr scale forms (double)t * (double)inv, exact in double, and rounds
+ *       it to float, the same value -- and SetPose gives Ow = -Rcw.t()*tcw as everywhere else; then pos of every point in kf_ini's
+ *       slots is multiplied the same way, ONCE PER SLOT THAT HOLDS IT (a point in two slots is scaled twice, as the loop at :702-709
+ *       does), bad or not: slot counts by integer atomics in scratch, then a thread per point that multiplies that many times.  A
+ *       median of +0 gives inf, as in the reference.  One workgroup, then a thread per slot and a thread per point; the median
+ *       travels in d_info, no host round trip.
+ *   pgorb_check_replaced / pgorb_increase_visible / pgorb_query_seen_from_outliers / pgorb_track_decide / pgorb_track_finish /
+ *   pgorb_scene_median_depth / pgorb_scale_initial_map   the same flat arrays in host memory, checked on the host before anything
+ *       else, byte for byte equal to the device forms (bytes a device form does not write keep their values).  PGORB_E_ARG: a negative
+ *       count, a NULL array (every array is required here, except frame, run, modes, point_bad, point_has_obs and obs_live), a
+ *       frame's count outside [0, cap_per_frame], a tracker's frame out of range, a slot or replacement outside [-1, npoints), a query
+ *       outside [0, npoints), a query count outside [0, qcap], an unknown mode, q < 1, obs_start not rising from 0 to nobs, a live
+ *       observation naming a frame out of range, two trackers on one frame row, a ref_kf out of range or equal to a tracker's frame
+ *       row, a list entry outside [-1, nframes), kf_ini or kf_cur out of range or equal.  pgorb_track_finish returns the number of key
+ *       frames made, pgorb_scale_initial_map the number of points scaled (0 with PGORB_DECIDE_WRONG_INIT), the others 0.
+ * Still left to the caller: the relocalisation bookkeeping (Relocalization itself and mnLastRelocFrameId), System::Reset, the stereo /
+ * RGB-D branches, localisation mode (mbOnlyTracking, mbVO), mCurrentFrame.mnId, and the table append of CreateNewMapPoints.
+ * Limits (PGORB_E_LIMIT): ntrack <= PGORB_TRACK_MAX, nframes <= PGORB_COVIS_MAX_KF, cap_per_frame and qcap <= 16000, nlist <=
+ * PGORB_DEPTH_MAX_LIST; query_seen: npoints <= 1048576; scale_initial_map: npoints <= 2^30.  Scratch arena: query_seen ntrack *
+ * ((npoints + 31) / 32 + 1) * 4 bytes, scale_initial_map npoints * 4 bytes, each rounded up to 64; the others none.  Determinism: integers
+ * and correctly rounded float / double operations only (the library is built with -ffp-contract=off); the only atomics are integer
+ * adds and ors, whose results no order of execution changes; a result depends on its inputs alone, not on the batch position, the
+ * stream or a repeat. */
+#define PGORB_DECIDE_MOTION_MODEL 0
+#define PGORB_DECIDE_REFERENCE_KF 1
+#define PGORB_DECIDE_LOCAL_MAP    2
+#define PGORB_DECIDE_WRONG_INIT   4
+#define PGORB_DECIDE_INFO         4
+#define PGORB_DEPTH_EMPTY         1
+#define PGORB_DEPTH_NAN           2
+#define PGORB_DEPTH_MAX_LIST      262144
+typedef struct pgorb_track_counters {
+    uint64_t frame_id;             /* mCurrentFrame.mnId */
+    uint32_t last_reloc_frame_id;  /* mnLastRelocFrameId */
+    uint32_t last_kf_frame_id;     /* mnLastKeyFrameId */
+    int32_t max_frames, min_frames, nkfs, ref_kf;
+    uint64_t next_kf_id;           /* KeyFrame::nNextId */
+    uint8_t stopped, stop_requested, accept_keyframes, set_not_stop_ok, pad[4];
+} pgorb_track_counters;
+int  pgorb_check_replaced(pgorb_ctx* ctx,
+        int ntrack, const int32_t* n /*[nframes]*/, int nframes, int cap_per_frame, const int32_t* frame /*[ntrack] or NULL*/,
+        int32_t* last_point /*[ntrack][cap_per_frame] in and out*/, int npoints, const int32_t* replaced /*[npoints]*/);
+int  pgorb_check_replaced_batch_device(pgorb_ctx* ctx,
+        int ntrack, const int32_t* d_n, int nframes, int cap_per_frame, const int32_t* d_frame, int32_t* d_last_point, int npoints,
+        const int32_t* d_replaced, void* hip_stream);
+int  pgorb_increase_visible(pgorb_ctx* ctx,
+        int ntrack, const int32_t* n, int nframes, int cap_per_frame, const int32_t* frame, const uint8_t* run /*[ntrack] or NULL*/,
+        const int32_t* kp_point /*[ntrack][cap_per_frame]*/, int qcap, const int32_t* nq /*[ntrack]*/,
+        const int32_t* queries /*[ntrack][qcap]*/, const uint8_t* in_view /*[ntrack][qcap]*/, int npoints, int32_t* visible /*in and out*/);
+int  pgorb_increase_visible_batch_device(pgorb_ctx* ctx,
+        int ntrack, const int32_t* d_n, int nframes, int cap_per_frame, const int32_t* d_frame, const uint8_t* d_run,
+        const int32_t* d_kp_point, int qcap, const int32_t* d_nq, const int32_t* d_queries, const uint8_t* d_in_view, int npoints,
+        int32_t* d_visible, void* hip_stream);
+int  pgorb_query_seen_from_outliers(pgorb_ctx* ctx,
+        int ntrack, const int32_t* n, int nframes, int cap_per_frame, const int32_t* frame, const int32_t* kp_point,
+        const uint8_t* outlier /*[ntrack][cap_per_frame] or NULL*/, const int32_t* kp_point_opt /*[ntrack][cap_per_frame] or NULL*/,
+        int qcap, const int32_t* nq, const int32_t* queries, int npoints, uint8_t* query_seen /*[ntrack][qcap]*/);
+int  pgorb_query_seen_from_outliers_batch_device(pgorb_ctx* ctx,
+        int ntrack, const int32_t* d_n, int nframes, int cap_per_frame, const int32_t* d_frame, const int32_t* d_kp_point,
+        const uint8_t* d_outlier, const int32_t* d_kp_point_opt, int qcap, const int32_t* d_nq, const int32_t* d_queries, int npoints,
+        uint8_t* d_query_seen, void* hip_stream);
+int  pgorb_track_decide(pgorb_ctx* ctx,
+        int ntrack, int mode, const int32_t* modes /*[ntrack] or NULL*/, int after_retry, const int32_t* n, int nframes,
+        int cap_per_frame, const int32_t* frame, const uint8_t* run, const int32_t* nmatches, const int32_t* nmatches_map /*[ntrack]*/,
+        const pgorb_kf_pose* pose_before /*[ntrack]*/, const int32_t* kp_point_before, const pgorb_kf_pose* pose_opt,
+        const int32_t* kp_point_opt, const uint8_t* outlier, int npoints, const uint8_t* point_has_obs, int32_t* found /*in and out*/,
+        const pgorb_track_counters* counters /*[ntrack]*/, uint8_t* ok, int32_t* inliers, uint8_t* retry /*[ntrack]*/,
+        pgorb_kf_pose* pose_final /*[ntrack]*/, int32_t* kp_point_final /*[ntrack][cap_per_frame]*/);
+int  pgorb_track_decide_batch_device(pgorb_ctx* ctx,
+        int ntrack, int mode, const int32_t* d_mode, int after_retry, const int32_t* d_n, int nframes, int cap_per_frame,
+        const int32_t* d_frame, const uint8_t* d_run, const int32_t* d_nmatches, const int32_t* d_nmatches_map,
+        const pgorb_kf_pose* d_pose_before, const int32_t* d_kp_point_before, const pgorb_kf_pose* d_pose_opt,
+        const int32_t* d_kp_point_opt, const uint8_t* d_outlier, int npoints, const uint8_t* d_point_has_obs, int32_t* d_found,
+        const pgorb_track_counters* d_counters, uint8_t* d_ok, int32_t* d_inliers, uint8_t* d_retry, pgorb_kf_pose* d_pose_final,
+        int32_t* d_kp_point_final, void* hip_stream);
+int  pgorb_track_finish(pgorb_ctx* ctx,
+        int ntrack, const int32_t* n, int nframes, int cap_per_frame, const int32_t* frame, const uint8_t* ok, const int32_t* inliers,
+        pgorb_track_counters* counters /*in and out*/, const pgorb_kf_pose* pose_final, const int32_t* kp_point,
+        uint8_t* outlier /*in and out*/, int npoints, const uint8_t* point_bad, const uint8_t* point_has_obs,
+        const int32_t* obs_start /*[npoints + 1]*/, const int32_t* obs_frame, int nobs, const uint8_t* obs_live,
+        int32_t* kf_point /*[nframes][cap_per_frame]*/, pgorb_kf_pose* kf_pose /*[nframes]*/, uint64_t* kf_id /*[nframes]*/,
+        int32_t* kp_point_out /*[ntrack][cap_per_frame]*/, int32_t* ref_kf_out, int32_t* new_kf, uint8_t* interrupt_ba /*[ntrack]*/);
+int  pgorb_track_finish_batch_device(pgorb_ctx* ctx,
+        int ntrack, const int32_t* d_n, int nframes, int cap_per_frame, const int32_t* d_frame, const uint8_t* d_ok,
+        const int32_t* d_inliers, pgorb_track_counters* d_counters, const pgorb_kf_pose* d_pose_final, const int32_t* d_kp_point,
+        uint8_t* d_outlier, int npoints, const uint8_t* d_point_bad, const uint8_t* d_point_has_obs, const int32_t* d_obs_start,
+        const int32_t* d_obs_frame, int nobs, const uint8_t* d_obs_live, int32_t* d_kf_point, pgorb_kf_pose* d_kf_pose,
+        uint64_t* d_kf_id, int32_t* d_kp_point_out, int32_t* d_ref_kf_out, int32_t* d_new_kf, uint8_t* d_interrupt_ba, void* hip_stream);
+int  pgorb_scene_median_depth(pgorb_ctx* ctx,
+        int nlist, const int32_t* kf /*[nlist]*/, int q, const int32_t* kf_point, const int32_t* n, int nframes, int cap_per_frame,
+        const pgorb_kf_pose* pose /*[nframes]*/, int npoints, const pgorb_map_point* points, float* median_depth /*[nlist]*/,
+        int32_t* status /*[nlist]*/);
+int  pgorb_scene_median_depth_batch_device(pgorb_ctx* ctx,
+        int nlist, const int32_t* d_kf, int q, const int32_t* d_kf_point, const int32_t* d_n, int nframes, int cap_per_frame,
+        const pgorb_kf_pose* d_pose, int npoints, const pgorb_map_point* d_points, float* d_median_depth, int32_t* d_status,
+        void* hip_stream);
+int  pgorb_scale_initial_map(pgorb_ctx* ctx,
+        int kf_ini, int kf_cur, const int32_t* kf_point, const int32_t* n, int nframes, int cap_per_frame,
+        pgorb_kf_pose* pose /*[nframes] in and out*/, int npoints, pgorb_map_point* points /*in and out: pos*/, const uint8_t* point_bad,
+        const int32_t* obs_start, const int32_t* obs_frame, int nobs, const uint8_t* obs_live, int32_t* info /*[PGORB_DECIDE_INFO]*/);
+int  pgorb_scale_initial_map_device(pgorb_ctx* ctx,
+        int kf_ini, int kf_cur, const int32_t* d_kf_point, const int32_t* d_n, int nframes, int cap_per_frame, pgorb_kf_pose* d_pose,
+        int npoints, pgorb_map_point* d_points, const uint8_t* d_point_bad, const int32_t* d_obs_start, const int32_t* d_obs_frame,
+        int nobs, const uint8_t* d_obs_live, int32_t* d_info, void* hip_stream);
 
 /* ---- ORB vocabulary (DBoW2 TemplatedVocabulary<FORB::TDescriptor, FORB>) -----------------
  *   pgorb_vocab_load_text     ORBVocabulary(text_file) -> TemplatedVocabulary::loadFromTextFile

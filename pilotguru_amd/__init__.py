@@ -30,6 +30,8 @@ from .orb import LC_BAD_INDEX, LC_INFO, LC_OVER_OBS, MU_INFO, LoopClosing  # noq
 from .orb import (TCP_INFO, TRACK_BAD_INDEX, TRACK_FULL, TRACK_MAX, TRACK_MOTION_MODEL, TRACK_NO_LAST, TRACK_NO_VELOCITY,  # noqa: F401
                   TRACK_REFERENCE_KF, TRACK_STATE_DTYPE, TRAJ_BAD_TIME, TRAJ_BROKEN, TRAJ_INFO, TRAJ_MAX_RECORDS, TRAJ_NO_ORIGIN,
                   TRAJECTORY_RECORD_DTYPE, System)
+from .orb import (DECIDE_INFO, DECIDE_LOCAL_MAP, DECIDE_MOTION_MODEL, DECIDE_REFERENCE_KF, DECIDE_WRONG_INIT, DEPTH_EMPTY, DEPTH_MAX_LIST,  # noqa: F401
+                  DEPTH_NAN, TRACK_COUNTERS_DTYPE)
 from .map_edit import (EDIT_ADD, EDIT_ALREADY, EDIT_APPLIED, EDIT_BAD_INDEX, EDIT_ERASE, EDIT_INFO, EDIT_LIMIT, EDIT_MAX_BAG,  # noqa: F401
                        EDIT_MAX_EDITS, EDIT_MAX_LIST, EDIT_NOP, EDIT_NOT_OBSERVED, EDIT_REPLACE, EDIT_SELF, EDIT_SET_REF, EDIT_TOUCH_CHANGED,
                        EDIT_TOUCH_STALE, EDIT_TOUCH_SURVIVOR, EDIT_WENT_BAD, MAP_EDIT_DTYPE, apply_map_edits, map_edits,

@@ -51,6 +51,10 @@ SYMBOLS = (
     "pgorb_correct_loop_poses", "pgorb_correct_loop_poses_device", "pgorb_global_ba_map_update", "pgorb_global_ba_map_update_device",
     "pgorb_track_predict", "pgorb_track_predict_batch_device", "pgorb_track_commit", "pgorb_track_commit_batch_device",
     "pgorb_keyframe_tcp", "pgorb_keyframe_tcp_device", "pgorb_get_trajectory", "pgorb_get_trajectory_device",
+    "pgorb_check_replaced", "pgorb_check_replaced_batch_device", "pgorb_increase_visible", "pgorb_increase_visible_batch_device",
+    "pgorb_query_seen_from_outliers", "pgorb_query_seen_from_outliers_batch_device", "pgorb_track_decide", "pgorb_track_decide_batch_device",
+    "pgorb_track_finish", "pgorb_track_finish_batch_device", "pgorb_scene_median_depth", "pgorb_scene_median_depth_batch_device",
+    "pgorb_scale_initial_map", "pgorb_scale_initial_map_device",
     "pgorb_bow_vectors_batch_device", "pgorb_bow_score_l1_batch_device",
     "pgorb_detect_relocalization_candidates", "pgorb_detect_relocalization_candidates_batch_device",
     "pgorb_detect_loop_candidates", "pgorb_detect_loop_candidates_batch_device",
@@ -91,6 +95,13 @@ PGORB_TRACK_MOTION_MODEL, PGORB_TRACK_REFERENCE_KF = 0, 1
 PGORB_TRACK_NO_LAST, PGORB_TRACK_NO_VELOCITY, PGORB_TRACK_BAD_INDEX, PGORB_TRACK_FULL, PGORB_TRACK_MAX = 1, 2, 4, 8, 4096
 PGORB_TRAJ_BROKEN, PGORB_TRAJ_BAD_TIME, PGORB_TRAJ_NO_ORIGIN, PGORB_TRAJ_INFO, PGORB_TRAJ_MAX_RECORDS = 1, 2, 4, 4, 1 << 22
 PGORB_TCP_INFO = 4
+# Tracking's decisions (include/pgorb.h: pgorb_track_counters and the PGORB_DECIDE_ / PGORB_DEPTH_ constants)
+TRACK_COUNTERS_DTYPE = np.dtype([("frame_id", "<u8"), ("last_reloc_frame_id", "<u4"), ("last_kf_frame_id", "<u4"), ("max_frames", "<i4"),
+                                 ("min_frames", "<i4"), ("nkfs", "<i4"), ("ref_kf", "<i4"), ("next_kf_id", "<u8"), ("stopped", "u1"),
+                                 ("stop_requested", "u1"), ("accept_keyframes", "u1"), ("set_not_stop_ok", "u1"), ("pad", "u1", (4,))])
+assert TRACK_COUNTERS_DTYPE.itemsize == 48
+PGORB_DECIDE_MOTION_MODEL, PGORB_DECIDE_REFERENCE_KF, PGORB_DECIDE_LOCAL_MAP, PGORB_DECIDE_WRONG_INIT, PGORB_DECIDE_INFO = 0, 1, 2, 4, 4
+PGORB_DEPTH_EMPTY, PGORB_DEPTH_NAN, PGORB_DEPTH_MAX_LIST = 1, 2, 262144
 
 
 class PgorbParams(C.Structure):
@@ -390,6 +401,27 @@ def lib():
     # (ctx, nkf, pose, kf_bad, parent, kf_id, tcp, n, traj, [count,] quat_wxyz, translation, time_usec, frame_id, is_lost, status, info[, stream])
     L.pgorb_get_trajectory.argtypes = [vp, C.c_int] + [vp] * 5 + [C.c_int] + [vp] * 8
     L.pgorb_get_trajectory_device.argtypes = [vp, C.c_int] + [vp] * 5 + [C.c_int] + [vp] * 10
+    # Tracking's decisions; the _batch_device / _device forms take the same arguments and a stream
+    # (ctx, ntrack, n, nframes, cap, frame, last_point, npoints, replaced)
+    td = [vp, C.c_int, vp, C.c_int, C.c_int, vp]
+    L.pgorb_check_replaced.argtypes = td + [vp, C.c_int, vp]
+    # (.., run, kp_point, qcap, nq, queries, in_view, npoints, visible)
+    L.pgorb_increase_visible.argtypes = td + [vp, vp, C.c_int, vp, vp, vp, C.c_int, vp]
+    # (.., kp_point, outlier, kp_point_opt, qcap, nq, queries, npoints, query_seen)
+    L.pgorb_query_seen_from_outliers.argtypes = td + [vp, vp, vp, C.c_int, vp, vp, C.c_int, vp]
+    # (ctx, ntrack, mode, modes, after_retry, n, nframes, cap, frame, run, nmatches, nmatches_map, pose_before, kp_point_before, pose_opt,
+    #  kp_point_opt, outlier, npoints, point_has_obs, found, counters, ok, inliers, retry, pose_final, kp_point_final)
+    L.pgorb_track_decide.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int] + [vp] * 9 + [C.c_int] + [vp] * 8
+    # (.., ok, inliers, counters, pose_final, kp_point, outlier, npoints, point_bad, point_has_obs, obs_start, obs_frame, nobs, obs_live,
+    #  kf_point, kf_pose, kf_id, kp_point_out, ref_kf_out, new_kf, interrupt_ba)
+    L.pgorb_track_finish.argtypes = td + [vp] * 6 + [C.c_int, vp, vp, vp, vp, C.c_int] + [vp] * 8
+    # (ctx, nlist, kf, q, kf_point, n, nframes, cap, pose, npoints, points, median_depth, status)
+    L.pgorb_scene_median_depth.argtypes = [vp, C.c_int, vp, C.c_int, vp, vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp]
+    # (ctx, kf_ini, kf_cur, kf_point, n, nframes, cap, pose, npoints, points, point_bad, obs_start, obs_frame, nobs, obs_live, info)
+    L.pgorb_scale_initial_map.argtypes = [vp, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, vp, C.c_int, vp, vp]
+    for name in ("check_replaced", "increase_visible", "query_seen_from_outliers", "track_decide", "track_finish", "scene_median_depth"):
+        getattr(L, "pgorb_%s_batch_device" % name).argtypes = getattr(L, "pgorb_" + name).argtypes + [vp]
+    L.pgorb_scale_initial_map_device.argtypes = L.pgorb_scale_initial_map.argtypes + [vp]
     # (ctx, word, weight, n, nframes, cap, bow_id, bow_val, nbow, stream)
     L.pgorb_bow_vectors_batch_device.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp]
     # (ctx, bow_id, bow_val, nbow, nframes, cap, pair_a, pair_b, npairs, score, stream)

@@ -2156,6 +2156,42 @@ class LocalMapping:
                                                    _p(rec if len(rec) else np.zeros((1, 4), np.int32)), _p(out), _p(info)))
         return dict(tcp=out[:nkf].copy(), info=info, written=int(ret))
 
+    @staticmethod
+    def _depth_table(fn, kf_point, n, poses, points):
+        """(kf_point [nframes][cap], n, poses, points, npoints), checked as pgorb_scene_median_depth checks them"""
+        kfp = np.ascontiguousarray(kf_point, np.int32)
+        if kfp.ndim != 2 or kfp.shape[0] > COVIS_MAX_KF or kfp.shape[1] > 16000:
+            raise ValueError(fn + ": kf_point is [nframes][cap_per_frame], at most COVIS_MAX_KF frames of 16000 keypoints")
+        nframes, cap = kfp.shape
+        nn = _arr(n, np.int32, nframes, fn + " n")
+        P = _arr(poses, KF_POSE_DTYPE, nframes, fn + " poses")
+        X = np.ascontiguousarray(points, MAP_POINT_DTYPE).reshape(-1)
+        if nframes and (nn.min() < 0 or nn.max() > cap):
+            raise ValueError(fn + ": a frame's count is outside [0, cap_per_frame]")
+        for f in range(nframes):
+            u = kfp[f, :nn[f]]
+            if len(u) and (u.min() < -1 or u.max() >= len(X)):
+                raise ValueError(fn + ": a slot names a point out of range")
+        return kfp, nn, P, X, len(X)
+
+    @staticmethod
+    def SceneMedianDepth(ext, kf_list, q, kf_point, n, poses, points):
+        """KeyFrame::ComputeSceneMedianDepth(q) (src/KeyFrame.cc:736-766) for every key frame of kf_list (-1 = skipped: its entries
+        come back as 0 / 0).  Returns (median float32 [nlist], status int32 [nlist]): -1 with DEPTH_EMPTY for a key frame without
+        points, -1 with DEPTH_NAN when a depth is NaN.  The medians of a key frame's neighbours are what CreateNewMapPoints takes as
+        median_depths.  Raises ValueError for what pgorb_scene_median_depth refuses."""
+        fn = "LocalMapping.SceneMedianDepth"
+        kfp, nn, P, X, npoints = LocalMapping._depth_table(fn, kf_point, n, poses, points)
+        lst = np.ascontiguousarray(kf_list, np.int32).reshape(-1)
+        if int(q) < 1 or len(lst) > DEPTH_MAX_LIST or (len(lst) and (lst.min() < -1 or lst.max() >= len(kfp))):
+            raise ValueError(fn + ": q < 1, more than DEPTH_MAX_LIST entries, or a key frame out of range")
+        med, st = np.zeros(max(len(lst), 1), np.float32), np.zeros(max(len(lst), 1), np.int32)
+        pad = lambda x, dt: x if len(x) else np.zeros(1, dt)
+        ext._check(ext._L.pgorb_scene_median_depth(ext._h, len(lst), _p(pad(lst, np.int32)), int(q), _p(pad(kfp.reshape(-1), np.int32)),
+                                                   _p(pad(nn, np.int32)), kfp.shape[0], kfp.shape[1], _p(pad(P, KF_POSE_DTYPE)), npoints,
+                                                   _p(pad(X, MAP_POINT_DTYPE)), _p(med), _p(st)))
+        return med[:len(lst)], st[:len(lst)]
+
 
 # the cullings (include/pgorb.h): MapPointCulling's and KeyFrameCulling's action codes, the row status bits
 CULL_MP_KEEP, CULL_MP_WAS_BAD, CULL_MP_FOUND_RATIO, CULL_MP_FEW_OBS, CULL_MP_AGED, CULL_MP_NONE = 0, 1, 2, 3, 4, 5
@@ -2425,6 +2461,186 @@ class Tracking:
             _p(traj if len(traj) else np.zeros(1, TRAJECTORY_RECORD_DTYPE)), len(traj), _p(cnt)))
         return dict(state=st, trajectory=traj, ntrajectory=int(cnt[0]), status=int(status))
 
+    # ---- the decisions between the numeric steps (include/pgorb.h: csrc/track_decide.hip).  Everywhere: n [nframes] = the frames'
+    # slot counts, frame [ntrack] (None = frame t) = each tracker's frame, per-tracker rows [ntrack][cap].  Nothing passed in is changed.
+    @staticmethod
+    def _td_rows(fn, n, frame, rows, npoints, lo=-1):
+        """(n, frame or None, ntrack, nframes, cap, the rows as int32 [ntrack][cap]), checked as the single calls check them"""
+        n = np.ascontiguousarray(n, np.int32).reshape(-1)
+        rows = [np.ascontiguousarray(r, np.int32) for r in rows]
+        if any(r.ndim != 2 or r.shape != rows[0].shape for r in rows):
+            raise ValueError(fn + ": the slot arrays are [ntrack][cap_per_frame]")
+        ntrack, cap = rows[0].shape
+        fr = None if frame is None else _arr(frame, np.int32, ntrack, fn + " frame")
+        if ntrack > TRACK_MAX or len(n) > COVIS_MAX_KF or cap > 16000:
+            raise ValueError(fn + ": more than TRACK_MAX trackers, COVIS_MAX_KF frames or 16000 keypoints per frame")
+        if len(n) and (n.min() < 0 or n.max() > cap):
+            raise ValueError(fn + ": a frame's count is outside [0, cap_per_frame]")
+        f = np.arange(ntrack, dtype=np.int32) if fr is None else fr
+        if ntrack and (f.min() < 0 or f.max() >= len(n)):
+            raise ValueError(fn + ": a tracker's frame is out of range")
+        for r in rows:
+            for t in range(ntrack):
+                u = r[t, :n[f[t]]]
+                if len(u) and (u.min() < lo or u.max() >= npoints):
+                    raise ValueError(fn + ": a slot names a point out of range")
+        return n, fr, ntrack, len(n), cap, rows
+
+    @staticmethod
+    def _td_obs(fn, npoints, obs_start, obs_frame, obs_live, nframes):
+        st = _arr(obs_start, np.int32, npoints + 1, fn + " obs_start")
+        of = np.ascontiguousarray(obs_frame, np.int32).reshape(-1)
+        lv = None if obs_live is None else _arr(obs_live, np.uint8, len(of), fn + " obs_live")
+        if st[0] != 0 or st[-1] != len(of) or np.any(np.diff(st) < 0):
+            raise ValueError(fn + ": obs_start does not rise from 0 to nobs")
+        live = of if lv is None else of[lv != 0]
+        if len(live) and (live.min() < 0 or live.max() >= nframes):
+            raise ValueError(fn + ": a live observation names a frame out of range")
+        return st, (of if len(of) else np.zeros(1, np.int32)), lv, len(of)
+
+    @staticmethod
+    def _opt(a):
+        return None if a is None else _p(a)
+
+    @staticmethod
+    def CheckReplacedInLastFrame(ext, last_point, n, npoints, replaced, frame=None):
+        """Tracking::CheckReplacedInLastFrame (Tracking.cc:735-745) for every tracker: a slot p with replaced[p] >= 0 becomes
+        replaced[p], ONE step.  Returns the slots afterwards.  Raises ValueError for what pgorb_check_replaced refuses."""
+        fn = "Tracking.CheckReplacedInLastFrame"
+        n, fr, ntrack, nframes, cap, (lp,) = Tracking._td_rows(fn, n, frame, [last_point], int(npoints))
+        rp = _arr(replaced, np.int32, int(npoints), fn + " replaced")
+        if len(rp) and (rp.min() < -1 or rp.max() >= npoints):
+            raise ValueError(fn + ": a replacement is out of range")
+        out = np.array(lp)
+        ext._check(ext._L.pgorb_check_replaced(ext._h, ntrack, _p(n), nframes, cap, Tracking._opt(fr), _p(out), int(npoints), _p(rp)))
+        return out
+
+    @staticmethod
+    def _td_queries(fn, ntrack, nq, queries, npoints, extra):
+        nq = _arr(nq, np.int32, ntrack, fn + " nq")
+        q = np.ascontiguousarray(queries, np.int32)
+        if q.ndim != 2 or q.shape[0] != ntrack or q.shape[1] > 16000 or (extra is not None and np.shape(extra) != q.shape):
+            raise ValueError(fn + ": the query arrays are [ntrack][qcap] with qcap <= 16000")
+        if ntrack and (nq.min() < 0 or nq.max() > q.shape[1]):
+            raise ValueError(fn + ": a query count is outside [0, qcap]")
+        for t in range(ntrack):
+            u = q[t, :nq[t]]
+            if len(u) and (u.min() < 0 or u.max() >= npoints):
+                raise ValueError(fn + ": a query names a point out of range")
+        return nq, q
+
+    @staticmethod
+    def IncreaseVisible(ext, kp_point, n, nq, queries, in_view, visible, frame=None, run=None):
+        """The two IncreaseVisible of SearchLocalPoints (Tracking.cc:1148, :1168) from SearchLocalPoints' kp_point_out and in_view.
+        Returns visible afterwards."""
+        fn = "Tracking.IncreaseVisible"
+        vis = np.array(np.ascontiguousarray(visible, np.int32).reshape(-1))
+        n, fr, ntrack, nframes, cap, (kp,) = Tracking._td_rows(fn, n, frame, [kp_point], len(vis))
+        nq, q = Tracking._td_queries(fn, ntrack, nq, queries, len(vis), in_view)
+        iv = np.ascontiguousarray(in_view, np.uint8)
+        rn = None if run is None else _arr(run, np.uint8, ntrack, fn + " run")
+        ext._check(ext._L.pgorb_increase_visible(ext._h, ntrack, _p(n), nframes, cap, Tracking._opt(fr), Tracking._opt(rn), _p(kp), q.shape[1],
+                                                 _p(nq), _p(q), _p(iv), len(vis), _p(vis)))
+        return vis
+
+    @staticmethod
+    def QuerySeenFromOutliers(ext, kp_point, outlier, n, nq, queries, npoints, frame=None, kp_point_opt=None):
+        """The query_seen of SearchLocalPoints: the queries whose point sat in a slot that the first stage discarded (mnLastFrameSeen
+        of Tracking.cc:781, :904).  kp_point = the slots BEFORE the discard; a slot was discarded when its outlier flag is set
+        (outlier None = no flags) or when kp_point_opt, PoseOptimization's slots after a discard_outliers = True run (which clears
+        the flags), differs from it.  Returns uint8 [ntrack][qcap], 0 past nq."""
+        fn = "Tracking.QuerySeenFromOutliers"
+        if npoints > 1048576:
+            raise ValueError(fn + ": more than 1048576 points")
+        if outlier is None and kp_point_opt is None:
+            raise ValueError(fn + ": outlier or kp_point_opt is required")
+        n, fr, ntrack, nframes, cap, rows = Tracking._td_rows(fn, n, frame, [kp_point] + ([] if kp_point_opt is None else [kp_point_opt]), int(npoints))
+        kp, ko = rows[0], (rows[1] if len(rows) > 1 else None)
+        ol = None if outlier is None else _arr(outlier, np.uint8, ntrack, fn + " outlier", cap)
+        nq, q = Tracking._td_queries(fn, ntrack, nq, queries, int(npoints), None)
+        seen = np.zeros(q.shape, np.uint8)
+        ext._check(ext._L.pgorb_query_seen_from_outliers(ext._h, ntrack, _p(n), nframes, cap, Tracking._opt(fr), _p(kp), Tracking._opt(ol), Tracking._opt(ko), q.shape[1], _p(nq),
+                                                         _p(q), int(npoints), _p(seen)))
+        return seen
+
+    @staticmethod
+    def Decide(ext, mode, n, nmatches, nmatches_map, pose_before, kp_point_before, pose_opt, kp_point_opt, outlier, npoints, found, counters,
+               point_has_obs=None, after_retry=False, frame=None, run=None):
+        """bOK of one stage for every tracker and what the reference leaves in mCurrentFrame (include/pgorb.h: pgorb_track_decide).  mode =
+        DECIDE_MOTION_MODEL | DECIDE_REFERENCE_KF | DECIDE_LOCAL_MAP, one for all or one per tracker.  Returns a dict: ok, inliers
+        (LOCAL_MAP only, else 0), retry, pose_final, kp_point_final, found."""
+        fn = "Tracking.Decide"
+        n, fr, ntrack, nframes, cap, (kb, ko) = Tracking._td_rows(fn, n, frame, [kp_point_before, kp_point_opt], int(npoints))
+        modes = None if np.ndim(mode) == 0 else _arr(mode, np.int32, ntrack, fn + " mode")
+        if not set([int(mode)] if modes is None else modes.tolist()) <= {DECIDE_MOTION_MODEL, DECIDE_REFERENCE_KF, DECIDE_LOCAL_MAP}:
+            raise ValueError(fn + ": an unknown mode")
+        nm, mp = _arr(nmatches, np.int32, ntrack, fn + " nmatches"), _arr(nmatches_map, np.int32, ntrack, fn + " nmatches_map")
+        pb, po = _arr(pose_before, KF_POSE_DTYPE, ntrack, fn + " pose_before"), _arr(pose_opt, KF_POSE_DTYPE, ntrack, fn + " pose_opt")
+        ol = _arr(outlier, np.uint8, ntrack, fn + " outlier", cap)
+        fd = np.array(_arr(found, np.int32, int(npoints), fn + " found"))
+        ho = None if point_has_obs is None else _arr(point_has_obs, np.uint8, int(npoints), fn + " point_has_obs")
+        ct = _arr(counters, TRACK_COUNTERS_DTYPE, ntrack, fn + " counters")
+        rn = None if run is None else _arr(run, np.uint8, ntrack, fn + " run")
+        ok, inl, rt = np.zeros(ntrack, np.uint8), np.zeros(ntrack, np.int32), np.zeros(ntrack, np.uint8)
+        pf, kf = np.zeros(ntrack, KF_POSE_DTYPE), np.full((ntrack, cap), -1, np.int32)
+        ext._check(ext._L.pgorb_track_decide(
+            ext._h, ntrack, 0 if modes is not None else int(mode), Tracking._opt(modes), int(bool(after_retry)), _p(n), nframes, cap, Tracking._opt(fr),
+            Tracking._opt(rn), _p(nm), _p(mp), _p(pb), _p(kb), _p(po), _p(ko), _p(ol), int(npoints), Tracking._opt(ho), _p(fd), _p(ct), _p(ok), _p(inl),
+            _p(rt), _p(pf), _p(kf)))
+        return dict(ok=ok, inliers=inl, retry=rt, pose_final=pf, kp_point_final=kf, found=fd)
+
+    @staticmethod
+    def FinishFrame(ext, n, ok, inliers, counters, pose_final, kp_point, outlier, npoints, obs_start, obs_frame, kf_point, kf_pose, kf_id,
+                    point_bad=None, point_has_obs=None, obs_live=None, frame=None):
+        """The tail of Tracking::Track for the trackers with ok (Tracking.cc:445-476): clean VO matches, NeedNewKeyFrame,
+        CreateNewKeyFrame (the tracker's frame becomes the key frame), the outlier discard.  Returns a dict: counters, outlier,
+        kf_point, kf_pose, kf_id (afterwards), kp_point_out (the next frame's last_point), ref_kf (what CommitFrame takes), new_kf,
+        interrupt_ba, made."""
+        fn = "Tracking.FinishFrame"
+        n, fr, ntrack, nframes, cap, (kp,) = Tracking._td_rows(fn, n, frame, [kp_point], int(npoints))
+        st, of, lv, nobs = Tracking._td_obs(fn, int(npoints), obs_start, obs_frame, obs_live, nframes)
+        okk, inl = _arr(ok, np.uint8, ntrack, fn + " ok"), _arr(inliers, np.int32, ntrack, fn + " inliers")
+        ct = np.array(_arr(counters, TRACK_COUNTERS_DTYPE, ntrack, fn + " counters"))
+        pf = _arr(pose_final, KF_POSE_DTYPE, ntrack, fn + " pose_final")
+        ol = np.array(_arr(outlier, np.uint8, ntrack, fn + " outlier", cap))
+        kfp = np.array(_arr(kf_point, np.int32, nframes, fn + " kf_point", cap))
+        kfq, kid = np.array(_arr(kf_pose, KF_POSE_DTYPE, nframes, fn + " kf_pose")), np.array(_arr(kf_id, np.uint64, nframes, fn + " kf_id"))
+        pbad = None if point_bad is None else _arr(point_bad, np.uint8, int(npoints), fn + " point_bad")
+        ho = None if point_has_obs is None else _arr(point_has_obs, np.uint8, int(npoints), fn + " point_has_obs")
+        rows = (np.arange(ntrack) if fr is None else fr).tolist()
+        if len(set(rows)) != ntrack:
+            raise ValueError(fn + ": two trackers name one frame row")
+        for t in range(ntrack):
+            r = int(ct[t]["ref_kf"])
+            if not 0 <= r < nframes or r in rows:
+                raise ValueError(fn + ": a reference key frame is out of range or a tracker's frame row")
+            u = kfp[r, :n[r]]
+            if len(u) and (u.min() < -1 or u.max() >= npoints):
+                raise ValueError(fn + ": a key frame's slot names a point out of range")
+        out, ref, new, ib = np.full((ntrack, cap), -1, np.int32), np.zeros(ntrack, np.int32), np.zeros(ntrack, np.int32), np.zeros(ntrack, np.uint8)
+        made = ext._check(ext._L.pgorb_track_finish(
+            ext._h, ntrack, _p(n), nframes, cap, Tracking._opt(fr), _p(okk), _p(inl), _p(ct), _p(pf), _p(kp), _p(ol), int(npoints), Tracking._opt(pbad),
+            Tracking._opt(ho), _p(st), _p(of), nobs, Tracking._opt(lv), _p(kfp), _p(kfq), _p(kid), _p(out), _p(ref), _p(new), _p(ib)))
+        return dict(counters=ct, outlier=ol, kf_point=kfp, kf_pose=kfq, kf_id=kid, kp_point_out=out, ref_kf=ref, new_kf=new, interrupt_ba=ib,
+                    made=int(made))
+
+    @staticmethod
+    def ScaleInitialMap(ext, kf_ini, kf_cur, kf_point, n, poses, points, obs_start, obs_frame, point_bad=None, obs_live=None):
+        """CreateInitialMapMonocular's unit median depth (Tracking.cc:684-709).  Returns a dict: poses, points (afterwards), info
+        [DECIDE_INFO] = (status, the median's float bits, TrackedMapPoints(1) of kf_cur, points scaled), median, wrong (the reference
+        would reset: nothing was changed)."""
+        fn = "Tracking.ScaleInitialMap"
+        kfp, nn, P, X, npoints = LocalMapping._depth_table(fn, kf_point, n, poses, points)
+        nframes, cap = kfp.shape
+        if not (0 <= int(kf_ini) < nframes and 0 <= int(kf_cur) < nframes) or int(kf_ini) == int(kf_cur):
+            raise ValueError(fn + ": a key frame is out of range, or both are one")
+        st, of, lv, nobs = Tracking._td_obs(fn, npoints, obs_start, obs_frame, obs_live, nframes)
+        pbad = None if point_bad is None else _arr(point_bad, np.uint8, npoints, fn + " point_bad")
+        P, X, info = np.array(P), np.array(X if npoints else np.zeros(1, MAP_POINT_DTYPE)), np.zeros(DECIDE_INFO, np.int32)
+        ext._check(ext._L.pgorb_scale_initial_map(ext._h, int(kf_ini), int(kf_cur), _p(kfp), _p(nn), nframes, cap, _p(P), npoints, _p(X),
+                                                  Tracking._opt(pbad), _p(st), _p(of), nobs, Tracking._opt(lv), _p(info)))
+        return dict(poses=P, points=X[:npoints], info=info, median=float(info[1:2].view(np.float32)[0]), wrong=bool(info[0] & DECIDE_WRONG_INIT))
+
 
 # the trajectory read-out (include/pgorb.h): the records, the modes, the status bits and the limits
 TRACK_STATE_DTYPE, TRAJECTORY_RECORD_DTYPE = _lib.TRACK_STATE_DTYPE, _lib.TRAJECTORY_RECORD_DTYPE
@@ -2432,6 +2648,10 @@ TRACK_MOTION_MODEL, TRACK_REFERENCE_KF = 0, 1
 TRACK_NO_LAST, TRACK_NO_VELOCITY, TRACK_BAD_INDEX, TRACK_FULL, TRACK_MAX = 1, 2, 4, 8, 4096
 TRAJ_BROKEN, TRAJ_BAD_TIME, TRAJ_NO_ORIGIN, TRAJ_INFO, TRAJ_MAX_RECORDS = 1, 2, 4, 4, 1 << 22
 TCP_INFO = 4
+# Tracking's decisions (include/pgorb.h): the counters record, the stages, the status bits and the limits
+TRACK_COUNTERS_DTYPE = _lib.TRACK_COUNTERS_DTYPE
+DECIDE_MOTION_MODEL, DECIDE_REFERENCE_KF, DECIDE_LOCAL_MAP, DECIDE_WRONG_INIT, DECIDE_INFO = 0, 1, 2, 4, 4
+DEPTH_EMPTY, DEPTH_NAN, DEPTH_MAX_LIST = 1, 2, 262144
 
 
 class System:
